@@ -12,13 +12,18 @@ configuration BASELINE.json's metric is quoted on — "MipNeRF360 bicycle, 1237x
 as a seeded synthetic stand-in (no datasets/checkpoints in the environment): scene_outdoor_like(6e6).
 Weak scaling: every rank renders its own view of the replicated scene each step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with the extra objects
+Prints ONE JSON line on rank 0: the headline (`metric`, `value` in images/s, `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+= wall milliseconds of one timed step), the configuration and the scene statistics N,V,M,T,P,E_f,E_b.  A plain run does only
+that: set-up, warm-up, the timed steps, the line.
+
+    --dump-outputs DIR   also writes what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs)
+    --full               then measures everything else, and the line carries the extra objects
   "roofline":     dominant HBM-bound kernel's algorithmic bytes / its mean hipEvent duration over the timed region,
   "roofline_valu": the same for the step's longest launch when that is one of the two compositors, which are bound by
                    vector-instruction issue (wave64 instructions per second against the chip's issue peak),
   "cpu_baseline": pure-PyTorch per-ray composite (oracle/per_ray_torch.py) on a bounded ray sample,
-plus "render_ms_per_frame" (forward-only, event time around the whole forward incl. sort + count readback,
-the reference's `forward_render` definition) and the scene statistics N,V,M,T,P,E_f,E_b.
+plus "per_kernel", "phase_ms", "drop_in", the "sensitivity" workloads and "render_ms_per_frame" (forward-only, event time
+around the whole forward incl. sort + count readback, the reference's `forward_render` definition).
 """
 import argparse
 import gc
@@ -271,9 +276,52 @@ def synthetic_optimizer_state(stepper):
         v_.fill_(1e-8)
 
 
-def run_workload(args, env, workload, steps, warmup, render_frames):
+DUMP_MAX_PIXELS = 1 << 21   # --dump-outputs: frames up to 2 M pixels are written whole (48 MB at most with the Gaussians' rows)
+DUMP_MAX_ROWS = 1 << 16     # --dump-outputs: a fixed, seeded sample of 65536 Gaussians (16 MB)
+
+
+def _fixed_sample(n, cap, seed):
+    """Sorted indices of a fixed, seeded sample of `cap` of `n` items, or None when all `n` fit."""
+    return None if n <= cap else np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def dump_outputs(out_dir, last, model):
+    """--dump-outputs: what the last timed train step handed its caller, as float32 .npy files in `out_dir`: `loss`, the rendered
+    `pred_rgb` and per-pixel `hits_count` (whole frames up to DUMP_MAX_PIXELS, else a seeded sample of pixels, one row each), and of
+    a seeded sample of DUMP_MAX_ROWS Gaussians the `mog_visibility` of the step and the parameters it left (`positions`, density
+    logit `density`, unnormalised quaternion `rotation`, log-scale `scale`, SH coefficients `features`).  Gaussian rows are taken in
+    the order the scene was given in, whatever order the trainer stores them in."""
+    os.makedirs(out_dir, exist_ok=True)
+    loss, aux = last
+    n = model.num_gaussians
+    dev = aux["pred_rgb"].device
+    rows = _fixed_sample(n, DUMP_MAX_ROWS, 1)
+    rows = torch.arange(n, device=dev) if rows is None else torch.as_tensor(rows, device=dev)
+    perm = getattr(model, "permutation", None)
+    if perm is not None:   # stored row i holds scene row perm[i]
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(n, device=perm.device)
+        rows = inv[rows]
+    if hasattr(model, "raw"):   # native trainer: [N,12] rows (position, density logit, quaternion, log-scale, unused) + [N,48]
+        raw = model.raw[rows]
+        params = dict(positions=raw[:, 0:3], density=raw[:, 3:4], rotation=raw[:, 4:8], scale=raw[:, 8:11], features=model.features[rows])
+    else:
+        params = dict(positions=model.positions[rows], density=model.density[rows], rotation=model.rotation[rows], scale=model.scale[rows],
+                      features=torch.cat([model.features_albedo[rows], model.features_specular[rows]], 1))
+    rgb, hits = aux["pred_rgb"], aux["hits_count"]
+    pix = _fixed_sample(rgb.shape[1] * rgb.shape[2], DUMP_MAX_PIXELS, 2)
+    if pix is not None:
+        pix = torch.as_tensor(pix, device=dev)
+        rgb, hits = rgb.reshape(-1, rgb.shape[-1])[pix], hits.reshape(-1, hits.shape[-1])[pix]
+    arrays = dict(loss=loss.reshape(1), pred_rgb=rgb, hits_count=hits, mog_visibility=aux["mog_visibility"][rows], **params)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t.detach().float().cpu().numpy()))
+
+
+def run_workload(args, env, workload, steps, warmup, render_frames, full=True, dump_dir=None):
     """Build the workload, run `warmup` untimed and `steps` timed train steps (barrier + synchronize on both sides, max over
-    ranks), then `render_frames` forward-only frames.  Returns the measurements and the objects the report needs."""
+    ranks), write what the last timed step computed to `dump_dir` (rank 0, if given), then — `full` — a second, instrumented pass
+    of `steps` steps and `render_frames` forward-only frames.  Returns the measurements and the objects the report needs."""
     rank, world, dev, dist = env["rank"], env["world"], env["dev"], env["dist"]
     gut = importlib.import_module("3dgrut_amd")
     scenes = importlib.import_module("3dgrut_amd.scenes")
@@ -356,9 +404,19 @@ def run_workload(args, env, workload, steps, warmup, render_frames):
             dist.barrier()
         torch.cuda.synchronize(dev)
 
+    probe_last = getattr(stepper, "PROBE_LAST", None)
+
+    def warmup_step(i):
+        # The trainer's overlap probe decides at the first step after its last sample at which every sample's events have completed,
+        # which depends on how far the host runs ahead.  Waiting for the queued samples first makes it decide at step PROBE_LAST + 1
+        # in every run, on the same samples, so the same arguments always apply the same number of steps (--dump-outputs).
+        if probe_last is not None and getattr(stepper, "probe_pending", False) and stepper.step_id > probe_last:
+            barrier()
+        stepper.step(batch_for(i))
+
     tune = (args.trainer == "native" and stepper.model.num_gaussians >= 1_000_000 and not getattr(args, "no_placement_tuning", False))
     for s in range(warmup):
-        stepper.step(batch_for(s))
+        warmup_step(s)
         if tune and s == min(1, warmup - 1):
             # Re-place the three [N,48] state tensors where that makes the optimiser's stream faster — after the first steps, when
             # the library has allocated its scratch.  (With the tuning's churn of gigabyte-sized allocations BEFORE the first step
@@ -369,7 +427,7 @@ def run_workload(args, env, workload, steps, warmup, render_frames):
     # the trainer's overlap probe times steps 2..9 in alternating forms and decides at step 10: never inside the timed region
     extra_warmup = 0
     while getattr(stepper, "probe_pending", False) and extra_warmup < 12:
-        stepper.step(batch_for(warmup + extra_warmup))
+        warmup_step(warmup + extra_warmup)
         extra_warmup += 1
     warmup += extra_warmup
     raster = tracer.tracer_wrapper
@@ -379,8 +437,8 @@ def run_workload(args, env, workload, steps, warmup, render_frames):
     raster.collect_times()
     # The timed region carries NO events: it is the product's default configuration (render.enable_kernel_timings = false).  The two dozen
     # event records per step (every kernel boundary, the phases) cost 5 - 7 % of a 2.4 ms step — measured, BENCH_NO_TIMING_EVENTS and
-    # DESIGN.md section 6.  Every per-kernel duration of the line — the roofline's kernel included — is measured right after the timed
-    # region by HIP events over a second pass of the same number of steps on the same views (`instrumented_pass`).
+    # DESIGN.md section 6.  Every per-kernel duration of the line — the roofline's kernel included — is measured (--full) right after the
+    # timed region by HIP events over a second pass of the same number of steps on the same views (`instrumented_pass`).
     bare_steps = hasattr(raster, "set_kernel_timing_set") and not no_events
     if bare_steps:
         raster.set_kernel_timing_set(2)
@@ -393,8 +451,9 @@ def run_workload(args, env, workload, steps, warmup, render_frames):
     # "the compositors' speed wanders".)
     gc.freeze()
     t0 = time.perf_counter()
-    for s in range(steps):
+    for s in range(steps - 1):
         stepper.step(batch_for(warmup + s))
+    last = stepper.step(batch_for(warmup + steps - 1))   # (loss, outputs): what a caller of the timed path receives
     barrier()
     gc.unfreeze()
     elapsed = time.perf_counter() - t0
@@ -402,11 +461,19 @@ def run_workload(args, env, workload, steps, warmup, render_frames):
         t = torch.tensor([elapsed], device=dev if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, last, stepper.model)
+    del last
 
     if no_events:   # developer A/B only: nothing of the line's per-kernel content can be filled in
         print(json.dumps({"metric": "A/B only: step without timing events", "value": world * steps / elapsed,
                           "ms_per_step": 1000.0 * elapsed / steps, "render_ms_per_frame": float("nan"), "per_kernel": {}, "phase_ms": {}}))
         sys.exit(0)
+    if not full:   # the headline needs nothing more
+        stats = raster.stats()
+        stats["lazy_moments"] = bool(getattr(stepper, "lazy_moments", False))
+        return dict(value=world * steps / elapsed, ms_per_step=1000.0 * elapsed / steps, stats=stats, stepper=stepper,
+                    extra_warmup=extra_warmup, W=W, H=H)
     instrumented_ms = None
     if bare_steps:
         raster.set_kernel_timing_set(0)
@@ -486,6 +553,181 @@ def run_drop_in(res, steps=16, warmup=5, optimizer_type="adam", raw_parameters=T
             "forward_render_ms": fb.get("forward_render"), "backward_render_ms": fb.get("backward_render"), "phase_ms": phases}
 
 
+def full_report(args, env, res, out):
+    """--full: adds to the line `out` what the headline does not need — per-kernel times, roofline blocks and phases of the
+    instrumented pass, the forward-only render time, the same workload through the reference's own surface (drop-in) and the
+    CPU legs."""
+    world, dev = env["world"], env["dev"]
+    ktimes, stats = res["ktimes"], res["stats"]
+    W, H, fx = res["W"], res["H"], res["fx"]
+    split = ktimes.get("optimizer_early", -1.0) > 0
+    bkey = lambda k: "optimizer_late" if (k == "optimizer" and split) else k   # byte model of the kernel as launched
+    # dominant kernel = the longest single launch of the step ("optimizer_early" is the span of the side stream's two launches,
+    # idle gap included, and is reported under per_kernel only; "optimizer_early_2" is its second launch, timed with events
+    # on the side stream it runs on)
+    longest = max((k for k in ktimes if ktimes[k] > 0 and k != "optimizer_early"), key=lambda k: ktimes[k])
+    # The two compositors are bound by vector-instruction issue, not by bytes or matrix flops (DESIGN.md section 5): when one of
+    # them is the step's longest launch it gets its own block (`roofline_valu`, below) and `roofline` — whose bound is "hbm" or
+    # "mfma" by contract — describes the longest launch of the HBM-bound kernels, which is also the one that moves most bytes.
+    VALU_BOUND = ("render", "render_bwd")
+    dom = max((k for k in ktimes if ktimes[k] > 0 and k != "optimizer_early" and k not in VALU_BOUND), key=lambda k: ktimes[k])
+    # achievable HBM bandwidth of THIS box, for context next to the 8 TB/s spec: device-to-device copy of 2 GB
+    a = torch.empty(1 << 29, dtype=torch.float32, device=dev); b = torch.empty_like(a)
+    b.copy_(a)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(4):
+        b.copy_(a)
+    e1.record(); torch.cuda.synchronize(dev)
+    copy_gbs = 4 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+    del a, b
+    abytes = algorithmic_bytes(stats, bkey(dom), stats["sort_end_bit"])
+    achieved = abytes / (ktimes[dom] * 1e-3) / 1e9
+    # PMC counters are NOT collected in this run (rocprofv3 --pmc needs its own passes): they are replayed from the
+    # tracked profile of the same command and workload, and say so
+    prof = profile_counters() if (args.workload == "bicycle_like_6M_1237x822" and not args.num_gaussians and not args.ply
+                                  and args.trainer == "native" and not args.scene_order) else {}
+    pk = lambda k: prof.get(k, {})
+    traffic = pk(dom).get("hbm_bytes")
+    roofline = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "traffic_source": (prof.get("_source") + " (separate rocprofv3 --pmc passes of the same workload, replayed here)") if traffic else None,
+                "algorithmic_bytes": abytes, "mean_launch_ms": ktimes[dom], "launches_averaged": res["kcount"],
+                "box_copy_GBps": copy_gbs}
+    if pk(dom).get("duration_ms_SQ_A"):
+        # the same kernel with nothing beside it: rocprofv3's PMC passes serialise the launches (tracked profile, replayed)
+        roofline["alone_in_profile"] = {"ms": pk(dom)["duration_ms_SQ_A"], "hbm_bytes": traffic,
+                                        "frac": (traffic or abytes) / (pk(dom)["duration_ms_SQ_A"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                        "source": prof.get("_source")}
+    if dom == "optimizer_early_2":
+        roofline["note"] = ("side-stream optimiser pass, second launch: a persistent kernel of two workgroups per CU that streams the "
+                            "Adam state of the Gaussians the forward walked nothing of (lazy moment decay: p, m, v read, p and the next "
+                            "activation row written) UNDER the VALU-bound backward compositor and then beside the pass over the walked "
+                            "waves; it shares the chip by design and is no longer on the step's critical path; alone it runs at the "
+                            "box's device-copy rate (profiles/: optimizer_early_2, PMC pass)")
+    # (always given, for the longer of the two compositors: which of K7 and the side stream's second launch is the step's
+    #  longest launch changes from box to box with the placement of the optimiser state, 0.77 - 0.95 against 0.87 ms)
+    roofline_valu = None
+    roofline["longest_launch_of_the_step"] = longest + (" (VALU-bound: see roofline_valu)" if longest in VALU_BOUND else "")
+    comp = [k for k in VALU_BOUND if ktimes.get(k, -1.0) > 0]
+    if comp:
+        longest = max(comp, key=lambda k: ktimes[k])
+        c = pk(longest)
+        if "SQ_INSTS_VALU" in c:
+            # wave64 vector instructions per launch (SQ_INSTS_VALU of the tracked PMC pass, same workload) / this run's mean
+            # launch duration, against one instruction per SIMD every 2 cycles at 2.4 GHz on 1024 SIMDs (VALU_PEAK_GINSTR_S)
+            rate = c["SQ_INSTS_VALU"] / (ktimes[longest] * 1e-3) / 1e9
+            roofline_valu = {"kernel": longest, "bound": "valu issue", "achieved": rate, "peak": VALU_PEAK_GINSTR_S,
+                             "unit": "G wave64-instructions/s", "frac": rate / VALU_PEAK_GINSTR_S,
+                             "frac_of_measured_issue_rate": c["SQ_INSTS_VALU"] * VALU_ISSUE_NS * 1e-9 / (1024 * ktimes[longest] * 1e-3),
+                             "wave_instructions_per_launch": c["SQ_INSTS_VALU"], "mean_launch_ms": ktimes[longest],
+                             "counters_source": prof.get("_source"),
+                             "note": "fp32 per-(pixel, Gaussian) arithmetic on the vector pipe (MFMA measured slower, DESIGN.md "
+                                     "section 5); the kernel shares its SIMDs with the side-stream optimiser pass while it runs"}
+    if split:
+        # context for the split optimiser: what the whole Adam step must move vs what of it is left on the critical path
+        roofline["optimizer_split"] = {
+            "whole_step_algorithmic_bytes": algorithmic_bytes(stats, "optimizer", stats["sort_end_bit"]),
+            "critical_path_kernel_bytes": algorithmic_bytes(stats, "optimizer_late", stats["sort_end_bit"]),
+            "side_stream_kernel_bytes": algorithmic_bytes(stats, "optimizer_early", stats["sort_end_bit"]),
+            "critical_path_ms": ktimes["optimizer"], "side_stream_span_ms": ktimes["optimizer_early"],
+            "side_stream_second_launch_ms": ktimes.get("optimizer_early_2")}
+    per_kernel = {}
+    for k in ktimes:
+        e = {"ms": ktimes[k],
+             "GBps": (algorithmic_bytes(stats, bkey(k), stats["sort_end_bit"]) / (ktimes[k] * 1e-3) / 1e9) if ktimes[k] > 0 else None}
+        c = pk(k)
+        if ktimes[k] > 0 and "SQ_INSTS_VALU" in c:
+            # share of the chip's measured wave64 VALU issue rate (1 instruction / 1.16 ns / SIMD, tools/pk_rate.hip):
+            # profile's VALU wave-instructions per launch / (this run's duration x 1024 SIMDs x that rate)
+            e["valu_frac"] = c["SQ_INSTS_VALU"] * VALU_ISSUE_NS * 1e-9 / (1024 * ktimes[k] * 1e-3)
+            e["valu_wave_instructions"] = c["SQ_INSTS_VALU"]
+            e["counters_source"] = prof.get("_source")
+        if "hbm_bytes" in c:
+            e["traffic"] = c["hbm_bytes"]
+        if k == "optimizer_early" and ktimes[k] > 0:
+            e["note"] = ("side stream, two launches (waves without tiles of the first 60 % of the row blocks under the forward "
+                         "compositor, in the kernel's 32-register form; the rest of them plus every wave the forward walked nothing of from the start of the backward "
+                         "compositor): ms is the span from the start of the first to the end of the second, idle gap included")
+        per_kernel[k] = e
+    sh_degree = 3
+    out.update({
+        "render_ms_per_frame": res["render_ms"],
+        "forward_render_ms_in_train": res["fb"].get("forward_render"), "backward_render_ms_in_train": res["fb"].get("backward_render"),
+        "phase_ms": res["phases"], "step_gpu_span_ms": res["step_spans"], "per_kernel": per_kernel, "roofline": roofline, "roofline_valu": roofline_valu,
+        "instrumented_pass": (None if res.get("instrumented_ms") is None else {
+            "ms_per_step": res["instrumented_ms"], "steps": args.steps,
+            "note": "`value` / `ms_per_step` are timed with no events in the steps (the product's default, enable_kernel_timings = false); "
+                    "`per_kernel`, `roofline`, `phase_ms`, `step_gpu_span_ms` and `*_render_ms_in_train` are HIP-event measurements over this "
+                    "second pass of the same number of steps, run right after the timed region with every kernel boundary and phase bracketed"}),
+    })
+    if world == 1 and not args.no_drop_in and args.trainer == "native":
+        try:
+            out["drop_in"] = run_drop_in(res)
+        except Exception as e:
+            out["drop_in"] = {"error": f"{type(e).__name__}: {e}"}
+        try:
+            out["drop_in"]["selective_adam"] = run_drop_in(res, optimizer_type="selective_adam")
+        except Exception as e:
+            out["drop_in"]["selective_adam"] = {"error": f"{type(e).__name__}: {e}"}
+        try:   # the same with the reference's own activation calls (what `drop_in` was until round 3)
+            out["drop_in"]["torch_activations"] = run_drop_in(res, raw_parameters=False)
+        except Exception as e:
+            out["drop_in"]["torch_activations"] = {"error": f"{type(e).__name__}: {e}"}
+    if world == 1 and not args.no_cpu_baseline and res.get("colmap"):
+        out["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": os.cpu_count(), "kind": "port",
+                               "sample": "not run: the CPU legs are wired for the named workloads' orbit cameras, not for --colmap views"}
+    elif world == 1 and not args.no_cpu_baseline:
+        try:
+            out["cpu_baseline"] = cpu_baseline(res["scene"], res["cams"], res["pose_mod"], W, H, fx, res["c2ws"][0], sh_degree,
+                                               fisheye=res["fisheye"])
+            # north_star's wording: a pure-PyTorch per-ray composite on the host cores, same run (second, smaller sample;
+            # wired for the pinhole workloads)
+            if not res["fisheye"]:
+                out["cpu_baseline_per_ray_torch"] = cpu_baseline_per_ray_torch(res["scene"], res["cams"], res["pose_mod"], W, H, fx,
+                                                                               res["c2ws"][0], sh_degree)
+        except Exception as e:  # the baseline is reported, never a gate
+            out["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": os.cpu_count(), "kind": "port",
+                                   "sample": f"failed: {type(e).__name__}: {e}"}
+
+
+def sensitivity_report(args, env, out):
+    """--full, headline workload: two short, labelled measurements on the other bicycle stand-ins, added to `out`."""
+    # workload sensitivity: the same train step on the denser stand-in with SURVEY §8d C3's literal parameters
+    # (a short, labelled second measurement; `value` above stays the headline workload)
+    r2 = None
+    try:
+        r2 = run_workload(args, env, "bicycle_like_6M_survey_c3", 10, 5, 5)   # (+ warm-up extended until the overlap probe has decided)
+        out["sensitivity"] = {"workload": "bicycle_like_6M_survey_c3",
+                              "note": "same step on the stand-in generated with SURVEY.md §8d C3's literal parameters (log-normal scales "
+                                      "mu = ln 0.01, opacity logits N(0, 1.5)): larger, more opaque splats, far more tile intersections",
+                              "value": r2["value"], "unit": "images/s", "ms_per_step": r2["ms_per_step"], "steps": 10, "warmup": 5 + r2.get("extra_warmup", 0),
+                              "render_ms_per_frame": r2["render_ms"], "phase_ms": r2["phases"], "scene_stats": r2["stats"],
+                              "per_kernel_ms": {k: v for k, v in r2["ktimes"].items()}}
+    except Exception as e:
+        out["sensitivity"] = {"workload": "bicycle_like_6M_survey_c3", "error": f"{type(e).__name__}: {e}"}
+    # ... and on the surface-like stand-in, the other end of the bracket around the headline (E/M 0.4 - 0.5 instead of 0.12)
+    try:
+        r2 = None
+        gc.collect()
+        torch.cuda.empty_cache()
+        r3 = run_workload(args, env, "bicycle_like_6M_surface", 10, 5, 5)
+        s3 = r3["stats"]
+        out["sensitivity_surface"] = {"workload": "bicycle_like_6M_surface",
+                                      "note": "same step on the surface-like stand-in (scenes.scene_surface_like: every Gaussian a flat, mostly "
+                                              "faint disc on a 2-D shell, nothing buried in opaque volumes): about half of every tile's list is "
+                                              "walked, four times the compositing work of the headline stand-in.  Nothing the reference publishes "
+                                              "pins where a trained bicycle sits between the two (unpinned): quote the headline as the range.",
+                                      "value": r3["value"], "unit": "images/s", "ms_per_step": r3["ms_per_step"], "steps": 10, "warmup": 5 + r3.get("extra_warmup", 0),
+                                      "render_ms_per_frame": r3["render_ms"], "phase_ms": r3["phases"], "scene_stats": s3,
+                                      "E_over_M": s3["traversed_fwd"] / max(1, s3["num_intersections"]), "M_over_V": s3["num_intersections"] / max(1, s3["num_visible"]),
+                                      "optimizer_overlap": bool(getattr(r3["stepper"], "overlap_optimizer", False)),
+                                      "per_kernel_ms": {k: v for k, v in r3["ktimes"].items()}}
+        out["headline_range_images_per_s"] = sorted([out["sensitivity_surface"]["value"], out["value"]])
+    except Exception as e:
+        out["sensitivity_surface"] = {"workload": "bicycle_like_6M_surface", "error": f"{type(e).__name__}: {e}"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -493,9 +735,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="bicycle_like_6M_1237x822", choices=list(WORKLOADS))
     ap.add_argument("--num-gaussians", type=int, default=0, help="override N (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sensitivity", action="store_true", help="skip the short second and third measurements on bicycle_like_6M_survey_c3 and bicycle_like_6M_surface")
-    ap.add_argument("--render-frames", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: per-kernel times, roofline blocks and phases (a second, "
+                         "instrumented pass), the forward-only render time, the drop-in and CPU legs, the sensitivity workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, image, hit counts, a seeded sample of the Gaussians' visibility "
+                         "and updated parameters) to DIR/<name>.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU legs")
+    ap.add_argument("--no-sensitivity", action="store_true", help="--full: skip the short second and third measurements on bicycle_like_6M_survey_c3 and bicycle_like_6M_surface")
+    ap.add_argument("--render-frames", type=int, default=10, help="--full: forward-only frames behind render_ms_per_frame")
     ap.add_argument("--trainer", default="native", choices=["native", "autograd"],
                     help="native: fused HIP activation/Adam around the renderer; autograd: torch.autograd + torch.optim.Adam")
     ap.add_argument("--dense-exchange", action="store_true",
@@ -534,7 +782,7 @@ def main():
                          "as targets where present) replace the orbit cameras (3dgrut_amd/io_colmap.py)")
     ap.add_argument("--colmap-downsample", type=int, default=1, help="images_<N>/ and intrinsics / N (MipNeRF360 runs use 4 for bicycle)")
     ap.add_argument("--no-drop-in", action="store_true",
-                    help="skip the short second measurement through the reference's own surface (Tracer.render -> _Autograd -> torch.optim.Adam)")
+                    help="--full: skip the short second measurement through the reference's own surface (Tracer.render -> _Autograd -> torch.optim.Adam)")
     ap.add_argument("--no-lazy-moments", action="store_true",
                     help="write both Adam moments of every row every step (default: waves that cannot receive a gradient read their moments, "
                          "bring them up to date in registers and do not write them back; gut_hip.h: GutLazyMoments)")
@@ -547,6 +795,10 @@ def main():
     ap.add_argument("--no-overlap-optimizer", action="store_true",
                     help="one optimiser kernel after the backward instead of the side-stream pass for the waves that cannot receive a gradient")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -586,101 +838,11 @@ def main():
             dist.init_process_group(backend=backend, rank=rank, world_size=world)
 
     env = dict(rank=rank, world=world, dev=dev, dist=dist)
-    res = run_workload(args, env, args.workload, args.steps, args.warmup, args.render_frames)
+    res = run_workload(args, env, args.workload, args.steps, args.warmup, args.render_frames, full=args.full, dump_dir=args.dump_outputs)
 
     if rank == 0:
-        ktimes, stats, stepper = res["ktimes"], res["stats"], res["stepper"]
-        W, H, fx = res["W"], res["H"], res["fx"]
-        split = ktimes.get("optimizer_early", -1.0) > 0
-        bkey = lambda k: "optimizer_late" if (k == "optimizer" and split) else k   # byte model of the kernel as launched
-        # dominant kernel = the longest single launch of the step ("optimizer_early" is the span of the side stream's two launches,
-        # idle gap included, and is reported under per_kernel only; "optimizer_early_2" is its second launch, timed with events
-        # on the side stream it runs on)
-        longest = max((k for k in ktimes if ktimes[k] > 0 and k != "optimizer_early"), key=lambda k: ktimes[k])
-        # The two compositors are bound by vector-instruction issue, not by bytes or matrix flops: when one of
-        # them is the step's longest launch it gets its own block (`roofline_valu`, below) and `roofline` — whose bound is "hbm" or
-        # "mfma" by contract — describes the longest launch of the HBM-bound kernels, which is also the one that moves most bytes.
-        VALU_BOUND = ("render", "render_bwd")
-        dom = max((k for k in ktimes if ktimes[k] > 0 and k != "optimizer_early" and k not in VALU_BOUND), key=lambda k: ktimes[k])
-        # achievable HBM bandwidth of THIS box, for context next to the 8 TB/s spec: device-to-device copy of 2 GB
-        a = torch.empty(1 << 29, dtype=torch.float32, device=dev); b = torch.empty_like(a)
-        b.copy_(a)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(4):
-            b.copy_(a)
-        e1.record(); torch.cuda.synchronize(dev)
-        copy_gbs = 4 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del a, b
-        abytes = algorithmic_bytes(stats, bkey(dom), stats["sort_end_bit"])
-        achieved = abytes / (ktimes[dom] * 1e-3) / 1e9
-        # PMC counters are NOT collected in this run (rocprofv3 --pmc needs its own passes): they are replayed from the
-        # tracked profile of the same command and workload, and say so
-        prof = profile_counters() if (args.workload == "bicycle_like_6M_1237x822" and not args.num_gaussians and not args.ply
-                                      and args.trainer == "native" and not args.scene_order) else {}
-        pk = lambda k: prof.get(k, {})
-        traffic = pk(dom).get("hbm_bytes")
-        roofline = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                    "traffic_source": (prof.get("_source") + " (separate rocprofv3 --pmc passes of the same workload, replayed here)") if traffic else None,
-                    "algorithmic_bytes": abytes, "mean_launch_ms": ktimes[dom], "launches_averaged": res["kcount"],
-                    "box_copy_GBps": copy_gbs}
-        if pk(dom).get("duration_ms_SQ_A"):
-            # the same kernel with nothing beside it: rocprofv3's PMC passes serialise the launches (tracked profile, replayed)
-            roofline["alone_in_profile"] = {"ms": pk(dom)["duration_ms_SQ_A"], "hbm_bytes": traffic,
-                                            "frac": (traffic or abytes) / (pk(dom)["duration_ms_SQ_A"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                            "source": prof.get("_source")}
-        if dom == "optimizer_early_2":
-            roofline["note"] = ("side-stream optimiser pass, second launch: a persistent kernel of two workgroups per CU that streams the "
-                                "Adam state of the Gaussians the forward walked nothing of (lazy moment decay: p, m, v read, p and the next "
-                                "activation row written) UNDER the VALU-bound backward compositor and then beside the pass over the walked "
-                                "waves; it shares the chip by design and is no longer on the step's critical path; alone it runs at the "
-                                "box's device-copy rate (profiles/: optimizer_early_2, PMC pass)")
-        # (always given, for the longer of the two compositors: which of K7 and the side stream's second launch is the step's
-        #  longest launch changes from box to box with the placement of the optimiser state, 0.77 - 0.95 against 0.87 ms)
-        roofline_valu = None
-        roofline["longest_launch_of_the_step"] = longest + (" (VALU-bound: see roofline_valu)" if longest in VALU_BOUND else "")
-        comp = [k for k in VALU_BOUND if ktimes.get(k, -1.0) > 0]
-        if comp:
-            longest = max(comp, key=lambda k: ktimes[k])
-            c = pk(longest)
-            if "SQ_INSTS_VALU" in c:
-                # wave64 vector instructions per launch (SQ_INSTS_VALU of the tracked PMC pass, same workload) / this run's mean
-                # launch duration, against one instruction per SIMD every 2 cycles at 2.4 GHz on 1024 SIMDs (MI355X_MICROARCH.md)
-                rate = c["SQ_INSTS_VALU"] / (ktimes[longest] * 1e-3) / 1e9
-                roofline_valu = {"kernel": longest, "bound": "valu issue", "achieved": rate, "peak": VALU_PEAK_GINSTR_S,
-                                 "unit": "G wave64-instructions/s", "frac": rate / VALU_PEAK_GINSTR_S,
-                                 "frac_of_measured_issue_rate": c["SQ_INSTS_VALU"] * VALU_ISSUE_NS * 1e-9 / (1024 * ktimes[longest] * 1e-3),
-                                 "wave_instructions_per_launch": c["SQ_INSTS_VALU"], "mean_launch_ms": ktimes[longest],
-                                 "counters_source": prof.get("_source"),
-                                 "note": "fp32 per-(pixel, Gaussian) arithmetic on the vector pipe (MFMA measured slower, DESIGN.md "
-                                         "section 5); the kernel shares its SIMDs with the side-stream optimiser pass while it runs"}
-        if split:
-            # context for the split optimiser: what the whole Adam step must move vs what of it is left on the critical path
-            roofline["optimizer_split"] = {
-                "whole_step_algorithmic_bytes": algorithmic_bytes(stats, "optimizer", stats["sort_end_bit"]),
-                "critical_path_kernel_bytes": algorithmic_bytes(stats, "optimizer_late", stats["sort_end_bit"]),
-                "side_stream_kernel_bytes": algorithmic_bytes(stats, "optimizer_early", stats["sort_end_bit"]),
-                "critical_path_ms": ktimes["optimizer"], "side_stream_span_ms": ktimes["optimizer_early"],
-                "side_stream_second_launch_ms": ktimes.get("optimizer_early_2")}
-        per_kernel = {}
-        for k in ktimes:
-            e = {"ms": ktimes[k],
-                 "GBps": (algorithmic_bytes(stats, bkey(k), stats["sort_end_bit"]) / (ktimes[k] * 1e-3) / 1e9) if ktimes[k] > 0 else None}
-            c = pk(k)
-            if ktimes[k] > 0 and "SQ_INSTS_VALU" in c:
-                # share of the chip's measured wave64 VALU issue rate (1 instruction / 1.16 ns / SIMD, tools/pk_rate.hip):
-                # profile's VALU wave-instructions per launch / (this run's duration x 1024 SIMDs x that rate)
-                e["valu_frac"] = c["SQ_INSTS_VALU"] * VALU_ISSUE_NS * 1e-9 / (1024 * ktimes[k] * 1e-3)
-                e["valu_wave_instructions"] = c["SQ_INSTS_VALU"]
-                e["counters_source"] = prof.get("_source")
-            if "hbm_bytes" in c:
-                e["traffic"] = c["hbm_bytes"]
-            if k == "optimizer_early" and ktimes[k] > 0:
-                e["note"] = ("side stream, two launches (waves without tiles of the first 60 % of the row blocks under the forward "
-                             "compositor, in the kernel's 32-register form; the rest of them plus every wave the forward walked nothing of from the start of the backward "
-                             "compositor): ms is the span from the start of the first to the end of the second, idle gap included")
-            per_kernel[k] = e
+        stats, stepper = res["stats"], res["stepper"]
+        W, H = res["W"], res["H"]
         sh_degree = 3
         out = {
             "metric": "train-step images/sec + render ms/frame, MipNeRF360 bicycle @1/2/4/8 GPU",
@@ -704,14 +866,7 @@ def main():
                        "densification_statistics": bool(getattr(stepper, "post_backward_hook", None) is not None),
                        "optimizer_overlap_probe_ms": ({k: round(v, 3) for k, v in stepper._overlap_probe.items() if k in ("ms_on", "ms_off")}
                                                       if getattr(stepper, "_overlap_probe", None) else None)},
-            "render_ms_per_frame": res["render_ms"],
-            "forward_render_ms_in_train": res["fb"].get("forward_render"), "backward_render_ms_in_train": res["fb"].get("backward_render"),
-            "phase_ms": res["phases"], "step_gpu_span_ms": res["step_spans"], "scene_stats": stats, "per_kernel": per_kernel, "roofline": roofline, "roofline_valu": roofline_valu,
-            "instrumented_pass": (None if res.get("instrumented_ms") is None else {
-                "ms_per_step": res["instrumented_ms"], "steps": args.steps,
-                "note": "`value` / `ms_per_step` are timed with no events in the steps (the product's default, enable_kernel_timings = false); "
-                        "`per_kernel`, `roofline`, `phase_ms`, `step_gpu_span_ms` and `*_render_ms_in_train` are HIP-event measurements over this "
-                        "second pass of the same number of steps, run right after the timed region with every kernel boundary and phase bracketed"}),
+            "scene_stats": stats,
             "reference_rtx5090": {"images_per_s": 31.6, "render_ms": 3.64, "note": "README.md:320, different hardware, real dataset"},
         }
         if world > 1 or args.force_exchange:
@@ -725,70 +880,12 @@ def main():
                                      hardware_status="the N > 1 path has run on multi-GPU hardware only in the driver's own scaling runs; "
                                                      "builder-side it is covered by gloo world-2/3 tests, a world-8 gloo test of the record exchange and two-process one-GPU tests")
         out["config"]["warmup_extended_by"] = res.get("extra_warmup", 0)
-        if world == 1 and not args.no_drop_in and args.trainer == "native":
-            try:
-                out["drop_in"] = run_drop_in(res)
-            except Exception as e:
-                out["drop_in"] = {"error": f"{type(e).__name__}: {e}"}
-            try:
-                out["drop_in"]["selective_adam"] = run_drop_in(res, optimizer_type="selective_adam")
-            except Exception as e:
-                out["drop_in"]["selective_adam"] = {"error": f"{type(e).__name__}: {e}"}
-            try:   # the same with the reference's own activation calls (what `drop_in` was until round 3)
-                out["drop_in"]["torch_activations"] = run_drop_in(res, raw_parameters=False)
-            except Exception as e:
-                out["drop_in"]["torch_activations"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline and res.get("colmap"):
-            out["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": os.cpu_count(), "kind": "port",
-                                   "sample": "not run: the CPU legs are wired for the named workloads' orbit cameras, not for --colmap views"}
-        elif world == 1 and not args.no_cpu_baseline:
-            try:
-                out["cpu_baseline"] = cpu_baseline(res["scene"], res["cams"], res["pose_mod"], W, H, fx, res["c2ws"][0], sh_degree,
-                                                   fisheye=res["fisheye"])
-                # north_star's wording: a pure-PyTorch per-ray composite on the host cores, same run (second, smaller sample;
-                # wired for the pinhole workloads)
-                if not res["fisheye"]:
-                    out["cpu_baseline_per_ray_torch"] = cpu_baseline_per_ray_torch(res["scene"], res["cams"], res["pose_mod"], W, H, fx,
-                                                                                   res["c2ws"][0], sh_degree)
-            except Exception as e:  # the baseline is reported, never a gate
-                out["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": os.cpu_count(), "kind": "port",
-                                       "sample": f"failed: {type(e).__name__}: {e}"}
-        # workload sensitivity: the same train step on the denser stand-in with SURVEY §8d C3's literal parameters
-        # (a short, labelled second measurement; `value` above stays the headline workload)
-        if world == 1 and args.workload == "bicycle_like_6M_1237x822" and not args.no_sensitivity and not args.num_gaussians and not args.ply:
-            r2 = None
-            try:
-                del res, stepper
+        if args.full:
+            full_report(args, env, res, out)
+            if world == 1 and args.workload == "bicycle_like_6M_1237x822" and not args.no_sensitivity and not args.num_gaussians and not args.ply:
+                del res, stepper   # the headline's model and trainer state go before two more workloads of its size
                 torch.cuda.empty_cache()
-                r2 = run_workload(args, env, "bicycle_like_6M_survey_c3", 10, 5, 5)   # (+ warm-up extended until the overlap probe has decided)
-                out["sensitivity"] = {"workload": "bicycle_like_6M_survey_c3",
-                                      "note": "same step on the stand-in generated with SURVEY.md §8d C3's literal parameters (log-normal scales "
-                                              "mu = ln 0.01, opacity logits N(0, 1.5)): larger, more opaque splats, far more tile intersections",
-                                      "value": r2["value"], "unit": "images/s", "ms_per_step": r2["ms_per_step"], "steps": 10, "warmup": 5 + r2.get("extra_warmup", 0),
-                                      "render_ms_per_frame": r2["render_ms"], "phase_ms": r2["phases"], "scene_stats": r2["stats"],
-                                      "per_kernel_ms": {k: v for k, v in r2["ktimes"].items()}}
-            except Exception as e:
-                out["sensitivity"] = {"workload": "bicycle_like_6M_survey_c3", "error": f"{type(e).__name__}: {e}"}
-            # ... and on the surface-like stand-in, the other end of the bracket around the headline (E/M 0.4 - 0.5 instead of 0.12)
-            try:
-                r2 = None
-                gc.collect()
-                torch.cuda.empty_cache()
-                r3 = run_workload(args, env, "bicycle_like_6M_surface", 10, 5, 5)
-                s3 = r3["stats"]
-                out["sensitivity_surface"] = {"workload": "bicycle_like_6M_surface",
-                                              "note": "same step on the surface-like stand-in (scenes.scene_surface_like: every Gaussian a flat, mostly "
-                                                      "faint disc on a 2-D shell, nothing buried in opaque volumes): about half of every tile's list is "
-                                                      "walked, four times the compositing work of the headline stand-in.  Nothing the reference publishes "
-                                                      "pins where a trained bicycle sits between the two (unpinned): quote the headline as the range.",
-                                              "value": r3["value"], "unit": "images/s", "ms_per_step": r3["ms_per_step"], "steps": 10, "warmup": 5 + r3.get("extra_warmup", 0),
-                                              "render_ms_per_frame": r3["render_ms"], "phase_ms": r3["phases"], "scene_stats": s3,
-                                              "E_over_M": s3["traversed_fwd"] / max(1, s3["num_intersections"]), "M_over_V": s3["num_intersections"] / max(1, s3["num_visible"]),
-                                              "optimizer_overlap": bool(getattr(r3["stepper"], "overlap_optimizer", False)),
-                                              "per_kernel_ms": {k: v for k, v in r3["ktimes"].items()}}
-                out["headline_range_images_per_s"] = sorted([out["sensitivity_surface"]["value"], out["value"]])
-            except Exception as e:
-                out["sensitivity_surface"] = {"workload": "bicycle_like_6M_surface", "error": f"{type(e).__name__}: {e}"}
+                sensitivity_report(args, env, out)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(out), flush=True)

@@ -14,6 +14,12 @@ if ROOT not in sys.path:
 # equal up to the last bits of expf — is tested where it is switched on explicitly (tests/test_gpu_parity.py::test_raw_parameter_*).
 os.environ.setdefault("GUT_TRACER_RAW_PARAMETERS", "0")
 
+# The strategy pins (tests/test_cpu_reference_pins.py) compare torch's CPU exp / log BIT FOR BIT with the reference's, recorded in
+# tests/golden.  torch computes them with MKL, whose default code branch is chosen per CPU vendor and differs in the last bit
+# (an AMD EPYC host and an Intel Xeon host disagree); its vendor-independent branch gives the same bits on both, and the fixtures
+# are written on it (tests/golden/gen_strategy_golden.py, gen_mcmc_golden.py).  MKL reads this when torch first calls it.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with `-m gpu` on the GPU box)")

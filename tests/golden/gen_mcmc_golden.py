@@ -31,6 +31,10 @@ import os
 import sys
 import types
 
+# torch's CPU exp / log go through MKL, whose default code branch differs by vendor in the last bit; the fixture is
+# written on MKL's vendor-independent branch, the one tests/conftest.py pins for the suite (set before torch loads MKL)
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
 import numpy as np
 import torch
 

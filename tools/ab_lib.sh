@@ -1,9 +1,10 @@
 # Dev helper (GPU box): the bench's headline and surface legs with two builds of the library, interleaved.  usage: bash tools/ab_lib.sh OTHER.so TAG
-mkdir -p gpurun_out/r4
+OUT=${OUT:-bench_runs}   # where the JSON lines go
+mkdir -p "$OUT"
 for i in 1 2; do
   for v in new prev; do
     if [ $v = prev ]; then export GUT_HIP_LIBRARY=$1; else unset GUT_HIP_LIBRARY; fi
-    python bench.py --no-sensitivity --no-drop-in --no-cpu-baseline > gpurun_out/r4/ab_$2_h_${v}_${i}.json 2> gpurun_out/r4/ab_$2.err
-    python bench.py --workload bicycle_like_6M_surface --no-drop-in --no-cpu-baseline > gpurun_out/r4/ab_$2_s_${v}_${i}.json 2>> gpurun_out/r4/ab_$2.err
+    python bench.py --full --no-sensitivity --no-drop-in --no-cpu-baseline > "$OUT/ab_$2_h_${v}_${i}.json" 2> "$OUT/ab_$2.err"
+    python bench.py --full --workload bicycle_like_6M_surface --no-drop-in --no-cpu-baseline > "$OUT/ab_$2_s_${v}_${i}.json" 2>> "$OUT/ab_$2.err"
   done
 done

@@ -163,7 +163,7 @@ plain = json.load(open(os.path.join(dst, "bench_plain.json")))
 prof = json.load(open(os.path.join(dst, "bench_under_rocprof.json")))
 L = ["# Profiles (" + rnd + ")\n",
      "Collected with `tools/collect_profiles.sh` on one MI355X (gpurun), post-processed by `tools/profile_report.py`.\n",
-     "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-sensitivity` (the plain run next to it: `python3 bench.py --steps 20 --warmup 5`)\n",
+     "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-sensitivity` (the run without the profiler next to it: `python3 bench.py --full --steps 20 --warmup 5`)\n",
      "Files: `bench_kernel_stats.csv` (rocprofv3 per-kernel summary of that run), `bench_under_rocprof.json` (the bench line printed "
      "under the profiler), `bench_plain.json` (same command without the profiler, same box), `pmc_traffic.json` (HBM bytes per launch "
      "from separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes), `pmc_sq.json` (SQ / TCC / GRBM counters per launch from three more "
