@@ -146,9 +146,13 @@ struct gut_context {
     bool packed_raw = false;   // packed12 holds rows ACTIVATED by the library from the model's raw tensors (gut_trace_raw_model_fields)
     // per-M scratch
     DevBuf keys_unsorted, keys_sorted, ids_unsorted, ids_sorted, sort_temp;
-    // lazy per-tile depth order (unsorted variant): keys_sorted / ids_sorted are grouped by tile only, the forward compositor
-    // writes the ids it consumed, in final order, to ids_ordered; the fully sorted lists exist only on debug request
+    // lazy per-tile depth order (unsorted variant): keys_sorted holds one {depth bits, particle id} word per entry, grouped by tile
+    // (k_expand_grouped), the forward compositor writes the ids it consumed, in final order, to ids_ordered; the unsorted and the
+    // fully sorted lists exist only on debug request
     DevBuf ids_ordered, dbg_keys_sorted, dbg_ids_sorted;
+    DevBuf tile_entries, tile_start, tile_cursor;   // grouped binning: K1's per-tile counts (zero between frames), their scan, slots
+    uint32_t tile_entries_zeroed = 0;               // words of tile_entries known to be zero
+    bool dbg_unsorted_valid = false;
     bool lazy_enabled = true;      // gut_set_option(GUT_OPT_LAZY_TILE_ORDER)
     bool sorted_reference_bwd = true;   // gut_set_option(GUT_OPT_SORTED_REFERENCE_BACKWARD): the reference's form is the default
     bool lazy_order = false;       // this forward used the lazy order
@@ -420,7 +424,8 @@ void gut_destroy(gut_handle h) {
                       &h->grad16, &h->scan_temp, &h->keys_unsorted, &h->keys_sorted, &h->ids_unsorted, &h->ids_sorted,
                       &h->sort_temp, &h->ranges, &h->trav_fwd, &h->trav_bwd, &h->tile_order, &h->counters, &h->ids_ordered,
                       &h->dbg_keys_sorted, &h->dbg_ids_sorted, &h->zero_word, &h->tile_ordered, &h->wave_walked, &h->packed12, &h->walk_sums,
-                      &h->wave_sums, &h->block_prefix, &h->scan_total, &h->sph_widened, &h->sph_grad_wide, &h->cam_pos};
+                      &h->wave_sums, &h->block_prefix, &h->scan_total, &h->sph_widened, &h->sph_grad_wide, &h->cam_pos,
+                      &h->tile_entries, &h->tile_start, &h->tile_cursor};
     for (DevBuf* b : bufs) b->release();
     if (h->host_count) (void)hipHostFree(h->host_count);
     if (h->count_event) (void)hipEventDestroy(h->count_event);
@@ -551,6 +556,18 @@ static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
         clears.wave_walked = h->wave_walked.as<uint8_t>();
         HIP_TRY(h->cam_pos.ensure(64));
         clears.cam_pos = h->cam_pos.as<float>();
+        if (h->lazy_enabled && h->cfg.k_buffer_size == 0) {   // the lazy order bins with per-tile counts (k_expand_grouped)
+            const void* before = h->tile_entries.p;
+            HIP_TRY(h->tile_entries.ensure(sizeof(uint32_t) * (size_t)tiles));
+            HIP_TRY(h->tile_start.ensure(sizeof(uint32_t) * ((size_t)tiles + 1)));
+            HIP_TRY(h->tile_cursor.ensure(sizeof(uint32_t) * (size_t)tiles));
+            if (h->tile_entries.p != before) h->tile_entries_zeroed = 0;
+            if (h->tile_entries_zeroed < (uint32_t)tiles) {   // (the scan leaves the counts it read zero: only fresh memory is cleared)
+                HIP_TRY(hipMemsetAsync(h->tile_entries.p, 0, h->tile_entries.cap, s));
+                h->tile_entries_zeroed = (uint32_t)(h->tile_entries.cap / sizeof(uint32_t));
+            }
+            clears.tile_entries = h->tile_entries.as<uint32_t>();
+        }
     } else {
         HIP_TRY(hipMemsetAsync(h->trav_bwd.p, 0, sizeof(uint32_t) * (size_t)tiles, s));
         HIP_TRY(hipMemsetAsync(h->ranges.p, 0, sizeof(uint32_t) * 2 * (size_t)tiles, s));
@@ -577,6 +594,7 @@ static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
     }
     const int end_bit = 32 + (int)bit_width_u32((uint32_t)tiles);
     h->dbg_sorted_valid = false;
+    h->dbg_unsorted_valid = false;
     h->dbg_ordered_valid = false;
     // device-side intersection count: written by the scan of the block sums (a zero word when there are no particles)
     const uint32_t* d_count = n ? h->scan_total.as<uint32_t>() : h->zero_word.as<uint32_t>();
@@ -588,7 +606,8 @@ static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
         // workgroup scans the per-block sums (and writes the count), K3 finishes inside each wave.  One 5 us launch instead of three
         // launches over 48 MB (0.047 ms at 6 M Gaussians).
         gut::launch_scan_wave_sums(s, n, h->wave_sums.as<uint32_t>(), h->block_prefix.as<uint32_t>(), h->scan_total.as<uint32_t>(),
-                                   h->host_count_dev, h->walk_sums.as<uint32_t>());
+                                   h->host_count_dev, h->walk_sums.as<uint32_t>(), clears.tile_entries, (uint32_t)tiles,
+                                   h->tile_start.as<uint32_t>(), h->tile_cursor.as<uint32_t>());
         // intersection count read-back (gutRenderer.cu:313-321).  The reference blocks on it before it can size the
         // binning buffers; here the copy is queued and the host only waits for it AFTER the rest of the forward has been
         // queued against a capacity taken from the previous frames (m_capacity), so the GPU never idles on the host.
@@ -603,7 +622,18 @@ static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
     // the lambda so that the rare overflow can run it a second time.
     auto bin_and_render = [&](uint32_t sort_n, bool lazy) -> int {
         h->lazy_order = lazy;
-        if (sort_n) {
+        if (sort_n && lazy) {
+            // grouped binning: each entry goes straight into its tile's slice (slices from K1's per-tile counts and the scan), the
+            // compositor orders every tile itself — no expansion into (tile | depth) keys, no sort, no K5.  The kernel-timer marks
+            // of the sort and the ranges follow at once.
+            HIP_TRY(h->keys_sorted.ensure(sizeof(uint64_t) * (size_t)sort_n));
+            HIP_TRY(h->ids_ordered.ensure(sizeof(uint32_t) * (size_t)sort_n));
+            gut::launch_expand_grouped(s, v, h->consts, n, h->proj_pos.as<float>(), h->conic_opacity.as<float>(), h->extent.as<float>(),
+                                       h->depth.as<float>(), (uint32_t)tiles, h->tile_start.as<uint32_t>(), h->tile_cursor.as<uint32_t>(),
+                                       h->ranges.as<uint32_t>(), h->keys_sorted.as<uint64_t>(), sort_n);
+            mark(3);
+            mark(4);
+        } else if (sort_n) {
             HIP_TRY(h->keys_unsorted.ensure(sizeof(uint64_t) * (size_t)sort_n));
             HIP_TRY(h->keys_sorted.ensure(sizeof(uint64_t) * (size_t)sort_n));
             HIP_TRY(h->ids_unsorted.ensure(sizeof(uint32_t) * (size_t)sort_n));
@@ -613,17 +643,9 @@ static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
                                h->conic_opacity.as<float>(), h->extent.as<float>(), h->depth.as<float>(),
                                h->keys_unsorted.as<uint64_t>(), h->ids_unsorted.as<uint32_t>(), sort_n);
             mark(3);
-            if (lazy) {
-                HIP_TRY(h->sort_temp.ensure(gut::sort_tiles_temp_bytes(sort_n, end_bit)));
-                HIP_TRY(h->ids_ordered.ensure(sizeof(uint32_t) * (size_t)sort_n));
-                HIP_TRY(gut::run_sort_tiles(s, h->sort_temp.p, h->sort_temp.cap, h->keys_unsorted.as<uint64_t>(),
-                                            h->keys_sorted.as<uint64_t>(), h->ids_unsorted.as<uint32_t>(), h->ids_sorted.as<uint32_t>(),
-                                            sort_n, end_bit));
-            } else {
-                HIP_TRY(h->sort_temp.ensure(gut::sort_temp_bytes(sort_n, end_bit)));
-                HIP_TRY(gut::run_sort(s, h->sort_temp.p, h->sort_temp.cap, h->keys_unsorted.as<uint64_t>(), h->keys_sorted.as<uint64_t>(),
-                                      h->ids_unsorted.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), sort_n, end_bit));
-            }
+            HIP_TRY(h->sort_temp.ensure(gut::sort_temp_bytes(sort_n, end_bit)));
+            HIP_TRY(gut::run_sort(s, h->sort_temp.p, h->sort_temp.cap, h->keys_unsorted.as<uint64_t>(), h->keys_sorted.as<uint64_t>(),
+                                  h->ids_unsorted.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), sort_n, end_bit));
             mark(4);
             gut::launch_tile_ranges(s, sort_n, h->keys_sorted.as<uint64_t>(), h->ranges.as<uint32_t>());
         } else {
@@ -690,8 +712,12 @@ static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
         }
         if (m > sort_n) {
             // the frame has more intersections than the capacity assumed: entries beyond it were dropped by the expansion.
-            // Redo binning and compositing with the real count (same stream: the second pass simply overwrites the first).
-            HIP_TRY(hipMemsetAsync(h->ranges.p, 0, sizeof(uint32_t) * 2 * (size_t)tiles, s));
+            // Redo binning and compositing with the real count (same stream: the second pass simply overwrites the first).  The
+            // grouped binning (lazy order; then the first pass had it too) restarts its slots, K5 its ranges.
+            if (want_lazy(m))
+                HIP_TRY(hipMemcpyAsync(h->tile_cursor.p, h->tile_start.p, sizeof(uint32_t) * (size_t)tiles, hipMemcpyDeviceToDevice, s));
+            else
+                HIP_TRY(hipMemsetAsync(h->ranges.p, 0, sizeof(uint32_t) * 2 * (size_t)tiles, s));
             h->overflows++;
             if (bin_and_render(m, want_lazy(m))) return 1;
             h->sort_n = m;
@@ -1432,14 +1458,30 @@ int gut_debug_buffer(gut_handle h, int32_t which, void** d_ptr, size_t* bytes) {
     case GUT_BUF_PROJ_EXTENT: *d_ptr = h->extent.p; *bytes = 8 * n; break;
     case GUT_BUF_GLOBAL_DEPTH: *d_ptr = h->depth.p; *bytes = 4 * n; break;
     case GUT_BUF_FEATURES: *d_ptr = h->feat.p; *bytes = 12 * n; break;
-    case GUT_BUF_UNSORTED_KEYS: *d_ptr = h->keys_unsorted.p; *bytes = 8 * m; break;
-    case GUT_BUF_UNSORTED_IDS: *d_ptr = h->ids_unsorted.p; *bytes = 4 * m; break;
+    case GUT_BUF_UNSORTED_KEYS:
+    case GUT_BUF_UNSORTED_IDS:
     case GUT_BUF_SORTED_KEYS:
     case GUT_BUF_SORTED_IDS:
+        if (h->lazy_order && !h->dbg_unsorted_valid && m) {
+            // the grouped binning never writes the (tile | depth, id) pairs: K3 writes them for the caller (the scan's block
+            // prefixes and K1's wave sums of the cached forward are still there)
+            DeviceGuard dev_guard;
+            HIP_TRY(dev_guard.set(h->device));
+            HIP_TRY(h->keys_unsorted.ensure(8 * m));
+            HIP_TRY(h->ids_unsorted.ensure(4 * m));
+            gut::launch_expand(h->fwd_stream, h->view, h->consts, (uint32_t)n, h->tiles_count.as<uint32_t>(), h->wave_sums.as<uint32_t>(),
+                               h->block_prefix.as<uint32_t>(), h->scan_total.as<uint32_t>(), h->proj_pos.as<float>(),
+                               h->conic_opacity.as<float>(), h->extent.as<float>(), h->depth.as<float>(),
+                               h->keys_unsorted.as<uint64_t>(), h->ids_unsorted.as<uint32_t>(), (uint32_t)m);
+            HIP_TRY(hipStreamSynchronize(h->fwd_stream));
+            h->dbg_unsorted_valid = true;
+        }
+        if (which == GUT_BUF_UNSORTED_KEYS) { *d_ptr = h->keys_unsorted.p; *bytes = 8 * m; break; }
+        if (which == GUT_BUF_UNSORTED_IDS) { *d_ptr = h->ids_unsorted.p; *bytes = 4 * m; break; }
         if (h->lazy_order) {  // the product path never needs the fully sorted lists: build them for the caller
             if (!h->dbg_sorted_valid && m) {
                 DeviceGuard dev_guard;
-    HIP_TRY(dev_guard.set(h->device));
+                HIP_TRY(dev_guard.set(h->device));
                 HIP_TRY(h->dbg_keys_sorted.ensure(8 * m));
                 HIP_TRY(h->dbg_ids_sorted.ensure(4 * m));
                 DevBuf tmp;

@@ -93,6 +93,7 @@ struct FrameClears {
     uint8_t* wave_walked = nullptr;
     uint32_t tiles = 0;
     float* cam_pos = nullptr;   // [3]: K1 also leaves the sensor position (ViewParams.s2w.t) on the device
+    uint32_t* tile_entries = nullptr;   // [tiles], zero on entry: K1 adds every tile's entry count (grouped binning), or null
 };
 
 // ---- launch wrappers implemented in the .hip files -------------------------------------------------
@@ -102,8 +103,16 @@ void launch_project(hipStream_t s, const ViewParams& v, const RenderConsts& c, u
                     uint32_t* wave_sums /* [4 * blocks]: tile count of every 64-row wave (first level of the scan) */, const float* sph_albedo /* non-null: sph48 is features_specular [N,45], this is features_albedo [N,3] */,
                     const FrameClears& clears);
 // second level of the scan of the tile counts: block_prefix[b] = list entries of the Gaussians before 256-row block b, *total = M
+// tile_entries (K1's per-tile counts, or null; left zero): tile_start [tiles + 1] = their exclusive scan (tile_start[tiles] = M), tile_cursor
+// [tiles] = the same
 void launch_scan_wave_sums(hipStream_t s, uint32_t n, const uint32_t* wave_sums, uint32_t* block_prefix, uint32_t* total,
-                           uint32_t* host_out /* device view of pinned host words, or null */, const uint32_t* walk_sums /* or null */);
+                           uint32_t* host_out /* device view of pinned host words, or null */, const uint32_t* walk_sums /* or null */,
+                           uint32_t* tile_entries, uint32_t tiles, uint32_t* tile_start, uint32_t* tile_cursor);
+// lazy order's binning (replaces K3 + sort + K5): entries[tile_start[t] ..] := {depth bits, particle id} of tile t's entries, in no
+// particular order; ranges := the tiles' slices clamped to capacity ((0, 0) for empty tiles); slots >= capacity are dropped
+void launch_expand_grouped(hipStream_t s, const ViewParams& v, const RenderConsts& c, uint32_t n, const float* proj_pos,
+                           const float* conic_opacity, const float* extent, const float* depth, uint32_t tiles,
+                           const uint32_t* tile_start, uint32_t* tile_cursor, uint32_t* ranges, uint64_t* entries, uint32_t capacity);
 void launch_expand(hipStream_t s, const ViewParams& v, const RenderConsts& c, uint32_t n, const uint32_t* tiles_count,
                    const uint32_t* wave_sums, const uint32_t* block_prefix, const uint32_t* total /* device word: M; the tail
                    [M, capacity) of keys / ids is padded here */, const float* proj_pos, const float* conic_opacity, const float* extent, const float* depth,
@@ -198,8 +207,5 @@ hipError_t run_scan(hipStream_t s, void* temp, size_t temp_bytes, const uint32_t
 size_t sort_temp_bytes(uint32_t m, int end_bit);
 hipError_t run_sort(hipStream_t s, void* temp, size_t temp_bytes, const uint64_t* keys_in, uint64_t* keys_out,
                     const uint32_t* vals_in, uint32_t* vals_out, uint32_t m, int end_bit);
-size_t sort_tiles_temp_bytes(uint32_t m, int end_bit);
-hipError_t run_sort_tiles(hipStream_t s, void* temp, size_t temp_bytes, const uint64_t* keys_in, uint64_t* keys_out,
-                          const uint32_t* vals_in, uint32_t* vals_out, uint32_t m, int end_bit);
 
 }  // namespace gut

@@ -337,6 +337,57 @@ __device__ float tile_min_power(float tx, float ty, float c0, float c1, float c2
 constexpr int kSerialTiles = 12;
 constexpr int kShRow = 49;  // padded LDS row stride (dwords)
 
+// ---- per-tile binning of a workgroup's entries (K1's per-tile counts, k_expand_grouped's slots) ----
+// The workgroup's 256 Gaussians are Morton neighbours in the trainer's storage order, so their tile lists fall into a compact
+// window: the union of the tile boxes of its small footprints (<= kSerialTiles tiles).  Entries inside the window are counted
+// in LDS bins, one global atomic per non-empty bin; entries outside it (large footprints, scattered workgroups, windows of
+// more than kBinWindow tiles) take one global atomic each.
+constexpr int kBinWindow = 1536;   // LDS bins per workgroup (6 KB: K1 keeps five workgroups per CU)
+
+struct TileWindow {
+    int x0, y0, w, h;   // block-uniform; w == 0: no window
+};
+
+// Called by all threads of the workgroup (contains barriers).  Leaves bins[0, w * h) zero.
+__device__ TileWindow tile_window(const TileBox& bb, bool small, uint32_t* bins, int* red /* [16] */, uint32_t tid) {
+    constexpr int kNone = 0x7fffffff;
+    int a = small ? bb.x0 : kNone, b = small ? bb.y0 : kNone, c = small ? -bb.x1 : kNone, d = small ? -bb.y1 : kNone;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a = min(a, __shfl_xor(a, o));
+        b = min(b, __shfl_xor(b, o));
+        c = min(c, __shfl_xor(c, o));
+        d = min(d, __shfl_xor(d, o));
+    }
+    if ((tid & 63u) == 0u) {
+        red[4 * (tid >> 6) + 0] = a;
+        red[4 * (tid >> 6) + 1] = b;
+        red[4 * (tid >> 6) + 2] = c;
+        red[4 * (tid >> 6) + 3] = d;
+    }
+    __syncthreads();
+    a = __builtin_amdgcn_readfirstlane(min(min(red[0], red[4]), min(red[8], red[12])));
+    b = __builtin_amdgcn_readfirstlane(min(min(red[1], red[5]), min(red[9], red[13])));
+    c = __builtin_amdgcn_readfirstlane(min(min(red[2], red[6]), min(red[10], red[14])));
+    d = __builtin_amdgcn_readfirstlane(min(min(red[3], red[7]), min(red[11], red[15])));
+    TileWindow W = {0, 0, 0, 0};
+    if (a != kNone && (-c - a) * (-d - b) <= kBinWindow) W = TileWindow{a, b, -c - a, -d - b};
+    for (int k = (int)tid; k < W.w * W.h; k += kBlock) bins[k] = 0u;
+    __syncthreads();
+    return W;
+}
+
+__device__ __forceinline__ bool in_window(const TileWindow& W, int x, int y, uint32_t& bin) {
+    const uint32_t bx = (uint32_t)(x - W.x0), by = (uint32_t)(y - W.y0);
+    bin = by * (uint32_t)W.w + bx;
+    return bx < (uint32_t)W.w && by < (uint32_t)W.h;
+}
+
+__device__ __forceinline__ uint32_t window_tile(const TileWindow& W, int grid_x, uint32_t bin) {
+    const uint32_t by = bin / (uint32_t)W.w;
+    return (uint32_t)(W.y0 + (int)by) * (uint32_t)grid_x + (uint32_t)W.x0 + (bin - by * (uint32_t)W.w);
+}
+
 __device__ __forceinline__ float bcast(float v, int src_lane) { return __shfl(v, src_lane); }
 __device__ __forceinline__ int bcast(int v, int src_lane) { return __shfl(v, src_lane); }
 
@@ -355,6 +406,8 @@ __global__ __launch_bounds__(kBlock, 5) void k_project_on_tiles(ViewParams v, Re
                                                             float* __restrict__ visibility, uint32_t* __restrict__ wave_sums,
                                                             FrameClears clr) {
     __shared__ float sh_lds[(kBlock / 64) * 32 * kShRow];
+    __shared__ uint32_t s_bins[kBinWindow];
+    __shared__ int s_red[16];
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     const int lane = (int)(threadIdx.x & 63);
     const int wave = (int)(threadIdx.x >> 6);
@@ -468,13 +521,29 @@ __global__ __launch_bounds__(kBlock, 5) void k_project_on_tiles(ViewParams v, Re
         bb = tile_bbox(v.grid_x, v.grid_y, cx, cy, ex, ey);
         area = (bb.x1 - bb.x0) * (bb.y1 - bb.y0);
     }
+    // per-tile entry counts of the frame (clr.tile_entries, zero on entry; grouped binning of the lazy order, k_expand_grouped)
+    uint32_t* const tile_entries = clr.tile_entries;
+    TileWindow W = {0, 0, 0, 0};
+    if (tile_entries) W = tile_window(bb, area > 0 && area <= kSerialTiles, s_bins, s_red, threadIdx.x);
+    auto count_entry = [&](int x, int y) {
+        if (!tile_entries) return;
+        uint32_t bin;
+        if (in_window(W, x, y, bin)) atomicAdd(&s_bins[bin], 1u);
+        else atomicAdd(&tile_entries[(uint32_t)y * (uint32_t)v.grid_x + (uint32_t)x], 1u);
+    };
     if (!c.tile_culling) {
         cnt = (uint32_t)area;
+        if (tile_entries)
+            for (int y = bb.y0; y < bb.y1; ++y)
+                for (int x = bb.x0; x < bb.x1; ++x) count_entry(x, y);
     } else {
         if (area > 0 && area <= kSerialTiles) {
             for (int y = bb.y0; y < bb.y1; ++y)
                 for (int x = bb.x0; x < bb.x1; ++x)
-                    if (tile_min_power((float)x, (float)y, con0, con1, con2, cx, cy) < max_power) cnt++;
+                    if (tile_min_power((float)x, (float)y, con0, con1, con2, cx, cy) < max_power) {
+                        cnt++;
+                        count_entry(x, y);
+                    }
         }
         unsigned long long todo = __ballot(area > kSerialTiles);
         while (todo) {
@@ -491,10 +560,18 @@ __global__ __launch_bounds__(kBlock, 5) void k_project_on_tiles(ViewParams v, Re
                     const int ty = t / jw;
                     const int tx = t - ty * jw;
                     pass = tile_min_power((float)(jx0 + tx), (float)(jy0 + ty), j0, j1, j2, jcx, jcy) < jmp;
+                    if (pass) count_entry(jx0 + tx, jy0 + ty);
                 }
                 total += (uint32_t)__popcll(__ballot(pass));
             }
             if (lane == j) cnt = total;
+        }
+    }
+    if (tile_entries) {   // block-uniform
+        __syncthreads();
+        for (int k = (int)threadIdx.x; k < W.w * W.h; k += kBlock) {
+            const uint32_t b = s_bins[k];
+            if (b) atomicAdd(&tile_entries[window_tile(W, v.grid_x, (uint32_t)k)], b);
         }
     }
 
@@ -641,75 +718,86 @@ __global__ __launch_bounds__(kBlock, 5) void k_project_on_tiles(ViewParams v, Re
 // K2, second level: exclusive scan of the per-256-row-block sums (one uint4 of wave sums per block) by ONE workgroup — 23 k values at
 // 6 M Gaussians, three iterations of 8192 through LDS — and the frame's intersection count.  block_prefix[b] = list entries of all Gaussians before
 // block b; *total = M.
+// tile_entries (or null): K1's per-tile entry counts, scanned the same way into tile_start[t] = first list slot of tile t (tile_start[tiles]
+// = M) and tile_cursor[t] = the same (k_expand_grouped's running slot); the counts are left zero for the next frame's K1.
 // host_out (pinned host memory, may be null): [0] = M, [2], [3] = walk_sums of the last frame that had a backward — what the host reads
 // once it has queued the rest of the frame; written from here instead of by two stream-ordered 4- and 8-byte copies (~12 us each).
 __global__ __launch_bounds__(1024) void k_scan_wave_sums(const uint4* __restrict__ wave_sums4, uint32_t nblocks,
                                                          uint32_t* __restrict__ block_prefix, uint32_t* __restrict__ total,
-                                                         uint32_t* __restrict__ host_out, const uint32_t* __restrict__ walk_sums) {
+                                                         uint32_t* __restrict__ host_out, const uint32_t* __restrict__ walk_sums,
+                                                         uint32_t* __restrict__ tile_entries, uint32_t tiles,
+                                                         uint32_t* __restrict__ tile_start, uint32_t* __restrict__ tile_cursor) {
     constexpr uint32_t kPer = 8;                 // block sums per thread and iteration
     constexpr uint32_t kChunk = 1024u * kPer;    // 8192 blocks = 2.1 M Gaussians per iteration
     __shared__ uint32_t s_val[kChunk + kChunk / 32];   // (+1 word per 32: a thread's eight consecutive words spread over the banks)
     __shared__ uint32_t s_wave[16];
     __shared__ uint32_t s_carry;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (tid == 0) s_carry = 0u;
-    __syncthreads();
     auto slot = [](uint32_t e) { return e + (e >> 5); };
-    for (uint32_t base = 0; base < nblocks; base += kChunk) {
-        // coalesced 16-byte loads (consecutive lanes, consecutive blocks): the first version gave every lane 24 consecutive uint4 —
-        // 64 different cache lines per load instruction, 25 k line requests through one CU's L1, and took 28 us
+    // exclusive scan of load(0 .. count) into store(e, prefix); returns the sum
+    auto scan = [&](uint32_t count, auto load, auto store) -> uint32_t {
+        if (tid == 0) s_carry = 0u;
+        __syncthreads();
+        for (uint32_t base = 0; base < count; base += kChunk) {
+            // coalesced loads (consecutive lanes, consecutive elements): the first version gave every lane 24 consecutive uint4 —
+            // 64 different cache lines per load instruction, 25 k line requests through one CU's L1, and took 28 us
 #pragma unroll
-        for (uint32_t k = 0; k < kPer; ++k) {
-            const uint32_t e = k * 1024u + tid, b = base + e;
-            uint32_t v = 0;
-            if (b < nblocks) {
-                const uint4 w = wave_sums4[b];
-                v = w.x + w.y + w.z + w.w;
+            for (uint32_t k = 0; k < kPer; ++k) {
+                const uint32_t e = k * 1024u + tid, b = base + e;
+                s_val[slot(e)] = b < count ? load(b) : 0u;
             }
-            s_val[slot(e)] = v;
-        }
-        __syncthreads();
-        uint32_t local[kPer];
-        uint32_t sum = 0;
+            __syncthreads();
+            uint32_t local[kPer];
+            uint32_t sum = 0;
 #pragma unroll
-        for (uint32_t k = 0; k < kPer; ++k) {   // this thread's eight consecutive blocks
-            local[k] = sum;
-            sum += s_val[slot(tid * kPer + k)];
-        }
-        uint32_t incl = sum;   // inclusive scan over the wave
+            for (uint32_t k = 0; k < kPer; ++k) {   // this thread's eight consecutive blocks
+                local[k] = sum;
+                sum += s_val[slot(tid * kPer + k)];
+            }
+            uint32_t incl = sum;   // inclusive scan over the wave
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-            if ((int)lane >= o) incl += up;
-        }
-        if (lane == 63u) s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t wave_excl = 0, iter_total = 0;
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
+                if ((int)lane >= o) incl += up;
+            }
+            if (lane == 63u) s_wave[wave] = incl;
+            __syncthreads();
+            uint32_t wave_excl = 0, iter_total = 0;
 #pragma unroll
-        for (uint32_t w = 0; w < 16; ++w) {
-            const uint32_t t = s_wave[w];
-            if (w < wave) wave_excl += t;
-            iter_total += t;
-        }
-        const uint32_t excl = s_carry + wave_excl + (incl - sum);
+            for (uint32_t w = 0; w < 16; ++w) {
+                const uint32_t t = s_wave[w];
+                if (w < wave) wave_excl += t;
+                iter_total += t;
+            }
+            const uint32_t excl = s_carry + wave_excl + (incl - sum);
 #pragma unroll
-        for (uint32_t k = 0; k < kPer; ++k) s_val[slot(tid * kPer + k)] = excl + local[k];
-        __syncthreads();
+            for (uint32_t k = 0; k < kPer; ++k) s_val[slot(tid * kPer + k)] = excl + local[k];
+            __syncthreads();
 #pragma unroll
-        for (uint32_t k = 0; k < kPer; ++k) {   // coalesced stores
-            const uint32_t e = k * 1024u + tid, b = base + e;
-            if (b < nblocks) block_prefix[b] = s_val[slot(e)];
+            for (uint32_t k = 0; k < kPer; ++k) {   // coalesced stores
+                const uint32_t e = k * 1024u + tid, b = base + e;
+                if (b < count) store(b, s_val[slot(e)]);
+            }
+            if (tid == 0) s_carry += iter_total;
+            __syncthreads();
         }
-        if (tid == 0) s_carry += iter_total;
-        __syncthreads();
+        return s_carry;
+    };
+    const uint32_t m = scan(nblocks, [&](uint32_t b) { const uint4 w = wave_sums4[b]; return w.x + w.y + w.z + w.w; },
+                            [&](uint32_t b, uint32_t x) { block_prefix[b] = x; });
+    if (tile_entries) {
+        __syncthreads();   // (every thread has read s_carry)
+        scan(tiles, [&](uint32_t t) { const uint32_t x = tile_entries[t]; tile_entries[t] = 0u; return x; },
+             [&](uint32_t t, uint32_t x) { tile_start[t] = x; tile_cursor[t] = x; });
+        if (tid == 0) tile_start[tiles] = m;
     }
     if (tid == 0) {
-        *total = s_carry;
+        *total = m;
         if (host_out) {
             // system-scope stores into coherent host memory: they bypass the caches, and the end of the kernel orders them before the
             // event the host waits on.  (NOT __threadfence_system(): on gfx950 that writes back the whole L2 — dirty from K1 — and made
             // this kernel 28 us long.)
-            __hip_atomic_store(&host_out[0], s_carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&host_out[0], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             if (walk_sums) {
                 __hip_atomic_store(&host_out[2], walk_sums[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 __hip_atomic_store(&host_out[3], walk_sums[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -838,6 +926,99 @@ __global__ __launch_bounds__(kBlock) void k_expand_tiles(ViewParams v, RenderCon
             keys[off] = ((uint64_t)kInvalid << 32) | f2u(3.4028235e+38f);
             ids[off] = kInvalid;
         }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Grouped expansion (lazy per-tile depth order): K3's enumeration, but every entry goes straight into its tile's slice of the
+// list, as one {depth bits, particle id} word — no sort, no K5.  k_scan_wave_sums turned K1's per-tile counts into the slices
+// (tile_start) and their running slots (tile_cursor).  Two passes over the workgroup's entries: the first counts them in the LDS
+// bins of its tile window; then one returning global atomic per non-empty bin reserves the workgroup's run of slots in that
+// tile; the second pass takes a slot per entry from its bin (LDS) — or, outside the window, straight from the tile's cursor.
+// The order inside a slice is therefore arbitrary; K6's selection orders by (depth, id).  No workgroup waits for another.
+// Slots >= capacity are dropped (the host redoes the binning with the real count); ranges are the slices, clamped to it.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_expand_grouped(ViewParams v, RenderConsts c, uint32_t n,
+                                                          const float2* __restrict__ proj_pos,
+                                                          const float4* __restrict__ conic_opacity,
+                                                          const float2* __restrict__ extent, const float* __restrict__ depth,
+                                                          uint32_t tiles, const uint32_t* __restrict__ tile_start,
+                                                          uint32_t* __restrict__ tile_cursor, uint2* __restrict__ ranges,
+                                                          uint2* __restrict__ entries, uint32_t capacity) {
+    __shared__ uint32_t s_bins[kBinWindow];
+    __shared__ int s_red[16];
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const int lane = (int)(threadIdx.x & 63);
+    for (uint32_t t = i; t < tiles; t += gridDim.x * kBlock) {
+        const uint32_t b = tile_start[t], e = tile_start[t + 1];
+        ranges[t] = b == e ? make_uint2(0u, 0u) : make_uint2(min(b, capacity), min(e, capacity));
+    }
+    bool active = false;
+    float2 e = make_float2(0.f, 0.f), p = make_float2(0.f, 0.f);
+    float4 con = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint32_t dkey = 0;
+    float max_power = 0.f;
+    TileBox bb = {0, 0, 0, 0};
+    int area = 0;
+    if (i < n) {
+        e = extent[i];
+        active = !(e.x <= 1e-06f);
+    }
+    if (active) {
+        dkey = f2u(depth[i]);
+        p = proj_pos[i];
+        bb = tile_bbox(v.grid_x, v.grid_y, p.x, p.y, e.x, e.y);
+        area = (bb.x1 - bb.x0) * (bb.y1 - bb.y0);
+        con = conic_opacity[i];
+        if (c.tile_culling) max_power = det_logf(con.w / c.alpha_threshold);
+    }
+    const TileWindow W = tile_window(bb, active && area > 0 && area <= kSerialTiles, s_bins, s_red, threadIdx.x);
+    // every entry of the workgroup, as K3 enumerates them: emit(tile x, tile y, particle id, depth bits)
+    auto enumerate = [&](auto emit) {
+        if (!c.tile_culling) {
+            if (active)
+                for (int y = bb.y0; y < bb.y1; ++y)
+                    for (int x = bb.x0; x < bb.x1; ++x) emit(x, y, i, dkey);
+            return;
+        }
+        if (active && area <= kSerialTiles)
+            for (int y = bb.y0; y < bb.y1; ++y)
+                for (int x = bb.x0; x < bb.x1; ++x)
+                    if (tile_min_power((float)x, (float)y, con.x, con.y, con.z, p.x, p.y) < max_power) emit(x, y, i, dkey);
+        unsigned long long todo = __ballot(active && area > kSerialTiles);
+        while (todo) {
+            const int j = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int jx0 = bcast(bb.x0, j), jy0 = bcast(bb.y0, j), jw = bcast(bb.x1 - bb.x0, j), jarea = bcast(area, j);
+            const float j0 = bcast(con.x, j), j1 = bcast(con.y, j), j2 = bcast(con.z, j), jcx = bcast(p.x, j), jcy = bcast(p.y, j),
+                        jmp = bcast(max_power, j);
+            const uint32_t jdkey = (uint32_t)bcast((int)dkey, j);
+            const uint32_t jid = blockIdx.x * kBlock + (threadIdx.x & ~63u) + (uint32_t)j;
+            for (int base = 0; base < jarea; base += 64) {
+                const int t = base + lane;
+                if (t < jarea) {
+                    const int ty = t / jw;
+                    const int tx = t - ty * jw;
+                    if (tile_min_power((float)(jx0 + tx), (float)(jy0 + ty), j0, j1, j2, jcx, jcy) < jmp) emit(jx0 + tx, jy0 + ty, jid, jdkey);
+                }
+            }
+        }
+    };
+    enumerate([&](int x, int y, uint32_t, uint32_t) {
+        uint32_t bin;
+        if (in_window(W, x, y, bin)) atomicAdd(&s_bins[bin], 1u);
+    });
+    __syncthreads();
+    for (int k = (int)threadIdx.x; k < W.w * W.h; k += kBlock) {
+        const uint32_t cnt = s_bins[k];
+        if (cnt) s_bins[k] = atomicAdd(&tile_cursor[window_tile(W, v.grid_x, (uint32_t)k)], cnt);
+    }
+    __syncthreads();
+    enumerate([&](int x, int y, uint32_t id, uint32_t dk) {
+        uint32_t bin;
+        const uint32_t slot = in_window(W, x, y, bin) ? atomicAdd(&s_bins[bin], 1u)
+                                                      : atomicAdd(&tile_cursor[(uint32_t)y * (uint32_t)v.grid_x + (uint32_t)x], 1u);
+        if (slot < capacity) entries[slot] = make_uint2(dk, id);
+    });
 }
 
 // Padding behind the last real entry: the sort runs over `sort_n` >= M entries (sized on the host before M is known), the tail
@@ -1128,10 +1309,20 @@ void launch_project(hipStream_t s, const ViewParams& v, const RenderConsts& c, u
 }
 
 void launch_scan_wave_sums(hipStream_t s, uint32_t n, const uint32_t* wave_sums, uint32_t* block_prefix, uint32_t* total,
-                           uint32_t* host_out, const uint32_t* walk_sums) {
+                           uint32_t* host_out, const uint32_t* walk_sums, uint32_t* tile_entries, uint32_t tiles, uint32_t* tile_start,
+                           uint32_t* tile_cursor) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_scan_wave_sums, dim3(1), dim3(1024), 0, s, reinterpret_cast<const uint4*>(wave_sums), blocks_for(n), block_prefix,
-                       total, host_out, walk_sums);
+                       total, host_out, walk_sums, tile_entries, tiles, tile_start, tile_cursor);
+}
+
+void launch_expand_grouped(hipStream_t s, const ViewParams& v, const RenderConsts& c, uint32_t n, const float* proj_pos,
+                           const float* conic_opacity, const float* extent, const float* depth, uint32_t tiles,
+                           const uint32_t* tile_start, uint32_t* tile_cursor, uint32_t* ranges, uint64_t* entries, uint32_t capacity) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_expand_grouped, dim3(blocks_for(n)), dim3(kBlock), 0, s, v, c, n, reinterpret_cast<const float2*>(proj_pos),
+                       reinterpret_cast<const float4*>(conic_opacity), reinterpret_cast<const float2*>(extent), depth, tiles, tile_start,
+                       tile_cursor, reinterpret_cast<uint2*>(ranges), reinterpret_cast<uint2*>(entries), capacity);
 }
 
 void launch_expand(hipStream_t s, const ViewParams& v, const RenderConsts& c, uint32_t n, const uint32_t* tiles_count,

@@ -118,8 +118,8 @@ __device__ __forceinline__ float wave_sum_lane63(float v) {
 // K6 forward
 // ---------------------------------------------------------------------------------------------------
 // (5 waves per SIMD: at the 103 VGPRs the compiler takes otherwise the kernel runs 7 % slower, at 6 it spills)
-// kLazy: sorted_ids / tile_keys are only grouped by tile; the kernel orders each chunk itself (lazy_select) and records the
-// ids it consumed in ordered_ids for the backward.
+// kLazy: tile_keys ({depth bits, particle id} words, sorted_ids unused) are only grouped by tile; the kernel orders each chunk
+// itself (lazy_select) and records the ids it consumed in ordered_ids for the backward.
 // kGeneral: render.particle_kernel_degree != 2 — the response comes from kernel_response(kernel_degree, .) (gut_render_common.h).
 template <bool kLazy, bool kGeneral = false>
 __global__ __launch_bounds__(kBlock, 5) void k_render(ViewParams v, RenderConsts c, const float4* __restrict__ density12,
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(kBlock, 5) void k_render(ViewParams v, RenderConsts
                 }
                 const uint32_t take = min((uint32_t)kBlock, batch_n - batch_used);
                 if (tid < take) {
-                    id = sorted_ids[range.x + (uint32_t)s_lazy.sel[batch_used + tid]];
+                    id = (uint32_t)s_lazy.sel[batch_used + tid];
                     ordered_ids[k] = id;
                 }
                 batch_used += take;

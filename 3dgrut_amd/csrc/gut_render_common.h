@@ -252,31 +252,34 @@ __device__ __forceinline__ uint32_t strip_mask(const StripPlanes& sp, const View
 
 // ---- lazy per-tile depth order ------------------------------------------------------------------------
 // Whole-tile termination leaves most of a tile's list untouched (bench frame: 1.28 M of 9.36 M entries are ever staged),
-// so the global sort only groups the (tile | depth, id) pairs by TILE (the two high radix passes; stable, so every tile's
-// entries stay in particle-id order) and the forward compositor orders each tile on demand: before it stages a chunk it
-// selects the next <= 512 entries in (depth bits, list position) order — list position == particle-id order, i.e. exactly
-// the order the full stable sort on (tile | depth) produces — writes their ids to the ordered-id list (the backward and
-// the tests read that) and stages them.  Selection = up to 4 x 8-bit radix select on the depth bits among the entries behind
-// the last one taken, one gather pass, one 512-element bitonic sort in LDS (lazy_select below).
+// so binning only groups the entries by TILE (k_expand_grouped: one {depth bits, particle id} word each, in no particular
+// order inside a tile's slice) and the forward compositor orders each tile on demand: before it stages a chunk it selects
+// the next <= 512 entries in (depth bits, particle id) order — exactly the order the full stable sort on (tile | depth) of
+// the particle-ordered list produces —, writes their ids to the ordered-id list (the backward and the tests read that) and
+// stages them.  Selection = up to 4 x 8-bit radix select on the depth bits among the entries behind the last one taken,
+// one gather pass, one 512-element bitonic sort in LDS (lazy_select below).
 constexpr uint32_t kLazyBatch = 512;  // entries ordered per selection: two 256-entry chunks (power of two for the bitonic sort)
 
 struct LazyOrder {
     uint32_t hist[256];
-    unsigned long long sel[kLazyBatch];  // (depth bits << 32) | list position: one 64-bit compare orders two entries
-    uint32_t wave_cnt[2][4][4];  // [less | equal][unrolled position][wave]
+    unsigned long long sel[kLazyBatch];  // (depth bits << 32) | particle id: one 64-bit compare orders two entries
     uint32_t bin, need, bin_count;
-    uint32_t cnt_lt, cnt_eq;  // slots handed out by the unordered gather
+    uint32_t cnt_lt, cnt_eq;  // slots handed out by the gather
 };
 
-// keys: the tile's slice of the tile-grouped (tile << 32 | depth bits) keys; total = its length; want = min(kLazyBatch,
-// entries not yet taken); (have_lo, lo) = the last entry taken so far, in sel[]'s form.  Called by all 256 threads (contains
-// barriers).  On return sel[t], t < want, hold the next `want` entries in final order.
+// keys: the tile's slice of {depth bits, particle id} words; total = its length; want = min(kLazyBatch, entries not yet
+// taken); (have_lo, lo) = the last entry taken so far, in sel[]'s form.  Called by all 256 threads (contains barriers).  On
+// return sel[t], t < want, hold the next `want` entries in final order; their low words are the particle ids.
 // The tile's depths (the first kLazyCache of them) are copied ONCE per selection into LDS the compositing loop is not using at
 // that moment (kcache = its staging area: the previous chunk has been walked, the next is not staged yet) and the four digit
 // passes and the gather read them from there: one round of L2 / HBM latency per selection instead of five.  Only lists longer
 // than the cache stream their remainder from memory in every pass, four 256-entry rows at a time with the four loads issued
 // back to back.  Histogram increments are aggregated per wave on the digit of the wave's first counting lane (the high digits
 // of a tile's depths are nearly all equal: one LDS atomic instead of 64 serialised ones).
+// The id word is read only where the depth bits alone cannot decide: entries at exactly lo's depth (decided once, in the
+// copy to the cache: the cached word of a tie that is not behind lo becomes lo's depth - 1), entries at exactly the selected
+// depth when more than 64 of them remain (an id radix select, rare: GS clones share their parent's depth), and the <= 512
+// entries the gather takes (one load each, which replaces the id lookup the compositor made before).
 // (Not inlined: inlined, its register needs made the compiler spill the compositing loop's state, 2.4x slower; keeping 8 or 12
 // rows of depths in REGISTERS across the passes instead of in LDS does the same to the caller even when not inlined — the
 // values the loop keeps live across the call no longer fit beside the callee's: 9 scratch accesses inside the per-entry loop.)
@@ -285,20 +288,28 @@ constexpr uint32_t kLazyCache = 4096;  // depth words: 16 KB = sizeof(PackEntry)
 __device__ __noinline__ void lazy_select(LazyOrder& S, uint32_t* __restrict__ kcache, const uint2* __restrict__ keys, uint32_t total,
                                          uint32_t want, bool have_lo, unsigned long long lo, uint32_t tid) {
     const uint32_t lane = tid & 63u, wave = tid >> 6;
-    auto behind_lo = [&](uint32_t d, uint32_t p) { return !have_lo || (((unsigned long long)d << 32) | p) > lo; };
+    const uint32_t lo_d = (uint32_t)(lo >> 32), lo_id = (uint32_t)lo;
+    const uint32_t cached = min(total, kLazyCache);
+    const bool fold = have_lo && lo_d != 0u;  // cached ties with lo that are not behind it are cached as lo_d - 1
+    // entry p (depth word d as read from the cache or the list) comes after lo in (depth, id) order
+    auto behind_lo = [&](uint32_t d, uint32_t p) -> bool {
+        bool b = !have_lo || d > lo_d;
+        if (have_lo && d == lo_d) b = (fold && p < cached) || keys[p].y > lo_id;
+        return b;
+    };
     // (the ballot of a condition as it stands in the condition register: __ballot() materialises an int per lane first)
     auto ballot = [](bool b) -> unsigned long long { return __builtin_amdgcn_ballot_w64(b); };
     auto lanes_below = [](unsigned long long b) -> uint32_t {
         return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
     };
-    const uint32_t cached = min(total, kLazyCache);
     for (uint32_t base = 0; base < cached; base += 8 * kBlock) {
-        uint32_t d[8];
+        uint2 kv[8];
 #pragma unroll
-        for (uint32_t u = 0; u < 8; ++u) d[u] = (base + u * kBlock + tid) < cached ? keys[base + u * kBlock + tid].x : 0u;
+        for (uint32_t u = 0; u < 8; ++u) kv[u] = (base + u * kBlock + tid) < cached ? keys[base + u * kBlock + tid] : make_uint2(0u, 0u);
 #pragma unroll
         for (uint32_t u = 0; u < 8; ++u)
-            if ((base + u * kBlock + tid) < cached) kcache[base + u * kBlock + tid] = d[u];
+            if ((base + u * kBlock + tid) < cached)
+                kcache[base + u * kBlock + tid] = (fold && kv[u].x == lo_d && kv[u].y <= lo_id) ? lo_d - 1u : kv[u].x;
     }
     // four consecutive 256-entry rows of depths starting at the block-uniform `base` (a multiple of 4 * kBlock, so a group is
     // cached as a whole or not at all)
@@ -311,36 +322,10 @@ __device__ __noinline__ void lazy_select(LazyOrder& S, uint32_t* __restrict__ kc
             for (uint32_t u = 0; u < 4; ++u) d[u] = (base + u * kBlock + tid) < total ? keys[base + u * kBlock + tid].x : 0u;
         }
     };
-    // 1. depth of the want-th smallest remaining entry, digit by digit
-    // The passes stop as soon as the bin that holds the want-th entry has at most 64 members (normally after the second: 16
-    // depth bits leave about a dozen): a single wave then ranks that bin's members exactly (step 2b) instead of two more
-    // passes over the whole list.
-    uint32_t prefix = 0, need = want, cmask = 0xFFFFFFFFu;  // cmask: the depth bits the passes have decided
-    bool short_bin = false;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        S.hist[tid] = 0u;
-        __syncthreads();  // (first pass: the cache is complete behind this barrier too)
-        const uint32_t hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
-        for (uint32_t base = 0; base < total; base += 4 * kBlock) {
-            uint32_t d[4];
-            fetch4(base, d);
-#pragma unroll
-            for (uint32_t u = 0; u < 4; ++u) {
-                const uint32_t p = base + u * kBlock + tid;
-                const bool ok = p < total && behind_lo(d[u], p) && ((d[u] & hi_mask) == (prefix & hi_mask));
-                const unsigned long long b_ok = ballot(ok);
-                if (b_ok == 0ull) continue;  // wave-uniform
-                const uint32_t digit = (d[u] >> shift) & 255u;
-                const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane(__ffsll((long long)b_ok) - 1);
-                const uint32_t lead = (uint32_t)__builtin_amdgcn_readlane((int)digit, (int)first);
-                const bool same = ok && digit == lead;
-                const unsigned long long b_same = ballot(same);
-                if (lane == first) atomicAdd(&S.hist[lead], (uint32_t)__popcll(b_same));
-                if (ok && !same) atomicAdd(&S.hist[digit], 1u);
-            }
-        }
-        __syncthreads();
-        if (wave == 0) {  // first bin at which the running count reaches `need`
+    // wave 0: the first histogram bin at which the running count reaches `need` -> S.bin, S.need (what is left to take inside
+    // it), S.bin_count
+    auto find_bin = [&](uint32_t need) {
+        if (wave == 0) {
             const uint32_t h0 = S.hist[4 * lane], h1 = S.hist[4 * lane + 1], h2 = S.hist[4 * lane + 2], h3 = S.hist[4 * lane + 3];
             const uint32_t mine = h0 + h1 + h2 + h3;
             uint32_t incl = mine;
@@ -361,95 +346,121 @@ __device__ __noinline__ void lazy_select(LazyOrder& S, uint32_t* __restrict__ kc
             }
         }
         __syncthreads();
-        prefix |= S.bin << shift;
-        need = S.need;
-        if (shift > 0 && S.bin_count <= 64u) {  // block-uniform
-            short_bin = true;
-            cmask = 0xFFFFFFFFu << shift;
-            break;
-        }
-    }
-    const uint32_t dstar = prefix;        // the decided depth bits of the want-th entry: `need` of the entries that share them are taken
-    const uint32_t n_less = want - need;  // entries below them: all taken
-    // the bin's members: straight into their slots in list order when the bin is one exact depth (only `need` of them fit), else
-    // into a side list (the histogram's storage, free now) that step 2b ranks
-    const uint32_t bin_count = S.bin_count;
-    unsigned long long* const eq_dst = short_bin ? reinterpret_cast<unsigned long long*>(S.hist) : S.sel + n_less;
-    const uint32_t eq_cap = short_bin ? bin_count : need;
-    // 2. gather.  Short bin: in any order — the sort orders the slots and step 2b ranks the bin's members —, a wave takes the
-    // slots of a row's entries with one returning LDS atomic.  Else ordered (list order = row, then wave, then lane): of the
-    // entries at the exact depth the first `need` of the list are the ones to take.
-    uint32_t got_lt = 0, got_eq = 0;
-    if (short_bin) {
+    };
+    // 1. depth of the want-th smallest remaining entry, digit by digit
+    // The passes stop as soon as the bin that holds the want-th entry has at most 64 members (normally after the second: 16
+    // depth bits leave about a dozen): a single wave then ranks that bin's members exactly (step 2b) instead of more passes
+    // over the whole list.
+    uint32_t prefix = 0, need = want, cmask = 0xFFFFFFFFu;  // cmask: the depth bits the passes have decided
+    bool short_bin = false;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        S.hist[tid] = 0u;
+        __syncthreads();  // (first pass: the cache is complete behind this barrier too)
+        const uint32_t hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
         for (uint32_t base = 0; base < total; base += 4 * kBlock) {
             uint32_t d[4];
             fetch4(base, d);
 #pragma unroll
             for (uint32_t u = 0; u < 4; ++u) {
                 const uint32_t p = base + u * kBlock + tid;
-                const bool cand = (p < total) && behind_lo(d[u], p);
-                const bool lt = cand && (d[u] & cmask) < dstar, eq = cand && (d[u] & cmask) == dstar;
-                const unsigned long long key = ((unsigned long long)d[u] << 32) | p;
-                const unsigned long long b_lt = ballot(lt), b_eq = ballot(eq);
-                if (b_lt != 0ull) {  // wave-uniform
-                    uint32_t off = 0;
-                    if (lane == 0) off = atomicAdd(&S.cnt_lt, (uint32_t)__popcll(b_lt));
-                    off = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
-                    if (lt) S.sel[off + lanes_below(b_lt)] = key;
-                }
-                if (b_eq != 0ull) {
-                    uint32_t off = 0;
-                    if (lane == 0) off = atomicAdd(&S.cnt_eq, (uint32_t)__popcll(b_eq));
-                    off = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
-                    if (eq) eq_dst[off + lanes_below(b_eq)] = key;
-                }
+                const bool ok = p < total && ((d[u] & hi_mask) == (prefix & hi_mask)) && behind_lo(d[u], p);
+                const unsigned long long b_ok = ballot(ok);
+                if (b_ok == 0ull) continue;  // wave-uniform
+                const uint32_t digit = (d[u] >> shift) & 255u;
+                const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane(__ffsll((long long)b_ok) - 1);
+                const uint32_t lead = (uint32_t)__builtin_amdgcn_readlane((int)digit, (int)first);
+                const bool same = ok && digit == lead;
+                const unsigned long long b_same = ballot(same);
+                if (lane == first) atomicAdd(&S.hist[lead], (uint32_t)__popcll(b_same));
+                if (ok && !same) atomicAdd(&S.hist[digit], 1u);
             }
         }
         __syncthreads();
-    } else
+        find_bin(need);
+        prefix |= S.bin << shift;
+        need = S.need;
+        if (S.bin_count <= 64u) {  // block-uniform
+            short_bin = true;
+            cmask = 0xFFFFFFFFu << shift;
+            break;
+        }
+    }
+    const uint32_t dstar = prefix;  // the decided depth bits of the want-th entry
+    // 1b. more than 64 remaining entries at exactly that depth: the same select on their ids (rare; ids are distinct inside a
+    // tile, so at the latest the last id digit leaves one member)
+    uint32_t istar = 0, imask = 0;
+    const bool by_id = !short_bin;
+    if (by_id) {
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            S.hist[tid] = 0u;
+            __syncthreads();
+            const uint32_t hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
+            for (uint32_t base = 0; base < total; base += 4 * kBlock) {
+                uint32_t d[4];
+                fetch4(base, d);
+#pragma unroll
+                for (uint32_t u = 0; u < 4; ++u) {
+                    const uint32_t p = base + u * kBlock + tid;
+                    if (p < total && d[u] == dstar && behind_lo(d[u], p)) {
+                        const uint32_t id = keys[p].y;
+                        if ((id & hi_mask) == (istar & hi_mask)) atomicAdd(&S.hist[(id >> shift) & 255u], 1u);
+                    }
+                }
+            }
+            __syncthreads();
+            find_bin(need);
+            istar |= S.bin << shift;
+            need = S.need;
+            if (S.bin_count <= 64u) {
+                imask = 0xFFFFFFFFu << shift;
+                break;
+            }
+        }
+    }
+    const uint32_t n_less = want - need;  // entries below the selected bin: all taken; `need` of the bin's members are taken
+    // 2. gather, in any order (the sort orders the slots, step 2b ranks the bin's members): a wave takes the slots of a row's
+    // entries with one returning LDS atomic.  The slots hold (depth << 32) | list position until the ids are read below.
+    const uint32_t bin_count = S.bin_count;
+    unsigned long long* const eq_dst = reinterpret_cast<unsigned long long*>(S.hist);  // the bin's members (histogram storage, free now)
     for (uint32_t base = 0; base < total; base += 4 * kBlock) {
-        if (got_lt == n_less && got_eq >= eq_cap) break;  // block-uniform
         uint32_t d[4];
-        unsigned long long b_lt[4], b_eq[4];
-        bool lt[4], eq[4];
         fetch4(base, d);
 #pragma unroll
         for (uint32_t u = 0; u < 4; ++u) {
             const uint32_t p = base + u * kBlock + tid;
             const bool cand = (p < total) && behind_lo(d[u], p);
-            lt[u] = cand && (d[u] & cmask) < dstar;
-            eq[u] = cand && (d[u] & cmask) == dstar;
-            b_lt[u] = ballot(lt[u]);
-            b_eq[u] = ballot(eq[u]);
-            if (lane == 0) {
-                S.wave_cnt[0][u][wave] = (uint32_t)__popcll(b_lt[u]);
-                S.wave_cnt[1][u][wave] = (uint32_t)__popcll(b_eq[u]);
+            bool lt = cand && (d[u] & cmask) < dstar, eq = cand && (d[u] & cmask) == dstar;
+            if (by_id && eq) {
+                const uint32_t id = keys[p].y & imask;
+                lt = id < istar;
+                eq = id == istar;
             }
-        }
-        __syncthreads();
-        uint32_t run_lt = got_lt, run_eq = got_eq;
-#pragma unroll
-        for (uint32_t u = 0; u < 4; ++u) {
-            uint32_t my_lt = run_lt, my_eq = run_eq;
-#pragma unroll
-            for (uint32_t w = 0; w < kBlock / 64; ++w) {
-                if (w < wave) { my_lt += S.wave_cnt[0][u][w]; my_eq += S.wave_cnt[1][u][w]; }
-                run_lt += S.wave_cnt[0][u][w];
-                run_eq += S.wave_cnt[1][u][w];
-            }
-            my_lt += lanes_below(b_lt[u]);
-            my_eq += lanes_below(b_eq[u]);
-            const uint32_t p = base + u * kBlock + tid;
             const unsigned long long key = ((unsigned long long)d[u] << 32) | p;
-            if (lt[u]) S.sel[my_lt] = key;
-            if (eq[u] && my_eq < eq_cap) eq_dst[my_eq] = key;
+            const unsigned long long b_lt = ballot(lt), b_eq = ballot(eq);
+            if (b_lt != 0ull) {  // wave-uniform
+                uint32_t off = 0;
+                if (lane == 0) off = atomicAdd(&S.cnt_lt, (uint32_t)__popcll(b_lt));
+                off = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
+                if (lt) S.sel[off + lanes_below(b_lt)] = key;
+            }
+            if (b_eq != 0ull) {
+                uint32_t off = 0;
+                if (lane == 0) off = atomicAdd(&S.cnt_eq, (uint32_t)__popcll(b_eq));
+                off = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
+                if (eq) eq_dst[off + lanes_below(b_eq)] = key;
+            }
         }
-        got_lt = run_lt;
-        got_eq = run_eq;
-        __syncthreads();
     }
-    // 2b. the `need` smallest of a short bin's members, each to the slot of its rank among them (keys are distinct)
-    if (short_bin && wave == 0) {
+    __syncthreads();
+    // list positions -> particle ids (n_less + bin_count <= 512 + 64 independent loads)
+    for (uint32_t t = tid; t < n_less + bin_count; t += kBlock) {
+        unsigned long long* slot = t < n_less ? &S.sel[t] : &eq_dst[t - n_less];
+        const unsigned long long k = *slot;
+        *slot = (k & 0xFFFFFFFF00000000ull) | keys[(uint32_t)k].y;
+    }
+    __syncthreads();
+    // 2b. the `need` smallest of the bin's members, each to the slot of its rank among them (keys are distinct)
+    if (wave == 0) {
         const unsigned long long key = lane < bin_count ? eq_dst[lane] : ~0ull;
         uint32_t rank = 0;
         for (uint32_t j = 0; j < bin_count; ++j) rank += eq_dst[j] < key ? 1u : 0u;  // (one broadcast LDS read per member)
@@ -458,7 +469,7 @@ __device__ __noinline__ void lazy_select(LazyOrder& S, uint32_t* __restrict__ kc
     for (uint32_t t = tid; t < kLazyBatch; t += kBlock)
         if (t >= want) S.sel[t] = ~0ull;
     __syncthreads();
-    // 3. bitonic sort of the kLazyBatch slots by (depth, position); every thread owns one compare-exchange per stage
+    // 3. bitonic sort of the kLazyBatch slots by (depth, id); every thread owns one compare-exchange per stage
     for (uint32_t k = 2; k <= kLazyBatch; k <<= 1)
         for (uint32_t j = k >> 1; j > 0; j >>= 1) {
             for (uint32_t t = tid; t < kLazyBatch / 2; t += kBlock) {
