@@ -10,7 +10,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GUT_HIP_LIB", os.path.join(HERE, "libgut_hip.so"))  # override: dev experiments only
 
-GUT_ABI_VERSION = 5   # include/gut_hip.h: bumped on every struct / array-length / signature change
+GUT_ABI_VERSION = 6   # include/gut_hip.h: bumped on every struct / array-length / signature change
 GUT_NUM_KERNEL_TIMERS = 11
 BWD_RAW_PARAMETER_GRADS = 1
 BWD_COMPACT_RADIANCE_GRADS = 2
@@ -71,6 +71,12 @@ class GutLazyMoments(C.Structure):
                 ("d_overrun", C.c_void_p)]
 
 
+class GutRegularisation(C.Structure):
+    """The MCMC regularisers (gut_hip.h): density_coeff = lambda_opacity / N, scale_coeff = lambda_scale / (3 N), d_partials
+    [ceil(N / 64), 2] floats for the loss value or None."""
+    _fields_ = [("density_coeff", C.c_float), ("scale_coeff", C.c_float), ("d_partials", C.c_void_p)]
+
+
 EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_trace_bwd", "gut_collect_times",
            "gut_get_stats", "gut_debug_buffer", "gut_debug_copy", "gut_kernel_times", "gut_kernel_times_mean", "gut_last_error", "gut_abi_version",
            "gut_ssim_workspace_bytes", "gut_ssim_forward", "gut_ssim_backward",
@@ -79,7 +85,9 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_sh_adam_step_ex", "gut_mark_walked_waves", "gut_adam_unwalked_waves", "gut_activate_pack", "gut_adam_step", "gut_sh_adam_step", "gut_mcmc_relocation",
            "gut_optimize_finish_without_gradient", "gut_scatter_gradient_records_dev", "gut_adam_unwalked_waves_ex", "gut_sync_moments", "gut_trace_fields", "gut_trace_bwd_fields", "gut_selective_adam",
            "gut_trace_model_fields", "gut_trace_bwd_model_fields", "gut_position_gradient_statistics",
-           "gut_set_position_gradient_statistics", "gut_mcmc_perturb", "gut_trace_raw_model_fields")
+           "gut_set_position_gradient_statistics", "gut_mcmc_perturb", "gut_trace_raw_model_fields", "gut_set_regularisation",
+           "gut_sh_adam_step_regularised", "gut_adam_unwalked_waves_regularised", "gut_sync_moments_ex", "gut_regularisation_gradient",
+           "gut_regularisation_loss")
 
 _lib = None
 
@@ -154,6 +162,13 @@ def load():
     lib.gut_mark_walked_waves.argtypes = [vp, vp, vp]
     lib.gut_adam_unwalked_waves.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, fptr, fptr, C.c_float, C.c_float, C.c_float, u32, vp]
     lib.gut_adam_unwalked_waves_ex.argtypes = lib.gut_adam_unwalked_waves.argtypes + [lazy_p]
+    reg_p = C.POINTER(GutRegularisation)
+    lib.gut_set_regularisation.argtypes = [vp, reg_p]
+    lib.gut_sh_adam_step_regularised.argtypes = lib.gut_sh_adam_step_ex.argtypes + [reg_p]
+    lib.gut_adam_unwalked_waves_regularised.argtypes = lib.gut_adam_unwalked_waves_ex.argtypes + [reg_p]
+    lib.gut_sync_moments_ex.argtypes = lib.gut_sync_moments.argtypes + [reg_p]
+    lib.gut_regularisation_gradient.argtypes = [vp, u32, vp, vp, reg_p]
+    lib.gut_regularisation_loss.argtypes = [vp, u32, vp, C.c_float, C.c_float, vp, vp, vp]
     lib.gut_compact_gradient_rows.argtypes = [vp, vp, vp, vp, u32, vp]
     lib.gut_scatter_gradient_records.argtypes = [vp, vp, u32, u32, vp, vp]
     lib.gut_scatter_gradient_records_dev.argtypes = [vp, vp, vp, u32, u32, vp, vp]

@@ -136,6 +136,7 @@ struct gut_context {
     DevBuf tiles_count, tiles_offset, proj_pos, conic_opacity, extent, depth, feat, grad16, scan_temp;
     float* stat_accum = nullptr;    // gut_set_position_gradient_statistics: consumed by the next gut_optimize_after_bwd
     int32_t* stat_denom = nullptr;
+    GutRegularisation reg{};        // gut_set_regularisation: consumed by the next optimiser step (both coefficients 0: none)
     DevBuf cam_pos;   // [3] floats: the sensor position of the cached forward (written by K1)
     DevBuf wave_sums, block_prefix, scan_total;   // two-level scan of the tile counts (K1 wave sums -> k_scan_wave_sums -> K3)
     bool timing_main_stream = true, timing_side_stream = true;   // GUT_OPT_KERNEL_TIMING_SET
@@ -177,6 +178,7 @@ struct gut_context {
         uint32_t step, block_begin, block_end;
         uint32_t extra_end;   // blocks < extra_end: waves with tiles the forward did not walk also go to the second launch
         GutLazyMoments lazy;  // lazy moment decay of this step (d_wave_step == NULL: off)
+        GutRegularisation reg;   // the regulariser of this step (gut_set_regularisation)
     } early_args{};
     bool marks_valid = false; // wave_walked holds the walked-wave marks of the cached forward for EVERY wave
     DevBuf wave_walked;       // one byte per 64-row wave (k_mark_walked_waves), valid when early_args.extra_end > 0
@@ -340,6 +342,7 @@ float drain_timers(std::deque<EventPair>& q) {
 
 static int launch_early_part2(gut_context* h, hipStream_t s);
 gut::LazyMoments gut_make_lazy(const GutLazyMoments* lazy, uint32_t step);   // gut_train.hip
+gut::Regularisation gut_make_reg(const GutRegularisation* reg);              // gut_train.hip
 
 extern "C" {
 
@@ -1067,6 +1070,9 @@ int gut_optimize_after_bwd(gut_handle h, void* stream_, int32_t num_active_featu
         return fail("gut_optimize_after_bwd: lazy moment decay must be the same as in gut_optimize_rows_without_gradient");
     if (launch_early_part2(h, s)) return 1;  // (normally queued by gut_trace_bwd_ex already)
     const gut::LazyMoments lz = gut_make_lazy(lazy, step);
+    // the regulariser of the step: the one the side stream's launches were given, if it began the step
+    const gut::Regularisation reg = gut_make_reg(h->early_ran ? &h->early_args.reg : &h->reg);
+    h->reg = GutRegularisation{};   // one optimiser step only
     // lazy moment decay: the waves that cannot receive a gradient are the same whichever kernel walks them — no tile, or no
     // Gaussian of the wave among the entries the forward walked (unsorted variant).  The marks exist already when the side
     // stream's second launch built them; otherwise (one-pass step) they are built here.
@@ -1084,7 +1090,7 @@ int gut_optimize_after_bwd(gut_handle h, void* stream_, int32_t num_active_featu
                                      (h->early_ran && h->early_args.extra_end) ? h->wave_walked.as<uint8_t>() : nullptr,
                                      h->early_args.block_begin, h->early_ran ? h->early_args.extra_end : 0u, lz,
                                      (lz.wave_step && h->marks_valid) ? h->wave_walked.as<uint8_t>() : nullptr,
-                                     h->stat_accum, h->stat_denom);
+                                     h->stat_accum, h->stat_denom, reg);
     h->stat_accum = nullptr;   // one optimiser call only (the caller may reallocate its buffers any time)
     h->stat_denom = nullptr;
     HIP_TRY(hipGetLastError());
@@ -1115,6 +1121,15 @@ int gut_set_position_gradient_statistics(gut_handle h, float* d_norm_accum, int3
     return 0;
 }
 
+int gut_set_regularisation(gut_handle h, const GutRegularisation* reg) {
+    if (!h) return fail("gut_set_regularisation: null handle");
+    if (reg && !(reg->density_coeff >= 0.0f && reg->scale_coeff >= 0.0f && reg->density_coeff < INFINITY && reg->scale_coeff < INFINITY))
+        return fail("gut_set_regularisation: coefficients must be finite and >= 0");
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->reg = reg ? *reg : GutRegularisation{};
+    return 0;
+}
+
 int gut_optimize_finish_without_gradient(gut_handle h, void* stream_) {
     if (!h) return fail("gut_optimize_finish_without_gradient: null handle");
     std::lock_guard<std::mutex> lock(h->mu);
@@ -1126,6 +1141,7 @@ int gut_optimize_finish_without_gradient(gut_handle h, void* stream_) {
     const gut_context::EarlyArgs ea = h->early_args;
     h->stat_accum = nullptr;   // (a step finished without its gradient has no statistics either)
     h->stat_denom = nullptr;
+    h->reg = GutRegularisation{};   // (the step's regulariser is ea.reg: it applies to every remaining row as well)
     // discard whatever the backward compositor may have accumulated: every remaining wave sees an exactly-zero gradient
     HIP_TRY(h->grad16.ensure(sizeof(float) * 16 * (size_t)h->n));
     HIP_TRY(hipMemsetAsync(h->grad16.p, 0, h->grad16.cap, s));
@@ -1134,7 +1150,8 @@ int gut_optimize_finish_without_gradient(gut_handle h, void* stream_) {
                                      h->grad16.as<float>(), h->tiles_count.as<uint32_t>(), h->feat.as<float>(), ea.raw12, ea.raw_m,
                                      ea.raw_v, ea.sh48, ea.sh_m, ea.sh_v, ea.lr12, ea.lr48, ea.beta1, ea.beta2, ea.eps, ea.step, nullptr,
                                      ea.act12, true, ea.extra_end ? h->wave_walked.as<uint8_t>() : nullptr, ea.block_begin, ea.extra_end,
-                                     gut_make_lazy(&ea.lazy, ea.step), h->marks_valid ? h->wave_walked.as<uint8_t>() : nullptr);
+                                     gut_make_lazy(&ea.lazy, ea.step), h->marks_valid ? h->wave_walked.as<uint8_t>() : nullptr,
+                                     nullptr, nullptr, gut_make_reg(&ea.reg));
     HIP_TRY(hipGetLastError());
     if (h->early_wait_pending) {
         HIP_TRY(hipStreamWaitEvent(s, h->ev_early_done, 0));
@@ -1234,11 +1251,15 @@ int gut_optimize_rows_without_gradient(gut_handle h, void* stream_, float* d_raw
     // share of the row blocks whose tile-less waves go to the first launch, beside the forward compositor: 60 % in the
     // 32-register form that launch has with lazy moments (about what it streams while K6 and the loss kernels run on the bench
     // frame: 50 / 75 / 100 % measured 2.30 / 2.29 / 2.40 ms per step), 25 % in the wide form (which takes K6's fifth wave)
-    const uint32_t percent = split_percent >= 0 ? (uint32_t)split_percent : ((lazy && lazy->d_wave_step) ? 60u : 25u);
+    // (a regulariser: the wide form in both launches, and the wide form's share — measured on the bench frame, regularised step,
+    //  median ms: first-launch share 10 / 25 / 45 / 60 % -> 2.48 / 2.46 / 2.53 / 2.66; the 32-register form with the regulariser,
+    //  which spills to scratch, at 25 / 60 % -> 2.44 / 2.59: no gain to pay for its scratch)
+    const gut::Regularisation reg = gut_make_reg(&h->reg);
+    const uint32_t percent = split_percent >= 0 ? (uint32_t)split_percent : ((lazy && lazy->d_wave_step && !reg.on()) ? 60u : 25u);
     const uint32_t first = (uint32_t)((uint64_t)nblocks * percent / 100u);
     gut::launch_adam_rows_without_gradient(h->side_stream, h->n, h->tiles_count.as<uint32_t>(), d_raw12, d_raw_m, d_raw_v, d_sh48,
                                            d_sh_m, d_sh_v, lr12, lr48, beta1, beta2, eps, step, d_act12_out, 0, first, nullptr, first, 0,
-                                           false, gut_make_lazy(lazy, step));
+                                           false, gut_make_lazy(lazy, step), reg);
     HIP_TRY(hipGetLastError());
     gut_context::EarlyArgs& ea = h->early_args;
     ea.raw12 = d_raw12; ea.raw_m = d_raw_m; ea.raw_v = d_raw_v; ea.sh48 = d_sh48; ea.sh_m = d_sh_m; ea.sh_v = d_sh_v;
@@ -1248,6 +1269,7 @@ int gut_optimize_rows_without_gradient(gut_handle h, void* stream_, float* d_raw
     ea.beta1 = beta1; ea.beta2 = beta2; ea.eps = eps; ea.step = step; ea.block_begin = first; ea.block_end = nblocks;
     ea.lazy = GutLazyMoments{};
     if (lazy) ea.lazy = *lazy;
+    ea.reg = h->reg;
     // unsorted variant with something to walk: the second launch also takes, in the first early_extra_percent of the blocks,
     // the waves with tiles in which the forward walked no Gaussian (see launch_early_part2)
     ea.extra_end = (h->cfg.k_buffer_size == 0 && h->m) ? (uint32_t)((uint64_t)nblocks * (uint32_t)h->early_extra_percent / 100u) : 0u;
@@ -1284,7 +1306,7 @@ static int launch_early_part2(gut_context* h, hipStream_t s) {
                                            ea.sh_m, ea.sh_v, ea.lr12, ea.lr48, ea.beta1, ea.beta2, ea.eps, ea.step, ea.act12,
                                            ea.extra_end ? 0u : ea.block_begin, ea.block_end,
                                            ea.extra_end ? h->wave_walked.as<uint8_t>() : nullptr, ea.block_begin, ea.extra_end, true,
-                                           gut_make_lazy(&ea.lazy, ea.step));
+                                           gut_make_lazy(&ea.lazy, ea.step), gut_make_reg(&ea.reg));
     HIP_TRY(hipGetLastError());
     const bool timing = h->cfg.enable_kernel_timings != 0 && h->timing_side_stream && h->kev[14] && h->kev[15];
     if (timing) {

@@ -86,6 +86,19 @@ struct LazyMoments {
     uint32_t* overrun = nullptr;   // GutLazyMoments.d_overrun
 };
 
+// The MCMC recipe's opacity / scale regularisers (GutRegularisation of the C ABI, configs/base_mcmc.yaml:13-18):
+//     dL/d(density logit) = density_coeff * sigmoid(d) (1 - sigmoid(d)),   dL/d(log-scale k) = scale_coeff * exp(s_k)
+// on the pre-update row, added to the row's photometric gradient (after any 1/world scaling) by whichever kernel updates the row.
+// With a regulariser no row is gradient-free in the [N,12] block: its moments are stored every step (eager), while the [N,48]
+// block keeps the lazy decay.  partials[w] = (sum of sigmoid(d), sum of exp(s_0) + exp(s_1) + exp(s_2)) over the rows of 64-row
+// wave w, written by the kernel that owns the wave (gut_regularisation_loss reduces them).
+struct Regularisation {
+    float density_coeff = 0.0f;   // lambda_opacity / N
+    float scale_coeff = 0.0f;     // lambda_scale / (3 N)
+    float2* partials = nullptr;   // [ceil(N / 64)] or null
+    __host__ __device__ bool on() const { return density_coeff != 0.0f || scale_coeff != 0.0f; }
+};
+
 // what K1 zeroes on its way (the frame's small clears): ranges [tiles] uint2, trav_bwd [tiles], wave_walked [4 * blocks] bytes (or null)
 struct FrameClears {
     uint2* ranges = nullptr;
@@ -183,7 +196,8 @@ void launch_sh_adam_from_scratch(hipStream_t s, uint32_t n, int sh_degree, const
                                  float eps, uint32_t step, const float* visibility, float* act12_out, bool rows_with_tiles_only,
                                  const uint8_t* wave_walked, uint32_t split_block, uint32_t extra_end,
                                  const LazyMoments& lazy, const uint8_t* rule_walked /* per-wave marks valid for EVERY wave, or null */,
-                                 float* stat_accum = nullptr, int32_t* stat_denom = nullptr /* gs.py:106-115 statistics, or null */);
+                                 float* stat_accum = nullptr, int32_t* stat_denom = nullptr /* gs.py:106-115 statistics, or null */,
+                                 const Regularisation& reg = Regularisation());
 // Adam step of the rows that get no gradient this iteration (tiles_count == 0), see k_adam_rows_without_gradient
 void launch_compact_gradient_rows(hipStream_t s, uint32_t n, const float* act12, const uint32_t* tiles_count, const float* feat,
                                   float* grad16, float* records, uint32_t capacity, uint32_t* count);
@@ -192,7 +206,7 @@ void launch_adam_rows_without_gradient(hipStream_t s, uint32_t n, const uint32_t
                                        float beta2, float eps, uint32_t step, float* act12_out,
                                        uint32_t block_begin, uint32_t block_end /* range of 256-row blocks */,
                                        const uint8_t* wave_walked, uint32_t split_block, uint32_t extra_end, bool second_launch,
-                                       const LazyMoments& lazy);
+                                       const LazyMoments& lazy, const Regularisation& reg = Regularisation());
 void launch_count_side_stream_rows(hipStream_t s, uint32_t n, const uint32_t* tiles_count, const uint8_t* wave_walked,
                                    uint32_t split_block, uint32_t extra_end, Counters* out);
 void launch_mark_waves_with_tiles(hipStream_t s, uint32_t n, const uint32_t* tiles_count, uint8_t* wave_flags);

@@ -6,6 +6,7 @@
 //                     torch.optim.Adam when bias correction is on and no mask is given)
 // Both are pure HBM streams: 16-byte accesses, one row (or one float4 of a row) per lane.
 #include <cstdlib>
+#include <type_traits>
 
 #include "gut_internal.h"
 
@@ -248,6 +249,10 @@ struct ShAdamParams {
     float* stat_accum;             // kScratch: the densification statistics of strategy/gs.py:106-115, or null
     int32_t* stat_denom;           //           (gut_set_position_gradient_statistics)
 };
+// the regularised kernel's argument (a type of its own: the unregularised kernel's arguments stay byte for byte what they were)
+struct ShAdamParamsReg : ShAdamParams {
+    Regularisation reg;
+};
 
 // strategy/gs.py:106-115 for one Gaussian with a non-zero position gradient of this view:
 //   accum += | grad * |position - sensor| | / 2,   denom += 1
@@ -371,12 +376,55 @@ __device__ __forceinline__ void adam4_lazy(const LazyAdam& la, const float4& lr,
 #undef GUT_ADAM_LANE
 }
 
+// ---- the MCMC regularisers (Regularisation, gut_internal.h) ----
+// Every kernel that updates a row forms the regulariser's gradient and its share of the loss value with these functions, from the
+// pre-update row it loads anyway: the one- and two-pass forms, lazy or eager, stay bit-identical.
+__device__ __forceinline__ float reg_sigmoid(float d) { return 1.0f / (1.0f + expf(-d)); }
+__device__ __forceinline__ float4 reg_density_grad(const Regularisation& r, float sig) {
+    return make_float4(0.0f, 0.0f, 0.0f, r.density_coeff * (sig * (1.0f - sig)));
+}
+__device__ __forceinline__ float4 reg_scale_grad(const Regularisation& r, float e0, float e1, float e2) {
+    return make_float4(r.scale_coeff * e0, r.scale_coeff * e1, r.scale_coeff * e2, 0.0f);
+}
+// (sum of sigmoid, sum of exp) over the wave's 64 lanes by a butterfly: both partners of every exchange add the same two values,
+// so every lane ends with the same bits, in the same order in every kernel.  Wave-uniform control flow only.
+__device__ __forceinline__ void reg_wave_partials(const Regularisation& r, float sig, float esum, uint32_t wave_index, uint32_t lane) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        sig += __shfl_xor(sig, o);
+        esum += __shfl_xor(esum, o);
+    }
+    if (r.partials && lane == 0) r.partials[wave_index] = make_float2(sig, esum);
+}
+// the eager raw [N,12] update of a regularised row that has no photometric gradient: moments current every step (no decay by
+// missed steps), stored; returns the row's partial-sum terms
+__device__ __forceinline__ void reg_adam_raw_row(const Regularisation& r, const AdamParams& a12, float4* __restrict__ p12,
+                                                 float4* __restrict__ m12, float4* __restrict__ v12, float4* __restrict__ act12, size_t i,
+                                                 float* sig_out, float* esum_out) {
+    float4 a = p12[3 * i + 0], m = m12[3 * i + 0], v = v12[3 * i + 0];
+    const float sig = reg_sigmoid(a.w);
+    adam4(a12, 0, reg_density_grad(r, sig), a, m, v);
+    p12[3 * i + 0] = a; m12[3 * i + 0] = m; v12[3 * i + 0] = v;
+    float4 b = p12[3 * i + 1];
+    m = m12[3 * i + 1]; v = v12[3 * i + 1];
+    adam4(a12, 4, make_float4(0.f, 0.f, 0.f, 0.f), b, m, v);
+    p12[3 * i + 1] = b; m12[3 * i + 1] = m; v12[3 * i + 1] = v;
+    float4 c = p12[3 * i + 2];
+    m = m12[3 * i + 2]; v = v12[3 * i + 2];
+    const float e0 = expf(c.x), e1 = expf(c.y), e2 = expf(c.z);
+    adam4(a12, 8, reg_scale_grad(r, e0, e1, e2), c, m, v);
+    p12[3 * i + 2] = c; m12[3 * i + 2] = m; v12[3 * i + 2] = v;
+    if (act12) activate_row(a, b, c, act12 + 3 * i);
+    *sig_out = sig;
+    *esum_out = (e0 + e1) + e2;
+}
+
 // kScratch = true (one view, no exchange): the per-Gaussian epilogue of the backward (K8c) is folded in — grad12 then points
 // at the renderer's 64-byte gradient rows [pos3, density, quat4, scale3, rgb3, pad2] w.r.t. the ACTIVATED parameters, which
 // are chained to the raw parameters here (the activations are recomputed from the raw row the optimiser loads anyway, with
 // the very function that produced the forward's inputs), and the masked dL/dRGB never leaves registers.
-template <bool kScratch>
-__global__ __launch_bounds__(kBlock) void k_sh_adam(ShAdamParams sp, float* __restrict__ mrgb,
+template <bool kScratch, bool kReg>   // kReg: the regularisers (sp.reg) — false: the unregularised kernel, unchanged
+__global__ __launch_bounds__(kBlock) void k_sh_adam(std::conditional_t<kReg, ShAdamParamsReg, ShAdamParams> sp, float* __restrict__ mrgb,
                                                    float4* __restrict__ grad12, float4* __restrict__ p12,
                                                    float4* __restrict__ m12, float4* __restrict__ v12, float4* __restrict__ p48,
                                                    float4* __restrict__ m48, float4* __restrict__ v48,
@@ -407,12 +455,28 @@ __global__ __launch_bounds__(kBlock) void k_sh_adam(ShAdamParams sp, float* __re
             lazy_wave = !has_tiles || (sp.rule_walked && sp.rule_walked[wave_index] == 0);
         }
     }
+    if constexpr (kReg) {
+        // this kernel owns the wave (the side-stream pass returned above): its loss partials, from the pre-update rows of ALL its
+        // rows, those SelectiveAdam leaves untouched included
+        float sig = 0.0f, esum = 0.0f;
+        if (i < sp.n) {
+            const float4 a = p12[3 * (size_t)i + 0], c = p12[3 * (size_t)i + 2];
+            sig = reg_sigmoid(a.w);
+            esum = (expf(c.x) + expf(c.y)) + expf(c.z);
+        }
+        if (wave_first < sp.n) reg_wave_partials(sp.reg, sig, esum, wave_index, lane);
+    }
     if (kScratch && lazy_wave) {
         // (wave-uniform) no row of this wave can receive a gradient — its gradient rows are exactly zero and are not even read —:
         // the arithmetic of the side-stream pass, value for value (adam4_lazy), so that the one-pass and two-pass forms agree bit
         // for bit; the stored moments stay those of wave_step[wave]
         const LazyAdam l12 = make_lazy_adam(sp.a12, dk), l48 = make_lazy_adam(sp.a48, dk);
-        if (i < sp.n) {
+        if constexpr (kReg) {   // regularised: the raw block is eager (the side-stream pass's reg_adam_raw_row)
+            if (i < sp.n) {
+                float sig, esum;
+                reg_adam_raw_row(sp.reg, sp.a12, p12, m12, v12, act12, i, &sig, &esum);
+            }
+        } else if (i < sp.n) {
             float4 a = p12[3 * (size_t)i + 0], b = p12[3 * (size_t)i + 1], c = p12[3 * (size_t)i + 2];
             adam4_lazy(l12, make_float4(sp.a12.lr[0], sp.a12.lr[1], sp.a12.lr[2], sp.a12.lr[3]), a, m12[3 * (size_t)i + 0], v12[3 * (size_t)i + 0]);
             adam4_lazy(l12, make_float4(sp.a12.lr[4], sp.a12.lr[5], sp.a12.lr[6], sp.a12.lr[7]), b, m12[3 * (size_t)i + 1], v12[3 * (size_t)i + 1]);
@@ -486,8 +550,16 @@ __global__ __launch_bounds__(kBlock) void k_sh_adam(ShAdamParams sp, float* __re
             g2.x *= gs; g2.y *= gs; g2.z *= gs; g2.w = 0.0f;
             float4 ma = m12[3 * (size_t)i + 0], mb = m12[3 * (size_t)i + 1], mc = m12[3 * (size_t)i + 2];
             float4 va = v12[3 * (size_t)i + 0], vb = v12[3 * (size_t)i + 1], vc = v12[3 * (size_t)i + 2];
-            scale4(ma, dk.x); scale4(mb, dk.x); scale4(mc, dk.x);
-            scale4(va, dk.y); scale4(vb, dk.y); scale4(vc, dk.y);
+            if constexpr (kReg) {
+                // the regulariser, once, after the 1/world scaling of the photometric part; the raw moments are current (eager)
+                const float4 rd = reg_density_grad(sp.reg, reg_sigmoid(a.w));
+                const float4 rs = reg_scale_grad(sp.reg, expf(c.x), expf(c.y), expf(c.z));
+                g0.w += rd.w;
+                g2.x += rs.x; g2.y += rs.y; g2.z += rs.z;
+            } else {
+                scale4(ma, dk.x); scale4(mb, dk.x); scale4(mc, dk.x);
+                scale4(va, dk.y); scale4(vb, dk.y); scale4(vc, dk.y);
+            }
             adam4(sp.a12, 0, g0, a, ma, va);
             adam4(sp.a12, 4, g1, b, mb, vb);
             adam4(sp.a12, 8, g2, c, mc, vc);
@@ -573,7 +645,10 @@ __global__ __launch_bounds__(kBlock) void k_sh_adam(ShAdamParams sp, float* __re
 // the pass is not latency-bound; two waves per SIMD at half the registers: same bytes, but scratch at the 64-VGPR bound;
 // skipping the stores of groups whose moments are all zero (fixed points of the update): the start of a training run 4 %
 // faster, its steady state 8 % slower (the test sits between the loads and their use).
-template <bool kLazy>   // kLazy: lazy moment decay (the moments are read, never stored) — uniform over the launch
+// kReg: the regularisers — every row of the wave gets them as its [N,12] gradient, the raw block's moments are stored every step
+// (reg_adam_raw_row), the [N,48] block is updated as without them (lazy or eager by kLazy); the wave's loss partials are written
+// (Reg...: one Regularisation when kReg, nothing otherwise — the unregularised kernel's arguments stay what they were)
+template <bool kLazy, bool kReg, typename... Reg>   // kLazy: lazy moment decay (the moments are read, never stored) — uniform over the launch
 __global__ __launch_bounds__(kBlock, 4) void k_adam_rows_without_gradient(AdamParams a12, AdamParams a48, uint32_t n,
                                                                           const uint32_t* __restrict__ tiles_count,
                                                                           float4* __restrict__ p12, float4* __restrict__ m12,
@@ -581,7 +656,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_adam_rows_without_gradient(AdamPa
                                                                           float4* __restrict__ m48, float4* __restrict__ v48,
                                                                           float4* __restrict__ act12, uint32_t block_begin,
                                                                           uint32_t block_end, EarlyOwnership own,
-                                                                          uint32_t second_launch, LazyMoments lazy) {
+                                                                          uint32_t second_launch, LazyMoments lazy, Reg... reg_arg) {
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     __builtin_amdgcn_s_setprio(1);  // its few instructions issue ahead of the VALU-saturated compositor next door (+1 % step rate)
@@ -611,6 +686,33 @@ __global__ __launch_bounds__(kBlock, 4) void k_adam_rows_without_gradient(AdamPa
         // (kLazy == false: left a run-time value — with `true` known at compile time the schedule needs 88 VGPRs instead of 69, and
         //  this kernel shares its SIMDs with the compositors' waves)
         const bool store_mv = kLazy ? false : (lazy.wave_step == nullptr);
+        if constexpr (kReg) {
+            const Regularisation reg = (reg_arg, ...);
+            float sig = 0.0f, esum = 0.0f;
+            if (mine) reg_adam_raw_row(reg, a12, p12, m12, v12, act12, i, &sig, &esum);
+            reg_wave_partials(reg, sig, esum, wave_first >> 6, lane);
+            float4* bp = p48 + (size_t)wave_first * 12;
+            float4* bm = m48 + (size_t)wave_first * 12;
+            float4* bv = v48 + (size_t)wave_first * 12;
+            const LazyAdam l48 = make_lazy_adam(a48, dk);
+#pragma unroll 4
+            for (int it = 0; it < 12; ++it) {
+                const uint32_t q = (uint32_t)it * 64u + lane;
+                if (q >= rows_here * 12u) continue;
+                const uint32_t row = q / 12u, col = (q - row * 12u) * 4u;
+                float4 pp = bp[q];
+                if (kLazy) {
+                    adam4_lazy(l48, s_lr48[col >> 2], pp, bm[q], bv[q]);
+                } else {
+                    float4 mm = bm[q], vv = bv[q];
+                    scale4(mm, dk.x); scale4(vv, dk.y);
+                    adam4_zero_grad(a48, s_lr48[col >> 2], pp, mm, vv);
+                    bm[q] = mm; bv[q] = vv;
+                }
+                bp[q] = pp;
+            }
+            continue;
+        }
         if (kLazy) {   // lazy moment decay: read p, m, v; write p and the activation row
             const LazyAdam l12 = make_lazy_adam(a12, dk), l48 = make_lazy_adam(a48, dk);
             if (mine) {
@@ -681,11 +783,20 @@ __global__ __launch_bounds__(kBlock, 4) void k_adam_rows_without_gradient(AdamPa
 // above takes the fifth.  One (p, m, v) group in flight per lane, wave-uniform bases with 32-bit lane offsets: latency-bound,
 // about a third of the streaming rate — still more rows than the wide form could be given under K6.  Same arithmetic, bit for
 // bit (adam4_lazy, the pieces of activate_row).  (amdgpu_num_vgpr counts each half of the unified file: 16 = 32 registers.)
+// kReg (Reg...: one Regularisation): the eager raw block of reg_adam_raw_row, one (p, m, v) group at a time, same arithmetic.
+// It does NOT fit: 32 VGPRs with 32 spilled and 100 bytes of scratch per lane (gfx950, -Rpass-analysis=kernel-resource-usage;
+// fencing the four columns of each adam4 apart: 38 spilled), where the side-stream kernels must use none.  So the product build
+// runs the regularised step's first launch in the wide form; GUT_NARROW_REGULARISED=1 builds this instance into a diagnostic
+// library (build.build_diagnostic, GUT_HIP_LIBRARY) to measure it against the wide form (the MCMC recipe's regularisers).
+#ifndef GUT_NARROW_REGULARISED
+#define GUT_NARROW_REGULARISED 0
+#endif
+template <bool kReg, typename... Reg>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_vgpr(16))) void k_adam_rows_without_gradient_narrow(
     AdamParams a12, AdamParams a48, uint32_t n, const uint32_t* __restrict__ tiles_count, float4* __restrict__ p12,
     float4* __restrict__ m12, float4* __restrict__ v12, float4* __restrict__ p48, float4* __restrict__ m48,
     float4* __restrict__ v48, float4* __restrict__ act12, uint32_t block_begin, uint32_t block_end, EarlyOwnership own,
-    uint32_t second_launch, LazyMoments lazy) {
+    uint32_t second_launch, LazyMoments lazy, Reg... reg_arg) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     __builtin_amdgcn_s_setprio(1);
@@ -701,7 +812,38 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_vgpr(16))) void k
         if (!side_stream_owns_wave(own, has_tiles, wave_first >> 6, blk, second_launch != 0u)) continue;
         const float2 dk = missed_decay(lazy, wave_first >> 6);
         const LazyAdam l12 = make_lazy_adam(a12, dk), l48 = make_lazy_adam(a48, dk);
-        if (lane < rows_here) {
+        if constexpr (kReg) {
+            const Regularisation reg = (reg_arg, ...);
+            float sig = 0.0f, esum = 0.0f;
+            if (lane < rows_here) {
+                float4* rp = p12 + 3 * (size_t)wave_first;
+                float4* rm = m12 + 3 * (size_t)wave_first;
+                float4* rv = v12 + 3 * (size_t)wave_first;
+                float4* ra = act12 + 3 * (size_t)wave_first;
+                uint32_t o = 3u * lane;
+                asm volatile("" : "+v"(o));
+                float4 x = rp[o], m = rm[o], v = rv[o];
+                sig = reg_sigmoid(x.w);
+                adam4(a12, 0, reg_density_grad(reg, sig), x, m, v);
+                rp[o] = x; rm[o] = m; rv[o] = v;
+                if (act12) ra[o] = activate_position_density(x);
+                __builtin_amdgcn_sched_barrier(0);
+                x = rp[o + 1]; m = rm[o + 1]; v = rv[o + 1];
+                adam4(a12, 4, make_float4(0.f, 0.f, 0.f, 0.f), x, m, v);
+                rp[o + 1] = x; rm[o + 1] = m; rv[o + 1] = v;
+                float nrm = 0.0f;
+                if (act12) ra[o + 1] = activate_quaternion(x, &nrm);
+                __builtin_amdgcn_sched_barrier(0);
+                x = rp[o + 2]; m = rm[o + 2]; v = rv[o + 2];
+                const float e0 = expf(x.x), e1 = expf(x.y), e2 = expf(x.z);
+                adam4(a12, 8, reg_scale_grad(reg, e0, e1, e2), x, m, v);
+                esum = (e0 + e1) + e2;
+                rp[o + 2] = x; rm[o + 2] = m; rv[o + 2] = v;
+                if (act12) ra[o + 2] = activate_scale(x, nrm);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            reg_wave_partials(reg, sig, esum, wave_first >> 6, lane);
+        } else if (lane < rows_here) {
             float4* rp = p12 + 3 * (size_t)wave_first;
             const float4* rm = m12 + 3 * (size_t)wave_first;
             const float4* rv = v12 + 3 * (size_t)wave_first;
@@ -848,9 +990,10 @@ void launch_sh_adam_from_scratch(hipStream_t s, uint32_t n, int sh_degree, const
                                  float* sh48, float* sh_m, float* sh_v, const float* lr12, const float* lr48, float beta1, float beta2,
                                  float eps, uint32_t step, const float* visibility, float* act12_out, bool rows_with_tiles_only,
                                  const uint8_t* wave_walked, uint32_t split_block, uint32_t extra_end, const LazyMoments& lazy,
-                                 const uint8_t* rule_walked, float* stat_accum, int32_t* stat_denom) {
+                                 const uint8_t* rule_walked, float* stat_accum, int32_t* stat_denom, const Regularisation& reg) {
     if (n == 0) return;
-    ShAdamParams sp;
+    ShAdamParamsReg sp;
+    sp.reg = reg;
     sp.stat_accum = stat_accum; sp.stat_denom = stat_denom;
     sp.lazy = lazy;
     sp.rule_walked = rule_walked;
@@ -861,17 +1004,21 @@ void launch_sh_adam_from_scratch(hipStream_t s, uint32_t n, int sh_degree, const
     fill_adam(sp.a48, lr48, 48, beta1, beta2, eps, step);
     sp.cam = d_camera_position;
     sp.n = n; sp.views = 1; sp.sh_degree = sh_degree; sp.grad_scale = 1.0f; sp.view_stride = n;
-    hipLaunchKernelGGL(k_sh_adam<true>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sp, (float*)nullptr,
-                       reinterpret_cast<float4*>(grad16), reinterpret_cast<float4*>(raw12), reinterpret_cast<float4*>(raw_m),
-                       reinterpret_cast<float4*>(raw_v), reinterpret_cast<float4*>(sh48), reinterpret_cast<float4*>(sh_m),
-                       reinterpret_cast<float4*>(sh_v), visibility, reinterpret_cast<float4*>(act12_out), tiles_count, feat);
+    auto launch = [&](auto kern, const auto& args) {
+        hipLaunchKernelGGL(kern, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, args, (float*)nullptr,
+                           reinterpret_cast<float4*>(grad16), reinterpret_cast<float4*>(raw12), reinterpret_cast<float4*>(raw_m),
+                           reinterpret_cast<float4*>(raw_v), reinterpret_cast<float4*>(sh48), reinterpret_cast<float4*>(sh_m),
+                           reinterpret_cast<float4*>(sh_v), visibility, reinterpret_cast<float4*>(act12_out), tiles_count, feat);
+    };
+    if (reg.on()) launch(k_sh_adam<true, true>, sp);
+    else launch(k_sh_adam<true, false>, static_cast<const ShAdamParams&>(sp));
 }
 
 void launch_adam_rows_without_gradient(hipStream_t s, uint32_t n, const uint32_t* tiles_count, float* raw12, float* raw_m, float* raw_v,
                                        float* sh48, float* sh_m, float* sh_v, const float* lr12, const float* lr48, float beta1,
                                        float beta2, float eps, uint32_t step, float* act12_out, uint32_t block_begin,
                                        uint32_t block_end, const uint8_t* wave_walked, uint32_t split_block, uint32_t extra_end,
-                                       bool second_launch, const LazyMoments& lazy) {
+                                       bool second_launch, const LazyMoments& lazy, const Regularisation& reg) {
     if (n == 0 || block_end <= block_begin) return;
     EarlyOwnership own;
     own.walked = wave_walked; own.split_block = split_block; own.extra_end = extra_end;
@@ -910,12 +1057,94 @@ void launch_adam_rows_without_gradient(hipStream_t s, uint32_t n, const uint32_t
         const char* e = getenv("GUT_EARLY_NARROW");  // tuning experiments only
         narrow_first = e ? atoi(e) : 1;
     }
-    auto kern = lazy.wave_step ? ((narrow_first && !second_launch) ? k_adam_rows_without_gradient_narrow : k_adam_rows_without_gradient<true>)
-                               : k_adam_rows_without_gradient<false>;
+    if (reg.on()) {
+        // regularised: the wide form in both launches — the 32-register form with the eager raw block spills 32 VGPRs to scratch
+        // (see k_adam_rows_without_gradient_narrow); measured against it and over first-launch shares in DESIGN.md
+#if GUT_NARROW_REGULARISED
+        auto kern = lazy.wave_step ? ((narrow_first && !second_launch) ? k_adam_rows_without_gradient_narrow<true, Regularisation>
+                                                                       : k_adam_rows_without_gradient<true, true, Regularisation>)
+                                   : k_adam_rows_without_gradient<false, true, Regularisation>;
+#else
+        auto kern = lazy.wave_step ? k_adam_rows_without_gradient<true, true, Regularisation>
+                                   : k_adam_rows_without_gradient<false, true, Regularisation>;
+#endif
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, a12, a48, n, tiles_count,
+                           reinterpret_cast<float4*>(raw12), reinterpret_cast<float4*>(raw_m), reinterpret_cast<float4*>(raw_v),
+                           reinterpret_cast<float4*>(sh48), reinterpret_cast<float4*>(sh_m), reinterpret_cast<float4*>(sh_v),
+                           reinterpret_cast<float4*>(act12_out), block_begin, block_end, own, second_launch ? 1u : 0u, lazy, reg);
+        return;
+    }
+    if (lazy.wave_step && narrow_first && !second_launch) {
+        hipLaunchKernelGGL(k_adam_rows_without_gradient_narrow<false>, dim3(grid), dim3(kBlock), 0, s, a12, a48, n, tiles_count,
+                           reinterpret_cast<float4*>(raw12), reinterpret_cast<float4*>(raw_m), reinterpret_cast<float4*>(raw_v),
+                           reinterpret_cast<float4*>(sh48), reinterpret_cast<float4*>(sh_m), reinterpret_cast<float4*>(sh_v),
+                           reinterpret_cast<float4*>(act12_out), block_begin, block_end, own, second_launch ? 1u : 0u, lazy);
+        return;
+    }
+    auto kern = lazy.wave_step ? k_adam_rows_without_gradient<true, false> : k_adam_rows_without_gradient<false, false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, a12, a48, n, tiles_count,
                        reinterpret_cast<float4*>(raw12), reinterpret_cast<float4*>(raw_m), reinterpret_cast<float4*>(raw_v),
                        reinterpret_cast<float4*>(sh48), reinterpret_cast<float4*>(sh_m), reinterpret_cast<float4*>(sh_v),
                        reinterpret_cast<float4*>(act12_out), block_begin, block_end, own, second_launch ? 1u : 0u, lazy);
+}
+
+// k_regularisation_loss: the loss values from the per-wave partials, in a fixed order (one workgroup of 1024 lanes, double
+// accumulation; lane t sums waves t, t + 1024, ... in that order, eight loads in flight — a 256-lane loop with one load at a time
+// took 0.15 ms at 6 M Gaussians, on the step's critical path):
+//   out[0] = lambda_opacity * mean sigmoid(d),  out[1] = lambda_scale * mean exp(s)  [ + onto *loss ]
+constexpr uint32_t kRegLossThreads = 1024;
+__global__ __launch_bounds__(kRegLossThreads) void k_regularisation_loss(uint32_t n, const float2* __restrict__ partials, float lambda_opacity,
+                                                                        float lambda_scale, float* __restrict__ out_opacity,
+                                                                        float* __restrict__ out_scale, float* __restrict__ loss) {
+    __shared__ double s_sig[kRegLossThreads], s_exp[kRegLossThreads];
+    const uint32_t waves = (n + 63u) / 64u;
+    double a = 0.0, b = 0.0;
+#pragma unroll 8
+    for (uint32_t w = threadIdx.x; w < waves; w += kRegLossThreads) {
+        const float2 p = partials[w];
+        a += (double)p.x;
+        b += (double)p.y;
+    }
+    s_sig[threadIdx.x] = a;
+    s_exp[threadIdx.x] = b;
+    __syncthreads();
+    for (uint32_t h = kRegLossThreads / 2; h > 0; h >>= 1) {
+        if (threadIdx.x < h) {
+            s_sig[threadIdx.x] += s_sig[threadIdx.x + h];
+            s_exp[threadIdx.x] += s_exp[threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float o = (float)((double)lambda_opacity * (s_sig[0] / (double)n));
+        const float sc = (float)((double)lambda_scale * (s_exp[0] / (3.0 * (double)n)));
+        out_opacity[0] = o;
+        out_scale[0] = sc;
+        if (loss) loss[0] = loss[0] + o + sc;
+    }
+}
+
+// k_add_regularisation_gradient: the unfused optimiser's form — the regulariser's gradient added into a materialised raw [N,12]
+// gradient (after any exchange), and the loss partials of every wave
+__global__ __launch_bounds__(kBlock) void k_add_regularisation_gradient(uint32_t n, const float4* __restrict__ raw12,
+                                                                       float4* __restrict__ g12, Regularisation reg) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    float sig = 0.0f, esum = 0.0f;
+    if (i < n) {
+        const float4 a = raw12[3 * (size_t)i + 0], c = raw12[3 * (size_t)i + 2];
+        sig = reg_sigmoid(a.w);
+        const float e0 = expf(c.x), e1 = expf(c.y), e2 = expf(c.z);
+        esum = (e0 + e1) + e2;
+        const float4 rd = reg_density_grad(reg, sig), rs = reg_scale_grad(reg, e0, e1, e2);
+        float4 g = g12[3 * (size_t)i + 0];
+        g.w += rd.w;
+        g12[3 * (size_t)i + 0] = g;
+        g = g12[3 * (size_t)i + 2];
+        g.x += rs.x; g.y += rs.y; g.z += rs.z;
+        g12[3 * (size_t)i + 2] = g;
+    }
+    const uint32_t wave_first = i & ~63u;
+    if (wave_first < n) reg_wave_partials(reg, sig, esum, wave_first >> 6, threadIdx.x & 63);
 }
 
 // k_mark_walked_waves: wave_walked[id / 64] = 1 for every Gaussian id among the list entries the forward compositor walked
@@ -975,6 +1204,8 @@ void launch_mark_walked_waves(hipStream_t s, uint32_t n, uint32_t tiles, const u
 namespace gut {
 // k_sync_moments: brings the stored moments of every wave up to step t (m *= beta1^(t - wave_step), same for v) and marks them so:
 // what any reader would compute on the fly.  Before anything that moves rows between waves or looks at the moments from outside.
+// kRawEager (a regulariser is on): the [N,12] moments are stored every step and are current already — only the [N,48] block
+template <bool kRawEager>
 __global__ __launch_bounds__(kBlock) void k_sync_moments(uint32_t n, float4* __restrict__ m12, float4* __restrict__ v12,
                                                         float4* __restrict__ m48, float4* __restrict__ v48, LazyMoments lz) {
     const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -987,7 +1218,7 @@ __global__ __launch_bounds__(kBlock) void k_sync_moments(uint32_t n, float4* __r
     if (d >= lz.len && lz.overrun && lane == 0) *lz.overrun = 1u;
     const float f1 = lz.pow1[k], f2 = lz.pow2[k];
     const uint32_t rows_here = min(64u, n - wave_first);
-    for (uint32_t q = lane; q < rows_here * 3u; q += 64u) {
+    for (uint32_t q = lane; !kRawEager && q < rows_here * 3u; q += 64u) {
         float4 a = m12[(size_t)wave_first * 3 + q], b = v12[(size_t)wave_first * 3 + q];
         scale4(a, f1); scale4(b, f2);
         m12[(size_t)wave_first * 3 + q] = a; v12[(size_t)wave_first * 3 + q] = b;
@@ -1035,19 +1266,58 @@ gut::LazyMoments gut_make_lazy(const GutLazyMoments* lazy, uint32_t step) {
     return lz;
 }
 
+// GutRegularisation of the C ABI -> the kernels' argument (NULL or both coefficients 0: off)
+gut::Regularisation gut_make_reg(const GutRegularisation* reg) {
+    gut::Regularisation r;
+    if (reg && (reg->density_coeff != 0.0f || reg->scale_coeff != 0.0f)) {
+        r.density_coeff = reg->density_coeff;
+        r.scale_coeff = reg->scale_coeff;
+        r.partials = reinterpret_cast<float2*>(reg->d_partials);
+    }
+    return r;
+}
+
 extern "C" {
 
-int gut_sync_moments(void* stream, uint32_t num_particles, float* d_raw_m, float* d_raw_v, float* d_sh_m, float* d_sh_v,
-                     const GutLazyMoments* lazy, uint32_t step) {
+int gut_sync_moments_ex(void* stream, uint32_t num_particles, float* d_raw_m, float* d_raw_v, float* d_sh_m, float* d_sh_v,
+                        const GutLazyMoments* lazy, uint32_t step, const GutRegularisation* reg) {
     if (num_particles == 0) return 0;
     if (!d_raw_m || !d_raw_v || !d_sh_m || !d_sh_v || !lazy) return 1;
     gut::LazyMoments lz = gut_make_lazy(lazy, step ? step : 1u);
     if (!lz.wave_step) return 3;
     lz.t = step;   // (step 0: nothing has been applied yet, nothing to bring up to date)
     const uint32_t waves = (num_particles + 63u) / 64u;
-    hipLaunchKernelGGL(gut::k_sync_moments, dim3((waves + 3u) / 4u), dim3(gut::kBlock), 0, static_cast<hipStream_t>(stream), num_particles,
+    auto kern = gut_make_reg(reg).on() ? gut::k_sync_moments<true> : gut::k_sync_moments<false>;
+    hipLaunchKernelGGL(kern, dim3((waves + 3u) / 4u), dim3(gut::kBlock), 0, static_cast<hipStream_t>(stream), num_particles,
                        reinterpret_cast<float4*>(d_raw_m), reinterpret_cast<float4*>(d_raw_v), reinterpret_cast<float4*>(d_sh_m),
                        reinterpret_cast<float4*>(d_sh_v), lz);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+int gut_sync_moments(void* stream, uint32_t num_particles, float* d_raw_m, float* d_raw_v, float* d_sh_m, float* d_sh_v,
+                     const GutLazyMoments* lazy, uint32_t step) {
+    return gut_sync_moments_ex(stream, num_particles, d_raw_m, d_raw_v, d_sh_m, d_sh_v, lazy, step, nullptr);
+}
+
+int gut_regularisation_loss(void* stream, uint32_t num_particles, const float* d_partials, float lambda_opacity, float lambda_scale,
+                            float* d_opacity_loss, float* d_scale_loss, float* d_loss) {
+    if (!d_opacity_loss || !d_scale_loss) return 1;
+    // (no Gaussians: the kernel reads no partial and writes the mean over nothing, nan, as torch does)
+    if (num_particles && !d_partials) return 1;
+    hipLaunchKernelGGL(gut::k_regularisation_loss, dim3(1), dim3(gut::kRegLossThreads), 0, static_cast<hipStream_t>(stream), num_particles,
+                       reinterpret_cast<const float2*>(d_partials), lambda_opacity, lambda_scale, d_opacity_loss, d_scale_loss, d_loss);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+int gut_regularisation_gradient(void* stream, uint32_t num_particles, const float* d_raw12, float* d_raw_grad12,
+                                const GutRegularisation* reg) {
+    if (num_particles == 0) return 0;
+    if (!d_raw12 || !d_raw_grad12) return 1;
+    const gut::Regularisation r = gut_make_reg(reg);
+    if (!r.on()) return 0;
+    hipLaunchKernelGGL(gut::k_add_regularisation_gradient, dim3((num_particles + gut::kBlock - 1) / gut::kBlock), dim3(gut::kBlock), 0,
+                       static_cast<hipStream_t>(stream), num_particles, reinterpret_cast<const float4*>(d_raw12),
+                       reinterpret_cast<float4*>(d_raw_grad12), r);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -1131,18 +1401,19 @@ int gut_mcmc_relocation(void* stream, int32_t n, const float* d_opacities, const
 }
 
 
-int gut_sh_adam_step_ex(void* stream, uint32_t num_particles, int32_t sh_degree, uint32_t num_views, const float* d_camera_positions,
-                        float* d_mrgb, float* d_raw_grad12, float grad_scale, float* d_raw12, float* d_raw_m,
-                        float* d_raw_v, float* d_sh48, float* d_sh_m, float* d_sh_v, const float* lr12, const float* lr48,
-                        float beta1, float beta2, float eps, uint32_t step, const float* d_visibility, float* d_act12_out,
-                        uint32_t mrgb_view_stride, uint32_t flags, const uint8_t* d_wave_flags, const GutLazyMoments* lazy) {
+int gut_sh_adam_step_regularised(void* stream, uint32_t num_particles, int32_t sh_degree, uint32_t num_views,
+                                 const float* d_camera_positions, float* d_mrgb, float* d_raw_grad12, float grad_scale, float* d_raw12,
+                                 float* d_raw_m, float* d_raw_v, float* d_sh48, float* d_sh_m, float* d_sh_v, const float* lr12,
+                                 const float* lr48, float beta1, float beta2, float eps, uint32_t step, const float* d_visibility,
+                                 float* d_act12_out, uint32_t mrgb_view_stride, uint32_t flags, const uint8_t* d_wave_flags,
+                                 const GutLazyMoments* lazy, const GutRegularisation* reg) {
     if (num_particles == 0) return 0;
     if (!d_camera_positions || !d_mrgb || !d_raw_grad12 || !d_raw12 || !d_raw_m || !d_raw_v || !d_sh48 || !d_sh_m || !d_sh_v ||
         !lr12 || !lr48)
         return 1;
     if (num_views == 0 || num_views > 1024 || sh_degree < 0 || sh_degree > 3) return 3;
     if (flags & ~(uint32_t)GUT_ADAM_CLEAR_CONSUMED_GRADS) return 3;
-    gut::ShAdamParams sp;
+    gut::ShAdamParamsReg sp;
     fill_adam(sp.a12, lr12, 12, beta1, beta2, eps, step);
     fill_adam(sp.a48, lr48, 48, beta1, beta2, eps, step);
     sp.cam = d_camera_positions;
@@ -1156,12 +1427,27 @@ int gut_sh_adam_step_ex(void* stream, uint32_t num_particles, int32_t sh_degree,
     sp.lazy = gut_make_lazy(lazy, step);
     sp.rule_walked = nullptr;
     sp.stat_accum = nullptr; sp.stat_denom = nullptr;
-    hipLaunchKernelGGL(gut::k_sh_adam<false>, dim3((num_particles + gut::kBlock - 1) / gut::kBlock), dim3(gut::kBlock), 0,
-                       static_cast<hipStream_t>(stream), sp, d_mrgb, reinterpret_cast<float4*>(d_raw_grad12),
-                       reinterpret_cast<float4*>(d_raw12), reinterpret_cast<float4*>(d_raw_m), reinterpret_cast<float4*>(d_raw_v),
-                       reinterpret_cast<float4*>(d_sh48), reinterpret_cast<float4*>(d_sh_m), reinterpret_cast<float4*>(d_sh_v),
-                       d_visibility, reinterpret_cast<float4*>(d_act12_out), (const uint32_t*)nullptr, (const float*)nullptr);
+    sp.reg = gut_make_reg(reg);
+    auto launch = [&](auto kern, const auto& args) {
+        hipLaunchKernelGGL(kern, dim3((num_particles + gut::kBlock - 1) / gut::kBlock), dim3(gut::kBlock), 0,
+                           static_cast<hipStream_t>(stream), args, d_mrgb, reinterpret_cast<float4*>(d_raw_grad12),
+                           reinterpret_cast<float4*>(d_raw12), reinterpret_cast<float4*>(d_raw_m), reinterpret_cast<float4*>(d_raw_v),
+                           reinterpret_cast<float4*>(d_sh48), reinterpret_cast<float4*>(d_sh_m), reinterpret_cast<float4*>(d_sh_v),
+                           d_visibility, reinterpret_cast<float4*>(d_act12_out), (const uint32_t*)nullptr, (const float*)nullptr);
+    };
+    if (sp.reg.on()) launch(gut::k_sh_adam<false, true>, sp);
+    else launch(gut::k_sh_adam<false, false>, static_cast<const gut::ShAdamParams&>(sp));
     return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+int gut_sh_adam_step_ex(void* stream, uint32_t num_particles, int32_t sh_degree, uint32_t num_views, const float* d_camera_positions,
+                        float* d_mrgb, float* d_raw_grad12, float grad_scale, float* d_raw12, float* d_raw_m,
+                        float* d_raw_v, float* d_sh48, float* d_sh_m, float* d_sh_v, const float* lr12, const float* lr48,
+                        float beta1, float beta2, float eps, uint32_t step, const float* d_visibility, float* d_act12_out,
+                        uint32_t mrgb_view_stride, uint32_t flags, const uint8_t* d_wave_flags, const GutLazyMoments* lazy) {
+    return gut_sh_adam_step_regularised(stream, num_particles, sh_degree, num_views, d_camera_positions, d_mrgb, d_raw_grad12, grad_scale,
+                                        d_raw12, d_raw_m, d_raw_v, d_sh48, d_sh_m, d_sh_v, lr12, lr48, beta1, beta2, eps, step,
+                                        d_visibility, d_act12_out, mrgb_view_stride, flags, d_wave_flags, lazy, nullptr);
 }
 
 int gut_sh_adam_step(void* stream, uint32_t num_particles, int32_t sh_degree, uint32_t num_views, const float* d_camera_positions,
@@ -1174,16 +1460,24 @@ int gut_sh_adam_step(void* stream, uint32_t num_particles, int32_t sh_degree, ui
                                lr48, beta1, beta2, eps, step, d_visibility, d_act12_out, mrgb_view_stride, 0u, nullptr, nullptr);
 }
 
-int gut_adam_unwalked_waves_ex(void* stream, uint32_t num_particles, const uint8_t* d_wave_flags, float* d_raw12, float* d_raw_m,
-                               float* d_raw_v, float* d_sh48, float* d_sh_m, float* d_sh_v, const float* lr12, const float* lr48,
-                               float beta1, float beta2, float eps, uint32_t step, float* d_act12_out, const GutLazyMoments* lazy) {
+int gut_adam_unwalked_waves_regularised(void* stream, uint32_t num_particles, const uint8_t* d_wave_flags, float* d_raw12,
+                                        float* d_raw_m, float* d_raw_v, float* d_sh48, float* d_sh_m, float* d_sh_v, const float* lr12,
+                                        const float* lr48, float beta1, float beta2, float eps, uint32_t step, float* d_act12_out,
+                                        const GutLazyMoments* lazy, const GutRegularisation* reg) {
     if (num_particles == 0) return 0;
     if (!d_wave_flags || !d_raw12 || !d_raw_m || !d_raw_v || !d_sh48 || !d_sh_m || !d_sh_v || !lr12 || !lr48) return 1;
     const uint32_t nblocks = (num_particles + gut::kBlock - 1) / gut::kBlock;
     gut::launch_adam_rows_without_gradient(static_cast<hipStream_t>(stream), num_particles, nullptr, d_raw12, d_raw_m, d_raw_v, d_sh48,
                                            d_sh_m, d_sh_v, lr12, lr48, beta1, beta2, eps, step, d_act12_out, 0, nblocks, d_wave_flags,
-                                           0, nblocks, true, gut_make_lazy(lazy, step));
+                                           0, nblocks, true, gut_make_lazy(lazy, step), gut_make_reg(reg));
     return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+int gut_adam_unwalked_waves_ex(void* stream, uint32_t num_particles, const uint8_t* d_wave_flags, float* d_raw12, float* d_raw_m,
+                               float* d_raw_v, float* d_sh48, float* d_sh_m, float* d_sh_v, const float* lr12, const float* lr48,
+                               float beta1, float beta2, float eps, uint32_t step, float* d_act12_out, const GutLazyMoments* lazy) {
+    return gut_adam_unwalked_waves_regularised(stream, num_particles, d_wave_flags, d_raw12, d_raw_m, d_raw_v, d_sh48, d_sh_m, d_sh_v,
+                                               lr12, lr48, beta1, beta2, eps, step, d_act12_out, lazy, nullptr);
 }
 
 int gut_adam_unwalked_waves(void* stream, uint32_t num_particles, const uint8_t* d_wave_flags, float* d_raw12, float* d_raw_m,

@@ -72,6 +72,22 @@ def l1_loss(network_output, gt):
     return torch.abs(network_output - gt).mean()
 
 
+def regularisation_loss(density, scale, lambda_opacity, lambda_scale):
+    """The MCMC recipe's regularisers (trainer.py:432-446): (lambda_opacity * mean |density|, lambda_scale * mean |scale|) for the
+    ACTIVATED density [N,1] and scale [N,3] (model.get_density() / get_scale()); the means run over N and 3N values."""
+    return lambda_opacity * density.abs().mean(), lambda_scale * scale.abs().mean()
+
+
+def loss_weights(loss_conf):
+    """The reference's `loss:` block (configs/base_gs.yaml:111-126, base_mcmc.yaml:13-18; a plain dict) -> the trainers' keyword
+    arguments dict(lambda_l1, lambda_ssim, lambda_opacity, lambda_scale), a term whose `use_*` switch is off (or absent) weighted 0
+    (trainer.py:406-447).  As in the reference, `use_l2` / `lambda_l2` do not enter the total loss: trainer.py:449 computes the L2 term
+    and sums only L1, SSIM, opacity and scale — so they are ignored here."""
+    def weight(name):
+        return float(loss_conf.get(f"lambda_{name}", 0.0)) if loss_conf.get(f"use_{name}", False) else 0.0
+    return dict(lambda_l1=weight("l1"), lambda_ssim=weight("ssim"), lambda_opacity=weight("opacity"), lambda_scale=weight("scale"))
+
+
 def photometric_loss(pred_rgb, gt_rgb, lambda_l1=0.8, lambda_ssim=0.2):
     """pred/gt [B,H,W,3].  lambda_l1*L1 + lambda_ssim*(1-SSIM)  (configs/base_gs.yaml:111-119, trainer.py:425-449)."""
     s = fused_ssim(pred_rgb.permute(0, 3, 1, 2), gt_rgb.permute(0, 3, 1, 2), padding="valid")

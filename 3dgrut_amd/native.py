@@ -27,6 +27,9 @@ from .tracer import SplatRaster, Tracer
 
 # column layout of the raw [N,12] tensor and the reference's Adam learning rates (configs/base_gs.yaml:81-109)
 RAW_COLS = dict(positions=slice(0, 3), density=slice(3, 4), rotation=slice(4, 8), scale=slice(8, 11))
+# gut_sync_moments_ex's setting "a regulariser is on" (the [N,12] moments are stored every step, only [N,48] is brought up to date):
+# the library only asks whether a coefficient is non-zero, so any non-zero pair says it; no gradient is formed by a sync
+_RAW_MOMENTS_EAGER = _capi.GutRegularisation(1.0, 1.0, None)
 
 
 def spatial_permutation(positions: torch.Tensor, bits: int = 10) -> torch.Tensor:
@@ -127,7 +130,8 @@ class NativeTrainStep:
     def __init__(self, model: NativeGaussianModel, tracer: Tracer, scene_extent=1.0, world_size=1, selective=False,
                  betas=(0.9, 0.999), eps=1e-15, fused_sh_adam=True, rank=0, fused_loss=True, lambda_l1=0.8, lambda_ssim=0.2,
                  dp_chunks=4, dp_chunk_min_rows=1 << 20, fuse_epilogue=True, schedule=None,
-                 overlap_optimizer=None, dp_exchange="sparse", dp_side_stream=True, lazy_moments=True):
+                 overlap_optimizer=None, dp_exchange="sparse", dp_side_stream=True, lazy_moments=True, lambda_opacity=0.0,
+                 lambda_scale=0.0):
         self.model = model
         self.tracer = tracer
         self.raster: SplatRaster = tracer.tracer_wrapper
@@ -198,6 +202,13 @@ class NativeTrainStep:
         self.dp_side_stream = bool(dp_side_stream) and not selective
         self._side = None
         self.lambda_l1, self.lambda_ssim = float(lambda_l1), float(lambda_ssim)
+        # The MCMC recipe's regularisers (configs/base_mcmc.yaml:13-18; strategy.MCMC_LOSS): lambda_opacity * mean sigmoid(density) +
+        # lambda_scale * mean exp(scale) join the loss.  Their gradient is formed inside whichever optimiser kernel updates a row
+        # (gut_hip.h: GutRegularisation), so the side-stream pass and the lazy [N,48] moments stay; the [N,12] moments are then
+        # stored every step.  Both may be changed between steps; 0 and 0 is the unregularised step, kernel for kernel.
+        self.lambda_opacity, self.lambda_scale = float(lambda_opacity), float(lambda_scale)
+        self._raw_eager = self._regularised()   # the setting the stored [N,12] moments follow (see _step / sync_moments)
+        self._reg_partials = None
         self._loss_ws = None
         self._loss3 = None
         self._cam_ring = None
@@ -240,6 +251,8 @@ class NativeTrainStep:
             self.wave_step = torch.full(((n + 63) // 64,), int(getattr(self, "step_id", 0)), dtype=torch.int32, device=dev)
         self.act = torch.empty((n, 12), dtype=torch.float32, device=dev)
         self.g12 = torch.empty((n, 12), dtype=torch.float32, device=dev)
+        # per 64-row wave: (sum sigmoid, sum exp) of the regularisers' loss value, written by the kernel that owns the wave
+        self._reg_partials = torch.empty((max(1, (n + 63) // 64), 2), dtype=torch.float32, device=dev)
         if self.fused:
             # compact exchange: per view only dL/dRGB (12 B per Gaussian) travels; the [N,48] SH gradient is rebuilt
             # inside the fused SH-gradient + Adam kernel (csrc/gut_train.hip: k_sh_adam).  With more than one rank the
@@ -270,6 +283,29 @@ class NativeTrainStep:
             self.g48 = None
         else:
             self.g48 = torch.empty((n, 48), dtype=torch.float32, device=dev)
+
+    def _regularised(self):
+        return self.lambda_opacity != 0.0 or self.lambda_scale != 0.0
+
+    def _regularisation(self, row0=0):
+        """GutRegularisation of this step (coefficients from the current number of Gaussians), or None; row0: first row of a
+        row-range call (a multiple of 64), whose partials start at wave row0 / 64."""
+        n = self.model.num_gaussians
+        if not self._regularised() or n == 0:
+            return None
+        return _capi.GutRegularisation(self.lambda_opacity / n, self.lambda_scale / (3 * n), self._reg_partials.data_ptr() + 8 * (row0 // 64))
+
+    def _regularisation_losses(self, loss_buffer=None):
+        """(opacity_loss, scale_loss) device scalars from the partials the step's optimiser kernels wrote (gut_regularisation_loss,
+        on the current stream, which is ordered behind every stream that wrote them); loss_buffer: a device float they are added to."""
+        out = torch.empty((2,), dtype=torch.float32, device=self.model.raw.device)
+        st = torch.cuda.current_stream(out.device).cuda_stream
+        rc = self._lib.gut_regularisation_loss(C.c_void_p(st), self.model.num_gaussians, self._reg_partials.data_ptr(), self.lambda_opacity,
+                                              self.lambda_scale, out.data_ptr(), out.data_ptr() + 4,
+                                              None if loss_buffer is None else loss_buffer.data_ptr())
+        if rc:
+            raise RuntimeError(f"[3dgut] regularisation_loss failed ({rc})")
+        return out[0], out[1]
 
     def _lazy(self):
         """GutLazyMoments for the optimiser entry points, or None."""
@@ -332,9 +368,12 @@ class NativeTrainStep:
         if lz is None or self.model.num_gaussians == 0 or not self.model.raw.is_cuda:
             return
         st = torch.cuda.current_stream(self.model.raw.device).cuda_stream
+        # with a regulariser the stored [N,12] moments are current every step: only the [N,48] block is brought up to date
+        eager = _RAW_MOMENTS_EAGER if self._raw_eager else None
         with torch.cuda.device(self.model.raw.device):
-            rc = self._lib.gut_sync_moments(C.c_void_p(st), self.model.num_gaussians, self.m12.data_ptr(), self.v12.data_ptr(),
-                                            self.m48.data_ptr(), self.v48.data_ptr(), C.byref(lz), int(self.step_id))
+            rc = self._lib.gut_sync_moments_ex(C.c_void_p(st), self.model.num_gaussians, self.m12.data_ptr(), self.v12.data_ptr(),
+                                               self.m48.data_ptr(), self.v48.data_ptr(), C.byref(lz), int(self.step_id),
+                                               None if eager is None else C.byref(eager))
         if rc:
             raise RuntimeError(f"[3dgut] sync_moments failed ({rc})")
         if int(self._lazy_overrun.item()):   # (a blocking read, on a path that runs every LAZY_TABLE / 2 steps and on row surgery)
@@ -522,6 +561,9 @@ class NativeTrainStep:
         try:
             return self._step(batch)
         except Exception as err:
+            if getattr(self, "_reg_set", False):   # (a regulariser handed to the handle and not consumed: not for the next step)
+                self._reg_set = False
+                self.raster.set_regularisation(None)
             # The side-stream optimiser pass may already be running for this iteration (it is queued right behind the forward):
             # finish the step for every other row with a zero gradient instead of leaving the parameters half advanced and the
             # handle refusing the next forward (gut_optimize_finish_without_gradient); then let the error through.
@@ -535,6 +577,8 @@ class NativeTrainStep:
                                        f"{type(err).__name__}: {err}; the trainer's state is not usable: {finish_err}") from err
                 self._act_key = None
                 self._probe_evs = None
+                # (with a regulariser, "a zero gradient" is the regulariser's gradient alone: the handle applies the setting the side
+                # stream's launches were given to every remaining row too)
                 # the iteration WAS applied — every row took its step, with a zero gradient — so it goes through the same
                 # bookkeeping as any other (learning-rate / SH-degree schedule, sync cadence of the lazy moments, step count)
                 self._end_of_step(None)
@@ -550,6 +594,12 @@ class NativeTrainStep:
                                       what=f"before the first step (step counter {self.step_id})")
         evs = [] if self.phase_timing else None
         self._mark(evs)
+        if self._regularised() != self._raw_eager:
+            # the regulariser switches on or off: bring every stored moment up to date under the OLD setting first, so that no
+            # [N,12] moment is read as current while it is stale (on) or decayed again by missed steps (off)
+            self.sync_moments()
+            self._raw_eager = self._regularised()
+        reg = self._regularisation()
         one_pass = self.fused and self.world_size <= 1 and not self.force_exchange and self.fuse_epilogue \
             and (self.post_backward_hook is None or self.fused_statistics is not None)
         use_overlap, probe_evs = self.overlap_optimizer, None
@@ -572,6 +622,9 @@ class NativeTrainStep:
         early = one_pass and use_overlap and not self.selective
         self._probe_evs = probe_evs
         rgba, dist_, hits, vis = self.forward(batch)
+        if one_pass and reg is not None:
+            self.raster.set_regularisation(reg)   # consumed by the step's optimiser calls on the handle
+            self._reg_set = True
         if early:
             self.raster.optimize_rows_without_gradient(m.raw, self.m12, self.v12, m.features, self.m48, self.v48, self.lr12,
                                                        self.lr48, self.betas, self.eps, self.step_id + 1, self.act, lazy=self._lazy())
@@ -630,15 +683,12 @@ class NativeTrainStep:
                 self.raster.optimize_after_bwd(m.n_active_features, None, m.raw, self.m12, self.v12, m.features,
                                                self.m48, self.v48, self.lr12, self.lr48, self.betas, self.eps,
                                                0 if self.selective else self.step_id + 1, vmask, self.act, lazy=self._lazy())
+                self._reg_set = False
                 self._act_key = (m.raw.data_ptr(), m.raw._version, m.raw.shape[0])
-                self._mark(evs)
-                self._end_of_step(evs)
-                return loss.detach(), dict(pred_rgb=pred_rgb.detach(), mog_visibility=vis, hits_count=hits)
+                return self._finish_step(evs, loss, pred_rgb, vis, hits, reg)
             if self.dp_exchange == "sparse":
-                self._sparse_exchange_and_update(batch, bwd_args, vis, evs, w, exchange)
-                self._mark(evs)
-                self._end_of_step(evs)
-                return loss.detach(), dict(pred_rgb=pred_rgb.detach(), mog_visibility=vis, hits_count=hits)
+                self._sparse_exchange_and_update(batch, bwd_args, vis, evs, w, exchange, reg)
+                return self._finish_step(evs, loss, pred_rgb, vis, hits, reg)
             # this view's compact radiance gradient: directly view 0 of the gathered layout when there is nothing to gather
             local_mrgb = self.mrgb_local if exchange else self.mrgb[0][0]
             self.raster.trace_bwd(*bwd_args, raw_parameter_grads=True, compact_radiance_grads=True, out=(self.g12, local_mrgb))
@@ -669,14 +719,15 @@ class NativeTrainStep:
                 lz = self._lazy()
                 if lz is not None:   # chunks are multiples of 256 rows: whole waves
                     lz = _capi.GutLazyMoments(self.wave_step.data_ptr() + 4 * (r0 // 64), self._pow1.data_ptr(), self._pow2.data_ptr(), self.LAZY_TABLE)
-                rc = self._lib.gut_sh_adam_step_ex(
+                reg_c = self._regularisation(r0)   # (chunks are whole 256-row blocks: their partials start at wave r0 / 64)
+                rc = self._lib.gut_sh_adam_step_regularised(
                     C.c_void_p(st), r1 - r0, m.n_active_features, w, self.cams.data_ptr(), gathered.data_ptr(),
                     self.g12.data_ptr() + 48 * r0, 1.0 / w, m.raw.data_ptr() + 48 * r0, self.m12.data_ptr() + 48 * r0,
                     self.v12.data_ptr() + 48 * r0, m.features.data_ptr() + 192 * r0, self.m48.data_ptr() + 192 * r0,
                     self.v48.data_ptr() + 192 * r0, self.lr12.ctypes.data_as(f32p), self.lr48.ctypes.data_as(f32p),
                     self.betas[0], self.betas[1], self.eps, 0 if self.selective else self.step_id + 1,
                     None if vmask is None else vmask.data_ptr() + 4 * r0, self.act.data_ptr() + 48 * r0, r1 - r0, 0, None,
-                    None if lz is None else C.byref(lz))
+                    None if lz is None else C.byref(lz), None if reg_c is None else C.byref(reg_c))
                 if rc:
                     raise RuntimeError(f"[3dgut] sh_adam_step failed ({rc})")
             # any in-place torch edit of raw (densification, MCMC noise, ...) bumps _version and forces a fresh activation
@@ -691,13 +742,31 @@ class NativeTrainStep:
                 if self.selective:
                     allreduce_max_(vis, self.world_size)
             vmask = vis.reshape(-1) if self.selective else None
+            if reg is not None:   # once, after the exchange's mean (every replica holds the same parameters)
+                rc = self._lib.gut_regularisation_gradient(C.c_void_p(torch.cuda.current_stream(m.raw.device).cuda_stream),
+                                                           m.num_gaussians, m.raw.data_ptr(), self.g12.data_ptr(), C.byref(reg))
+                if rc:
+                    raise RuntimeError(f"[3dgut] regularisation_gradient failed ({rc})")
             self._adam(m.raw, self.g12, self.m12, self.v12, self.lr12, vmask)
             self._adam(m.features, self.g48, self.m48, self.v48, self.lr48, vmask)
+        return self._finish_step(evs, loss, pred_rgb, vis, hits, reg)
+
+    def _finish_step(self, evs, loss, pred_rgb, vis, hits, reg):
+        """End of every path of _step: the regularisers' loss values (behind the optimiser kernels that wrote their partials), the
+        bookkeeping of _end_of_step, the results."""
+        out = dict(pred_rgb=pred_rgb.detach(), mog_visibility=vis, hits_count=hits)
+        loss = loss.detach()
+        if reg is not None:
+            # the fused loss: added in place to its device float (`loss` is a view of it); the torch loss: added here
+            in_place = self._loss3 is not None and loss.data_ptr() == self._loss3.data_ptr()
+            out["opacity_loss"], out["scale_loss"] = self._regularisation_losses(self._loss3 if in_place else None)
+            if not in_place:
+                loss = loss + out["opacity_loss"] + out["scale_loss"]
         self._mark(evs)
         self._end_of_step(evs)
-        return loss.detach(), dict(pred_rgb=pred_rgb.detach(), mog_visibility=vis, hits_count=hits)
+        return loss, out
 
-    def _sparse_exchange_and_update(self, batch, bwd_args, vis, evs, w, exchange):
+    def _sparse_exchange_and_update(self, batch, bwd_args, vis, evs, w, exchange, reg=None):
         """Backward + sparse gradient exchange + optimiser of a data-parallel step (dp_exchange == "sparse")."""
         m = self.model
         n = m.num_gaussians
@@ -720,11 +789,11 @@ class NativeTrainStep:
                 if flags_work is not None:
                     flags_work.wait()
                 lz = self._lazy()
-                rc = self._lib.gut_adam_unwalked_waves_ex(
+                rc = self._lib.gut_adam_unwalked_waves_regularised(
                     C.c_void_p(self._side.cuda_stream), n, self.wave_flags.data_ptr(), m.raw.data_ptr(), self.m12.data_ptr(),
                     self.v12.data_ptr(), m.features.data_ptr(), self.m48.data_ptr(), self.v48.data_ptr(),
                     self.lr12.ctypes.data_as(f32p), self.lr48.ctypes.data_as(f32p), self.betas[0], self.betas[1], self.eps,
-                    self.step_id + 1, self.act.data_ptr(), None if lz is None else C.byref(lz))
+                    self.step_id + 1, self.act.data_ptr(), None if lz is None else C.byref(lz), None if reg is None else C.byref(reg))
                 if rc:
                     raise RuntimeError(f"[3dgut] adam_unwalked_waves failed ({rc})")
             if flags_work is not None:
@@ -771,13 +840,13 @@ class NativeTrainStep:
             pg[mine[:, 11].contiguous().view(torch.int32).long()] = mine[:, 0:3]
             self.post_backward_hook(pg, cam_local)
         vmask = vis.reshape(-1) if self.selective else None
-        rc = self._lib.gut_sh_adam_step_ex(
+        rc = self._lib.gut_sh_adam_step_regularised(
             C.c_void_p(st), n, m.n_active_features, w, self.cams.data_ptr(), slabs.data_ptr(), self.g12.data_ptr(), 1.0 / w,
             m.raw.data_ptr(), self.m12.data_ptr(), self.v12.data_ptr(), m.features.data_ptr(), self.m48.data_ptr(),
             self.v48.data_ptr(), self.lr12.ctypes.data_as(f32p), self.lr48.ctypes.data_as(f32p), self.betas[0], self.betas[1],
             self.eps, 0 if self.selective else self.step_id + 1, None if vmask is None else vmask.data_ptr(), self.act.data_ptr(),
             n, _capi.ADAM_CLEAR_CONSUMED_GRADS, self.wave_flags.data_ptr() if side_on else None,
-            None if self._lazy() is None else C.byref(self._lazy()))
+            None if self._lazy() is None else C.byref(self._lazy()), None if reg is None else C.byref(reg))
         if rc:
             raise RuntimeError(f"[3dgut] sh_adam_step failed ({rc})")
         if side_on:

@@ -271,6 +271,9 @@ class GSStrategy:
 
 # configs/strategy/mcmc.yaml: (start_iteration, end_iteration, frequency) of each operation
 MCMC_SCHEDULE = dict(relocate=(500, 25000, 100), add=(500, 25000, 100), perturb=(0, 27500, 1))
+# configs/base_mcmc.yaml:13-18: the loss regularisers the MCMC recipe trains with (NativeTrainStep / TrainStep keyword arguments;
+# losses.loss_weights maps a whole `loss:` block)
+MCMC_LOSS = dict(lambda_opacity=0.01, lambda_scale=0.01)
 
 
 class MCMCStrategy:

@@ -432,6 +432,12 @@ class SplatRaster:
         _capi.check(self._lib.gut_set_position_gradient_statistics(self._handle, norm_accum.data_ptr(), norm_denom.data_ptr()),
                     "set_position_gradient_statistics")
 
+    def set_regularisation(self, reg):
+        """The NEXT optimiser step on the handle (optimize_rows_without_gradient + optimize_after_bwd, or
+        finish_optimizer_step_without_gradient) adds the MCMC regularisers' gradient to every row it updates and writes the loss
+        partials (gut_set_regularisation).  reg: _capi.GutRegularisation, or None to clear it."""
+        _capi.check(self._lib.gut_set_regularisation(self._handle, None if reg is None else C.byref(reg)), "set_regularisation")
+
     def optimize_after_bwd(self, num_active_features, camera_position, raw12, raw_m, raw_v, sh48, sh_m, sh_v, lr12, lr48, betas, eps,
                            step, visibility=None, act_out=None, lazy=None):
         """Per-Gaussian backward epilogue + SH-gradient rebuild + Adam in one pass (gut_optimize_after_bwd); follows a

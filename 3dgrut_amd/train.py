@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from .dp import allreduce_mean_
-from .losses import photometric_loss
+from .losses import photometric_loss, regularisation_loss
 from .optimizers import SelectiveAdam
 
 
@@ -58,8 +58,10 @@ def photometric_loss_torch(pred_rgb, gt_rgb, lambda_l1=0.8, lambda_ssim=0.2, win
 
 
 class TrainStep:
-    def __init__(self, model, tracer, scene_extent=1.0, world_size=1, fused_adam=True, schedule=None, optimizer_type="adam"):
-        """optimizer_type: configs/base_gs.yaml:82 `optimizer.type` — "adam" (torch.optim.Adam) or "selective_adam" (model.py:512-513:
+    def __init__(self, model, tracer, scene_extent=1.0, world_size=1, fused_adam=True, schedule=None, optimizer_type="adam",
+                 lambda_opacity=0.0, lambda_scale=0.0):
+        """lambda_opacity / lambda_scale: the MCMC recipe's regularisers (strategy.MCMC_LOSS, losses.regularisation_loss); 0 = off.
+        optimizer_type: configs/base_gs.yaml:82 `optimizer.type` — "adam" (torch.optim.Adam) or "selective_adam" (model.py:512-513:
         the reference's SelectiveAdam plugin, here optimizers.SelectiveAdam over `gut_selective_adam`; the step then passes the view's
         visibility, trainer.py:747-749)."""
         self.model = model
@@ -78,6 +80,7 @@ class TrainStep:
             raise ValueError(f"Unknown optimizer type: {optimizer_type}")
         self.window = _gauss_window(device=next(model.parameters()).device)
         self.step_id = 0
+        self.lambda_opacity, self.lambda_scale = float(lambda_opacity), float(lambda_scale)
         self.schedule = schedule   # schedule.TrainSchedule or None (constant rates, fixed SH degree)
         if schedule is not None:
             self._set_schedule_state(schedule.position_lr, schedule.n_active_features)
@@ -118,6 +121,11 @@ class TrainStep:
         out = self.render(batch, train=True)
         self._mark(evs)
         loss = photometric_loss(out["pred_rgb"], batch.rgb_gt)
+        if self.lambda_opacity != 0.0 or self.lambda_scale != 0.0:
+            # trainer.py:432-449; with data parallelism every rank adds the same term, and the all-reduce's mean keeps it once
+            out["opacity_loss"], out["scale_loss"] = regularisation_loss(self.model.get_density(), self.model.get_scale(),
+                                                                         self.lambda_opacity, self.lambda_scale)
+            loss = loss + out["opacity_loss"] + out["scale_loss"]
         self._mark(evs)
         loss.backward()
         if self.world_size > 1:

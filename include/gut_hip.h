@@ -37,8 +37,10 @@ extern "C" {
  * GutLazyMoments.d_overrun; gut_trace_raw_model_fields; GUT_OPT_FORWARD_TILE_ORDER).  Added under 5 without a bump, nothing that was
  * accepted changed meaning: gut_create takes every value of GutConfig the reference has a kernel for (kernel degree, SH storage degree,
  * rolling-shutter iterations, hit counts), gut_optimize_after_bwd takes a NULL camera position, GUT_OPT_KERNEL_TIMING_SET, and the
- * unsorted backward clamps alpha with the reference's literal 0.99 whatever particle_kernel_max_alpha is. */
-#define GUT_ABI_VERSION 5
+ * unsorted backward clamps alpha with the reference's literal 0.99 whatever particle_kernel_max_alpha is; 6: GutRegularisation,
+ * gut_set_regularisation, gut_sh_adam_step_regularised, gut_adam_unwalked_waves_regularised, gut_sync_moments_ex,
+ * gut_regularisation_gradient, gut_regularisation_loss). */
+#define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
 
@@ -480,6 +482,51 @@ int gut_adam_unwalked_waves(void* stream, uint32_t num_particles, const uint8_t*
 int gut_adam_unwalked_waves_ex(void* stream, uint32_t num_particles, const uint8_t* d_wave_flags, float* d_raw12, float* d_raw_m,
                                float* d_raw_v, float* d_sh48, float* d_sh_m, float* d_sh_v, const float* lr12, const float* lr48,
                                float beta1, float beta2, float eps, uint32_t step, float* d_act12_out, const GutLazyMoments* lazy);
+
+/* ---- The MCMC recipe's opacity and scale regularisers (configs/base_mcmc.yaml:13-18, threedgrut/trainer.py:432-449) ----
+ *     loss_opacity = lambda_opacity * mean |sigmoid(d)|  over N,   loss_scale = lambda_scale * mean |exp(s)|  over 3N
+ * Their gradient w.r.t. a raw row (density logit d, column 3; log-scales s_k, columns 8..10) depends on that row alone:
+ *     dL/dd = density_coeff * sigmoid(d) (1 - sigmoid(d)),   dL/ds_k = scale_coeff * exp(s_k)
+ * with density_coeff = lambda_opacity / N and scale_coeff = lambda_scale / (3 N), evaluated on the parameters BEFORE the update.
+ * Every optimiser kernel that updates a row adds it to the row's photometric gradient (after the 1/world scaling of the data-parallel
+ * forms: it is counted once).  With a visibility mask (SelectiveAdam) rows with visibility 0 stay untouched, regulariser included.
+ * With a regulariser no row is gradient-free in the [N,12] block, so its moments are stored every step for every row; the lazy
+ * decay (GutLazyMoments) then governs the [N,48] block only, and gut_sync_moments_ex must be given the same setting.  Switching
+ * between "no regulariser" and "a regulariser" needs a gut_sync_moments(_ex) under the OLD setting first.
+ * d_partials (optional): [ceil(N / 64), 2] floats; the kernel that owns 64-row wave w writes (sum of sigmoid(d), sum of exp(s_k)) of
+ * the wave's pre-update rows, all of them (SelectiveAdam's untouched rows included).  Row-range calls (chunks) offset it by r0 / 64.
+ * A GutRegularisation with both coefficients 0 is the same as NULL: the unregularised kernels, bit for bit. */
+typedef struct GutRegularisation {
+    float density_coeff;   /* lambda_opacity / N */
+    float scale_coeff;     /* lambda_scale / (3 N) */
+    float* d_partials;     /* [ceil(N / 64), 2] or NULL */
+} GutRegularisation;
+/* handle paths (gut_optimize_rows_without_gradient + gut_optimize_after_bwd, or gut_optimize_finish_without_gradient): consumed by the
+ * next optimiser step; NULL clears it */
+int gut_set_regularisation(gut_handle h, const GutRegularisation* reg);
+/* stateless data-parallel paths: gut_sh_adam_step_ex / gut_adam_unwalked_waves_ex with a regulariser (NULL = none) */
+int gut_sh_adam_step_regularised(void* stream, uint32_t num_particles, int32_t sh_degree, uint32_t num_views,
+                                 const float* d_camera_positions, float* d_mrgb, float* d_raw_grad12, float grad_scale,
+                                 float* d_raw12, float* d_raw_m, float* d_raw_v, float* d_sh48, float* d_sh_m, float* d_sh_v,
+                                 const float* lr12, const float* lr48, float beta1, float beta2, float eps, uint32_t step,
+                                 const float* d_visibility, float* d_act12_out, uint32_t mrgb_view_stride, uint32_t flags,
+                                 const uint8_t* d_wave_flags, const GutLazyMoments* lazy, const GutRegularisation* reg);
+int gut_adam_unwalked_waves_regularised(void* stream, uint32_t num_particles, const uint8_t* d_wave_flags, float* d_raw12,
+                                        float* d_raw_m, float* d_raw_v, float* d_sh48, float* d_sh_m, float* d_sh_v, const float* lr12,
+                                        const float* lr48, float beta1, float beta2, float eps, uint32_t step, float* d_act12_out,
+                                        const GutLazyMoments* lazy, const GutRegularisation* reg);
+/* gut_sync_moments under a regulariser setting (non-NULL with a coefficient != 0: only the [N,48] moments are brought up to date) */
+int gut_sync_moments_ex(void* stream, uint32_t num_particles, float* d_raw_m, float* d_raw_v, float* d_sh_m, float* d_sh_v,
+                        const GutLazyMoments* lazy, uint32_t step, const GutRegularisation* reg);
+/* the unfused optimiser (gut_adam_step on a materialised raw gradient): adds the regulariser's gradient into d_raw_grad12 [N,12]
+ * (after any exchange) and writes the partials */
+int gut_regularisation_gradient(void* stream, uint32_t num_particles, const float* d_raw12, float* d_raw_grad12,
+                                const GutRegularisation* reg);
+/* the loss values from the partials of the last step, reduced in a fixed order: *d_opacity_loss = lambda_opacity * mean sigmoid,
+ * *d_scale_loss = lambda_scale * mean exp (device floats); d_loss (may be NULL): both are added onto that device float.  Order it
+ * behind every stream that wrote partials. */
+int gut_regularisation_loss(void* stream, uint32_t num_particles, const float* d_partials, float lambda_opacity, float lambda_scale,
+                            float* d_opacity_loss, float* d_scale_loss, float* d_loss);
 
 /* ---- "next" row N3: the densification statistics of GSStrategy.update_gradient_buffer (threedgrut/strategy/gs.py:
  * 106-115), which the reference's trainer runs between backward and optimiser in every iteration up to densify.end_iteration
