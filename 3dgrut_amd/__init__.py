@@ -6,6 +6,7 @@ The directory name starts with a digit, so import it with importlib:
 
 or through the drop-in alias package at the repository root: `import threedgut_tracer`.
 """
+from .evaluate import evaluate  # noqa: F401
 from .protocols import Batch  # noqa: F401
 from .tracer import (  # noqa: F401
     CameraModelParameters,
@@ -15,6 +16,7 @@ from .tracer import (  # noqa: F401
     fromOpenCVFisheyeCameraModelParameters,
     fromOpenCVPinholeCameraModelParameters,
 )
+from .trainer import Trainer  # noqa: F401
 
 __all__ = ["Tracer", "SplatRaster", "ShutterType", "CameraModelParameters", "Batch",
-           "fromOpenCVPinholeCameraModelParameters", "fromOpenCVFisheyeCameraModelParameters"]
+           "fromOpenCVPinholeCameraModelParameters", "fromOpenCVFisheyeCameraModelParameters", "Trainer", "evaluate"]

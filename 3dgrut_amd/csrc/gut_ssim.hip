@@ -11,6 +11,7 @@
 // staged in LDS once, the separable window runs horizontally into LDS and vertically in registers.
 // Forward also stores the three partial-derivative maps d(ssim)/d(mu1), d(ssim)/d(sigma1^2),
 // d(ssim)/d(sigma12) the backward needs (same scheme as fused-ssim); backward convolves them with the window.
+// The evaluation metrics (gut_image_metrics: MSE, PSNR, SSIM, L1) run the same forward without those maps.
 #include "gut_internal.h"
 
 namespace gut {
@@ -53,11 +54,14 @@ __device__ __forceinline__ float load_px(const float* __restrict__ img, const Im
 }
 
 // forward: partial sums of the valid-region SSIM map per workgroup + derivative maps (planar [C,H,W])
+// kMetrics (gut_image_metrics, no backward follows): the three derivative maps are not stored (their pointers may be null) and the
+// workgroup's sum of squared errors goes to partial_sq, next to the L1 partials.
+template <bool kMetrics>
 __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const float* __restrict__ img1,
                                                  const float* __restrict__ img2, float* __restrict__ partial,
                                                  float* __restrict__ partial_l1, float* __restrict__ dm_dmu1,
                                                  float* __restrict__ dm_dsigma1_sq, float* __restrict__ dm_dsigma12,
-                                                 uint32_t gx, uint32_t gy) {
+                                                 uint32_t gx, uint32_t gy, float* __restrict__ partial_sq) {
     // row strides chosen for the two 16-lane rows a 32-lane LDS access group covers: 48 = 16 mod 32 for the patches (row r and
     // r + 1 fall on disjoint halves of the 32 banks while the 11-tap window slides), 16 for the filtered rows (ditto for the
     // column pass).  With the earlier 27 / 17 the window passes lost 46 % of their LDS cycles to 2-way conflicts.
@@ -96,19 +100,23 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const f
         e11 += w * h[2][oy + k][ox]; e22 += w * h[3][oy + k][ox]; e12 += w * h[4][oy + k][ox];
     }
     const int x = x0 + ox, y = y0 + oy;
-    float val = 0.0f, l1 = 0.0f;
+    float val = 0.0f, l1 = 0.0f, sq = 0.0f;
     if (x < v.W && y < v.H) {
-        l1 = fabsf(s1[oy + kHalo][ox + kHalo] - s2[oy + kHalo][ox + kHalo]);
+        const float d = s1[oy + kHalo][ox + kHalo] - s2[oy + kHalo][ox + kHalo];
+        l1 = fabsf(d);
+        if constexpr (kMetrics) sq = d * d;
         const float C1 = 0.0001f, C2 = 0.0009f;
         const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
         const float sg1 = e11 - mu1_sq, sg2 = e22 - mu2_sq, sg12 = e12 - mu12;
         const float A = mu1_sq + mu2_sq + C1, B = sg1 + sg2 + C2, Cc = 2.0f * mu12 + C1, D = 2.0f * sg12 + C2;
         const float m = (Cc * D) / (A * B);
-        const size_t o = ((size_t)c * v.H + y) * v.W + x;
-        dm_dmu1[o] = (mu2 * 2.0f * D) / (A * B) - (mu2 * 2.0f * Cc) / (A * B) - (mu1 * 2.0f * Cc * D) / (A * A * B) +
-                     (mu1 * 2.0f * Cc * D) / (A * B * B);
-        dm_dsigma1_sq[o] = (-Cc * D) / (A * B * B);
-        dm_dsigma12[o] = (2.0f * Cc) / (A * B);
+        if constexpr (!kMetrics) {
+            const size_t o = ((size_t)c * v.H + y) * v.W + x;
+            dm_dmu1[o] = (mu2 * 2.0f * D) / (A * B) - (mu2 * 2.0f * Cc) / (A * B) - (mu1 * 2.0f * Cc * D) / (A * A * B) +
+                         (mu1 * 2.0f * Cc * D) / (A * B * B);
+            dm_dsigma1_sq[o] = (-Cc * D) / (A * B * B);
+            dm_dsigma12[o] = (2.0f * Cc) / (A * B);
+        }
         const bool valid = x >= kHalo && y >= kHalo && x < v.W - kHalo && y < v.H - kHalo;
         val = valid ? m : 0.0f;
     }
@@ -123,6 +131,13 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const f
         if ((tid & 63) == 0) red[tid >> 6] = l1;
         __syncthreads();
         if (tid == 0) partial_l1[slot] = red[0] + red[1] + red[2] + red[3];
+    }
+    if constexpr (kMetrics) {
+        __syncthreads();
+        for (int mk = 32; mk >= 1; mk >>= 1) sq += __shfl_xor(sq, mk);
+        if ((tid & 63) == 0) red[tid >> 6] = sq;
+        __syncthreads();
+        if (tid == 0) partial_sq[slot] = red[0] + red[1] + red[2] + red[3];
     }
 }
 
@@ -150,31 +165,52 @@ struct FinishArgs {
     float* out3 = nullptr;   // nullptr: nothing to finish (gut_ssim_backward)
 };
 
+// kMetrics (k_metrics_finish): the squared-error partials are summed as well, in the same order, and the output is the four
+// floats { MSE, PSNR, SSIM, L1 } (MSE over the same numel as L1); lambda_l1 / lambda_ssim are not used then.
+template <bool kMetrics>
 __device__ __forceinline__ void photometric_finish(const float* __restrict__ partial, const float* __restrict__ partial_l1,
                                                    int n, float inv_count_ssim, float inv_count_l1, float lambda_l1,
-                                                   float lambda_ssim, float* __restrict__ out3) {
-    __shared__ double red[2][4];
-    double a = 0.0, b = 0.0;
+                                                   float lambda_ssim, float* __restrict__ out3,
+                                                   const float* __restrict__ partial_sq = nullptr) {
+    __shared__ double red[kMetrics ? 3 : 2][4];
+    double a = 0.0, b = 0.0, q = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) {
         a += (double)partial[i];
         b += (double)partial_l1[i];
+        if constexpr (kMetrics) q += (double)partial_sq[i];
     }
     for (int mk = 32; mk >= 1; mk >>= 1) {
         a += __shfl_xor(a, mk);
         b += __shfl_xor(b, mk);
+        if constexpr (kMetrics) q += __shfl_xor(q, mk);
     }
     if ((threadIdx.x & 63) == 0) {
         red[0][threadIdx.x >> 6] = a;
         red[1][threadIdx.x >> 6] = b;
+        if constexpr (kMetrics) red[2][threadIdx.x >> 6] = q;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         const float ssim = (float)((red[0][0] + red[0][1] + red[0][2] + red[0][3]) * (double)inv_count_ssim);
         const float l1 = (float)((red[1][0] + red[1][1] + red[1][2] + red[1][3]) * (double)inv_count_l1);
-        out3[0] = lambda_l1 * l1 + lambda_ssim * (1.0f - ssim);
-        out3[1] = l1;
-        out3[2] = ssim;
+        if constexpr (kMetrics) {
+            const double mse = (red[2][0] + red[2][1] + red[2][2] + red[2][3]) * (double)inv_count_l1;
+            out3[0] = (float)mse;
+            out3[1] = mse > 0.0 ? (float)(10.0 * log10(1.0 / mse)) : __builtin_huge_valf();   // PSNR for a data range of 1
+            out3[2] = ssim;
+            out3[3] = l1;
+        } else {
+            out3[0] = lambda_l1 * l1 + lambda_ssim * (1.0f - ssim);
+            out3[1] = l1;
+            out3[2] = ssim;
+        }
     }
+}
+
+__global__ __launch_bounds__(256) void k_metrics_finish(const float* __restrict__ partial, const float* __restrict__ partial_l1,
+                                                       const float* __restrict__ partial_sq, int n, float inv_count_ssim,
+                                                       float inv_numel, float* __restrict__ out4) {
+    photometric_finish<true>(partial, partial_l1, n, inv_count_ssim, inv_numel, 0.f, 0.f, out4, partial_sq);
 }
 
 // backward: d(mean ssim)/d(img1) * upstream, written through the same strides as img1
@@ -189,7 +225,8 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const f
     __shared__ float s[3][kPatch][kRowStride];
     __shared__ float h[3][kPatch][kSTile];
     if (fin.out3 && blockIdx.x == 0 && blockIdx.z == 0)   // (block-uniform)
-        photometric_finish(fin.partial, fin.partial_l1, fin.n, fin.inv_count_ssim, fin.inv_count_l1, fin.lambda_l1, fin.lambda_ssim, fin.out3);
+        photometric_finish<false>(fin.partial, fin.partial_l1, fin.n, fin.inv_count_ssim, fin.inv_count_l1, fin.lambda_l1,
+                                  fin.lambda_ssim, fin.out3);
     const int c = blockIdx.z;
     int tx, ty;
     xcd_tile(blockIdx.x, gx, gy, &tx, &ty);
@@ -276,8 +313,8 @@ int gut_ssim_forward(void* stream, int32_t channels, int32_t height, int32_t wid
     const uint32_t gx = (width + 15) / 16, gy = (height + 15) / 16;
     const dim3 grid(gx * gy, 1, channels);
     const gut::ImgView v = make_view(channels, height, width, stride_c, stride_h, stride_w);
-    hipLaunchKernelGGL(gut::k_ssim_fwd, grid, dim3(256), 0, s, v, v, d_img1, d_img2, partial, (float*)nullptr, maps, maps + plane,
-                       maps + 2 * plane, gx, gy);
+    hipLaunchKernelGGL(gut::k_ssim_fwd<false>, grid, dim3(256), 0, s, v, v, d_img1, d_img2, partial, (float*)nullptr, maps,
+                       maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr);
     const double count = (double)channels * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     hipLaunchKernelGGL(gut::k_ssim_finish, dim3(1), dim3(256), 0, s, partial, (int)(grid.x * grid.z), (float)(1.0 / count),
                        d_mean_ssim);
@@ -321,8 +358,8 @@ int gut_photometric_loss(void* stream, int32_t height, int32_t width, const floa
     v.alpha_offset = 3;
     v.background = background;
     const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
-    hipLaunchKernelGGL(gut::k_ssim_fwd, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, maps, maps + plane,
-                       maps + 2 * plane, gx, gy);
+    hipLaunchKernelGGL(gut::k_ssim_fwd<false>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, maps,
+                       maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr);
     const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     const double numel = 3.0 * height * width;
     gut::FinishArgs fin;
@@ -335,6 +372,36 @@ int gut_photometric_loss(void* stream, int32_t height, int32_t width, const floa
         const int pixels = height * width;
         hipLaunchKernelGGL(gut::k_alpha_grad, dim3((pixels + 255) / 256), dim3(256), 0, s, pixels, background, d_rgba_grad);
     }
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// three arrays of per-workgroup partials (SSIM, L1, squared error; 3 channels x tiles entries, 64 floats of slack after each)
+size_t gut_image_metrics_workspace_bytes(int32_t height, int32_t width) {
+    const size_t blocks = (size_t)((width + 15) / 16) * ((height + 15) / 16) * 3;
+    return 3 * (blocks + 64) * sizeof(float) + 256;
+}
+
+int gut_image_metrics(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
+                      void* d_workspace, float* d_out4) {
+    if (!d_rgba || !d_gt_rgb || !d_workspace || !d_out4) return 1;
+    if (height <= 2 * gut::kHalo || width <= 2 * gut::kHalo) return 1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t gx = (width + 15) / 16, gy = (height + 15) / 16;
+    const dim3 grid(gx * gy, 1, 3);
+    const int nblocks = (int)(grid.x * grid.z);
+    float* partial = static_cast<float*>(d_workspace);
+    float* partial_l1 = partial + nblocks + 64;
+    float* partial_sq = partial_l1 + nblocks + 64;
+    gut::ImgView v = make_view(3, height, width, 1, 4 * (int64_t)width, 4);   // rgba, interleaved
+    v.alpha_offset = 3;
+    v.background = background;
+    const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
+    hipLaunchKernelGGL(gut::k_ssim_fwd<true>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, (float*)nullptr,
+                       (float*)nullptr, (float*)nullptr, gx, gy, partial_sq);
+    const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
+    const double numel = 3.0 * height * width;
+    hipLaunchKernelGGL(gut::k_metrics_finish, dim3(1), dim3(256), 0, s, partial, partial_l1, partial_sq, nblocks,
+                       (float)(1.0 / count), (float)(1.0 / numel), d_out4);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

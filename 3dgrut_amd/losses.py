@@ -88,6 +88,37 @@ def loss_weights(loss_conf):
     return dict(lambda_l1=weight("l1"), lambda_ssim=weight("ssim"), lambda_opacity=weight("opacity"), lambda_scale=weight("scale"))
 
 
+def image_metrics(rgba, gt_rgb, background="black", out=None):
+    """Evaluation metrics of one view on the GPU (gut_image_metrics, csrc/gut_ssim.hip): a float32 device tensor [4] = (MSE, PSNR,
+    SSIM, L1) of image = rgb + background * (1 - alpha) against gt_rgb, unclamped, as the reference scores outputs["pred_rgb"]
+    (render.py:137-285; PSNR for a data range of 1, SSIM the valid-region mean of the training loss).  rgba: [H,W,4] (or [1,H,W,4]),
+    gt_rgb: [H,W,3] (or [1,H,W,3]), both float32 on the GPU; background: "black", "white" or 0.0 / 1.0.  out: a float32 device
+    tensor of 4 contiguous elements to write into (e.g. row i of an evaluation pass's [V,4] tensor); nothing is read back."""
+    bg = {"black": 0.0, "white": 1.0}.get(background, background)
+    if isinstance(bg, str):
+        raise ValueError(f"image_metrics: background must be 'black', 'white' or a number, got {background!r}")
+    rgba = rgba.reshape(rgba.shape[-3:]) if rgba.dim() == 4 and rgba.shape[0] == 1 else rgba
+    gt_rgb = gt_rgb.reshape(gt_rgb.shape[-3:]) if gt_rgb.dim() == 4 and gt_rgb.shape[0] == 1 else gt_rgb
+    if rgba.dim() != 3 or rgba.shape[2] != 4 or tuple(gt_rgb.shape) != (rgba.shape[0], rgba.shape[1], 3):
+        raise RuntimeError(f"[image_metrics] expected rgba [H,W,4] and gt [H,W,3], got {tuple(rgba.shape)} and {tuple(gt_rgb.shape)}")
+    if not rgba.is_cuda or rgba.dtype != torch.float32 or gt_rgb.dtype != torch.float32 or gt_rgb.device != rgba.device:
+        raise RuntimeError("[image_metrics] expected float32 GPU tensors on one device (there is no CPU path)")
+    rgba, gt_rgb = rgba.contiguous(), gt_rgb.contiguous()
+    if out is None:
+        out = torch.empty((4,), dtype=torch.float32, device=rgba.device)
+    elif out.dtype != torch.float32 or out.device != rgba.device or out.numel() != 4 or not out.is_contiguous():
+        raise RuntimeError("[image_metrics] out must be a contiguous float32 tensor of 4 elements on the images' device")
+    lib = _capi.load()
+    H, W = int(rgba.shape[0]), int(rgba.shape[1])
+    ws = torch.empty(((lib.gut_image_metrics_workspace_bytes(H, W) + 3) // 4,), dtype=torch.float32, device=rgba.device)
+    stream = torch.cuda.current_stream(rgba.device).cuda_stream
+    with torch.cuda.device(rgba.device):
+        rc = lib.gut_image_metrics(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(), float(bg), ws.data_ptr(), out.data_ptr())
+    if rc:
+        raise RuntimeError(f"[image_metrics] failed ({rc}); images must exceed 10x10")
+    return out
+
+
 def photometric_loss(pred_rgb, gt_rgb, lambda_l1=0.8, lambda_ssim=0.2):
     """pred/gt [B,H,W,3].  lambda_l1*L1 + lambda_ssim*(1-SSIM)  (configs/base_gs.yaml:111-119, trainer.py:425-449)."""
     s = fused_ssim(pred_rgb.permute(0, 3, 1, 2), gt_rgb.permute(0, 3, 1, 2), padding="valid")

@@ -1,0 +1,436 @@
+"""End-to-end trainer: the reference's `python train.py --config-name apps/colmap_3dgut.yaml path=...` (threedgrut/trainer.py:
+693-806 `run_train_pass`, 861-886 `run_training`, render.py:137-285 for the test split) composed from this tree's pieces:
+
+    NativeGaussianModel(spatial_order=True)      parameters in the tracer's layouts
+    NativeTrainStep(schedule=TrainSchedule)      fused loss, lazy Adam moments, side-stream optimiser, in-kernel densification
+                                                 statistics; the position-lr decay and the SH-degree ramp run at the end of step()
+    GSStrategy(...).attach() / MCMCStrategy      densify / prune / reset / decay, or relocate / add / perturb
+    evaluate()                                   held-out PSNR / SSIM on the GPU (gut_image_metrics)
+
+`conf` is a plain dict with the reference's key names; what it leaves out comes from configs/base_gs.yaml + strategy/gs.yaml, or
+base_mcmc.yaml + strategy/mcmc.yaml for `strategy.method == "MCMCStrategy"` (`default_config`).  The loop adds no host
+synchronisation between events: the loss is read back only when a validation runs.
+
+Checkpoints hold the reference's get_model_parameters() keys (model/model.py:107-134) with the optimiser state in
+torch.optim.Adam.state_dict() layout (six groups, named and ordered as configs/base_gs.yaml), `global_step`, `epoch`, the GS
+strategy's densification buffers as 1-tuples (strategy/gs.py:42-48), and one key `native` with what only this trainer needs.
+Everything in it is a tensor, number, string, list, tuple or dict: `torch.load(path, weights_only=True)` reads it.  Checkpoints
+written by the reference itself (an OmegaConf config inside) are not read.
+
+    python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
+                                 [--test-split-interval 8] [--resume CKPT]
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+from . import losses
+from .evaluate import _check_batch, evaluate
+
+# configs/base_gs.yaml + configs/strategy/gs.yaml: the keys this trainer reads
+GS_CONFIG = {
+    "out_dir": "./runs", "resume": "", "n_iterations": 30000, "val_frequency": 5000, "validate_first": False, "test_last": True,
+    "seed": 0,
+    "checkpoint": {"iterations": [7000, 30000]},
+    "model": {"default_density": 0.1, "default_scale_factor": 1.0,
+              "progressive_training": {"feature_type": "sh", "init_n_features": 0, "max_n_features": 3, "increase_frequency": 1000,
+                                       "increase_step": 1},
+              "background": {"name": "background-color", "color": "black"}},
+    "optimizer": {"type": "adam", "eps": 1e-15,
+                  "params": {"positions": {"lr": 0.00016}, "density": {"lr": 0.05}, "features_albedo": {"lr": 0.0025},
+                             "features_specular": {"lr": 0.0025 / 20}, "rotation": {"lr": 0.001}, "scale": {"lr": 0.005}}},
+    "scheduler": {"positions": {"type": "exp", "lr_final": 0.0000016, "max_steps": 30000}},
+    "loss": {"use_l1": True, "lambda_l1": 0.8, "use_l2": False, "lambda_l2": 1.0, "use_ssim": True, "lambda_ssim": 0.2,
+             "use_opacity": False, "lambda_opacity": 0.0, "use_scale": False, "lambda_scale": 0.0},
+    "render": {"enable_kernel_timings": False},
+    "strategy": {"method": "GSStrategy",
+                 "densify": {"frequency": 300, "start_iteration": 500, "end_iteration": 15000, "clone_grad_threshold": 0.0002,
+                             "split_grad_threshold": 0.0002, "relative_size_threshold": 0.01, "split": {"n_gaussians": 2}},
+                 "prune": {"frequency": 100, "start_iteration": 500, "end_iteration": 15000, "density_threshold": 0.005},
+                 # end_iteration None: ${strategy.densify.end_iteration}, as the yaml interpolates it
+                 "reset_density": {"frequency": 3000, "start_iteration": 0, "end_iteration": None, "new_max_density": 0.01},
+                 "density_decay": {"gamma": 0.99, "start_iteration": -1, "end_iteration": -1, "frequency": 50}},
+}
+# configs/base_mcmc.yaml + configs/strategy/mcmc.yaml over GS_CONFIG
+MCMC_OVERRIDES = {
+    "model": {"default_density": 0.5, "default_scale_factor": 0.1},
+    "loss": {"use_opacity": True, "lambda_opacity": 0.01, "use_scale": True, "lambda_scale": 0.01},
+    "strategy": {"method": "MCMCStrategy", "binom_n_max": 51, "opacity_threshold": 0.005,
+                 "relocate": {"start_iteration": 500, "end_iteration": 25000, "frequency": 100},
+                 "perturb": {"start_iteration": 0, "end_iteration": 27500, "frequency": 1, "noise_lr": 500000.0},
+                 "add": {"start_iteration": 500, "end_iteration": 25000, "frequency": 100, "max_n_gaussians": 1000000}},
+}
+# the reference's optimiser groups, in configs/base_gs.yaml order, and where each lives in the native tensors
+PARAM_GROUPS = ("positions", "density", "features_albedo", "features_specular", "rotation", "scale")
+_GROUP_COLS = {"positions": ("12", slice(0, 3)), "density": ("12", slice(3, 4)), "rotation": ("12", slice(4, 8)),
+               "scale": ("12", slice(8, 11)), "features_albedo": ("48", slice(0, 3)), "features_specular": ("48", slice(3, 48))}
+
+
+def _merge(base, over):
+    """Deep merge of plain dicts: `over` wins, nested dicts are merged key by key."""
+    out = copy.deepcopy(base)
+    for k, v in (over or {}).items():
+        out[k] = _merge(out[k], v) if isinstance(v, dict) and isinstance(out.get(k), dict) else copy.deepcopy(v)
+    return out
+
+
+def default_config(method="GSStrategy"):
+    """The reference's defaults for `method` ("GSStrategy" or "MCMCStrategy") as a plain dict."""
+    if method == "GSStrategy":
+        return copy.deepcopy(GS_CONFIG)
+    if method == "MCMCStrategy":
+        base = copy.deepcopy(GS_CONFIG)
+        base["strategy"] = {}
+        return _merge(base, MCMC_OVERRIDES)
+    raise ValueError(f"unknown strategy.method {method!r} (GSStrategy or MCMCStrategy)")
+
+
+def resolve_config(conf):
+    """conf (a plain dict, any subset of the reference's keys) over the defaults of its strategy.method."""
+    conf = dict(conf or {})
+    method = (conf.get("strategy") or {}).get("method", "GSStrategy")
+    out = _merge(default_config(method), conf)
+    if method == "GSStrategy" and out["strategy"]["reset_density"].get("end_iteration") is None:
+        out["strategy"]["reset_density"]["end_iteration"] = out["strategy"]["densify"]["end_iteration"]
+    if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
+        # ${div:${optimizer.params.features_albedo.lr},20}
+        out["optimizer"]["params"]["features_specular"] = {"lr": float(out["optimizer"]["params"]["features_albedo"]["lr"]) / 20}
+    return out
+
+
+def _stage(t, s):
+    """(start, end, frequency) of a strategy block (utils/misc.check_step_condition's arguments)."""
+    return (int(t[s]["start_iteration"]), int(t[s]["end_iteration"]), int(t[s]["frequency"]))
+
+
+def gs_schedule(conf):
+    s = conf["strategy"]
+    return dict(densify=_stage(s, "densify"), prune=_stage(s, "prune"), reset_density=_stage(s, "reset_density"),
+                density_decay=_stage(s, "density_decay"))
+
+
+def mcmc_schedule(conf):
+    s = conf["strategy"]
+    return dict(relocate=_stage(s, "relocate"), add=_stage(s, "add"), perturb=_stage(s, "perturb"))
+
+
+def epoch_permutation(seed, epoch, n):
+    """View order of one epoch: a permutation from a torch.Generator seeded with (seed, epoch), so that a resumed run walks the
+    same order from the same step on (the reference uses a shuffling DataLoader)."""
+    g = torch.Generator().manual_seed(int(seed) * 1_000_003 + int(epoch))
+    return torch.randperm(int(n), generator=g).tolist()
+
+
+def _plain(x):
+    """conf -> only dicts, lists, strings, numbers, bools and None (what torch.load(weights_only=True) accepts)."""
+    if isinstance(x, dict):
+        return {str(k): _plain(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_plain(v) for v in x]
+    if isinstance(x, (bool, int, float, str)) or x is None:
+        return x
+    if isinstance(x, np.generic):
+        return x.item()
+    return str(x)
+
+
+def _adam_group_template(betas, eps):
+    """The param_groups entry torch.optim.Adam itself would write (every key of the installed torch version)."""
+    g = torch.optim.Adam([torch.zeros(1)], lr=1.0, betas=tuple(betas), eps=float(eps)).state_dict()["param_groups"][0]
+    g.pop("params")
+    return g
+
+
+def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=None):
+    """The checkpoint dictionary of a NativeTrainStep's state (see the module docstring)."""
+    from .io_ply import checkpoint_dict
+    st = stepper.state_dict()   # moments brought up to date (sync_moments) and cloned
+    m = stepper.model
+    moments = {("12", 0): st["exp_avg_raw"], ("12", 1): st["exp_avg_sq_raw"], ("48", 0): st["exp_avg_features"],
+               ("48", 1): st["exp_avg_sq_features"]}
+    lr = {"12": np.asarray(stepper.lr12, np.float32), "48": np.asarray(stepper.lr48, np.float32)}
+    tmpl = _adam_group_template(getattr(stepper, "betas", (0.9, 0.999)), getattr(stepper, "eps", 1e-15))
+    state, groups = {}, []
+    for i, name in enumerate(PARAM_GROUPS):
+        block, cols = _GROUP_COLS[name]
+        state[i] = {"step": torch.tensor(float(st["step"])), "exp_avg": moments[(block, 0)][:, cols].contiguous(),
+                    "exp_avg_sq": moments[(block, 1)][:, cols].contiguous()}
+        groups.append(dict(tmpl, lr=float(lr[block][cols.start]), name=name, params=[i]))
+    prog = conf["model"]["progressive_training"]
+    sched = getattr(stepper, "schedule", None)
+    progressive = int(prog["init_n_features"]) < int(prog["max_n_features"])
+    color = conf["model"]["background"]["color"]
+    extra = {
+        "background": {"color": torch.full((3,), 1.0 if color == "white" else 0.0, dtype=torch.float32)},
+        "progressive_training": progressive, "scene_extent": float(scene_extent), "config": _plain(conf),
+        "optimizer": {"state": state, "param_groups": groups}, "global_step": int(global_step), "epoch": int(epoch),
+        "native": {"step": int(st["step"]), "lr_raw": torch.as_tensor(lr["12"]).clone(), "lr_features": torch.as_tensor(lr["48"]).clone(),
+                   "position_lr": float(sched.position_lr) if sched is not None else float(lr["12"][0]),
+                   # column 11 of the raw rows (unused by the kernels) and of their two moments: not a reference parameter
+                   "pad": torch.stack([m.raw[:, 11], st["exp_avg_raw"][:, 11], st["exp_avg_sq_raw"][:, 11]], 1).detach().clone(),
+                   "permutation": None if getattr(m, "permutation", None) is None else m.permutation.detach().clone(),
+                   "spatial_order": bool(getattr(m, "spatial_order", False))},
+    }
+    if progressive:
+        extra["feature_dim_increase_interval"] = int(prog["increase_frequency"])
+        extra["feature_dim_increase_step"] = int(prog["increase_step"])
+    if strategy is not None and hasattr(strategy, "grad_norm_accum"):
+        extra["densify_grad_norm_accum"] = (strategy.grad_norm_accum.detach().clone(),)
+        extra["densify_grad_norm_denom"] = (strategy.grad_norm_denom.detach().clone(),)
+    return checkpoint_dict(m, extra)
+
+
+def checkpoint_tensors(ckpt, device):
+    """(raw [N,12], features [N,48], optimiser state for NativeTrainStep.load_state_dict) of a checkpoint dictionary."""
+    dev = torch.device(device)
+    t = lambda x: x.to(dev)
+    nat = ckpt["native"]
+    pad = t(nat["pad"])
+    raw = torch.cat([t(ckpt["positions"]), t(ckpt["density"]), t(ckpt["rotation"]), t(ckpt["scale"]), pad[:, 0:1]], 1).contiguous()
+    features = torch.cat([t(ckpt["features_albedo"]), t(ckpt["features_specular"])], 1).contiguous()
+    st = ckpt["optimizer"]["state"]
+    by_name = {g["name"]: st[g["params"][0]] for g in ckpt["optimizer"]["param_groups"]}
+    state = {"step": int(nat["step"]), "lr_raw": nat["lr_raw"].cpu().numpy()}
+    for k, key in ((0, "exp_avg"), (1, "exp_avg_sq")):
+        raw_m = torch.cat([t(by_name[n][key]) for n in ("positions", "density", "rotation", "scale")] + [pad[:, 1 + k:2 + k]], 1)
+        feat_m = torch.cat([t(by_name[n][key]) for n in ("features_albedo", "features_specular")], 1)
+        state["exp_avg_raw" if k == 0 else "exp_avg_sq_raw"] = raw_m.contiguous()
+        state["exp_avg_features" if k == 0 else "exp_avg_sq_features"] = feat_m.contiguous()
+    return raw, features, state
+
+
+class Trainer:
+    """The reference's training run on the native pieces.  `scene`: the initial Gaussians (activated parameters, the dict
+    io_colmap.ColmapScene.initial_gaussians / scenes.* return); `*_batches`: protocols.Batch with rgb_gt (no mask).
+
+    stepper / strategy / evaluator: replacements of the NativeTrainStep, the strategy object and `evaluate` (tests); with a
+    stepper given, `scene` is not used and the model is stepper.model."""
+
+    def __init__(self, conf, scene, train_batches, val_batches=(), test_batches=(), scene_extent=1.0, stepper=None, strategy=None,
+                 evaluator=None, tracer=None):
+        self.conf = resolve_config(conf)
+        c = self.conf
+        self.train_batches, self.val_batches, self.test_batches = list(train_batches), list(val_batches), list(test_batches)
+        if not self.train_batches:
+            raise ValueError("Trainer: no training views")
+        for what, bs in (("train", self.train_batches), ("validation", self.val_batches), ("test", self.test_batches)):
+            for b in bs:
+                _check_batch(b, f"Trainer ({what} batch)")
+        self.scene_extent = float(scene_extent)
+        self.method = c["strategy"]["method"]
+        self.evaluator = evaluate if evaluator is None else evaluator
+        self.global_step = 0
+        self.validations = []    # dict(step, loss, mean_psnr, ...) per validation pass
+        self.stats = None
+        self.test_metrics = None
+        resume = c.get("resume") or ""
+        ckpt = torch.load(resume, map_location="cpu", weights_only=True) if resume else None
+        if stepper is None:
+            stepper, tracer = self._build(scene, ckpt, tracer)
+        self.stepper, self.tracer = stepper, tracer if tracer is not None else getattr(stepper, "tracer", None)
+        self.model = stepper.model
+        self.strategy = self._build_strategy(ckpt) if strategy is None else strategy
+        if ckpt is not None:
+            self.global_step = int(ckpt["global_step"])
+
+    # ---- construction ----
+    def _build(self, scene, ckpt, tracer):
+        from .native import NativeGaussianModel, NativeTrainStep
+        from .schedule import TrainSchedule
+        from .tracer import Tracer
+        c = self.conf
+        prog = c["model"]["progressive_training"]
+        if int(prog["max_n_features"]) != 3:
+            raise ValueError("Trainer: model.progressive_training.max_n_features must be 3 (the fused optimiser's SH layout)")
+        if c["optimizer"]["type"] not in ("adam", "selective_adam"):
+            raise ValueError(f"Unknown optimizer type: {c['optimizer']['type']}")
+        lr = {k: float(v["lr"]) for k, v in c["optimizer"]["params"].items()}
+        sp = c["scheduler"]["positions"]
+        sched = TrainSchedule(self.scene_extent, lr_init=lr["positions"], lr_final=float(sp["lr_final"]), max_steps=int(sp["max_steps"]),
+                              init_n_features=int(prog["init_n_features"]), max_n_features=int(prog["max_n_features"]),
+                              increase_frequency=int(prog["increase_frequency"]), increase_step=int(prog["increase_step"]))
+        if tracer is None:
+            tracer = Tracer({"render": dict(c.get("render") or {})})
+        bg = c["model"]["background"]["color"]
+        if ckpt is None:
+            model = NativeGaussianModel(scene, sh_degree=sched.n_active_features, background_color=bg, spatial_order=True)
+            state = None
+        else:
+            raw, features, state = checkpoint_tensors(ckpt, "cuda")
+            nat = ckpt["native"]
+            perm = nat.get("permutation")
+            model = NativeGaussianModel.from_tensors(raw, features, sh_degree=int(ckpt["n_active_features"]), background_color=bg,
+                                                     spatial_order=bool(nat.get("spatial_order", True)),
+                                                     permutation=None if perm is None else perm.to(raw.device))
+            sched.position_lr = float(nat["position_lr"])      # the schedule's state: current position rate and SH degree
+            sched.n_active_features = int(ckpt["n_active_features"])
+        stepper = NativeTrainStep(model, tracer, scene_extent=self.scene_extent, selective=c["optimizer"]["type"] == "selective_adam",
+                                  eps=float(c["optimizer"].get("eps", 1e-15)), schedule=sched, **losses.loss_weights(c["loss"]))
+        stepper.lr12[0:3] = sched.position_lr
+        stepper.lr12[3] = lr["density"]
+        stepper.lr12[4:8] = lr["rotation"]
+        stepper.lr12[8:11] = lr["scale"]
+        stepper.lr48[0:3] = lr["features_albedo"]
+        stepper.lr48[3:] = lr["features_specular"]
+        if state is not None:
+            stepper.load_state_dict(state)   # moments, step counter (the lazy waves re-based on it), learning rates
+        return stepper, tracer
+
+    def _build_strategy(self, ckpt):
+        from .strategy import GSStrategy, MCMCStrategy
+        s, seed = self.conf["strategy"], int(self.conf["seed"])
+        if self.method == "GSStrategy":
+            d = s["densify"]
+            gs = GSStrategy(self.stepper, clone_grad_threshold=float(d["clone_grad_threshold"]), split_grad_threshold=float(d["split_grad_threshold"]),
+                            relative_size_threshold=float(d["relative_size_threshold"]), split_n_gaussians=int(d["split"]["n_gaussians"]),
+                            prune_density_threshold=float(s["prune"]["density_threshold"]),
+                            new_max_density=float(s["reset_density"]["new_max_density"]), density_decay_gamma=float(s["density_decay"]["gamma"]),
+                            seed=seed, schedule=gs_schedule(self.conf))
+            if ckpt is not None and "densify_grad_norm_accum" in ckpt:
+                dev = self.model.raw.device
+                gs.grad_norm_accum = ckpt["densify_grad_norm_accum"][0].to(dev).contiguous()
+                gs.grad_norm_denom = ckpt["densify_grad_norm_denom"][0].to(dev).contiguous()
+            step = int(ckpt["global_step"]) if ckpt is not None else 0
+            if step < gs.schedule["densify"][1]:
+                gs.attach()
+            return gs
+        if self.method == "MCMCStrategy":
+            return MCMCStrategy(self.stepper, opacity_threshold=float(s["opacity_threshold"]), binom_n_max=int(s["binom_n_max"]),
+                                max_n_gaussians=int(s["add"]["max_n_gaussians"]), noise_lr=float(s["perturb"]["noise_lr"]), seed=seed,
+                                schedule=mcmc_schedule(self.conf))
+        raise ValueError(f"unknown strategy.method {self.method!r}")
+
+    # ---- the loop ----
+    def batch_index(self, step):
+        """Index into train_batches of global step `step`: epoch step // V walks epoch_permutation(seed, epoch)."""
+        n = len(self.train_batches)
+        epoch = step // n
+        if getattr(self, "_perm_epoch", None) != epoch:
+            self._perm, self._perm_epoch = epoch_permutation(self.conf["seed"], epoch, n), epoch
+        return self._perm[step % n]
+
+    @property
+    def epoch(self):
+        return self.global_step // len(self.train_batches)
+
+    def _out_dir(self):
+        d = self.conf.get("out_dir") or ""
+        return d or None
+
+    def _sync(self):
+        raw = getattr(self.model, "raw", None)
+        if raw is not None and raw.is_cuda:
+            torch.cuda.synchronize(raw.device)
+
+    def validate(self):
+        """Validation pass on val_batches (trainer.py:805-842): held-out metrics and the last training loss."""
+        if not self.val_batches:
+            return None
+        res = self.evaluator(self.model, self.tracer, self.val_batches, None, self.global_step)
+        loss = getattr(self, "_last_loss", None)
+        entry = dict(step=self.global_step, loss=None if loss is None else float(loss), mean_psnr=res["mean_psnr"],
+                     mean_ssim=res["mean_ssim"], n_gaussians=int(self.model.num_gaussians))
+        self.validations.append(entry)
+        if self.conf.get("verbose", False):
+            print(f"[trainer] step {entry['step']}: loss {entry['loss']} val psnr {entry['mean_psnr']:.3f} ssim {entry['mean_ssim']:.4f} "
+                  f"N {entry['n_gaussians']}", flush=True)
+        return res
+
+    def _post_optimizer_step(self, step):
+        if self.method == "MCMCStrategy":
+            return self.strategy.post_optimizer_step(step, float(self.stepper.lr12[0]))
+        return self.strategy.post_optimizer_step(step, self.scene_extent)
+
+    def checkpoint(self):
+        return make_checkpoint(self.stepper, self.conf, self.global_step, self.epoch, self.scene_extent,
+                               self.strategy if self.method == "GSStrategy" else None)
+
+    def save_checkpoint(self, last=False):
+        out = self._out_dir()
+        if out is None:
+            return None
+        g = self.global_step
+        path = os.path.join(out, "ckpt_last.pt") if last else os.path.join(out, f"ours_{g}", f"ckpt_{g}.pt")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        torch.save(self.checkpoint(), path)
+        return path
+
+    def train(self):
+        """run_train_pass over as many epochs as n_iterations needs.  Returns the statistics table."""
+        c = self.conf
+        n_iter = int(c["n_iterations"])
+        val_freq = max(1, int(c["val_frequency"]))
+        ckpt_steps = {int(k) for k in c["checkpoint"]["iterations"]}
+        start = self.global_step
+        self._sync()
+        t0 = time.perf_counter()
+        while self.global_step < n_iter:
+            g = self.global_step
+            batch = self.train_batches[self.batch_index(g)]
+            if (g > 0 or c["validate_first"]) and g % val_freq == 0:
+                self.validate()
+            self._last_loss, _ = self.stepper.step(batch)   # scheduler + SH ramp run at the end of step()
+            self._post_optimizer_step(g)
+            self.global_step = g + 1
+            if self.global_step in ckpt_steps:
+                self.save_checkpoint()
+        self._sync()
+        elapsed = time.perf_counter() - t0
+        self.stats = dict(n_steps=self.global_step, n_epochs=-(-self.global_step // len(self.train_batches)), steps_run=self.global_step - start,
+                          training_time=elapsed, iteration_speed=self.global_step / elapsed if elapsed > 0 else float("inf"),
+                          n_gaussians=int(self.model.num_gaussians))
+        return self.stats
+
+    def run(self):
+        """train(), print the statistics table, then (test_last) save ckpt_last.pt and evaluate the test split."""
+        stats = self.train()
+        print("Training Statistics: " + json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in stats.items()}), flush=True)
+        if self.conf["test_last"] and self.test_batches:
+            self.save_checkpoint(last=True)
+            self.test_metrics = self.evaluator(self.model, self.tracer, self.test_batches, self._out_dir(), self.global_step)
+        return dict(stats=stats, test=self.test_metrics)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m 3dgrut_amd.trainer", description="Train a COLMAP scene and score its test split.")
+    ap.add_argument("--path", required=True, help="COLMAP scene directory (sparse/0 + images[_F])")
+    ap.add_argument("--out-dir", default=None)
+    ap.add_argument("--n-iterations", type=int, default=None)
+    ap.add_argument("--strategy", choices=("gs", "mcmc"), default="gs")
+    ap.add_argument("--downsample", type=int, default=1)
+    ap.add_argument("--test-split-interval", type=int, default=8)
+    ap.add_argument("--resume", default="")
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    from .io_colmap import ColmapScene
+    conf = default_config("MCMCStrategy" if a.strategy == "mcmc" else "GSStrategy")
+    if a.out_dir is not None:
+        conf["out_dir"] = a.out_dir
+    if a.n_iterations is not None:
+        conf["n_iterations"] = a.n_iterations
+    conf["resume"], conf["seed"] = a.resume, a.seed
+    train = ColmapScene(a.path, "train", a.downsample, a.test_split_interval)
+    test = ColmapScene(a.path, "test", a.downsample, a.test_split_interval)
+    # configs/initialization/colmap.yaml: observation-point scales, the model's default density / scale factor
+    init = None if a.resume else train.initial_gaussians(use_observation_points=True, default_density=conf["model"]["default_density"],
+                                                         default_scale_factor=conf["model"]["default_scale_factor"], seed=a.seed)
+    tb = [train.batch(i) for i in range(len(train))]
+    vb = [test.batch(i) for i in range(len(test))]
+    trainer = Trainer(conf, init, tb, val_batches=vb, test_batches=vb, scene_extent=train.cameras_extent)
+    res = trainer.run()
+    test_res = res["test"]
+    out = dict(stats=res["stats"])
+    if test_res is not None:
+        out["test"] = {k: test_res[k] for k in ("mean_psnr", "std_psnr", "mean_ssim", "n_views", "mean_inference_time") if k in test_res}
+    print(json.dumps(out), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -327,6 +327,17 @@ size_t gut_photometric_workspace_bytes(int32_t height, int32_t width);
 int gut_photometric_loss(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
                          float lambda_l1, float lambda_ssim, void* d_workspace, float* d_loss3, float* d_rgba_grad);
 
+/* Evaluation metrics of one view (the reference's test-split scoring, threedgrut/render.py:137-285), forward only, no gradient:
+ * d_out4 receives { MSE, PSNR, SSIM, L1 } of image = rgb + background * (1 - alpha) against d_gt_rgb, values unclamped.
+ * PSNR = 10 log10(1 / MSE) (a data range of 1; +inf for MSE == 0), SSIM = the valid-region mean SSIM of gut_photometric_loss (equal to
+ * the reflect-padded, border-cropped mean of torchmetrics' StructuralSimilarityIndexMeasure).  The same forward kernel as the loss
+ * without the derivative maps; the per-workgroup partials are summed in double in a fixed order (identical inputs, identical bits).
+ * d_out4 may point into a caller's [V,4] device tensor.  Returns 1 for a null pointer or height / width <= 10.  Workspace: caller-owned
+ * device memory of gut_image_metrics_workspace_bytes(). */
+size_t gut_image_metrics_workspace_bytes(int32_t height, int32_t width);
+int gut_image_metrics(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
+                      void* d_workspace, float* d_out4);
+
 /* ---- "next" row N2: parameter activation + fused Adam ----
  * gut_activate_pack: raw rows [N,12] (pos3, density logit, quat4, log-scale3, unused) -> activated rows
  *   (pos3, sigmoid, quat/|quat|, exp, |quat|) = the particle_density the tracer consumes (model.py:74-93 +
