@@ -309,3 +309,28 @@ def densified_like_scene(n=20000, seed=5):
 # K_BAND = 2.5 is the one factor between "two CPU evaluations" and "the GPU": the GPU adds fp32 (instead of double) sums over
 # the pixels of a wave and float atomics across waves on top of what variant 2 models.
 K_BAND = 2.5
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The element-wise optimiser / activation tests (tests/reference_step.py, tests/test_gpu_step_elements.py): every element obeys
+#       |gpu - float64| <= K x 2^-23 x S + (half an ulp of the result, the format's underflow steps, the inputs' own uncertainty)
+# with S the sum of the ABSOLUTE terms the element is formed from (reference_step.Cond).  The one constant per family is measured on
+# the CPU, between float64 and two float32 evaluations that are both legitimate — (a) one IEEE rounding per operation, (b) products
+# rounded once (FMA), host-side reciprocals of the bias corrections, 1/x and sqrt(x) moved by -1 / 0 / +1 ulp (numpy float32 and
+# torch-CPU float32 for the activations and their chain rule) — on the whole input table (v from denormal to 1e20, cancelling
+# moments, steps 0 ... 1e6, eps 1e-15 and 1e-8, logits -100 ... 89, quaternion norms 1e-20 ... 1e6), and
+# tests/test_cpu_reference_step.py asserts that the model with K / K_BAND bounds that band on EVERY element:
+#     measured worst (|fp32 - fp64| - non-scaling terms) / (2^-23 S)                               K = K_BAND x that, rounded up
+#     Adam, parameter, fast-math form (b): 3.66                                                      K_ADAM      = 10
+#     Adam, parameter, IEEE forms — (a), and (a') = (a) with the moment sums rounded once, what                K_ADAM_IEEE = 6
+#       contraction makes of k_adam_step / k_selective_adam: 2.39 both (2.39 x 2.5 = 5.97)
+#     Adam, first moment 0.47, second moment 0.88, in every form                                     K_MOMENT    = 2.5
+#       (no growth in the denormal-v band: sqrt(v) <= 1e-19 << eps there)
+#     activations (sigmoid, normalise, exp, norm): 1.58 (numpy), 1.33 (torch)                        K_ACT   = 5
+#     chain rule (g y (1 - y), projection / |q|, g exp): 4.09 (torch fp32 autograd; 4.06 - 4.47 over four draws), 5.56 (numpy)    K_CHAIN = 15
+#       (expf counts with a relative error of K_ACT 2^-23 + 2^-23 |x| in the sigmoid, in exp and in their derivatives)
+#     SH gradient: a count of roundings, not a constant (reference_step.sh_n_ops); an fp32 evaluation uses 0.27 of it at most
+K_ADAM = 10.0
+K_ADAM_IEEE = 6.0
+K_MOMENT = 2.5
+K_ACT = 5.0
+K_CHAIN = 15.0

@@ -22,6 +22,9 @@ DEV = "cuda:0"
 
 
 def test_fused_adam_matches_torch():
+    """gut_adam_step, i.e. k_adam_step (the IEEE form: `/`, sqrtf), ONLY: five steps on benign values against torch.optim.Adam, block
+    relative L2.  The trainer's fast-math forms (adam4, adam4_zero_grad, adam4_lazy) and every entry point's edges are held against
+    float64 element by element in tests/test_gpu_step_elements.py."""
     g = torch.Generator().manual_seed(0)
     p0 = torch.randn((1000, 12), generator=g)
     lr = np.linspace(1e-3, 5e-2, 12).astype(np.float32)
