@@ -12,6 +12,8 @@
 // Forward also stores the three partial-derivative maps d(ssim)/d(mu1), d(ssim)/d(sigma1^2),
 // d(ssim)/d(sigma12) the backward needs (same scheme as fused-ssim); backward convolves them with the window.
 // The evaluation metrics (gut_image_metrics: MSE, PSNR, SSIM, L1) run the same forward without those maps.
+// Masked views (gut_photometric_loss_masked): a second instantiation of the forward and the backward (kMasked) multiplies both
+// images by a per-pixel mask where they are loaded; the unmasked instantiations do not see the mask at all.
 #include "gut_internal.h"
 
 namespace gut {
@@ -53,15 +55,25 @@ __device__ __forceinline__ float load_px(const float* __restrict__ img, const Im
     return p;
 }
 
+// kMasked: the pixel of either image times mask[y,x] ([H,W] floats; the reference multiplies prediction and ground truth by the
+// batch's mask before its losses, trainer.py:397-404).  A halo pixel takes ITS OWN mask value, whichever tile it belongs to.
+__device__ __forceinline__ float mask_px(const float* __restrict__ mask, const ImgView& v, int y, int x) {
+    if (x < 0 || y < 0 || x >= v.W || y >= v.H) return 0.0f;   // (load_px is 0 there: the mask is not read outside the image)
+    return mask[(size_t)y * v.W + x];
+}
+
 // forward: partial sums of the valid-region SSIM map per workgroup + derivative maps (planar [C,H,W])
 // kMetrics (gut_image_metrics, no backward follows): the three derivative maps are not stored (their pointers may be null) and the
 // workgroup's sum of squared errors goes to partial_sq, next to the L1 partials.
-template <bool kMetrics>
+// kMasked: both patches are staged times the mask, so the SSIM statistics, the L1 partials and the derivative maps are those of the
+// two masked images; `mask` is not read otherwise.
+template <bool kMetrics, bool kMasked = false>
 __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const float* __restrict__ img1,
                                                  const float* __restrict__ img2, float* __restrict__ partial,
                                                  float* __restrict__ partial_l1, float* __restrict__ dm_dmu1,
                                                  float* __restrict__ dm_dsigma1_sq, float* __restrict__ dm_dsigma12,
-                                                 uint32_t gx, uint32_t gy, float* __restrict__ partial_sq) {
+                                                 uint32_t gx, uint32_t gy, float* __restrict__ partial_sq,
+                                                 const float* __restrict__ mask) {
     // row strides chosen for the two 16-lane rows a 32-lane LDS access group covers: 48 = 16 mod 32 for the patches (row r and
     // r + 1 fall on disjoint halves of the 32 banks while the 11-tap window slides), 16 for the filtered rows (ditto for the
     // column pass).  With the earlier 27 / 17 the window passes lost 46 % of their LDS cycles to 2-way conflicts.
@@ -75,8 +87,14 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const f
     const int tid = threadIdx.x;
     for (int i = tid; i < kPatch * kPatch; i += 256) {
         const int py = i / kPatch, pxx = i - py * kPatch;
-        s1[py][pxx] = load_px(img1, v, c, y0 + py - kHalo, x0 + pxx - kHalo);
-        s2[py][pxx] = load_px(img2, v2, c, y0 + py - kHalo, x0 + pxx - kHalo);
+        if constexpr (kMasked) {
+            const float mk = mask_px(mask, v, y0 + py - kHalo, x0 + pxx - kHalo);
+            s1[py][pxx] = load_px(img1, v, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
+            s2[py][pxx] = load_px(img2, v2, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
+        } else {
+            s1[py][pxx] = load_px(img1, v, c, y0 + py - kHalo, x0 + pxx - kHalo);
+            s2[py][pxx] = load_px(img2, v2, c, y0 + py - kHalo, x0 + pxx - kHalo);
+        }
     }
     __syncthreads();
     for (int i = tid; i < kPatch * kSTile; i += 256) {
@@ -217,11 +235,15 @@ __global__ __launch_bounds__(256) void k_metrics_finish(const float* __restrict_
 // fused photometric loss (upstream == nullptr): grad = -lambda_ssim * d(mean ssim) + lambda_l1 * sign(p - q) / numel, and
 // channel 0's workgroups also write the alpha gradient slot (-background * sum of the colour gradients is added by
 // k_alpha_grad for a non-black background; zero for black).
+// kMasked (fused photometric loss of a masked view): p and q are the masked pixels the forward saw, and the finished gradient, L1
+// term included, is multiplied by mask[y,x] (d image_masked / d rgb); where the mask is 0 it is written as 0.0f whatever g is.
+template <bool kMasked>
 __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const float* __restrict__ img1,
                                                  const float* __restrict__ img2, const float* __restrict__ dm_dmu1,
                                                  const float* __restrict__ dm_dsigma1_sq, const float* __restrict__ dm_dsigma12,
                                                  const float* __restrict__ upstream, float inv_count, float ssim_weight,
-                                                 float l1_weight, float* __restrict__ grad, uint32_t gx, uint32_t gy, FinishArgs fin) {
+                                                 float l1_weight, float* __restrict__ grad, uint32_t gx, uint32_t gy, FinishArgs fin,
+                                                 const float* __restrict__ mask) {
     __shared__ float s[3][kPatch][kRowStride];
     __shared__ float h[3][kPatch][kSTile];
     if (fin.out3 && blockIdx.x == 0 && blockIdx.z == 0)   // (block-uniform)
@@ -265,9 +287,15 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const f
     const int x = x0 + ox, y = y0 + oy;
     if (x < v.W && y < v.H) {
         const long long o = (long long)c * v.sc + (long long)y * v.sh + (long long)x * v.sw;
-        const float p = load_px(img1, v, c, y, x), q = load_px(img2, v2, c, y, x);
+        float p = load_px(img1, v, c, y, x), q = load_px(img2, v2, c, y, x);
+        float mk = 1.0f;
+        if constexpr (kMasked) {
+            mk = mask_px(mask, v, y, x);
+            p *= mk; q *= mk;
+        }
         float g = scale * (a + 2.0f * p * b + q * d);
         if (l1_weight != 0.0f) g += l1_weight * (float)((p > q) - (p < q));
+        if constexpr (kMasked) g = mk == 0.0f ? 0.0f : g * mk;
         grad[o] = g;
         if (v.alpha_offset >= 0 && c == 0) grad[o + v.alpha_offset] = 0.0f;
     }
@@ -314,7 +342,7 @@ int gut_ssim_forward(void* stream, int32_t channels, int32_t height, int32_t wid
     const dim3 grid(gx * gy, 1, channels);
     const gut::ImgView v = make_view(channels, height, width, stride_c, stride_h, stride_w);
     hipLaunchKernelGGL(gut::k_ssim_fwd<false>, grid, dim3(256), 0, s, v, v, d_img1, d_img2, partial, (float*)nullptr, maps,
-                       maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr);
+                       maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr, (const float*)nullptr);
     const double count = (double)channels * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     hipLaunchKernelGGL(gut::k_ssim_finish, dim3(1), dim3(256), 0, s, partial, (int)(grid.x * grid.z), (float)(1.0 / count),
                        d_mean_ssim);
@@ -332,8 +360,8 @@ int gut_ssim_backward(void* stream, int32_t channels, int32_t height, int32_t wi
     const dim3 grid(gx * gy, 1, channels);
     const gut::ImgView v = make_view(channels, height, width, stride_c, stride_h, stride_w);
     const double count = (double)channels * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
-    hipLaunchKernelGGL(gut::k_ssim_bwd, grid, dim3(256), 0, s, v, v, d_img1, d_img2, maps, maps + plane, maps + 2 * plane, d_upstream,
-                       (float)(1.0 / count), 0.0f, 0.0f, d_grad_img1, gx, gy, gut::FinishArgs());
+    hipLaunchKernelGGL(gut::k_ssim_bwd<false>, grid, dim3(256), 0, s, v, v, d_img1, d_img2, maps, maps + plane, maps + 2 * plane, d_upstream,
+                       (float)(1.0 / count), 0.0f, 0.0f, d_grad_img1, gx, gy, gut::FinishArgs(), (const float*)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -342,8 +370,10 @@ size_t gut_photometric_workspace_bytes(int32_t height, int32_t width) {
     return gut_ssim_workspace_bytes(3, height, width) + tiles;
 }
 
-int gut_photometric_loss(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
-                         float lambda_l1, float lambda_ssim, void* d_workspace, float* d_loss3, float* d_rgba_grad) {
+// d_mask == nullptr: the unmasked instantiations, the very kernels this launched before there was a mask
+static int photometric_loss_launch(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
+                                   const float* d_mask, float background, float lambda_l1, float lambda_ssim, void* d_workspace,
+                                   float* d_loss3, float* d_rgba_grad) {
     if (!d_rgba || !d_gt_rgb || !d_workspace || !d_loss3 || !d_rgba_grad) return 1;
     if (height <= 2 * gut::kHalo || width <= 2 * gut::kHalo) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -358,21 +388,44 @@ int gut_photometric_loss(void* stream, int32_t height, int32_t width, const floa
     v.alpha_offset = 3;
     v.background = background;
     const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
-    hipLaunchKernelGGL(gut::k_ssim_fwd<false>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, maps,
-                       maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr);
+    if (d_mask)
+        hipLaunchKernelGGL((gut::k_ssim_fwd<false, true>), grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, maps,
+                           maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr, d_mask);
+    else
+        hipLaunchKernelGGL(gut::k_ssim_fwd<false>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, maps,
+                           maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr, (const float*)nullptr);
     const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     const double numel = 3.0 * height * width;
     gut::FinishArgs fin;
     fin.partial = partial; fin.partial_l1 = partial_l1; fin.n = nblocks;
     fin.inv_count_ssim = (float)(1.0 / count); fin.inv_count_l1 = (float)(1.0 / numel);
     fin.lambda_l1 = lambda_l1; fin.lambda_ssim = lambda_ssim; fin.out3 = d_loss3;
-    hipLaunchKernelGGL(gut::k_ssim_bwd, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, maps, maps + plane, maps + 2 * plane,
-                       (const float*)nullptr, (float)(1.0 / count), -lambda_ssim, (float)(lambda_l1 / numel), d_rgba_grad, gx, gy, fin);
+    if (d_mask)
+        hipLaunchKernelGGL(gut::k_ssim_bwd<true>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, maps, maps + plane, maps + 2 * plane,
+                           (const float*)nullptr, (float)(1.0 / count), -lambda_ssim, (float)(lambda_l1 / numel), d_rgba_grad, gx, gy, fin,
+                           d_mask);
+    else
+        hipLaunchKernelGGL(gut::k_ssim_bwd<false>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, maps, maps + plane, maps + 2 * plane,
+                           (const float*)nullptr, (float)(1.0 / count), -lambda_ssim, (float)(lambda_l1 / numel), d_rgba_grad, gx, gy, fin,
+                           (const float*)nullptr);
     if (background != 0.0f) {
         const int pixels = height * width;
         hipLaunchKernelGGL(gut::k_alpha_grad, dim3((pixels + 255) / 256), dim3(256), 0, s, pixels, background, d_rgba_grad);
     }
     return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+int gut_photometric_loss(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
+                         float lambda_l1, float lambda_ssim, void* d_workspace, float* d_loss3, float* d_rgba_grad) {
+    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, nullptr, background, lambda_l1, lambda_ssim, d_workspace,
+                                   d_loss3, d_rgba_grad);
+}
+
+int gut_photometric_loss_masked(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
+                                const float* d_mask, float background, float lambda_l1, float lambda_ssim, void* d_workspace,
+                                float* d_loss3, float* d_rgba_grad) {
+    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, d_mask, background, lambda_l1, lambda_ssim, d_workspace,
+                                   d_loss3, d_rgba_grad);
 }
 
 // three arrays of per-workgroup partials (SSIM, L1, squared error; 3 channels x tiles entries, 64 floats of slack after each)
@@ -397,7 +450,7 @@ int gut_image_metrics(void* stream, int32_t height, int32_t width, const float* 
     v.background = background;
     const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
     hipLaunchKernelGGL(gut::k_ssim_fwd<true>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, (float*)nullptr,
-                       (float*)nullptr, (float*)nullptr, gx, gy, partial_sq);
+                       (float*)nullptr, (float*)nullptr, gx, gy, partial_sq, (const float*)nullptr);
     const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     const double numel = 3.0 * height * width;
     hipLaunchKernelGGL(gut::k_metrics_finish, dim3(1), dim3(256), 0, s, partial, partial_l1, partial_sq, nblocks,

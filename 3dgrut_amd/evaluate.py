@@ -20,15 +20,15 @@ from .losses import image_metrics
 def _check_batch(batch, what):
     if getattr(batch, "rgb_gt", None) is None:
         raise ValueError(f"{what}: every batch needs rgb_gt")
-    if getattr(batch, "mask", None) is not None:
-        raise ValueError(f"{what}: masked batches are not supported (the native loss and the metrics ignore masks)")
 
 
 def evaluate(model, tracer, batches, out_dir=None, step=0):
-    """Render and score `batches`.  Returns dict(psnr=[...], ssim=[...], mse=[...], l1=[...], mean_psnr, std_psnr (population
-    std, as np.std), mean_ssim, n_views) and, when the tracer was built with render.enable_kernel_timings, mean_inference_time (ms
-    per frame, the mean of the library's forward_render times).  out_dir: the renders are written to
-    out_dir/ours_{step}/renders/{i:05d}.png (clamped and rounded as torchvision.utils.save_image does)."""
+    """Render and score `batches`.  A batch's mask is ignored: every metric is of the full image, as in the reference, whose
+    render.py and validation metrics never read the mask (it enters the training losses only).  Returns dict(psnr=[...],
+    ssim=[...], mse=[...], l1=[...], mean_psnr, std_psnr (population std, as np.std), mean_ssim, n_views) and, when the tracer was
+    built with render.enable_kernel_timings, mean_inference_time (ms per frame, the mean of the library's forward_render times).
+    out_dir: the renders are written to out_dir/ours_{step}/renders/{i:05d}.png (clamped and rounded as torchvision.utils.save_image
+    does)."""
     batches = list(batches)
     if not batches:
         raise ValueError("evaluate: no views")

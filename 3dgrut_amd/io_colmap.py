@@ -11,7 +11,8 @@ What it mirrors (behaviour, not code):
   * threedgrut/model/model.py:207-248, 438-483 — Gaussians from the SfM points: scale = 0.01 * distance to the nearest
     camera (`use_observation_points`) or the RMS distance to the 3 nearest points, density 0.1, SH dc from the point
     colour, random rotations.
-Images are optional (there are none in the build environment): `batch()` attaches `rgb_gt` only if the file exists.
+Images are optional (there are none in the build environment): `batch()` attaches `rgb_gt` only if the file exists, and `mask`
+only if `<image stem>_mask.png` lies next to it (dataset_colmap.py:275, 376-381, 408-411).
 """
 import os
 import struct
@@ -270,9 +271,11 @@ class ColmapScene:
         pose = torch.as_tensor(self.poses[i])[None]
         kw = {key: K}
         rgb = self.load_image(i)
+        mask = self.load_mask(i, size=None if rgb is None else (rgb.shape[1], rgb.shape[0]))
         return Batch(rays_ori=torch.as_tensor(ro, device=device), rays_dir=torch.as_tensor(rd, device=device),
                      T_to_world=pose if pose_on_host else pose.to(device),
-                     rgb_gt=None if rgb is None else torch.as_tensor(rgb, device=device)[None], **kw)
+                     rgb_gt=None if rgb is None else torch.as_tensor(rgb, device=device)[None],
+                     mask=None if mask is None else torch.as_tensor(mask, device=device), **kw)
 
     def load_image(self, i):
         path = os.path.join(self.root, self.images_folder(), self.images[i].name)
@@ -281,6 +284,29 @@ class ColmapScene:
         from PIL import Image
         with Image.open(path) as img:
             return np.asarray(img.convert("RGB"), np.float32) / 255.0
+
+    def load_mask(self, i, size=None):
+        """The view's mask, float32 [1,H,W,1] of 0 / 1, or None: `<image stem>_mask.png` next to the image, in the same (down-
+        sampled) images folder, converted to 8-bit grey and thresholded at value / 255 > 0.5 (dataset_colmap.py:376-381, 408-411).
+        Raises ValueError when its size is not the image's: `size` (width, height) if the caller has decoded the image already,
+        else the image file's if it is there, else the camera's resolution."""
+        path = os.path.join(self.root, self.images_folder(), self.images[i].name)
+        mask_path = os.path.splitext(path)[0] + "_mask.png"
+        if not os.path.isfile(mask_path):
+            return None
+        from PIL import Image
+        if size is not None:
+            pass
+        elif os.path.isfile(path):
+            with Image.open(path) as img:
+                size = img.size
+        else:
+            size = self.resolution(self.cameras[self.images[i].camera_id])
+        with Image.open(mask_path) as img:
+            if tuple(img.size) != tuple(size):
+                raise ValueError(f"mask {mask_path} is {img.size[0]}x{img.size[1]}, its image {size[0]}x{size[1]}")
+            mask = np.asarray(img.convert("L"), np.float32) / 255.0 > 0.5
+        return mask.astype(np.float32)[None, :, :, None]
 
     def points(self):
         sparse = os.path.join(self.root, "sparse", "0")

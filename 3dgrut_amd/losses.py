@@ -119,7 +119,73 @@ def image_metrics(rgba, gt_rgb, background="black", out=None):
     return out
 
 
-def photometric_loss(pred_rgb, gt_rgb, lambda_l1=0.8, lambda_ssim=0.2):
-    """pred/gt [B,H,W,3].  lambda_l1*L1 + lambda_ssim*(1-SSIM)  (configs/base_gs.yaml:111-119, trainer.py:425-449)."""
+def photometric_loss(pred_rgb, gt_rgb, lambda_l1=0.8, lambda_ssim=0.2, mask=None):
+    """pred/gt [B,H,W,3].  lambda_l1*L1 + lambda_ssim*(1-SSIM)  (configs/base_gs.yaml:111-119, trainer.py:425-449).
+    mask [B,H,W,1] (Batch.mask) or None: both images are multiplied by it first, as the reference's get_losses does
+    (trainer.py:397-404); the means keep their full-image counts."""
+    if mask is not None:
+        mask = mask.to(device=pred_rgb.device, dtype=pred_rgb.dtype)
+        pred_rgb, gt_rgb = pred_rgb * mask, gt_rgb * mask
     s = fused_ssim(pred_rgb.permute(0, 3, 1, 2), gt_rgb.permute(0, 3, 1, 2), padding="valid")
     return lambda_l1 * l1_loss(pred_rgb, gt_rgb) + lambda_ssim * (1.0 - s)
+
+
+def _plane_mask(mask, H, W, device):
+    """A mask given as [H,W], [H,W,1] or [1,H,W,1] (Batch.mask of one view; any dtype) as contiguous float32 [H,W] on `device`."""
+    shape = tuple(mask.shape)
+    if shape not in ((H, W), (H, W, 1), (1, H, W, 1)):
+        raise ValueError(f"fused_photometric_loss: mask must be [{H},{W}], [{H},{W},1] or [1,{H},{W},1] for these images, "
+                         f"got {shape}")
+    return mask.reshape(H, W).to(device=device, dtype=torch.float32).contiguous()
+
+
+def fused_photometric_loss(rgba, gt_rgb, background, lambda_l1=0.8, lambda_ssim=0.2, mask=None, workspace=None):
+    """The train step's loss and its gradient without autograd (gut_photometric_loss / gut_photometric_loss_masked,
+    csrc/gut_ssim.hip): image = rgb + background * (1 - alpha), loss = lambda_l1 * L1 + lambda_ssim * (1 - SSIM) against gt_rgb.
+    rgba [H,W,4] (or [1,H,W,4]) and gt_rgb [H,W,3] (or [1,H,W,3]): contiguous float32 on one GPU; background: "black", "white"
+    or 0.0 / 1.0.  mask: None, or [H,W] / [H,W,1] / [1,H,W,1] of any dtype — image and gt_rgb are both multiplied by it
+    (trainer.py:397-404), the means keep their full-image counts, and a pixel whose mask is 0 gets a gradient of exactly zero.
+    workspace: a float32 device tensor of at least gut_photometric_workspace_bytes(H, W) bytes to reuse, or None.
+    Returns (loss3, rgba_grad): a float32 device tensor (loss, L1, SSIM) and d(loss)/d(rgba) [H,W,4]."""
+    bg = {"black": 0.0, "white": 1.0}.get(background, background)
+    if isinstance(bg, str):
+        raise ValueError(f"fused_photometric_loss: background must be 'black', 'white' or a number, got {background!r}")
+    rgba = rgba.reshape(rgba.shape[-3:]) if rgba.dim() == 4 and rgba.shape[0] == 1 else rgba
+    gt_rgb = gt_rgb.reshape(gt_rgb.shape[-3:]) if gt_rgb.dim() == 4 and gt_rgb.shape[0] == 1 else gt_rgb
+    if rgba.dim() != 3 or rgba.shape[2] != 4 or tuple(gt_rgb.shape) != (rgba.shape[0], rgba.shape[1], 3):
+        raise RuntimeError(f"[fused_photometric_loss] expected rgba [H,W,4] and gt [H,W,3], got {tuple(rgba.shape)} and {tuple(gt_rgb.shape)}")
+    if not rgba.is_cuda or rgba.dtype != torch.float32 or gt_rgb.dtype != torch.float32 or gt_rgb.device != rgba.device:
+        raise RuntimeError("[fused_photometric_loss] expected float32 GPU tensors on one device (there is no CPU path)")
+    if not rgba.is_contiguous() or not gt_rgb.is_contiguous():
+        raise RuntimeError("[fused_photometric_loss] expected contiguous tensors")
+    lib = _capi.load()
+    H, W = int(rgba.shape[0]), int(rgba.shape[1])
+    if mask is not None:
+        mask = _plane_mask(mask, H, W, rgba.device)
+    need = lib.gut_photometric_workspace_bytes(H, W)
+    if workspace is None:
+        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=rgba.device)
+    elif workspace.dtype != torch.float32 or workspace.device != rgba.device or workspace.numel() * 4 < need or not workspace.is_contiguous():
+        raise RuntimeError(f"[fused_photometric_loss] workspace must be a contiguous float32 tensor of at least {need} bytes on the images' device")
+    with torch.cuda.device(rgba.device):
+        return _photometric_loss_call(lib, H, W, rgba, gt_rgb, float(bg), lambda_l1, lambda_ssim, mask, workspace)
+
+
+def _photometric_loss_call(lib, H, W, rgba, gt_rgb, bg, lambda_l1, lambda_ssim, mask, workspace):
+    """The two C calls behind fused_photometric_loss, nothing checked: contiguous float32 device tensors (gt_rgb with or without a
+    leading 1), mask a float32 [H,W] plane or None, a workspace of gut_photometric_workspace_bytes(H, W), the images' device current.
+    NativeTrainStep calls this directly every step, on buffers it sized itself."""
+    # three fresh floats every call (the caching allocator, no kernel): callers return views of them
+    loss3 = torch.empty((3,), dtype=torch.float32, device=rgba.device)
+    rgba_grad = torch.empty_like(rgba)
+    stream = torch.cuda.current_stream(rgba.device).cuda_stream
+    if mask is None:
+        rc = lib.gut_photometric_loss(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(), bg, lambda_l1, lambda_ssim,
+                                      workspace.data_ptr(), loss3.data_ptr(), rgba_grad.data_ptr())
+    else:
+        rc = lib.gut_photometric_loss_masked(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(), mask.data_ptr(), bg,
+                                             lambda_l1, lambda_ssim, workspace.data_ptr(), loss3.data_ptr(), rgba_grad.data_ptr())
+    if rc:
+        raise RuntimeError(f"[3dgut] photometric_loss failed ({rc}): " + ("a null pointer, or an image of 10x10 pixels or less"
+                                                                         if rc == 1 else "the kernel launch failed"))
+    return loss3, rgba_grad

@@ -22,7 +22,7 @@ import torch
 from . import _capi
 from .dp import (RecordExchange, allgather_rows_, allgather_rows_async, allreduce_max_, allreduce_max_async, allreduce_mean_, allreduce_sum_async,
                  assert_replicas_identical)
-from .losses import photometric_loss
+from .losses import _photometric_loss_call, _plane_mask, photometric_loss
 from .tracer import SplatRaster, Tracer
 
 # column layout of the raw [N,12] tensor and the reference's Adam learning rates (configs/base_gs.yaml:81-109)
@@ -126,6 +126,7 @@ class NativeGaussianModel:
 class NativeTrainStep:
     OVERLAP_MIN_GAUSSIANS = 1_000_000   # size from which the two-pass optimiser is on by default (see __init__)
     PROBE_FIRST, PROBE_LAST = 2, 9       # steps in which the default-on overlap is timed against the one-pass form, alternating
+    supports_masks = True                # step() honours Batch.mask in both loss branches (trainer.Trainer asks before it takes masked views)
 
     def __init__(self, model: NativeGaussianModel, tracer: Tracer, scene_extent=1.0, world_size=1, selective=False,
                  betas=(0.9, 0.999), eps=1e-15, fused_sh_adam=True, rank=0, fused_loss=True, lambda_l1=0.8, lambda_ssim=0.2,
@@ -631,23 +632,23 @@ class NativeTrainStep:
             self._early_queued = True
         self._mark(evs)
         gt = batch.rgb_gt
+        # Batch.mask [1,H,W,1] or None: prediction and ground truth are multiplied by it inside the loss (trainer.py:397-404); the
+        # pred_rgb returned stays unmasked, as the reference masks only the locals of get_losses
+        mask = getattr(batch, "mask", None)
         if self.fused_loss and m.background_color in ("black", "white") and gt.dtype == torch.float32 and gt.is_contiguous() \
                 and gt.numel() == rgba.shape[0] * rgba.shape[1] * 3:
-            # loss value and d(loss)/d(rgba) in two HIP launches (csrc/gut_ssim.hip: gut_photometric_loss)
+            # loss value and d(loss)/d(rgba) in two HIP launches (csrc/gut_ssim.hip: gut_photometric_loss[_masked])
             H, W = rgba.shape[0], rgba.shape[1]
             need = self._lib.gut_photometric_workspace_bytes(H, W)
             if self._loss_ws is None or self._loss_ws.numel() * 4 < need:
                 self._loss_ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=rgba.device)
             # three fresh floats every step (the caching allocator, no kernel): the loss returned below is a VIEW of them — a
             # `.clone()` of a buffer kept across steps was a 7 us copy kernel between the loss and the backward
-            self._loss3 = torch.empty((3,), dtype=torch.float32, device=rgba.device)
-            rgba_grad = torch.empty_like(rgba)
-            st = torch.cuda.current_stream(rgba.device).cuda_stream
-            rc = self._lib.gut_photometric_loss(C.c_void_p(st), H, W, rgba.data_ptr(), gt.data_ptr(),
-                                                1.0 if m.background_color == "white" else 0.0, self.lambda_l1, self.lambda_ssim,
-                                                self._loss_ws.data_ptr(), self._loss3.data_ptr(), rgba_grad.data_ptr())
-            if rc:
-                raise RuntimeError(f"[3dgut] photometric_loss failed ({rc})")
+            # (_plane_mask: a view for the reader's float32 [1,H,W,1] device mask, no kernel; a mask of another dtype or device is
+            # converted here, one copy per step — keep such masks converted in the batch)
+            self._loss3, rgba_grad = _photometric_loss_call(self._lib, H, W, rgba, gt, 1.0 if m.background_color == "white" else 0.0,
+                                                            self.lambda_l1, self.lambda_ssim,
+                                                            None if mask is None else _plane_mask(mask, H, W, rgba.device), self._loss_ws)
             loss = self._loss3[0]
             pred_rgb = rgba[..., :3].unsqueeze(0)
             if m.background_color == "white":
@@ -657,7 +658,7 @@ class NativeTrainStep:
             pred_rgb = rgba_leaf[..., :3].unsqueeze(0)
             pred_opacity = rgba_leaf[..., 3:].unsqueeze(0)
             pred_rgb, pred_opacity = m.background(batch.T_to_world, batch.rays_dir, pred_rgb, pred_opacity, True)
-            loss = photometric_loss(pred_rgb, gt, self.lambda_l1, self.lambda_ssim)
+            loss = photometric_loss(pred_rgb, gt, self.lambda_l1, self.lambda_ssim, mask=mask)
             loss.backward()  # image-sized autograd only
             rgba_grad = rgba_leaf.grad
         self._mark(evs)

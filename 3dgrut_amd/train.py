@@ -58,6 +58,8 @@ def photometric_loss_torch(pred_rgb, gt_rgb, lambda_l1=0.8, lambda_ssim=0.2, win
 
 
 class TrainStep:
+    supports_masks = True   # step() multiplies prediction and ground truth by Batch.mask before the loss
+
     def __init__(self, model, tracer, scene_extent=1.0, world_size=1, fused_adam=True, schedule=None, optimizer_type="adam",
                  lambda_opacity=0.0, lambda_scale=0.0):
         """lambda_opacity / lambda_scale: the MCMC recipe's regularisers (strategy.MCMC_LOSS, losses.regularisation_loss); 0 = off.
@@ -120,7 +122,7 @@ class TrainStep:
         self._mark(evs)
         out = self.render(batch, train=True)
         self._mark(evs)
-        loss = photometric_loss(out["pred_rgb"], batch.rgb_gt)
+        loss = photometric_loss(out["pred_rgb"], batch.rgb_gt, mask=getattr(batch, "mask", None))   # trainer.py:397-404
         if self.lambda_opacity != 0.0 or self.lambda_scale != 0.0:
             # trainer.py:432-449; with data parallelism every rank adds the same term, and the all-reduce's mean keeps it once
             out["opacity_loss"], out["scale_loss"] = regularisation_loss(self.model.get_density(), self.model.get_scale(),

@@ -9,7 +9,8 @@
 
 `conf` is a plain dict with the reference's key names; what it leaves out comes from configs/base_gs.yaml + strategy/gs.yaml, or
 base_mcmc.yaml + strategy/mcmc.yaml for `strategy.method == "MCMCStrategy"` (`default_config`).  The loop adds no host
-synchronisation between events: the loss is read back only when a validation runs.
+synchronisation between events: the loss is read back only when a validation runs.  Views with a mask (`<image stem>_mask.png` next
+to the image, io_colmap.ColmapScene.load_mask) train through the masked form of the fused loss; evaluation scores the full image.
 
 Checkpoints hold the reference's get_model_parameters() keys (model/model.py:107-134) with the optimiser state in
 torch.optim.Adam.state_dict() layout (six groups, named and ordered as configs/base_gs.yaml), `global_step`, `epoch`, the GS
@@ -207,7 +208,11 @@ def checkpoint_tensors(ckpt, device):
 
 class Trainer:
     """The reference's training run on the native pieces.  `scene`: the initial Gaussians (activated parameters, the dict
-    io_colmap.ColmapScene.initial_gaussians / scenes.* return); `*_batches`: protocols.Batch with rgb_gt (no mask).
+    io_colmap.ColmapScene.initial_gaussians / scenes.* return); `*_batches`: protocols.Batch with rgb_gt.  A training batch may carry a
+    mask [1,H,W,1]: the stepper multiplies prediction and ground truth by it inside the loss (trainer.py:397-404), so it must say
+    `supports_masks = True` (NativeTrainStep and train.TrainStep do) — with one that does not, a masked training batch is a
+    ValueError, not a view silently trained on its masked-out pixels.  Masks of validation and test batches are accepted and
+    ignored: held-out metrics are of the full image, as in the reference.
 
     stepper / strategy / evaluator: replacements of the NativeTrainStep, the strategy object and `evaluate` (tests); with a
     stepper given, `scene` is not used and the model is stepper.model."""
@@ -222,6 +227,11 @@ class Trainer:
         for what, bs in (("train", self.train_batches), ("validation", self.val_batches), ("test", self.test_batches)):
             for b in bs:
                 _check_batch(b, f"Trainer ({what} batch)")
+        # (a stepper built here is a NativeTrainStep, which honours masks)
+        if stepper is not None and not getattr(stepper, "supports_masks", False) \
+                and any(getattr(b, "mask", None) is not None for b in self.train_batches):
+            raise ValueError(f"Trainer (train batch): a batch carries a mask and {type(stepper).__name__} does not honour masks "
+                             "(no `supports_masks = True`): it would train on the masked-out pixels")
         self.scene_extent = float(scene_extent)
         self.method = c["strategy"]["method"]
         self.evaluator = evaluate if evaluator is None else evaluator

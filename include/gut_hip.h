@@ -39,7 +39,8 @@ extern "C" {
  * rolling-shutter iterations, hit counts), gut_optimize_after_bwd takes a NULL camera position, GUT_OPT_KERNEL_TIMING_SET, and the
  * unsorted backward clamps alpha with the reference's literal 0.99 whatever particle_kernel_max_alpha is; 6: GutRegularisation,
  * gut_set_regularisation, gut_sh_adam_step_regularised, gut_adam_unwalked_waves_regularised, gut_sync_moments_ex,
- * gut_regularisation_gradient, gut_regularisation_loss). */
+ * gut_regularisation_gradient, gut_regularisation_loss.  Added under 6 without a bump, nothing that was accepted changed meaning:
+ * gut_photometric_loss_masked, a new entry point next to gut_photometric_loss, which is untouched). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -326,6 +327,19 @@ int gut_ssim_backward(void* stream, int32_t channels, int32_t height, int32_t wi
 size_t gut_photometric_workspace_bytes(int32_t height, int32_t width);
 int gut_photometric_loss(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
                          float lambda_l1, float lambda_ssim, void* d_workspace, float* d_loss3, float* d_rgba_grad);
+
+/* The same loss of a MASKED view: the reference multiplies prediction and ground truth by the batch's mask before its losses
+ * (trainer.py:397-404).  d_mask: float32 [H,W], multiplied as it is (the readers produce 0 / 1):
+ *     image = (rgb + background * (1 - alpha)) * mask,  gt' = gt * mask,
+ *     L1 = sum |image - gt'| / (3 H W),  SSIM = the valid-region mean over the two masked images, count 3 (H - 10)(W - 10)
+ * (neither denominator shrinks with the mask); d_loss3 receives {loss, L1, SSIM} of the masked images.  d(loss)/d(rgb) =
+ * mask * d(loss)/d(image) and d(loss)/d(alpha) = -background * sum_c d(loss)/d(rgb_c); a pixel whose mask is 0 gets 0 in all four
+ * channels of d_rgba_grad, whatever its colours are.  d_mask == NULL is gut_photometric_loss: the same kernel instantiations, the
+ * same bits (so is, in value, an all-ones mask: a product with 1.0f is exact).  Workspace, launch count (the masked forms are
+ * compile-time variants of the same two kernels) and stream behaviour as gut_photometric_loss. */
+int gut_photometric_loss_masked(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
+                                const float* d_mask, float background, float lambda_l1, float lambda_ssim, void* d_workspace,
+                                float* d_loss3, float* d_rgba_grad);
 
 /* Evaluation metrics of one view (the reference's test-split scoring, threedgrut/render.py:137-285), forward only, no gradient:
  * d_out4 receives { MSE, PSNR, SSIM, L1 } of image = rgb + background * (1 - alpha) against d_gt_rgb, values unclamped.
