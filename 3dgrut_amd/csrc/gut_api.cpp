@@ -172,16 +172,14 @@ struct gut_context {
     // the pass runs in two launches: the first block range under the forward compositor, the second under the backward
     // compositor (queued by gut_trace_bwd_ex), so that the short, latency-bound loss kernels in between are left alone
     struct EarlyArgs {
-        float *raw12, *raw_m, *raw_v, *sh48, *sh_m, *sh_v, *act12;
-        float lr12[12], lr48[48];
-        float beta1, beta2, eps;
-        uint32_t step, block_begin, block_end;
-        uint32_t extra_end;   // blocks < extra_end: waves with tiles the forward did not walk also go to the second launch
+        gut::OptimiserState state;
+        gut::AdamSettings adam;
+        gut::SideStreamBlocks blocks;   // the second launch; the first took the tile-less waves of the blocks below split_block
         GutLazyMoments lazy;  // lazy moment decay of this step (d_wave_step == NULL: off)
         GutRegularisation reg;   // the regulariser of this step (gut_set_regularisation)
     } early_args{};
     bool marks_valid = false; // wave_walked holds the walked-wave marks of the cached forward for EVERY wave
-    DevBuf wave_walked;       // one byte per 64-row wave (k_mark_walked_waves), valid when early_args.extra_end > 0
+    DevBuf wave_walked;       // one byte per 64-row wave (k_mark_walked_waves), valid when early_args.blocks.extra_end > 0
     int early_extra_percent = 100;
     bool stats_early = false;   // the last optimiser step used the side stream (for gut_get_stats)
     uint32_t stats_split = 0, stats_extra_end = 0;
@@ -341,6 +339,10 @@ float drain_timers(std::deque<EventPair>& q) {
 }  // namespace
 
 static int launch_early_part2(gut_context* h, hipStream_t s);
+// the handle's rows the single-view optimiser kernel reads, with the sensor position it is to use
+static gut::ScratchGradients scratch_gradients(gut_context* h, const float* d_camera_position) {
+    return gut::ScratchGradients{d_camera_position, h->grad16.as<float>(), h->tiles_count.as<uint32_t>(), h->feat.as<float>()};
+}
 gut::LazyMoments gut_make_lazy(const GutLazyMoments* lazy, uint32_t step);   // gut_train.hip
 gut::Regularisation gut_make_reg(const GutRegularisation* reg);              // gut_train.hip
 
@@ -796,6 +798,22 @@ int gut_trace_bwd_ex(gut_handle h, void* stream_, uint32_t frame_number, int32_t
                           gut::GradFields());
 }
 
+// The [N,12] rows of the *_fields forwards: packed (or activated and packed) from the caller's four tensors into handle scratch by
+// `pack`, where they stay for the backward.  Invalidates whatever the scratch held; the caller marks it valid once its forward succeeded.
+using PackLauncher = void (*)(hipStream_t, uint32_t, const float*, const float*, const float*, const float*, float*);
+static int pack_rows(gut_handle h, void* stream_, uint32_t num_particles, PackLauncher pack, const float* d_positions,
+                     const float* d_density, const float* d_rotation, const float* d_scale) {
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dev_guard;
+    HIP_TRY(dev_guard.set(h->device));
+    h->packed_valid = false;
+    h->packed_raw = false;
+    HIP_TRY(h->packed12.ensure(sizeof(float) * 12 * (size_t)num_particles + 64));
+    pack(static_cast<hipStream_t>(stream_), num_particles, d_positions, d_density, d_rotation, d_scale, h->packed12.as<float>());
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // SplatRaster::trace with the four activated tensors the reference's Tracer hands to _Autograd (tracer.py:317-327) instead of
 // their concatenation: the [N,12] rows are packed into handle scratch by one coalesced kernel (the torch.cat of tracer.py:176-178
 // runs at a quarter of that rate) and stay there for gut_trace_bwd_fields.
@@ -808,17 +826,7 @@ int gut_trace_fields(gut_handle h, void* stream_, uint32_t frame_number, int32_t
     if (num_particles && (!d_positions || !d_density || !d_rotation || !d_scale))
         return fail("gut_trace_fields: null particle buffers with %u particles", num_particles);
     if (((uintptr_t)d_rotation & 15u) != 0) return fail("gut_trace_fields: the rotation tensor must be 16-byte aligned");
-    {
-        std::lock_guard<std::mutex> lock(h->mu);
-        DeviceGuard dev_guard;
-        HIP_TRY(dev_guard.set(h->device));
-        h->packed_valid = false;
-        h->packed_raw = false;
-        HIP_TRY(h->packed12.ensure(sizeof(float) * 12 * (size_t)num_particles + 64));
-        gut::launch_pack_fields(static_cast<hipStream_t>(stream_), num_particles, d_positions, d_density, d_rotation, d_scale,
-                                h->packed12.as<float>());
-        HIP_TRY(hipGetLastError());
-    }
+    if (pack_rows(h, stream_, num_particles, gut::launch_pack_fields, d_positions, d_density, d_rotation, d_scale)) return 1;
     const int rc = gut_trace(h, stream_, frame_number, num_active_features, num_particles, h->packed12.as<float>(), d_particle_radiance,
                              width, height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density, d_ray_hit_distance,
                              d_ray_hit_count, d_particle_visibility);
@@ -860,17 +868,7 @@ int gut_trace_model_fields(gut_handle h, void* stream_, uint32_t frame_number, i
         return fail("gut_trace_model_fields: null particle buffers with %u particles", num_particles);
     if ((((uintptr_t)d_rotation | (uintptr_t)d_features_specular) & 15u) != 0)
         return fail("gut_trace_model_fields: the rotation and features_specular tensors must be 16-byte aligned");
-    {
-        std::lock_guard<std::mutex> lock(h->mu);
-        DeviceGuard dev_guard;
-        HIP_TRY(dev_guard.set(h->device));
-        h->packed_valid = false;
-        h->packed_raw = false;
-        HIP_TRY(h->packed12.ensure(sizeof(float) * 12 * (size_t)num_particles + 64));
-        gut::launch_pack_fields(static_cast<hipStream_t>(stream_), num_particles, d_positions, d_density, d_rotation, d_scale,
-                                h->packed12.as<float>());
-        HIP_TRY(hipGetLastError());
-    }
+    if (pack_rows(h, stream_, num_particles, gut::launch_pack_fields, d_positions, d_density, d_rotation, d_scale)) return 1;
     const int rc = trace_fwd_impl(h, stream_, frame_number, num_active_features, num_particles, h->packed12.as<float>(),
                                   d_features_specular, width, height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density,
                                   d_ray_hit_distance, d_ray_hit_count, d_particle_visibility,
@@ -894,17 +892,7 @@ int gut_trace_raw_model_fields(gut_handle h, void* stream_, uint32_t frame_numbe
         return fail("gut_trace_raw_model_fields: null particle buffers with %u particles", num_particles);
     if ((((uintptr_t)d_rotation_raw | (uintptr_t)d_features_specular) & 15u) != 0)
         return fail("gut_trace_raw_model_fields: the rotation and features_specular tensors must be 16-byte aligned");
-    {
-        std::lock_guard<std::mutex> lock(h->mu);
-        DeviceGuard dev_guard;
-        HIP_TRY(dev_guard.set(h->device));
-        h->packed_valid = false;
-        h->packed_raw = false;
-        HIP_TRY(h->packed12.ensure(sizeof(float) * 12 * (size_t)num_particles + 64));
-        gut::launch_pack_activate_fields(static_cast<hipStream_t>(stream_), num_particles, d_positions, d_density_logit, d_rotation_raw,
-                                         d_log_scale, h->packed12.as<float>());
-        HIP_TRY(hipGetLastError());
-    }
+    if (pack_rows(h, stream_, num_particles, gut::launch_pack_activate_fields, d_positions, d_density_logit, d_rotation_raw, d_log_scale)) return 1;
     const int rc = trace_fwd_impl(h, stream_, frame_number, num_active_features, num_particles, h->packed12.as<float>(),
                                   d_features_specular, width, height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density,
                                   d_ray_hit_distance, d_ray_hit_count, d_particle_visibility,
@@ -1060,6 +1048,8 @@ int gut_optimize_after_bwd(gut_handle h, void* stream_, int32_t num_active_featu
     if (h->n == 0) return 0;
     if (!d_raw12 || !d_raw_m || !d_raw_v || !d_sh48 || !d_sh_m || !d_sh_v || !lr12 || !lr48)
         return fail("gut_optimize_after_bwd: null pointer argument");
+    const gut::OptimiserState state{d_raw12, d_raw_m, d_raw_v, d_sh48, d_sh_m, d_sh_v, d_act12_out};
+    const gut::AdamSettings adam = gut::make_adam_settings(lr12, lr48, beta1, beta2, eps, step);
     if (!d_camera_position) d_camera_position = h->cam_pos.as<float>();   // the cached forward's own sensor position (K1 left it there)
     if (h->early_ran && d_visibility)
         return fail("gut_optimize_after_bwd: a visibility mask cannot follow gut_optimize_rows_without_gradient");
@@ -1084,13 +1074,11 @@ int gut_optimize_after_bwd(gut_handle h, void* stream_, int32_t num_active_featu
     }
     const bool timing = h->cfg.enable_kernel_timings != 0 && h->timing_main_stream && h->kev[12] && h->kev[13];
     if (timing) (void)hipEventRecord(h->kev[12], s);
-    gut::launch_sh_adam_from_scratch(s, h->n, h->sh_degree, d_camera_position, h->grad16.as<float>(), h->tiles_count.as<uint32_t>(),
-                                     h->feat.as<float>(), d_raw12, d_raw_m, d_raw_v, d_sh48, d_sh_m, d_sh_v, lr12, lr48, beta1, beta2,
-                                     eps, step, d_visibility, d_act12_out, h->early_ran,
-                                     (h->early_ran && h->early_args.extra_end) ? h->wave_walked.as<uint8_t>() : nullptr,
-                                     h->early_args.block_begin, h->early_ran ? h->early_args.extra_end : 0u, lz,
+    const gut::SideStreamBlocks& early = h->early_args.blocks;
+    gut::launch_sh_adam_from_scratch(s, h->n, h->sh_degree, scratch_gradients(h, d_camera_position), state, adam, d_visibility,
+                                     h->early_ran ? &early : nullptr, lz,
                                      (lz.wave_step && h->marks_valid) ? h->wave_walked.as<uint8_t>() : nullptr,
-                                     h->stat_accum, h->stat_denom, reg);
+                                     gut::PositionStatistics{h->stat_accum, h->stat_denom}, reg);
     h->stat_accum = nullptr;   // one optimiser call only (the caller may reallocate its buffers any time)
     h->stat_denom = nullptr;
     HIP_TRY(hipGetLastError());
@@ -1103,8 +1091,8 @@ int gut_optimize_after_bwd(gut_handle h, void* stream_, int32_t num_active_featu
         h->early_wait_pending = false;
     }
     h->stats_early = h->early_ran;
-    h->stats_split = h->early_args.block_begin;
-    h->stats_extra_end = h->early_ran ? h->early_args.extra_end : 0u;
+    h->stats_split = early.split_block;
+    h->stats_extra_end = h->early_ran ? early.extra_end : 0u;
     h->early_ran = false;
     h->have_backward = false;  // the gradient rows are consumed ...
     h->grad16_zero = true;     // ... and left zero by the kernel
@@ -1146,20 +1134,19 @@ int gut_optimize_finish_without_gradient(gut_handle h, void* stream_) {
     HIP_TRY(h->grad16.ensure(sizeof(float) * 16 * (size_t)h->n));
     HIP_TRY(hipMemsetAsync(h->grad16.p, 0, h->grad16.cap, s));
     if (launch_early_part2(h, s)) return 1;
-    gut::launch_sh_adam_from_scratch(s, h->n, h->sh_degree, h->zero_word.as<float>() /* never read: no row has a colour gradient */,
-                                     h->grad16.as<float>(), h->tiles_count.as<uint32_t>(), h->feat.as<float>(), ea.raw12, ea.raw_m,
-                                     ea.raw_v, ea.sh48, ea.sh_m, ea.sh_v, ea.lr12, ea.lr48, ea.beta1, ea.beta2, ea.eps, ea.step, nullptr,
-                                     ea.act12, true, ea.extra_end ? h->wave_walked.as<uint8_t>() : nullptr, ea.block_begin, ea.extra_end,
-                                     gut_make_lazy(&ea.lazy, ea.step), h->marks_valid ? h->wave_walked.as<uint8_t>() : nullptr,
-                                     nullptr, nullptr, gut_make_reg(&ea.reg));
+    gut::launch_sh_adam_from_scratch(s, h->n, h->sh_degree,
+                                     scratch_gradients(h, h->zero_word.as<float>() /* never read: no row has a colour gradient */),
+                                     ea.state, ea.adam, nullptr, &ea.blocks, gut_make_lazy(&ea.lazy, ea.adam.step),
+                                     h->marks_valid ? h->wave_walked.as<uint8_t>() : nullptr, gut::PositionStatistics(),
+                                     gut_make_reg(&ea.reg));
     HIP_TRY(hipGetLastError());
     if (h->early_wait_pending) {
         HIP_TRY(hipStreamWaitEvent(s, h->ev_early_done, 0));
         h->early_wait_pending = false;
     }
     h->stats_early = true;
-    h->stats_split = ea.block_begin;
-    h->stats_extra_end = ea.extra_end;
+    h->stats_split = ea.blocks.split_block;
+    h->stats_extra_end = ea.blocks.extra_end;
     h->early_ran = false;
     h->have_backward = false;
     h->grad16_zero = true;
@@ -1223,6 +1210,8 @@ int gut_optimize_rows_without_gradient(gut_handle h, void* stream_, float* d_raw
     if (h->n == 0) return 0;
     if (!d_raw12 || !d_raw_m || !d_raw_v || !d_sh48 || !d_sh_m || !d_sh_v || !lr12 || !lr48)
         return fail("gut_optimize_rows_without_gradient: null pointer argument");
+    const gut::OptimiserState state{d_raw12, d_raw_m, d_raw_v, d_sh48, d_sh_m, d_sh_v, d_act12_out};
+    const gut::AdamSettings adam = gut::make_adam_settings(lr12, lr48, beta1, beta2, eps, step);
     DeviceGuard dev_guard;
     HIP_TRY(dev_guard.set(h->device));
     if (!h->side_stream) {
@@ -1257,24 +1246,30 @@ int gut_optimize_rows_without_gradient(gut_handle h, void* stream_, float* d_raw
     const gut::Regularisation reg = gut_make_reg(&h->reg);
     const uint32_t percent = split_percent >= 0 ? (uint32_t)split_percent : ((lazy && lazy->d_wave_step && !reg.on()) ? 60u : 25u);
     const uint32_t first = (uint32_t)((uint64_t)nblocks * percent / 100u);
-    gut::launch_adam_rows_without_gradient(h->side_stream, h->n, h->tiles_count.as<uint32_t>(), d_raw12, d_raw_m, d_raw_v, d_sh48,
-                                           d_sh_m, d_sh_v, lr12, lr48, beta1, beta2, eps, step, d_act12_out, 0, first, nullptr, first, 0,
-                                           false, gut_make_lazy(lazy, step), reg);
+    gut::SideStreamBlocks first_launch;   // the tile-less waves of the blocks [0, first)
+    first_launch.block_end = first_launch.split_block = first;
+    gut::launch_adam_rows_without_gradient(h->side_stream, h->n, h->tiles_count.as<uint32_t>(), state, adam, first_launch,
+                                           gut_make_lazy(lazy, step), reg);
     HIP_TRY(hipGetLastError());
     gut_context::EarlyArgs& ea = h->early_args;
-    ea.raw12 = d_raw12; ea.raw_m = d_raw_m; ea.raw_v = d_raw_v; ea.sh48 = d_sh48; ea.sh_m = d_sh_m; ea.sh_v = d_sh_v;
-    ea.act12 = d_act12_out;
-    memcpy(ea.lr12, lr12, sizeof(ea.lr12));
-    memcpy(ea.lr48, lr48, sizeof(ea.lr48));
-    ea.beta1 = beta1; ea.beta2 = beta2; ea.eps = eps; ea.step = step; ea.block_begin = first; ea.block_end = nblocks;
-    ea.lazy = GutLazyMoments{};
-    if (lazy) ea.lazy = *lazy;
+    ea.state = state;
+    ea.adam = adam;
+    ea.lazy = lazy ? *lazy : GutLazyMoments{};
     ea.reg = h->reg;
+    ea.blocks = gut::SideStreamBlocks{};
+    ea.blocks.block_begin = ea.blocks.split_block = first;
+    ea.blocks.block_end = nblocks;
+    ea.blocks.second_launch = true;
     // unsorted variant with something to walk: the second launch also takes, in the first early_extra_percent of the blocks,
-    // the waves with tiles in which the forward walked no Gaussian (see launch_early_part2)
-    ea.extra_end = (h->cfg.k_buffer_size == 0 && h->m) ? (uint32_t)((uint64_t)nblocks * (uint32_t)h->early_extra_percent / 100u) : 0u;
-    // (wave_walked was sized and cleared by the forward)
-    h->early_part2_pending = first < nblocks || ea.extra_end > 0;
+    // the waves with tiles in which the forward walked no Gaussian (see launch_early_part2) — so it starts at block 0
+    ea.blocks.extra_end = (h->cfg.k_buffer_size == 0 && h->m) ? (uint32_t)((uint64_t)nblocks * (uint32_t)h->early_extra_percent / 100u) : 0u;
+    if (ea.blocks.extra_end) {
+        ea.blocks.block_begin = 0;
+        // (sized and cleared by the forward, and only the forward's ensure() can move it: the pointer kept here stays valid until
+        //  the step ends — whoever lets anything else reallocate wave_walked must fetch it at the launches instead)
+        ea.blocks.wave_walked = h->wave_walked.as<uint8_t>();
+    }
+    h->early_part2_pending = first < nblocks || ea.blocks.extra_end > 0;
     if (timing) {
         (void)hipEventRecord(h->kev[15], h->side_stream);  // re-recorded behind the second launch
         h->ring[h->ring_cur].early = true;
@@ -1291,7 +1286,7 @@ static int launch_early_part2(gut_context* h, hipStream_t s) {
     h->early_part2_pending = false;
     if (!h->ev_bwd_start) HIP_TRY(hipEventCreateWithFlags(&h->ev_bwd_start, kOrderingEvent));
     const gut_context::EarlyArgs& ea = h->early_args;
-    if (ea.extra_end) {
+    if (ea.blocks.extra_end) {
         // The forward compositor is done by now: mark the waves that hold a Gaussian it walked.  The backward compositor walks
         // no further than the forward did (it is bounded by the forward's per-tile depth), so every other wave is gradient-free.
         // (zero since K1 of this frame)
@@ -1302,11 +1297,8 @@ static int launch_early_part2(gut_context* h, hipStream_t s) {
     HIP_TRY(hipEventRecord(h->ev_bwd_start, s));
     HIP_TRY(hipStreamWaitEvent(h->side_stream, h->ev_bwd_start, 0));
     if (h->cfg.enable_kernel_timings != 0 && h->timing_side_stream && h->kev[7]) (void)hipEventRecord(h->kev[7], h->side_stream);  // start of the second launch
-    gut::launch_adam_rows_without_gradient(h->side_stream, h->n, h->tiles_count.as<uint32_t>(), ea.raw12, ea.raw_m, ea.raw_v, ea.sh48,
-                                           ea.sh_m, ea.sh_v, ea.lr12, ea.lr48, ea.beta1, ea.beta2, ea.eps, ea.step, ea.act12,
-                                           ea.extra_end ? 0u : ea.block_begin, ea.block_end,
-                                           ea.extra_end ? h->wave_walked.as<uint8_t>() : nullptr, ea.block_begin, ea.extra_end, true,
-                                           gut_make_lazy(&ea.lazy, ea.step), gut_make_reg(&ea.reg));
+    gut::launch_adam_rows_without_gradient(h->side_stream, h->n, h->tiles_count.as<uint32_t>(), ea.state, ea.adam, ea.blocks,
+                                           gut_make_lazy(&ea.lazy, ea.adam.step), gut_make_reg(&ea.reg));
     HIP_TRY(hipGetLastError());
     const bool timing = h->cfg.enable_kernel_timings != 0 && h->timing_side_stream && h->kev[14] && h->kev[15];
     if (timing) {

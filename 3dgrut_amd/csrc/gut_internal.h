@@ -99,6 +99,48 @@ struct Regularisation {
     __host__ __device__ bool on() const { return density_coeff != 0.0f || scale_coeff != 0.0f; }
 };
 
+// ---- what the fused optimiser's host code hands from the ABI boundary down to the launches (host side only) ----
+// the seven device tensors of the optimiser's state; act12 receives the activated rows of the updated parameters (or null)
+struct OptimiserState {
+    float *raw12 = nullptr, *raw_m = nullptr, *raw_v = nullptr;   // [N,12] parameters and their two moments
+    float *sh48 = nullptr, *sh_m = nullptr, *sh_v = nullptr;      // [N,48]
+    float* act12 = nullptr;
+};
+// Adam's settings for one step; the learning rates by value, so that a stored copy outlives the caller's arrays
+struct AdamSettings {
+    float lr12[12], lr48[48];
+    float beta1, beta2, eps;
+    uint32_t step;   // 1-based; 0 = no bias correction
+};
+inline AdamSettings make_adam_settings(const float* lr12, const float* lr48, float beta1, float beta2, float eps, uint32_t step) {
+    AdamSettings a;
+    for (int i = 0; i < 12; ++i) a.lr12[i] = lr12[i];
+    for (int i = 0; i < 48; ++i) a.lr48[i] = lr48[i];
+    a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.step = step;
+    return a;
+}
+// one launch of the side-stream pass (k_adam_rows_without_gradient): its 256-row blocks and which of their waves it owns
+struct SideStreamBlocks {
+    uint32_t block_begin = 0, block_end = 0;
+    const uint8_t* wave_walked = nullptr;   // per-wave marks of the forward's walk, or null
+    uint32_t split_block = 0;               // first block of the second launch's share of the waves without tiles
+    uint32_t extra_end = 0;                 // blocks < extra_end: unwalked waves with tiles also go to the second launch
+    bool second_launch = false;
+};
+// the handle's rows the single-view optimiser reads: the sensor position [3], the gradient rows the backward compositor left
+// (zeroed as they are read), the tile counts and the per-Gaussian features of the cached forward
+struct ScratchGradients {
+    const float* camera_position = nullptr;
+    float* grad16 = nullptr;
+    const uint32_t* tiles_count = nullptr;
+    const float* feat = nullptr;
+};
+// gs.py:106-115 statistics accumulated by the optimiser kernel (gut_set_position_gradient_statistics), or null
+struct PositionStatistics {
+    float* accum = nullptr;
+    int32_t* denom = nullptr;
+};
+
 // what K1 zeroes on its way (the frame's small clears): ranges [tiles] uint2, trav_bwd [tiles], wave_walked [4 * blocks] bytes (or null)
 struct FrameClears {
     uint2* ranges = nullptr;
@@ -190,23 +232,17 @@ void launch_render_sorted_bwd(hipStream_t s, const ViewParams& v, const RenderCo
 void launch_project_bwd_compact(hipStream_t s, uint32_t n, const float* density12, const uint32_t* tiles_count,
                                 const float* feat, float* grad16 /* rows read are left zero */, float* raw_grad12, float* mrgb);
 // fused per-Gaussian backward epilogue + SH-gradient + Adam (gut_train.hip), single view, reads the handle's gradient rows
-void launch_sh_adam_from_scratch(hipStream_t s, uint32_t n, int sh_degree, const float* d_camera_position, float* grad16,
-                                 const uint32_t* tiles_count, const float* feat, float* raw12, float* raw_m, float* raw_v,
-                                 float* sh48, float* sh_m, float* sh_v, const float* lr12, const float* lr48, float beta1, float beta2,
-                                 float eps, uint32_t step, const float* visibility, float* act12_out, bool rows_with_tiles_only,
-                                 const uint8_t* wave_walked, uint32_t split_block, uint32_t extra_end,
+void launch_sh_adam_from_scratch(hipStream_t s, uint32_t n, int sh_degree, const ScratchGradients& grads, const OptimiserState& state,
+                                 const AdamSettings& adam, const float* visibility,
+                                 const SideStreamBlocks* early /* the side stream's second launch if it took waves of this step, or null */,
                                  const LazyMoments& lazy, const uint8_t* rule_walked /* per-wave marks valid for EVERY wave, or null */,
-                                 float* stat_accum = nullptr, int32_t* stat_denom = nullptr /* gs.py:106-115 statistics, or null */,
-                                 const Regularisation& reg = Regularisation());
-// Adam step of the rows that get no gradient this iteration (tiles_count == 0), see k_adam_rows_without_gradient
+                                 const PositionStatistics& stats = PositionStatistics(), const Regularisation& reg = Regularisation());
 void launch_compact_gradient_rows(hipStream_t s, uint32_t n, const float* act12, const uint32_t* tiles_count, const float* feat,
                                   float* grad16, float* records, uint32_t capacity, uint32_t* count);
-void launch_adam_rows_without_gradient(hipStream_t s, uint32_t n, const uint32_t* tiles_count, float* raw12, float* raw_m, float* raw_v,
-                                       float* sh48, float* sh_m, float* sh_v, const float* lr12, const float* lr48, float beta1,
-                                       float beta2, float eps, uint32_t step, float* act12_out,
-                                       uint32_t block_begin, uint32_t block_end /* range of 256-row blocks */,
-                                       const uint8_t* wave_walked, uint32_t split_block, uint32_t extra_end, bool second_launch,
-                                       const LazyMoments& lazy, const Regularisation& reg = Regularisation());
+// Adam step of the rows that get no gradient this iteration (tiles_count == 0), see k_adam_rows_without_gradient
+void launch_adam_rows_without_gradient(hipStream_t s, uint32_t n, const uint32_t* tiles_count, const OptimiserState& state,
+                                       const AdamSettings& adam, const SideStreamBlocks& blocks, const LazyMoments& lazy,
+                                       const Regularisation& reg = Regularisation());
 void launch_count_side_stream_rows(hipStream_t s, uint32_t n, const uint32_t* tiles_count, const uint8_t* wave_walked,
                                    uint32_t split_block, uint32_t extra_end, Counters* out);
 void launch_mark_waves_with_tiles(hipStream_t s, uint32_t n, const uint32_t* tiles_count, uint8_t* wave_flags);

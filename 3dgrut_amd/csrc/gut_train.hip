@@ -973,61 +973,74 @@ void launch_compact_gradient_rows(hipStream_t s, uint32_t n, const float* act12,
 
 }  // namespace gut
 
-// AdamParams for the adam4 kernels: lr[] already holds lr / (1 - beta1^t) and bias2_sqrt holds 1 / sqrt(1 - beta2^t)
-// (both 1-free when bias correction is off), so the device code multiplies only.  k_adam_step keeps the plain form.
-static void fill_adam(gut::AdamParams& ap, const float* lr, uint32_t cols, float beta1, float beta2, float eps, uint32_t step) {
+// AdamParams in the PLAIN form (k_adam_step): lr[] as given (0 beyond `cols`), bias1 = 1 - beta1^t and bias2_sqrt = sqrt(1 - beta2^t)
+// kept as the divisors of the textbook update (both 1 when bias correction is off, step == 0)
+static void fill_adam_plain(gut::AdamParams& ap, const float* lr, uint32_t cols, float beta1, float beta2, float eps, uint32_t step) {
     ap.beta1 = beta1; ap.beta2 = beta2; ap.eps = eps; ap.cols = cols;
-    float bias1 = 1.0f, bias2_sqrt = 1.0f;
+    ap.bias1 = 1.0f; ap.bias2_sqrt = 1.0f;
     if (step) {
-        bias1 = (float)(1.0 - pow((double)beta1, (double)step));
-        bias2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+        ap.bias1 = (float)(1.0 - pow((double)beta1, (double)step));
+        ap.bias2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     }
-    for (uint32_t i = 0; i < 64; ++i) ap.lr[i] = i < cols ? lr[i] / bias1 : 0.0f;
+    for (uint32_t i = 0; i < 64; ++i) ap.lr[i] = i < cols ? lr[i] : 0.0f;
+}
+
+// AdamParams for the adam4 kernels: the plain form with the bias corrections FOLDED in, so that the device code multiplies only:
+// lr[] holds lr / (1 - beta1^t) and bias2_sqrt holds 1 / sqrt(1 - beta2^t).  This fold is the only difference from k_adam_step's.
+static void fill_adam(gut::AdamParams& ap, const float* lr, uint32_t cols, const gut::AdamSettings& adam) {
+    fill_adam_plain(ap, lr, cols, adam.beta1, adam.beta2, adam.eps, adam.step);
+    for (uint32_t i = 0; i < cols; ++i) ap.lr[i] = ap.lr[i] / ap.bias1;
+    ap.bias2_sqrt = 1.0f / ap.bias2_sqrt;
     ap.bias1 = 1.0f;
-    ap.bias2_sqrt = 1.0f / bias2_sqrt;
+}
+
+// the one launch of k_sh_adam<kScratch, .>: the regularised instance takes the whole argument, the other its base (whose bytes stay
+// what they were).  mrgb / tiles_count / feat: whichever the instance reads, the rest null.
+template <bool kScratch>
+static void launch_k_sh_adam(hipStream_t s, const gut::ShAdamParamsReg& sp, float* mrgb, float* grad, const gut::OptimiserState& st,
+                             const float* visibility, const uint32_t* tiles_count, const float* feat) {
+    auto launch = [&](auto kern, const auto& args) {
+        hipLaunchKernelGGL(kern, dim3((sp.n + gut::kBlock - 1) / gut::kBlock), dim3(gut::kBlock), 0, s, args, mrgb,
+                           reinterpret_cast<float4*>(grad), reinterpret_cast<float4*>(st.raw12), reinterpret_cast<float4*>(st.raw_m),
+                           reinterpret_cast<float4*>(st.raw_v), reinterpret_cast<float4*>(st.sh48), reinterpret_cast<float4*>(st.sh_m),
+                           reinterpret_cast<float4*>(st.sh_v), visibility, reinterpret_cast<float4*>(st.act12), tiles_count, feat);
+    };
+    if (sp.reg.on()) launch(gut::k_sh_adam<kScratch, true>, sp);
+    else launch(gut::k_sh_adam<kScratch, false>, static_cast<const gut::ShAdamParams&>(sp));
 }
 
 namespace gut {
-void launch_sh_adam_from_scratch(hipStream_t s, uint32_t n, int sh_degree, const float* d_camera_position, float* grad16,
-                                 const uint32_t* tiles_count, const float* feat, float* raw12, float* raw_m, float* raw_v,
-                                 float* sh48, float* sh_m, float* sh_v, const float* lr12, const float* lr48, float beta1, float beta2,
-                                 float eps, uint32_t step, const float* visibility, float* act12_out, bool rows_with_tiles_only,
-                                 const uint8_t* wave_walked, uint32_t split_block, uint32_t extra_end, const LazyMoments& lazy,
-                                 const uint8_t* rule_walked, float* stat_accum, int32_t* stat_denom, const Regularisation& reg) {
+void launch_sh_adam_from_scratch(hipStream_t s, uint32_t n, int sh_degree, const ScratchGradients& grads, const OptimiserState& state,
+                                 const AdamSettings& adam, const float* visibility, const SideStreamBlocks* early,
+                                 const LazyMoments& lazy, const uint8_t* rule_walked, const PositionStatistics& stats,
+                                 const Regularisation& reg) {
     if (n == 0) return;
     ShAdamParamsReg sp;
     sp.reg = reg;
-    sp.stat_accum = stat_accum; sp.stat_denom = stat_denom;
+    sp.stat_accum = stats.accum; sp.stat_denom = stats.denom;
     sp.lazy = lazy;
     sp.rule_walked = rule_walked;
-    sp.rows_with_tiles_only = rows_with_tiles_only ? 1 : 0;
-    sp.own.walked = wave_walked; sp.own.split_block = split_block; sp.own.extra_end = extra_end;
+    sp.rows_with_tiles_only = early ? 1 : 0;   // (the kernel reads `own` only then)
+    const SideStreamBlocks own = early ? *early : SideStreamBlocks();
+    sp.own.walked = own.wave_walked; sp.own.split_block = own.split_block; sp.own.extra_end = own.extra_end;
     sp.clear_consumed = 0;
-    fill_adam(sp.a12, lr12, 12, beta1, beta2, eps, step);
-    fill_adam(sp.a48, lr48, 48, beta1, beta2, eps, step);
-    sp.cam = d_camera_position;
+    fill_adam(sp.a12, adam.lr12, 12, adam);
+    fill_adam(sp.a48, adam.lr48, 48, adam);
+    sp.cam = grads.camera_position;
     sp.n = n; sp.views = 1; sp.sh_degree = sh_degree; sp.grad_scale = 1.0f; sp.view_stride = n;
-    auto launch = [&](auto kern, const auto& args) {
-        hipLaunchKernelGGL(kern, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, args, (float*)nullptr,
-                           reinterpret_cast<float4*>(grad16), reinterpret_cast<float4*>(raw12), reinterpret_cast<float4*>(raw_m),
-                           reinterpret_cast<float4*>(raw_v), reinterpret_cast<float4*>(sh48), reinterpret_cast<float4*>(sh_m),
-                           reinterpret_cast<float4*>(sh_v), visibility, reinterpret_cast<float4*>(act12_out), tiles_count, feat);
-    };
-    if (reg.on()) launch(k_sh_adam<true, true>, sp);
-    else launch(k_sh_adam<true, false>, static_cast<const ShAdamParams&>(sp));
+    launch_k_sh_adam<true>(s, sp, nullptr, grads.grad16, state, visibility, grads.tiles_count, grads.feat);
 }
 
-void launch_adam_rows_without_gradient(hipStream_t s, uint32_t n, const uint32_t* tiles_count, float* raw12, float* raw_m, float* raw_v,
-                                       float* sh48, float* sh_m, float* sh_v, const float* lr12, const float* lr48, float beta1,
-                                       float beta2, float eps, uint32_t step, float* act12_out, uint32_t block_begin,
-                                       uint32_t block_end, const uint8_t* wave_walked, uint32_t split_block, uint32_t extra_end,
-                                       bool second_launch, const LazyMoments& lazy, const Regularisation& reg) {
-    if (n == 0 || block_end <= block_begin) return;
+void launch_adam_rows_without_gradient(hipStream_t s, uint32_t n, const uint32_t* tiles_count, const OptimiserState& state,
+                                       const AdamSettings& adam, const SideStreamBlocks& blocks, const LazyMoments& lazy,
+                                       const Regularisation& reg) {
+    if (n == 0 || blocks.block_end <= blocks.block_begin) return;
+    const bool second_launch = blocks.second_launch;
     EarlyOwnership own;
-    own.walked = wave_walked; own.split_block = split_block; own.extra_end = extra_end;
+    own.walked = blocks.wave_walked; own.split_block = blocks.split_block; own.extra_end = blocks.extra_end;
     AdamParams a12, a48;
-    fill_adam(a12, lr12, 12, beta1, beta2, eps, step);
-    fill_adam(a48, lr48, 48, beta1, beta2, eps, step);
+    fill_adam(a12, adam.lr12, 12, adam);
+    fill_adam(a48, adam.lr48, 48, adam);
     static int num_cus = 0;  // same for every device of a node
     if (num_cus == 0) {
         int dev = 0;
@@ -1035,7 +1048,7 @@ void launch_adam_rows_without_gradient(hipStream_t s, uint32_t n, const uint32_t
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) num_cus = prop.multiProcessorCount;
         if (num_cus <= 0) num_cus = 256;
     }
-    const uint32_t nblocks = block_end - block_begin;
+    const uint32_t nblocks = blocks.block_end - blocks.block_begin;
     static int wgs_per_cu = 0, wgs_per_cu2 = 0;
     if (wgs_per_cu == 0) {
         const char* e = getenv("GUT_EARLY_WGS_PER_CU");  // tuning experiments only
@@ -1060,35 +1073,28 @@ void launch_adam_rows_without_gradient(hipStream_t s, uint32_t n, const uint32_t
         const char* e = getenv("GUT_EARLY_NARROW");  // tuning experiments only
         narrow_first = e ? atoi(e) : 1;
     }
+    // Reg...: the regularised instances take one more argument (the unregularised kernels' arguments stay what they were)
+    auto launch = [&](auto kern, const auto&... reg_arg) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, a12, a48, n, tiles_count, reinterpret_cast<float4*>(state.raw12),
+                           reinterpret_cast<float4*>(state.raw_m), reinterpret_cast<float4*>(state.raw_v),
+                           reinterpret_cast<float4*>(state.sh48), reinterpret_cast<float4*>(state.sh_m),
+                           reinterpret_cast<float4*>(state.sh_v), reinterpret_cast<float4*>(state.act12), blocks.block_begin,
+                           blocks.block_end, own, second_launch ? 1u : 0u, lazy, reg_arg...);
+    };
+    const bool narrow = lazy.wave_step && narrow_first && !second_launch;
     if (reg.on()) {
         // regularised: the wide form in both launches — the 32-register form with the eager raw block spills 32 VGPRs to scratch
         // (see k_adam_rows_without_gradient_narrow); measured against it and over first-launch shares in DESIGN.md
 #if GUT_NARROW_REGULARISED
-        auto kern = lazy.wave_step ? ((narrow_first && !second_launch) ? k_adam_rows_without_gradient_narrow<true, Regularisation>
-                                                                       : k_adam_rows_without_gradient<true, true, Regularisation>)
-                                   : k_adam_rows_without_gradient<false, true, Regularisation>;
-#else
-        auto kern = lazy.wave_step ? k_adam_rows_without_gradient<true, true, Regularisation>
-                                   : k_adam_rows_without_gradient<false, true, Regularisation>;
+        if (narrow) return launch(k_adam_rows_without_gradient_narrow<true, Regularisation>, reg);
 #endif
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, a12, a48, n, tiles_count,
-                           reinterpret_cast<float4*>(raw12), reinterpret_cast<float4*>(raw_m), reinterpret_cast<float4*>(raw_v),
-                           reinterpret_cast<float4*>(sh48), reinterpret_cast<float4*>(sh_m), reinterpret_cast<float4*>(sh_v),
-                           reinterpret_cast<float4*>(act12_out), block_begin, block_end, own, second_launch ? 1u : 0u, lazy, reg);
-        return;
+        launch(lazy.wave_step ? k_adam_rows_without_gradient<true, true, Regularisation>
+                              : k_adam_rows_without_gradient<false, true, Regularisation>, reg);
+    } else if (narrow) {
+        launch(k_adam_rows_without_gradient_narrow<false>);
+    } else {
+        launch(lazy.wave_step ? k_adam_rows_without_gradient<true, false> : k_adam_rows_without_gradient<false, false>);
     }
-    if (lazy.wave_step && narrow_first && !second_launch) {
-        hipLaunchKernelGGL(k_adam_rows_without_gradient_narrow<false>, dim3(grid), dim3(kBlock), 0, s, a12, a48, n, tiles_count,
-                           reinterpret_cast<float4*>(raw12), reinterpret_cast<float4*>(raw_m), reinterpret_cast<float4*>(raw_v),
-                           reinterpret_cast<float4*>(sh48), reinterpret_cast<float4*>(sh_m), reinterpret_cast<float4*>(sh_v),
-                           reinterpret_cast<float4*>(act12_out), block_begin, block_end, own, second_launch ? 1u : 0u, lazy);
-        return;
-    }
-    auto kern = lazy.wave_step ? k_adam_rows_without_gradient<true, false> : k_adam_rows_without_gradient<false, false>;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, a12, a48, n, tiles_count,
-                       reinterpret_cast<float4*>(raw12), reinterpret_cast<float4*>(raw_m), reinterpret_cast<float4*>(raw_v),
-                       reinterpret_cast<float4*>(sh48), reinterpret_cast<float4*>(sh_m), reinterpret_cast<float4*>(sh_v),
-                       reinterpret_cast<float4*>(act12_out), block_begin, block_end, own, second_launch ? 1u : 0u, lazy);
 }
 
 // k_regularisation_loss: the loss values from the per-wave partials, in a fixed order (one workgroup of 1024 lanes, double
@@ -1341,14 +1347,7 @@ int gut_adam_step(void* stream, uint64_t rows, uint32_t cols, float* d_param, co
     if (!d_param || !d_grad || !d_exp_avg || !d_exp_avg_sq || !lr_per_col) return 1;
     if (cols == 0 || cols > 64 || (cols & 3)) return 3;  // rows are processed as float4 groups
     gut::AdamParams ap;
-    for (uint32_t i = 0; i < 64; ++i) ap.lr[i] = i < cols ? lr_per_col[i] : 0.0f;
-    ap.beta1 = beta1; ap.beta2 = beta2; ap.eps = eps; ap.cols = cols;
-    if (step) {
-        ap.bias1 = (float)(1.0 - pow((double)beta1, (double)step));
-        ap.bias2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-    } else {
-        ap.bias1 = 1.0f; ap.bias2_sqrt = 1.0f;
-    }
+    fill_adam_plain(ap, lr_per_col, cols, beta1, beta2, eps, step);   // k_adam_step divides by the bias corrections itself
     const uint64_t n_vec4 = rows * (cols / 4);
     const uint64_t blocks = (n_vec4 + gut::kBlock - 1) / gut::kBlock;
     if (blocks > 0x7fffffffull) return 4;
@@ -1416,9 +1415,11 @@ int gut_sh_adam_step_regularised(void* stream, uint32_t num_particles, int32_t s
         return 1;
     if (num_views == 0 || num_views > 1024 || sh_degree < 0 || sh_degree > 3) return 3;
     if (flags & ~(uint32_t)GUT_ADAM_CLEAR_CONSUMED_GRADS) return 3;
+    const gut::OptimiserState state{d_raw12, d_raw_m, d_raw_v, d_sh48, d_sh_m, d_sh_v, d_act12_out};
+    const gut::AdamSettings adam = gut::make_adam_settings(lr12, lr48, beta1, beta2, eps, step);
     gut::ShAdamParamsReg sp;
-    fill_adam(sp.a12, lr12, 12, beta1, beta2, eps, step);
-    fill_adam(sp.a48, lr48, 48, beta1, beta2, eps, step);
+    fill_adam(sp.a12, adam.lr12, 12, adam);
+    fill_adam(sp.a48, adam.lr48, 48, adam);
     sp.cam = d_camera_positions;
     sp.n = num_particles; sp.views = num_views; sp.sh_degree = sh_degree; sp.grad_scale = grad_scale;
     sp.view_stride = mrgb_view_stride ? mrgb_view_stride : num_particles;
@@ -1431,15 +1432,7 @@ int gut_sh_adam_step_regularised(void* stream, uint32_t num_particles, int32_t s
     sp.rule_walked = nullptr;
     sp.stat_accum = nullptr; sp.stat_denom = nullptr;
     sp.reg = gut_make_reg(reg);
-    auto launch = [&](auto kern, const auto& args) {
-        hipLaunchKernelGGL(kern, dim3((num_particles + gut::kBlock - 1) / gut::kBlock), dim3(gut::kBlock), 0,
-                           static_cast<hipStream_t>(stream), args, d_mrgb, reinterpret_cast<float4*>(d_raw_grad12),
-                           reinterpret_cast<float4*>(d_raw12), reinterpret_cast<float4*>(d_raw_m), reinterpret_cast<float4*>(d_raw_v),
-                           reinterpret_cast<float4*>(d_sh48), reinterpret_cast<float4*>(d_sh_m), reinterpret_cast<float4*>(d_sh_v),
-                           d_visibility, reinterpret_cast<float4*>(d_act12_out), (const uint32_t*)nullptr, (const float*)nullptr);
-    };
-    if (sp.reg.on()) launch(gut::k_sh_adam<false, true>, sp);
-    else launch(gut::k_sh_adam<false, false>, static_cast<const gut::ShAdamParams&>(sp));
+    launch_k_sh_adam<false>(static_cast<hipStream_t>(stream), sp, d_mrgb, d_raw_grad12, state, d_visibility, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -1469,10 +1462,13 @@ int gut_adam_unwalked_waves_regularised(void* stream, uint32_t num_particles, co
                                         const GutLazyMoments* lazy, const GutRegularisation* reg) {
     if (num_particles == 0) return 0;
     if (!d_wave_flags || !d_raw12 || !d_raw_m || !d_raw_v || !d_sh48 || !d_sh_m || !d_sh_v || !lr12 || !lr48) return 1;
+    const gut::OptimiserState state{d_raw12, d_raw_m, d_raw_v, d_sh48, d_sh_m, d_sh_v, d_act12_out};
+    const gut::AdamSettings adam = gut::make_adam_settings(lr12, lr48, beta1, beta2, eps, step);
     const uint32_t nblocks = (num_particles + gut::kBlock - 1) / gut::kBlock;
-    gut::launch_adam_rows_without_gradient(static_cast<hipStream_t>(stream), num_particles, nullptr, d_raw12, d_raw_m, d_raw_v, d_sh48,
-                                           d_sh_m, d_sh_v, lr12, lr48, beta1, beta2, eps, step, d_act12_out, 0, nblocks, d_wave_flags,
-                                           0, nblocks, true, gut_make_lazy(lazy, step), gut_make_reg(reg));
+    gut::SideStreamBlocks blocks;   // every block, as the second launch: the waves whose flag is zero
+    blocks.block_end = nblocks; blocks.wave_walked = d_wave_flags; blocks.extra_end = nblocks; blocks.second_launch = true;
+    gut::launch_adam_rows_without_gradient(static_cast<hipStream_t>(stream), num_particles, nullptr, state, adam, blocks,
+                                           gut_make_lazy(lazy, step), gut_make_reg(reg));
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -19,7 +19,7 @@ import math
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, optim_calls
 from .dp import (RecordExchange, allgather_rows_, allgather_rows_async, allreduce_max_, allreduce_max_async, allreduce_mean_, allreduce_sum_async,
                  assert_replicas_identical)
 from .losses import _photometric_loss_call, _plane_mask, photometric_loss
@@ -238,8 +238,7 @@ class NativeTrainStep:
         """True while the default-on optimiser overlap is still being timed against the one-pass form (steps PROBE_FIRST ..
         PROBE_LAST of single-view steps with the fused epilogue; data-parallel and hooked steps never probe)."""
         p = self._overlap_probe
-        one_pass = self.fused and self.world_size <= 1 and not self.force_exchange and self.fuse_epilogue \
-            and (self.post_backward_hook is None or self.fused_statistics is not None)
+        one_pass = self._one_pass()
         return p is not None and not p["done"] and one_pass and not self.selective
 
     def resize_workspace(self):
@@ -294,26 +293,35 @@ class NativeTrainStep:
         n = self.model.num_gaussians
         if not self._regularised() or n == 0:
             return None
-        return _capi.GutRegularisation(self.lambda_opacity / n, self.lambda_scale / (3 * n), self._reg_partials.data_ptr() + 8 * (row0 // 64))
+        return optim_calls.regularisation(self.lambda_opacity / n, self.lambda_scale / (3 * n), self._reg_partials, row0)
 
     def _regularisation_losses(self, loss_buffer=None):
         """(opacity_loss, scale_loss) device scalars from the partials the step's optimiser kernels wrote (gut_regularisation_loss,
         on the current stream, which is ordered behind every stream that wrote them); loss_buffer: a device float they are added to."""
         out = torch.empty((2,), dtype=torch.float32, device=self.model.raw.device)
-        st = torch.cuda.current_stream(out.device).cuda_stream
-        rc = self._lib.gut_regularisation_loss(C.c_void_p(st), self.model.num_gaussians, self._reg_partials.data_ptr(), self.lambda_opacity,
-                                              self.lambda_scale, out.data_ptr(), out.data_ptr() + 4,
-                                              None if loss_buffer is None else loss_buffer.data_ptr())
-        if rc:
-            raise RuntimeError(f"[3dgut] regularisation_loss failed ({rc})")
-        return out[0], out[1]
+        opacity_loss, scale_loss = out[0], out[1]
+        optim_calls.regularisation_loss(self._lib, self._stream(), self.model.num_gaussians, self._reg_partials, self.lambda_opacity,
+                                        self.lambda_scale, opacity_loss, scale_loss, loss_buffer)
+        return opacity_loss, scale_loss
 
-    def _lazy(self):
-        """GutLazyMoments for the optimiser entry points, or None."""
+    def _lazy(self, row0=0):
+        """GutLazyMoments for the optimiser entry points, or None; row0: first row of a row-range call (a multiple of 64)."""
         if not self.lazy_moments or self.wave_step is None:
             return None
-        return _capi.GutLazyMoments(self.wave_step.data_ptr(), self._pow1.data_ptr(), self._pow2.data_ptr(), self.LAZY_TABLE,
-                                    self._lazy_overrun.data_ptr())
+        return optim_calls.lazy_moments(self.wave_step, self._pow1, self._pow2, self.LAZY_TABLE, self._lazy_overrun, row0)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.model.raw.device).cuda_stream
+
+    def _state(self):
+        """The six tensors of the optimiser's state, in the order every optimiser call takes them."""
+        m = self.model
+        return m.raw, self.m12, self.v12, m.features, self.m48, self.v48
+
+    def _adam_settings(self):
+        """Adam's settings for the step being applied, in the order every optimiser call takes them (SelectiveAdam: step 0, no
+        bias correction)."""
+        return self.lr12, self.lr48, self.betas, self.eps, 0 if self.selective else self.step_id + 1
 
     # The step counter and the per-wave `wave_step` of the lazy moment decay belong together: a wave's stored moments are current up
     # to wave_step[w] and every reader multiplies them by beta^(step - wave_step[w]).  So the counter cannot simply be assigned
@@ -368,15 +376,10 @@ class NativeTrainStep:
         lz = self._lazy()
         if lz is None or self.model.num_gaussians == 0 or not self.model.raw.is_cuda:
             return
-        st = torch.cuda.current_stream(self.model.raw.device).cuda_stream
         # with a regulariser the stored [N,12] moments are current every step: only the [N,48] block is brought up to date
         eager = _RAW_MOMENTS_EAGER if self._raw_eager else None
         with torch.cuda.device(self.model.raw.device):
-            rc = self._lib.gut_sync_moments_ex(C.c_void_p(st), self.model.num_gaussians, self.m12.data_ptr(), self.v12.data_ptr(),
-                                               self.m48.data_ptr(), self.v48.data_ptr(), C.byref(lz), int(self.step_id),
-                                               None if eager is None else C.byref(eager))
-        if rc:
-            raise RuntimeError(f"[3dgut] sync_moments failed ({rc})")
+            optim_calls.sync_moments(self._lib, self._stream(), self.m12, self.v12, self.m48, self.v48, lz, int(self.step_id), eager)
         if int(self._lazy_overrun.item()):   # (a blocking read, on a path that runs every LAZY_TABLE / 2 steps and on row surgery)
             self._lazy_overrun.zero_()
             raise RuntimeError(f"[3dgut] lazy moment decay: a wave's stored Adam moments had missed {self.LAZY_TABLE} or more steps "
@@ -425,12 +428,10 @@ class NativeTrainStep:
         stream = torch.cuda.current_stream(dev)
 
         def noop_pass():
-            rc = self._lib.gut_adam_unwalked_waves(
+            optim_calls.check(self._lib.gut_adam_unwalked_waves(
                 C.c_void_p(stream.cuda_stream), n, flags.data_ptr(), m.raw.data_ptr(), self.m12.data_ptr(), self.v12.data_ptr(),
                 m.features.data_ptr(), self.m48.data_ptr(), self.v48.data_ptr(), zero12, zero48, 1.0, 1.0, self.eps, 0,
-                self.act.data_ptr())
-            if rc:
-                raise RuntimeError(f"[3dgut] adam_unwalked_waves failed ({rc})")
+                self.act.data_ptr()), "adam_unwalked_waves")
 
         def timed(reps=3):
             noop_pass()
@@ -485,21 +486,8 @@ class NativeTrainStep:
         raw = self.model.raw
         if self._act_key == (raw.data_ptr(), raw._version, raw.shape[0]):
             return self.act  # written by the previous step's fused Adam kernel; raw untouched since
-        st = torch.cuda.current_stream(self.model.raw.device).cuda_stream
-        rc = self._lib.gut_activate_pack(C.c_void_p(st), self.model.num_gaussians, self.model.raw.data_ptr(), self.act.data_ptr())
-        if rc:
-            raise RuntimeError(f"[3dgut] activate_pack failed ({rc})")
+        optim_calls.activate_pack(self._lib, self._stream(), raw, self.act)
         return self.act
-
-    def _adam(self, p, g, m, v, lr, vis):
-        st = torch.cuda.current_stream(p.device).cuda_stream
-        lr_arr = (C.c_float * len(lr))(*[float(x) for x in lr])
-        rc = self._lib.gut_adam_step(C.c_void_p(st), p.shape[0], p.shape[1], p.data_ptr(), g.data_ptr(), m.data_ptr(),
-                                     v.data_ptr(), lr_arr, self.betas[0], self.betas[1], self.eps,
-                                     0 if self.selective else self.step_id + 1,
-                                     None if vis is None else vis.data_ptr())
-        if rc:
-            raise RuntimeError(f"[3dgut] adam_step failed ({rc})")
 
     def forward(self, batch, train=True):
         """Returns (pred_rgb [1,H,W,3] leaf requiring grad, pred_opacity, aux) without involving Gaussian-sized autograd."""
@@ -585,24 +573,62 @@ class NativeTrainStep:
                 self._end_of_step(None)
             raise
 
+    def _one_pass(self):
+        """One view and nobody else needs the per-Gaussian gradients: the step can run on the handle's fused optimiser."""
+        return self.fused and self.world_size <= 1 and not self.force_exchange and self.fuse_epilogue \
+            and (self.post_backward_hook is None or self.fused_statistics is not None)
+
     def _step(self, batch):
         m = self.model
+        # the replica check comes BEFORE the first update of this trainer (ADVICE r3: `step_id % every == 0` alone fires after it):
+        # ranks that were built from different scenes, seeds or checkpoints are caught while nothing has been applied yet
         if self.world_size > 1 and self.replica_check_every and not getattr(self, "_replicas_checked_at_start", False):
-            # BEFORE the first update of this trainer (`step_id % every == 0` alone fires after it): ranks that were built from
-            # different scenes, seeds or checkpoints are caught while nothing has been applied yet
             self._replicas_checked_at_start = True
             assert_replicas_identical([self.model.raw, self.model.features, self.m12, self.v12, self.m48, self.v48], self.world_size,
                                       what=f"before the first step (step counter {self.step_id})")
         evs = [] if self.phase_timing else None
-        self._mark(evs)
+        self._mark(evs)                                  # mark 1: start of the step
         if self._regularised() != self._raw_eager:
-            # the regulariser switches on or off: bring every stored moment up to date under the OLD setting first, so that no
-            # [N,12] moment is read as current while it is stale (on) or decayed again by missed steps (off)
+            # the regulariser switches on or off: bring every stored moment up to date under the OLD setting first — and before the
+            # forward — so that no [N,12] moment is read as current while it is stale (on) or decayed again by missed steps (off)
             self.sync_moments()
             self._raw_eager = self._regularised()
         reg = self._regularisation()
-        one_pass = self.fused and self.world_size <= 1 and not self.force_exchange and self.fuse_epilogue \
-            and (self.post_backward_hook is None or self.fused_statistics is not None)
+        one_pass = self._one_pass()
+        # (the probe records probe_evs[0] here, before the forward: it times the whole step; _end_of_step records probe_evs[1])
+        use_overlap, self._probe_evs = self._probe_overlap(one_pass)
+        early = one_pass and use_overlap and not self.selective
+        rgba, dist_, hits, vis = self.forward(batch)
+        # after the forward and before the early optimiser launch: the handle hands the regulariser to the step's optimiser calls
+        if one_pass and reg is not None:
+            self.raster.set_regularisation(reg)
+            self._reg_set = True
+        if early:
+            self.raster.optimize_rows_without_gradient(*self._state(), *self._adam_settings(), self.act, lazy=self._lazy())
+            self._early_queued = True                    # directly after the launch: step()'s recovery finishes what it began
+        self._mark(evs)                                  # mark 2: forward (and the early launch) queued
+        loss, pred_rgb, rgba_grad = self._loss(batch, rgba)
+        self._mark(evs)                                  # mark 3: loss queued
+        _, sensor, poses, _, _ = self._ctx
+        bwd_args = (self.step_id, m.n_active_features, self.act, m.features, batch.rays_ori.contiguous(),
+                    batch.rays_dir.contiguous(), None, sensor, poses.timestamps_us[0], poses.timestamps_us[1],
+                    poses.T_world_sensors[0], poses.T_world_sensors[1], rgba, rgba_grad, dist_, None)
+        # every update path queues the backward and sets mark 4 behind it (the sparse one behind compact_gradient_rows); the fused
+        # ones set _act_key, and only after the optimiser call that wrote `act`
+        if not self.fused:
+            self._update_unfused(batch, bwd_args, vis, evs, reg)
+        elif one_pass:
+            self._update_one_pass(bwd_args, vis, evs)
+        elif self.dp_exchange == "sparse":
+            self._sparse_exchange_and_update(batch, bwd_args, vis, evs, reg)
+        else:
+            self._update_dense_exchange(batch, bwd_args, vis, evs)
+        return self._finish_step(evs, loss, pred_rgb, vis, hits, reg)
+
+    def _probe_overlap(self, one_pass):
+        """The optimiser overlap of this step, (use_overlap, probe_evs): the setting in force, except while the default-on overlap is
+        timed against the one-pass form — steps PROBE_FIRST .. PROBE_LAST alternate the two under an event pair (probe_evs, whose
+        first event is recorded HERE, i.e. before the forward), and the first step after them keeps the faster form."""
         use_overlap, probe_evs = self.overlap_optimizer, None
         probe = self._overlap_probe
         if probe is not None and one_pass and not self.selective:
@@ -620,17 +646,12 @@ class NativeTrainStep:
                 probe.update(done=True, ms_on=t_on, ms_off=t_off)
                 if probe["on"] and probe["off"]:   # (a trainer whose step counter starts beyond the probing steps keeps the default)
                     self.overlap_optimizer = use_overlap = t_on <= t_off
-        early = one_pass and use_overlap and not self.selective
-        self._probe_evs = probe_evs
-        rgba, dist_, hits, vis = self.forward(batch)
-        if one_pass and reg is not None:
-            self.raster.set_regularisation(reg)   # consumed by the step's optimiser calls on the handle
-            self._reg_set = True
-        if early:
-            self.raster.optimize_rows_without_gradient(m.raw, self.m12, self.v12, m.features, self.m48, self.v48, self.lr12,
-                                                       self.lr48, self.betas, self.eps, self.step_id + 1, self.act, lazy=self._lazy())
-            self._early_queued = True
-        self._mark(evs)
+        return use_overlap, probe_evs
+
+    def _loss(self, batch, rgba):
+        """(loss, pred_rgb, rgba_grad) of the rendered rgba [H,W,4] against batch.rgb_gt: the fused HIP loss where it applies, else
+        image-sized torch autograd."""
+        m = self.model
         gt = batch.rgb_gt
         # Batch.mask [1,H,W,1] or None: prediction and ground truth are multiplied by it inside the loss (trainer.py:397-404); the
         # pred_rgb returned stays unmasked, as the reference masks only the locals of get_losses
@@ -649,108 +670,97 @@ class NativeTrainStep:
             self._loss3, rgba_grad = _photometric_loss_call(self._lib, H, W, rgba, gt, 1.0 if m.background_color == "white" else 0.0,
                                                             self.lambda_l1, self.lambda_ssim,
                                                             None if mask is None else _plane_mask(mask, H, W, rgba.device), self._loss_ws)
-            loss = self._loss3[0]
             pred_rgb = rgba[..., :3].unsqueeze(0)
             if m.background_color == "white":
                 pred_rgb = pred_rgb + (1.0 - rgba[..., 3:].unsqueeze(0))
-        else:
-            rgba_leaf = rgba.detach().requires_grad_(True)
-            pred_rgb = rgba_leaf[..., :3].unsqueeze(0)
-            pred_opacity = rgba_leaf[..., 3:].unsqueeze(0)
-            pred_rgb, pred_opacity = m.background(batch.T_to_world, batch.rays_dir, pred_rgb, pred_opacity, True)
-            loss = photometric_loss(pred_rgb, gt, self.lambda_l1, self.lambda_ssim, mask=mask)
-            loss.backward()  # image-sized autograd only
-            rgba_grad = rgba_leaf.grad
-        self._mark(evs)
-        _, sensor, poses, _, _ = self._ctx
-        bwd_args = (self.step_id, m.n_active_features, self.act, m.features, batch.rays_ori.contiguous(),
-                    batch.rays_dir.contiguous(), None, sensor, poses.timestamps_us[0], poses.timestamps_us[1],
-                    poses.T_world_sensors[0], poses.T_world_sensors[1], rgba, rgba_grad, dist_, None)
-        vmask = None
-        if self.fused:
-            w = max(1, self.world_size)
-            exchange = w > 1 or self.force_exchange
-            if one_pass:
-                # one view, nobody else needs the per-Gaussian gradients: K8's epilogue, the SH-gradient rebuild and Adam run
-                # as ONE pass over the Gaussians, straight from the renderer's gradient rows (gut_optimize_after_bwd)
-                self.raster.trace_bwd(*bwd_args, skip_epilogue=True)
-                self._mark(evs)
-                vmask = vis.reshape(-1) if self.selective else None
-                stats = self.fused_statistics() if self.fused_statistics is not None else None
-                if stats is not None:
-                    self.raster.set_position_gradient_statistics(*stats)
-                # camera position None: the library uses the sensor position of its cached forward (the very floats K1 evaluated the
-                # colours from; an 18 us host-to-device copy sat here, between K7 and the pass over the walked waves, until round 4)
-                self.raster.optimize_after_bwd(m.n_active_features, None, m.raw, self.m12, self.v12, m.features,
-                                               self.m48, self.v48, self.lr12, self.lr48, self.betas, self.eps,
-                                               0 if self.selective else self.step_id + 1, vmask, self.act, lazy=self._lazy())
-                self._reg_set = False
-                self._act_key = (m.raw.data_ptr(), m.raw._version, m.raw.shape[0])
-                return self._finish_step(evs, loss, pred_rgb, vis, hits, reg)
-            if self.dp_exchange == "sparse":
-                self._sparse_exchange_and_update(batch, bwd_args, vis, evs, w, exchange, reg)
-                return self._finish_step(evs, loss, pred_rgb, vis, hits, reg)
-            # this view's compact radiance gradient: directly view 0 of the gathered layout when there is nothing to gather
-            local_mrgb = self.mrgb_local if exchange else self.mrgb[0][0]
-            self.raster.trace_bwd(*bwd_args, raw_parameter_grads=True, compact_radiance_grads=True, out=(self.g12, local_mrgb))
-            self._mark(evs)
-            cam_local = self._sensor_position(batch)
-            if self.post_backward_hook is not None:  # per-view statistics, before the exchange (strategy/gs.py:106-115)
-                self.post_backward_hook(self.g12[:, 0:3], cam_local)
-            works = []
-            if exchange:
-                # Chunk-pipelined exchange: the collectives of chunk c+1 run on RCCL's stream while the optimiser kernel
-                # of chunk c runs on the compute stream (the optimiser is HBM-bound, the exchange xGMI-bound).
-                allgather_rows_(self.cams, cam_local, w)
-                if self.selective:
-                    allreduce_max_(vis, w)
-                for (r0, r1), gathered in zip(self.chunks, self.mrgb):
-                    works.append((allreduce_sum_async(self.g12[r0:r1], w),
-                                  allgather_rows_async(gathered, self.mrgb_local[r0:r1], w)))
-            else:
-                self.cams[0].copy_(cam_local)
+            return self._loss3[0], pred_rgb, rgba_grad
+        rgba_leaf = rgba.detach().requires_grad_(True)
+        pred_rgb = rgba_leaf[..., :3].unsqueeze(0)
+        pred_opacity = rgba_leaf[..., 3:].unsqueeze(0)
+        pred_rgb, pred_opacity = m.background(batch.T_to_world, batch.rays_dir, pred_rgb, pred_opacity, True)
+        loss = photometric_loss(pred_rgb, gt, self.lambda_l1, self.lambda_ssim, mask=mask)
+        loss.backward()  # image-sized autograd only
+        return loss, pred_rgb, rgba_leaf.grad
+
+    def _act_written(self):
+        """`act` holds the activated rows of the parameters the optimiser call just wrote: the next step need not activate.  Any
+        in-place torch edit of raw (densification, MCMC noise, ...) bumps _version and forces a fresh activation."""
+        raw = self.model.raw
+        self._act_key = (raw.data_ptr(), raw._version, raw.shape[0])
+
+    def _update_one_pass(self, bwd_args, vis, evs):
+        """One view, nobody else needs the per-Gaussian gradients: K8's epilogue, the SH-gradient rebuild and Adam run as ONE pass over
+        the Gaussians, straight from the renderer's gradient rows (gut_optimize_after_bwd)."""
+        m = self.model
+        self.raster.trace_bwd(*bwd_args, skip_epilogue=True)
+        self._mark(evs)                                  # mark 4: backward queued
+        vmask = vis.reshape(-1) if self.selective else None
+        stats = self.fused_statistics() if self.fused_statistics is not None else None
+        if stats is not None:
+            self.raster.set_position_gradient_statistics(*stats)
+        # camera position None: the library uses the sensor position of its cached forward (the very floats K1 evaluated the
+        # colours from; an 18 us host-to-device copy sat here, between K7 and the pass over the walked waves, until round 4)
+        self.raster.optimize_after_bwd(m.n_active_features, None, *self._state(), *self._adam_settings(), vmask, self.act, lazy=self._lazy())
+        self._reg_set = False
+        self._act_written()
+
+    def _update_dense_exchange(self, batch, bwd_args, vis, evs):
+        """Backward + dense gradient exchange + optimiser of a data-parallel step (dp_exchange == "dense"): [N,12] all-reduce and
+        [N,3] per-view all-gather, pipelined over the row chunks of resize_workspace()."""
+        m = self.model
+        w = max(1, self.world_size)
+        exchange = w > 1 or self.force_exchange
+        # this view's compact radiance gradient: directly view 0 of the gathered layout when there is nothing to gather
+        local_mrgb = self.mrgb_local if exchange else self.mrgb[0][0]
+        self.raster.trace_bwd(*bwd_args, raw_parameter_grads=True, compact_radiance_grads=True, out=(self.g12, local_mrgb))
+        self._mark(evs)                                  # mark 4: backward queued
+        cam_local = self._sensor_position(batch)
+        if self.post_backward_hook is not None:  # per-view statistics, before the exchange (strategy/gs.py:106-115)
+            self.post_backward_hook(self.g12[:, 0:3], cam_local)
+        works = []
+        if exchange:
+            # Chunk-pipelined exchange: the collectives of chunk c+1 run on RCCL's stream while the optimiser kernel
+            # of chunk c runs on the compute stream (the optimiser is HBM-bound, the exchange xGMI-bound).
+            allgather_rows_(self.cams, cam_local, w)
             if self.selective:
-                vmask = vis.reshape(-1)
-            st = torch.cuda.current_stream(m.raw.device).cuda_stream
-            f32p = C.POINTER(C.c_float)
-            for k, ((r0, r1), gathered) in enumerate(zip(self.chunks, self.mrgb)):
-                if works:
-                    works[k][0].wait()
-                    works[k][1].wait()
-                lz = self._lazy()
-                if lz is not None:   # chunks are multiples of 256 rows: whole waves
-                    lz = _capi.GutLazyMoments(self.wave_step.data_ptr() + 4 * (r0 // 64), self._pow1.data_ptr(), self._pow2.data_ptr(), self.LAZY_TABLE)
-                reg_c = self._regularisation(r0)   # (chunks are whole 256-row blocks: their partials start at wave r0 / 64)
-                rc = self._lib.gut_sh_adam_step_regularised(
-                    C.c_void_p(st), r1 - r0, m.n_active_features, w, self.cams.data_ptr(), gathered.data_ptr(),
-                    self.g12.data_ptr() + 48 * r0, 1.0 / w, m.raw.data_ptr() + 48 * r0, self.m12.data_ptr() + 48 * r0,
-                    self.v12.data_ptr() + 48 * r0, m.features.data_ptr() + 192 * r0, self.m48.data_ptr() + 192 * r0,
-                    self.v48.data_ptr() + 192 * r0, self.lr12.ctypes.data_as(f32p), self.lr48.ctypes.data_as(f32p),
-                    self.betas[0], self.betas[1], self.eps, 0 if self.selective else self.step_id + 1,
-                    None if vmask is None else vmask.data_ptr() + 4 * r0, self.act.data_ptr() + 48 * r0, r1 - r0, 0, None,
-                    None if lz is None else C.byref(lz), None if reg_c is None else C.byref(reg_c))
-                if rc:
-                    raise RuntimeError(f"[3dgut] sh_adam_step failed ({rc})")
-            # any in-place torch edit of raw (densification, MCMC noise, ...) bumps _version and forces a fresh activation
-            self._act_key = (m.raw.data_ptr(), m.raw._version, m.raw.shape[0])
+                allreduce_max_(vis, w)
+            for (r0, r1), gathered in zip(self.chunks, self.mrgb):
+                works.append((allreduce_sum_async(self.g12[r0:r1], w),
+                              allgather_rows_async(gathered, self.mrgb_local[r0:r1], w)))
         else:
-            self.raster.trace_bwd(*bwd_args, raw_parameter_grads=True, out=(self.g12, self.g48))
-            self._mark(evs)
-            if self.post_backward_hook is not None:
-                self.post_backward_hook(self.g12[:, 0:3], batch.T_to_world.reshape(4, 4)[:3, 3].to(torch.float32))
-            if self.world_size > 1 or self.force_exchange:
-                allreduce_mean_([self.g48, self.g12], self.world_size)
-                if self.selective:
-                    allreduce_max_(vis, self.world_size)
-            vmask = vis.reshape(-1) if self.selective else None
-            if reg is not None:   # once, after the exchange's mean (every replica holds the same parameters)
-                rc = self._lib.gut_regularisation_gradient(C.c_void_p(torch.cuda.current_stream(m.raw.device).cuda_stream),
-                                                           m.num_gaussians, m.raw.data_ptr(), self.g12.data_ptr(), C.byref(reg))
-                if rc:
-                    raise RuntimeError(f"[3dgut] regularisation_gradient failed ({rc})")
-            self._adam(m.raw, self.g12, self.m12, self.v12, self.lr12, vmask)
-            self._adam(m.features, self.g48, self.m48, self.v48, self.lr48, vmask)
-        return self._finish_step(evs, loss, pred_rgb, vis, hits, reg)
+            self.cams[0].copy_(cam_local)
+        vmask = vis.reshape(-1) if self.selective else None
+        st, adam = self._stream(), self._adam_settings()
+        tensors = (*self._state(), self.g12, vmask, self.act)
+        for k, ((r0, r1), gathered) in enumerate(zip(self.chunks, self.mrgb)):
+            if works:
+                works[k][0].wait()
+                works[k][1].wait()
+            # chunks are whole 256-row blocks, so whole waves: wave_step and the partials of the chunk start at wave r0 / 64
+            # (views of the rows only where they really are chunked)
+            *state_c, g12_c, vmask_c, act_c = tensors if len(self.chunks) == 1 else optim_calls.rows(r0, r1, *tensors)
+            optim_calls.sh_adam_step(self._lib, st, state_c, adam, m.n_active_features, self.cams, gathered, g12_c, 1.0 / w, act_c,
+                                     vmask_c, lazy=self._lazy(r0), reg=self._regularisation(r0))
+        self._act_written()
+
+    def _update_unfused(self, batch, bwd_args, vis, evs, reg):
+        """Backward to dense [N,12] / [N,48] gradients, their exchange, and one gut_adam_step per tensor (fused_sh_adam=False)."""
+        m = self.model
+        self.raster.trace_bwd(*bwd_args, raw_parameter_grads=True, out=(self.g12, self.g48))
+        self._mark(evs)                                  # mark 4: backward queued
+        if self.post_backward_hook is not None:
+            self.post_backward_hook(self.g12[:, 0:3], batch.T_to_world.reshape(4, 4)[:3, 3].to(torch.float32))
+        if self.world_size > 1 or self.force_exchange:
+            allreduce_mean_([self.g48, self.g12], self.world_size)
+            if self.selective:
+                allreduce_max_(vis, self.world_size)
+        vmask = vis.reshape(-1) if self.selective else None
+        st = self._stream()
+        if reg is not None:   # once, after the exchange's mean (every replica holds the same parameters)
+            optim_calls.regularisation_gradient(self._lib, st, m.raw, self.g12, reg)
+        lr12, lr48, betas, eps, step = self._adam_settings()
+        optim_calls.adam_step(self._lib, st, m.raw, self.g12, self.m12, self.v12, lr12, betas, eps, step, vmask)
+        optim_calls.adam_step(self._lib, st, m.features, self.g48, self.m48, self.v48, lr48, betas, eps, step, vmask)
 
     def _finish_step(self, evs, loss, pred_rgb, vis, hits, reg):
         """End of every path of _step: the regularisers' loss values (behind the optimiser kernels that wrote their partials), the
@@ -763,17 +773,19 @@ class NativeTrainStep:
             out["opacity_loss"], out["scale_loss"] = self._regularisation_losses(self._loss3 if in_place else None)
             if not in_place:
                 loss = loss + out["opacity_loss"] + out["scale_loss"]
-        self._mark(evs)
+        self._mark(evs)                                  # mark 5: update queued
         self._end_of_step(evs)
         return loss, out
 
-    def _sparse_exchange_and_update(self, batch, bwd_args, vis, evs, w, exchange, reg=None):
+    def _sparse_exchange_and_update(self, batch, bwd_args, vis, evs, reg=None):
         """Backward + sparse gradient exchange + optimiser of a data-parallel step (dp_exchange == "sparse")."""
         m = self.model
         n = m.num_gaussians
-        f32p = C.POINTER(C.c_float)
+        w = max(1, self.world_size)
+        exchange = w > 1 or self.force_exchange
         main = torch.cuda.current_stream(m.raw.device)
         side_on = self.dp_side_stream and n > 0
+        state, adam = self._state(), self._adam_settings()
         if side_on:
             # one byte per wave: did THIS view's forward walk a Gaussian of it?  MAX over the ranks while the backward runs.
             rc = self._lib.gut_mark_walked_waves(self.raster._handle, C.c_void_p(main.cuda_stream), self.wave_flags.data_ptr())
@@ -789,18 +801,12 @@ class NativeTrainStep:
             with torch.cuda.stream(self._side):
                 if flags_work is not None:
                     flags_work.wait()
-                lz = self._lazy()
-                rc = self._lib.gut_adam_unwalked_waves_regularised(
-                    C.c_void_p(self._side.cuda_stream), n, self.wave_flags.data_ptr(), m.raw.data_ptr(), self.m12.data_ptr(),
-                    self.v12.data_ptr(), m.features.data_ptr(), self.m48.data_ptr(), self.v48.data_ptr(),
-                    self.lr12.ctypes.data_as(f32p), self.lr48.ctypes.data_as(f32p), self.betas[0], self.betas[1], self.eps,
-                    self.step_id + 1, self.act.data_ptr(), None if lz is None else C.byref(lz), None if reg is None else C.byref(reg))
-                if rc:
-                    raise RuntimeError(f"[3dgut] adam_unwalked_waves failed ({rc})")
+                optim_calls.adam_unwalked_waves(self._lib, self._side.cuda_stream, self.wave_flags, state, adam, self.act,
+                                                self._lazy(), reg)
             if flags_work is not None:
                 flags_work.wait()                  # the main stream's optimiser call reads the reduced flags too
         self.raster.compact_gradient_rows(self.act, self.records, self.rec_count)
-        self._mark(evs)
+        self._mark(evs)                                  # mark 4: backward and its compaction queued
         cam_local = self._sensor_position(batch)
         if exchange:
             allgather_rows_(self.cams, cam_local, w)
@@ -813,23 +819,17 @@ class NativeTrainStep:
         # count taken on the device
         ex = self._exchange
         gathered, counts_dev, cap = ex.start(self.records, self.rec_count)
-        st = torch.cuda.current_stream(m.raw.device).cuda_stream
+        st = self._stream()
         slabs = self.mrgb[0]
         for v in range(gathered.shape[0]):
             if cap:
-                rc = self._lib.gut_scatter_gradient_records_dev(C.c_void_p(st), gathered[v].data_ptr(), counts_dev.data_ptr() + 4 * v, cap, n,
-                                                                self.g12.data_ptr(), slabs[v].data_ptr())
-                if rc:
-                    raise RuntimeError(f"[3dgut] scatter_gradient_records failed ({rc})")
+                optim_calls.scatter_gradient_records_dev(self._lib, st, gathered[v], counts_dev, v, cap, self.g12, slabs[v])
         counts = ex.host_counts()         # everything above is queued: the GPU keeps working while the host waits for 4 W bytes
         tail = ex.tail(self.records)      # a rank had more records than the capacity assumed: the rest, same order on every rank
         if tail is not None:
             for v, c in enumerate(tail[1]):
                 if c:
-                    rc = self._lib.gut_scatter_gradient_records(C.c_void_p(st), tail[0][v].data_ptr(), c, n, self.g12.data_ptr(),
-                                                                slabs[v].data_ptr())
-                    if rc:
-                        raise RuntimeError(f"[3dgut] scatter_gradient_records failed ({rc})")
+                    optim_calls.scatter_gradient_records(self._lib, st, tail[0][v], c, self.g12, slabs[v])
         self.exchanged_records = int(sum(counts))
         self.exchanged_bytes_per_rank = int(ex.payload_bytes_per_rank)
         if self.post_backward_hook is not None:  # per-view statistics of THIS rank's view (strategy/gs.py:106-115)
@@ -841,18 +841,12 @@ class NativeTrainStep:
             pg[mine[:, 11].contiguous().view(torch.int32).long()] = mine[:, 0:3]
             self.post_backward_hook(pg, cam_local)
         vmask = vis.reshape(-1) if self.selective else None
-        rc = self._lib.gut_sh_adam_step_regularised(
-            C.c_void_p(st), n, m.n_active_features, w, self.cams.data_ptr(), slabs.data_ptr(), self.g12.data_ptr(), 1.0 / w,
-            m.raw.data_ptr(), self.m12.data_ptr(), self.v12.data_ptr(), m.features.data_ptr(), self.m48.data_ptr(),
-            self.v48.data_ptr(), self.lr12.ctypes.data_as(f32p), self.lr48.ctypes.data_as(f32p), self.betas[0], self.betas[1],
-            self.eps, 0 if self.selective else self.step_id + 1, None if vmask is None else vmask.data_ptr(), self.act.data_ptr(),
-            n, _capi.ADAM_CLEAR_CONSUMED_GRADS, self.wave_flags.data_ptr() if side_on else None,
-            None if self._lazy() is None else C.byref(self._lazy()), None if reg is None else C.byref(reg))
-        if rc:
-            raise RuntimeError(f"[3dgut] sh_adam_step failed ({rc})")
+        optim_calls.sh_adam_step(self._lib, st, state, adam, m.n_active_features, self.cams, slabs, self.g12, 1.0 / w, self.act, vmask,
+                                 flags=_capi.ADAM_CLEAR_CONSUMED_GRADS, wave_flags=self.wave_flags if side_on else None,
+                                 lazy=self._lazy(), reg=reg)
         if side_on:
             main.wait_stream(self._side)           # the next forward reads every row
-        self._act_key = (m.raw.data_ptr(), m.raw._version, m.raw.shape[0])
+        self._act_written()
 
     def _end_of_step(self, evs):
         self._early_queued = False

@@ -795,6 +795,32 @@ def test_checkpoint_resume_beyond_the_decay_tables():
         bad.sync_moments()
 
 
+def test_dense_chunk_exchange_reports_a_decay_table_overrun():
+    """The dense-exchange chunk loop hands every chunk the trainer's overrun word (GutLazyMoments.d_overrun), like every other
+    optimiser path: three chunks (0,1024), (1024,2048), (2048,3000) — the last ends in a partial wave; collectives skipped without a
+    process group.  Two ordinary steps leave nothing to report; a step counter forced 1500 steps ahead of wave_step (the unsafe resume
+    of test_checkpoint_resume_beyond_the_decay_tables) is REPORTED by sync_moments() — the kernel clamps the table index, so this is
+    a reported condition, not a fault."""
+    sc = scenes.scene_c1(3000, 35)
+    W, H = 128, 96
+    b = to_batch(make_view("pinhole", W, H, cams.look_at_c2w((0.3, 0.1, -3.5), (0, 0, 0)), fx=120.0), DEV)
+    b.rgb_gt = torch.rand((1, H, W, 3), generator=torch.Generator().manual_seed(10)).to(DEV)
+    model = native.NativeGaussianModel(sc, device=DEV)
+    st = native.NativeTrainStep(model, gut.Tracer({"render": {}}), scene_extent=1.0, fuse_epilogue=False, dp_exchange="dense",
+                                dp_chunks=3, dp_chunk_min_rows=1, lazy_moments=True)
+    st.force_exchange = True
+    st.resize_workspace()
+    assert st.chunks == [(0, 1024), (1024, 2048), (2048, 3000)] and st.lazy_moments
+    for _ in range(2):
+        st.step(b)
+    st.sync_moments()                      # healthy: nothing ran off the tables
+    assert int(st.wave_step.max()) <= 2
+    st._step_id = 1512                     # wave_step stays behind
+    st.step(b)
+    with pytest.raises(RuntimeError, match="missed 1024 or more steps"):
+        st.sync_moments()
+
+
 def test_spatial_storage_order_is_transparent():
     """NativeGaussianModel(spatial_order=True) only permutes the rows: same image, and after two train steps the parameters
     are those of the scene-order model, row for row through `permutation` (up to the float-atomic noise of the backward);
