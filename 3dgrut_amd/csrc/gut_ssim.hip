@@ -14,6 +14,9 @@
 // The evaluation metrics (gut_image_metrics: MSE, PSNR, SSIM, L1) run the same forward without those maps.
 // Masked views (gut_photometric_loss_masked): a second instantiation of the forward and the backward (kMasked) multiplies both
 // images by a per-pixel mask where they are loaded; the unmasked instantiations do not see the mask at all.
+// Background image (gut_photometric_loss_background): further instantiations (kBgImage) composite every pixel over its own colour,
+// image = rgb + B[y,x,:] * (1 - alpha), for the reference's `random` background (model/background.py:83-89), a constant RGB colour or
+// an environment image; the constant-background instantiations do not read the plane.
 #include "gut_internal.h"
 
 namespace gut {
@@ -62,18 +65,28 @@ __device__ __forceinline__ float mask_px(const float* __restrict__ mask, const I
     return mask[(size_t)y * v.W + x];
 }
 
+// kBgImage: the rgba pixel composited over ITS OWN background colour, bg[y,x,c] ([H,W,3] floats, interleaved like the ground truth):
+// rgb + B * (1 - alpha) as one fma, the same in the forward and the backward.  Outside the image 0, and nothing is read.
+__device__ __forceinline__ float load_px_bg(const float* __restrict__ img, const ImgView& v, const float* __restrict__ bg, int c, int y,
+                                            int x) {
+    if (x < 0 || y < 0 || x >= v.W || y >= v.H) return 0.0f;
+    const long long o = (long long)y * v.sh + (long long)x * v.sw;
+    return fmaf(bg[((size_t)y * v.W + x) * 3 + c], 1.0f - img[o + v.alpha_offset], img[o + (long long)c * v.sc]);
+}
+
 // forward: partial sums of the valid-region SSIM map per workgroup + derivative maps (planar [C,H,W])
 // kMetrics (gut_image_metrics, no backward follows): the three derivative maps are not stored (their pointers may be null) and the
 // workgroup's sum of squared errors goes to partial_sq, next to the L1 partials.
 // kMasked: both patches are staged times the mask, so the SSIM statistics, the L1 partials and the derivative maps are those of the
 // two masked images; `mask` is not read otherwise.
-template <bool kMetrics, bool kMasked = false>
+// kBgImage: img1 is staged through load_px_bg (v.background is not used); `bg` is not read otherwise.  Combines with kMasked.
+template <bool kMetrics, bool kMasked = false, bool kBgImage = false>
 __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const float* __restrict__ img1,
                                                  const float* __restrict__ img2, float* __restrict__ partial,
                                                  float* __restrict__ partial_l1, float* __restrict__ dm_dmu1,
                                                  float* __restrict__ dm_dsigma1_sq, float* __restrict__ dm_dsigma12,
                                                  uint32_t gx, uint32_t gy, float* __restrict__ partial_sq,
-                                                 const float* __restrict__ mask) {
+                                                 const float* __restrict__ mask, const float* __restrict__ bg) {
     // row strides chosen for the two 16-lane rows a 32-lane LDS access group covers: 48 = 16 mod 32 for the patches (row r and
     // r + 1 fall on disjoint halves of the 32 banks while the 11-tap window slides), 16 for the filtered rows (ditto for the
     // column pass).  With the earlier 27 / 17 the window passes lost 46 % of their LDS cycles to 2-way conflicts.
@@ -87,7 +100,12 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const f
     const int tid = threadIdx.x;
     for (int i = tid; i < kPatch * kPatch; i += 256) {
         const int py = i / kPatch, pxx = i - py * kPatch;
-        if constexpr (kMasked) {
+        if constexpr (kBgImage) {
+            float mk = 1.0f;
+            if constexpr (kMasked) mk = mask_px(mask, v, y0 + py - kHalo, x0 + pxx - kHalo);
+            s1[py][pxx] = load_px_bg(img1, v, bg, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
+            s2[py][pxx] = load_px(img2, v2, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
+        } else if constexpr (kMasked) {
             const float mk = mask_px(mask, v, y0 + py - kHalo, x0 + pxx - kHalo);
             s1[py][pxx] = load_px(img1, v, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
             s2[py][pxx] = load_px(img2, v2, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
@@ -237,13 +255,14 @@ __global__ __launch_bounds__(256) void k_metrics_finish(const float* __restrict_
 // k_alpha_grad for a non-black background; zero for black).
 // kMasked (fused photometric loss of a masked view): p and q are the masked pixels the forward saw, and the finished gradient, L1
 // term included, is multiplied by mask[y,x] (d image_masked / d rgb); where the mask is 0 it is written as 0.0f whatever g is.
-template <bool kMasked>
+// kBgImage: p is the pixel over its own background colour, as the forward staged it; the alpha slot is written by k_alpha_grad_image.
+template <bool kMasked, bool kBgImage = false>
 __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const float* __restrict__ img1,
                                                  const float* __restrict__ img2, const float* __restrict__ dm_dmu1,
                                                  const float* __restrict__ dm_dsigma1_sq, const float* __restrict__ dm_dsigma12,
                                                  const float* __restrict__ upstream, float inv_count, float ssim_weight,
                                                  float l1_weight, float* __restrict__ grad, uint32_t gx, uint32_t gy, FinishArgs fin,
-                                                 const float* __restrict__ mask) {
+                                                 const float* __restrict__ mask, const float* __restrict__ bg) {
     __shared__ float s[3][kPatch][kRowStride];
     __shared__ float h[3][kPatch][kSTile];
     if (fin.out3 && blockIdx.x == 0 && blockIdx.z == 0)   // (block-uniform)
@@ -287,7 +306,10 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const f
     const int x = x0 + ox, y = y0 + oy;
     if (x < v.W && y < v.H) {
         const long long o = (long long)c * v.sc + (long long)y * v.sh + (long long)x * v.sw;
-        float p = load_px(img1, v, c, y, x), q = load_px(img2, v2, c, y, x);
+        float p;
+        if constexpr (kBgImage) p = load_px_bg(img1, v, bg, c, y, x);
+        else p = load_px(img1, v, c, y, x);
+        float q = load_px(img2, v2, c, y, x);
         float mk = 1.0f;
         if constexpr (kMasked) {
             mk = mask_px(mask, v, y, x);
@@ -308,6 +330,19 @@ __global__ __launch_bounds__(256) void k_alpha_grad(int pixels, float background
         float4* g = reinterpret_cast<float4*>(rgba_grad) + i;
         float4 t = *g;
         t.w = -background * (t.x + t.y + t.z);
+        *g = t;
+    }
+}
+
+// the same for a background image: d(loss)/d(alpha) = -(B_r g_r + B_g g_g + B_b g_b), B = bg[pixel] ([H,W,3]); the colour gradients of
+// a masked view are already multiplied by the mask
+__global__ __launch_bounds__(256) void k_alpha_grad_image(int pixels, const float* __restrict__ bg, float* __restrict__ rgba_grad) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < pixels) {
+        float4* g = reinterpret_cast<float4*>(rgba_grad) + i;
+        float4 t = *g;
+        const float* b = bg + (size_t)i * 3;
+        t.w = -(b[0] * t.x + b[1] * t.y + b[2] * t.z);
         *g = t;
     }
 }
@@ -342,7 +377,7 @@ int gut_ssim_forward(void* stream, int32_t channels, int32_t height, int32_t wid
     const dim3 grid(gx * gy, 1, channels);
     const gut::ImgView v = make_view(channels, height, width, stride_c, stride_h, stride_w);
     hipLaunchKernelGGL(gut::k_ssim_fwd<false>, grid, dim3(256), 0, s, v, v, d_img1, d_img2, partial, (float*)nullptr, maps,
-                       maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr, (const float*)nullptr);
+                       maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
     const double count = (double)channels * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     hipLaunchKernelGGL(gut::k_ssim_finish, dim3(1), dim3(256), 0, s, partial, (int)(grid.x * grid.z), (float)(1.0 / count),
                        d_mean_ssim);
@@ -361,7 +396,7 @@ int gut_ssim_backward(void* stream, int32_t channels, int32_t height, int32_t wi
     const gut::ImgView v = make_view(channels, height, width, stride_c, stride_h, stride_w);
     const double count = (double)channels * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     hipLaunchKernelGGL(gut::k_ssim_bwd<false>, grid, dim3(256), 0, s, v, v, d_img1, d_img2, maps, maps + plane, maps + 2 * plane, d_upstream,
-                       (float)(1.0 / count), 0.0f, 0.0f, d_grad_img1, gx, gy, gut::FinishArgs(), (const float*)nullptr);
+                       (float)(1.0 / count), 0.0f, 0.0f, d_grad_img1, gx, gy, gut::FinishArgs(), (const float*)nullptr, (const float*)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -370,10 +405,11 @@ size_t gut_photometric_workspace_bytes(int32_t height, int32_t width) {
     return gut_ssim_workspace_bytes(3, height, width) + tiles;
 }
 
-// d_mask == nullptr: the unmasked instantiations, the very kernels this launched before there was a mask
+// d_mask == nullptr: the unmasked instantiations, the very kernels this launched before there was a mask; d_bg == nullptr: the
+// constant-background instantiations, likewise (`background` is not used with a plane)
 static int photometric_loss_launch(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
-                                   const float* d_mask, float background, float lambda_l1, float lambda_ssim, void* d_workspace,
-                                   float* d_loss3, float* d_rgba_grad) {
+                                   const float* d_mask, const float* d_bg, float background, float lambda_l1, float lambda_ssim,
+                                   void* d_workspace, float* d_loss3, float* d_rgba_grad) {
     if (!d_rgba || !d_gt_rgb || !d_workspace || !d_loss3 || !d_rgba_grad) return 1;
     if (height <= 2 * gut::kHalo || width <= 2 * gut::kHalo) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -386,46 +422,50 @@ static int photometric_loss_launch(void* stream, int32_t height, int32_t width, 
     float* partial_l1 = partial + nblocks + 64;
     gut::ImgView v = make_view(3, height, width, 1, 4 * (int64_t)width, 4);   // rgba, interleaved
     v.alpha_offset = 3;
-    v.background = background;
+    v.background = d_bg ? 0.0f : background;
     const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
-    if (d_mask)
-        hipLaunchKernelGGL((gut::k_ssim_fwd<false, true>), grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, maps,
-                           maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr, d_mask);
-    else
-        hipLaunchKernelGGL(gut::k_ssim_fwd<false>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, maps,
-                           maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr, (const float*)nullptr);
+    const float* no_upstream = nullptr;   // the fused loss has no upstream gradient: the weights below
+    auto fwd = d_bg ? (d_mask ? gut::k_ssim_fwd<false, true, true> : gut::k_ssim_fwd<false, false, true>)
+                    : (d_mask ? gut::k_ssim_fwd<false, true> : gut::k_ssim_fwd<false>);
+    hipLaunchKernelGGL(fwd, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, maps, maps + plane, maps + 2 * plane, gx, gy,
+                       (float*)nullptr, d_mask, d_bg);
     const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     const double numel = 3.0 * height * width;
     gut::FinishArgs fin;
     fin.partial = partial; fin.partial_l1 = partial_l1; fin.n = nblocks;
     fin.inv_count_ssim = (float)(1.0 / count); fin.inv_count_l1 = (float)(1.0 / numel);
     fin.lambda_l1 = lambda_l1; fin.lambda_ssim = lambda_ssim; fin.out3 = d_loss3;
-    if (d_mask)
-        hipLaunchKernelGGL(gut::k_ssim_bwd<true>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, maps, maps + plane, maps + 2 * plane,
-                           (const float*)nullptr, (float)(1.0 / count), -lambda_ssim, (float)(lambda_l1 / numel), d_rgba_grad, gx, gy, fin,
-                           d_mask);
-    else
-        hipLaunchKernelGGL(gut::k_ssim_bwd<false>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, maps, maps + plane, maps + 2 * plane,
-                           (const float*)nullptr, (float)(1.0 / count), -lambda_ssim, (float)(lambda_l1 / numel), d_rgba_grad, gx, gy, fin,
-                           (const float*)nullptr);
-    if (background != 0.0f) {
-        const int pixels = height * width;
+    auto bwd = d_bg ? (d_mask ? gut::k_ssim_bwd<true, true> : gut::k_ssim_bwd<false, true>)
+                    : (d_mask ? gut::k_ssim_bwd<true> : gut::k_ssim_bwd<false>);
+    hipLaunchKernelGGL(bwd, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, maps, maps + plane, maps + 2 * plane, no_upstream,
+                       (float)(1.0 / count), -lambda_ssim, (float)(lambda_l1 / numel), d_rgba_grad, gx, gy, fin, d_mask, d_bg);
+    const int pixels = height * width;
+    if (d_bg)
+        hipLaunchKernelGGL(gut::k_alpha_grad_image, dim3((pixels + 255) / 256), dim3(256), 0, s, pixels, d_bg, d_rgba_grad);
+    else if (background != 0.0f)
         hipLaunchKernelGGL(gut::k_alpha_grad, dim3((pixels + 255) / 256), dim3(256), 0, s, pixels, background, d_rgba_grad);
-    }
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
 int gut_photometric_loss(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
                          float lambda_l1, float lambda_ssim, void* d_workspace, float* d_loss3, float* d_rgba_grad) {
-    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, nullptr, background, lambda_l1, lambda_ssim, d_workspace,
-                                   d_loss3, d_rgba_grad);
+    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, nullptr, nullptr, background, lambda_l1, lambda_ssim,
+                                   d_workspace, d_loss3, d_rgba_grad);
 }
 
 int gut_photometric_loss_masked(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
                                 const float* d_mask, float background, float lambda_l1, float lambda_ssim, void* d_workspace,
                                 float* d_loss3, float* d_rgba_grad) {
-    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, d_mask, background, lambda_l1, lambda_ssim, d_workspace,
-                                   d_loss3, d_rgba_grad);
+    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, d_mask, nullptr, background, lambda_l1, lambda_ssim,
+                                   d_workspace, d_loss3, d_rgba_grad);
+}
+
+int gut_photometric_loss_background(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
+                                    const float* d_mask, const float* d_background, float lambda_l1, float lambda_ssim,
+                                    void* d_workspace, float* d_loss3, float* d_rgba_grad) {
+    if (!d_background) return 1;
+    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, d_mask, d_background, 0.0f, lambda_l1, lambda_ssim,
+                                   d_workspace, d_loss3, d_rgba_grad);
 }
 
 // three arrays of per-workgroup partials (SSIM, L1, squared error; 3 channels x tiles entries, 64 floats of slack after each)
@@ -450,7 +490,7 @@ int gut_image_metrics(void* stream, int32_t height, int32_t width, const float* 
     v.background = background;
     const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
     hipLaunchKernelGGL(gut::k_ssim_fwd<true>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, (float*)nullptr,
-                       (float*)nullptr, (float*)nullptr, gx, gy, partial_sq, (const float*)nullptr);
+                       (float*)nullptr, (float*)nullptr, gx, gy, partial_sq, (const float*)nullptr, (const float*)nullptr);
     const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     const double numel = 3.0 * height * width;
     hipLaunchKernelGGL(gut::k_metrics_finish, dim3(1), dim3(256), 0, s, partial, partial_l1, partial_sq, nblocks,

@@ -139,17 +139,33 @@ def _plane_mask(mask, H, W, device):
     return mask.reshape(H, W).to(device=device, dtype=torch.float32).contiguous()
 
 
+def _plane_background(background, H, W, device):
+    """A background tensor given as [H,W,3], [1,H,W,3] or [3] (one RGB colour, expanded here; any dtype or device) as contiguous
+    float32 [H,W,3] on `device`."""
+    shape = tuple(background.shape)
+    if shape == (3,):
+        background = background.reshape(1, 1, 3).expand(H, W, 3)
+    elif shape not in ((H, W, 3), (1, H, W, 3)):
+        raise ValueError(f"fused_photometric_loss: a background tensor must be [{H},{W},3], [1,{H},{W},3] or [3] for these images, "
+                         f"got {shape}")
+    return background.reshape(H, W, 3).to(device=device, dtype=torch.float32).contiguous()
+
+
 def fused_photometric_loss(rgba, gt_rgb, background, lambda_l1=0.8, lambda_ssim=0.2, mask=None, workspace=None):
-    """The train step's loss and its gradient without autograd (gut_photometric_loss / gut_photometric_loss_masked,
-    csrc/gut_ssim.hip): image = rgb + background * (1 - alpha), loss = lambda_l1 * L1 + lambda_ssim * (1 - SSIM) against gt_rgb.
+    """The train step's loss and its gradient without autograd (gut_photometric_loss / gut_photometric_loss_masked /
+    gut_photometric_loss_background, csrc/gut_ssim.hip): image = rgb + background * (1 - alpha), loss = lambda_l1 * L1 +
+    lambda_ssim * (1 - SSIM) against gt_rgb.
     rgba [H,W,4] (or [1,H,W,4]) and gt_rgb [H,W,3] (or [1,H,W,3]): contiguous float32 on one GPU; background: "black", "white"
-    or 0.0 / 1.0.  mask: None, or [H,W] / [H,W,1] / [1,H,W,1] of any dtype — image and gt_rgb are both multiplied by it
+    or 0.0 / 1.0, or a tensor — [H,W,3] / [1,H,W,3], every pixel over its own colour (the reference's `random` background,
+    model/background.py:83-89, or an environment image), or [3], one RGB colour; any dtype or device.
+    mask: None, or [H,W] / [H,W,1] / [1,H,W,1] of any dtype — image and gt_rgb are both multiplied by it
     (trainer.py:397-404), the means keep their full-image counts, and a pixel whose mask is 0 gets a gradient of exactly zero.
     workspace: a float32 device tensor of at least gut_photometric_workspace_bytes(H, W) bytes to reuse, or None.
     Returns (loss3, rgba_grad): a float32 device tensor (loss, L1, SSIM) and d(loss)/d(rgba) [H,W,4]."""
-    bg = {"black": 0.0, "white": 1.0}.get(background, background)
+    plane = isinstance(background, torch.Tensor)
+    bg = background if plane else {"black": 0.0, "white": 1.0}.get(background, background)
     if isinstance(bg, str):
-        raise ValueError(f"fused_photometric_loss: background must be 'black', 'white' or a number, got {background!r}")
+        raise ValueError(f"fused_photometric_loss: background must be 'black', 'white', a number or a tensor, got {background!r}")
     rgba = rgba.reshape(rgba.shape[-3:]) if rgba.dim() == 4 and rgba.shape[0] == 1 else rgba
     gt_rgb = gt_rgb.reshape(gt_rgb.shape[-3:]) if gt_rgb.dim() == 4 and gt_rgb.shape[0] == 1 else gt_rgb
     if rgba.dim() != 3 or rgba.shape[2] != 4 or tuple(gt_rgb.shape) != (rgba.shape[0], rgba.shape[1], 3):
@@ -162,24 +178,30 @@ def fused_photometric_loss(rgba, gt_rgb, background, lambda_l1=0.8, lambda_ssim=
     H, W = int(rgba.shape[0]), int(rgba.shape[1])
     if mask is not None:
         mask = _plane_mask(mask, H, W, rgba.device)
+    bg = _plane_background(bg, H, W, rgba.device) if plane else float(bg)
     need = lib.gut_photometric_workspace_bytes(H, W)
     if workspace is None:
         workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=rgba.device)
     elif workspace.dtype != torch.float32 or workspace.device != rgba.device or workspace.numel() * 4 < need or not workspace.is_contiguous():
         raise RuntimeError(f"[fused_photometric_loss] workspace must be a contiguous float32 tensor of at least {need} bytes on the images' device")
     with torch.cuda.device(rgba.device):
-        return _photometric_loss_call(lib, H, W, rgba, gt_rgb, float(bg), lambda_l1, lambda_ssim, mask, workspace)
+        return _photometric_loss_call(lib, H, W, rgba, gt_rgb, bg, lambda_l1, lambda_ssim, mask, workspace)
 
 
 def _photometric_loss_call(lib, H, W, rgba, gt_rgb, bg, lambda_l1, lambda_ssim, mask, workspace):
     """The two C calls behind fused_photometric_loss, nothing checked: contiguous float32 device tensors (gt_rgb with or without a
-    leading 1), mask a float32 [H,W] plane or None, a workspace of gut_photometric_workspace_bytes(H, W), the images' device current.
+    leading 1), bg a float or a float32 [H,W,3] device plane, mask a float32 [H,W] plane or None, a workspace of
+    gut_photometric_workspace_bytes(H, W), the images' device current.
     NativeTrainStep calls this directly every step, on buffers it sized itself."""
     # three fresh floats every call (the caching allocator, no kernel): callers return views of them
     loss3 = torch.empty((3,), dtype=torch.float32, device=rgba.device)
     rgba_grad = torch.empty_like(rgba)
     stream = torch.cuda.current_stream(rgba.device).cuda_stream
-    if mask is None:
+    if isinstance(bg, torch.Tensor):
+        rc = lib.gut_photometric_loss_background(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(),
+                                                 None if mask is None else mask.data_ptr(), bg.data_ptr(), lambda_l1, lambda_ssim,
+                                                 workspace.data_ptr(), loss3.data_ptr(), rgba_grad.data_ptr())
+    elif mask is None:
         rc = lib.gut_photometric_loss(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(), bg, lambda_l1, lambda_ssim,
                                       workspace.data_ptr(), loss3.data_ptr(), rgba_grad.data_ptr())
     else:

@@ -22,7 +22,7 @@ import torch
 from . import _capi, optim_calls
 from .dp import (RecordExchange, allgather_rows_, allgather_rows_async, allreduce_max_, allreduce_max_async, allreduce_mean_, allreduce_sum_async,
                  assert_replicas_identical)
-from .losses import _photometric_loss_call, _plane_mask, photometric_loss
+from .losses import _photometric_loss_call, _plane_background, _plane_mask, photometric_loss
 from .tracer import SplatRaster, Tracer
 
 # column layout of the raw [N,12] tensor and the reference's Adam learning rates (configs/base_gs.yaml:81-109)
@@ -115,11 +115,20 @@ class NativeGaussianModel:
     def get_features(self):
         return self.features
 
+    last_background = None   # the `random` background's latest draw, [H,W,3] (the reference keeps its last colour too, background.py:88)
+
+    def draw_background(self, rays_d):
+        """The `random` training background of one step: a uniform colour per pixel (background.py:83-89, torch.rand_like(rays_d)
+        from the device's default generator), kept as last_background [H,W,3].  One draw per step, whichever loss branch runs."""
+        bg = torch.rand_like(rays_d, dtype=torch.float32)
+        self.last_background = bg[0] if bg.dim() == 4 and bg.shape[0] == 1 else bg
+        return self.last_background
+
     def background(self, T_to_world, rays_d, rgb, opacity, train=False):
         if self.background_color == "white":
             rgb = rgb + (1.0 - opacity)
         elif self.background_color == "random" and train:
-            rgb = rgb + torch.rand_like(rays_d) * (1.0 - opacity)
+            rgb = rgb + self.draw_background(rays_d).reshape(rays_d.shape) * (1.0 - opacity)
         return rgb, opacity
 
 
@@ -656,9 +665,9 @@ class NativeTrainStep:
         # Batch.mask [1,H,W,1] or None: prediction and ground truth are multiplied by it inside the loss (trainer.py:397-404); the
         # pred_rgb returned stays unmasked, as the reference masks only the locals of get_losses
         mask = getattr(batch, "mask", None)
-        if self.fused_loss and m.background_color in ("black", "white") and gt.dtype == torch.float32 and gt.is_contiguous() \
+        if self.fused_loss and m.background_color in ("black", "white", "random") and gt.dtype == torch.float32 and gt.is_contiguous() \
                 and gt.numel() == rgba.shape[0] * rgba.shape[1] * 3:
-            # loss value and d(loss)/d(rgba) in two HIP launches (csrc/gut_ssim.hip: gut_photometric_loss[_masked])
+            # loss value and d(loss)/d(rgba) in two HIP launches (csrc/gut_ssim.hip: gut_photometric_loss[_masked | _background])
             H, W = rgba.shape[0], rgba.shape[1]
             need = self._lib.gut_photometric_workspace_bytes(H, W)
             if self._loss_ws is None or self._loss_ws.numel() * 4 < need:
@@ -667,12 +676,18 @@ class NativeTrainStep:
             # `.clone()` of a buffer kept across steps was a 7 us copy kernel between the loss and the backward
             # (_plane_mask: a view for the reader's float32 [1,H,W,1] device mask, no kernel; a mask of another dtype or device is
             # converted here, one copy per step — keep such masks converted in the batch)
-            self._loss3, rgba_grad = _photometric_loss_call(self._lib, H, W, rgba, gt, 1.0 if m.background_color == "white" else 0.0,
-                                                            self.lambda_l1, self.lambda_ssim,
+            # (`random`: this step's draw, every pixel over its own colour — the same draw the torch branch below makes)
+            if m.background_color == "random":
+                bg = _plane_background(m.draw_background(batch.rays_dir), H, W, rgba.device)   # (a view: float32 [H,W,3] already)
+            else:
+                bg = 1.0 if m.background_color == "white" else 0.0
+            self._loss3, rgba_grad = _photometric_loss_call(self._lib, H, W, rgba, gt, bg, self.lambda_l1, self.lambda_ssim,
                                                             None if mask is None else _plane_mask(mask, H, W, rgba.device), self._loss_ws)
             pred_rgb = rgba[..., :3].unsqueeze(0)
             if m.background_color == "white":
                 pred_rgb = pred_rgb + (1.0 - rgba[..., 3:].unsqueeze(0))
+            elif m.background_color == "random":
+                pred_rgb = pred_rgb + bg.unsqueeze(0) * (1.0 - rgba[..., 3:].unsqueeze(0))
             return self._loss3[0], pred_rgb, rgba_grad
         rgba_leaf = rgba.detach().requires_grad_(True)
         pred_rgb = rgba_leaf[..., :3].unsqueeze(0)

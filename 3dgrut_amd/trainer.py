@@ -11,6 +11,8 @@
 base_mcmc.yaml + strategy/mcmc.yaml for `strategy.method == "MCMCStrategy"` (`default_config`).  The loop adds no host
 synchronisation between events: the loss is read back only when a validation runs.  Views with a mask (`<image stem>_mask.png` next
 to the image, io_colmap.ColmapScene.load_mask) train through the masked form of the fused loss; evaluation scores the full image.
+`model.background.color: random` composites every training pixel over its own uniform colour, drawn once per step and handed to the
+fused loss as a plane (model/background.py:83-89); evaluation scores such a model over black.
 
 Checkpoints hold the reference's get_model_parameters() keys (model/model.py:107-134) with the optimiser state in
 torch.optim.Adam.state_dict() layout (six groups, named and ordered as configs/base_gs.yaml), `global_step`, `epoch`, the GS
@@ -19,7 +21,7 @@ Everything in it is a tensor, number, string, list, tuple or dict: `torch.load(p
 written by the reference itself (an OmegaConf config inside) are not read.
 
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
-                                 [--test-split-interval 8] [--resume CKPT]
+                                 [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
 """
 import argparse
 import copy
@@ -105,6 +107,17 @@ def resolve_config(conf):
     return out
 
 
+BACKGROUND_COLORS = ("black", "white", "random")   # configs/base_gs.yaml:72-74
+
+
+def check_background_color(conf):
+    """model.background.color of a resolved conf must be one the reference's BackgroundColor.setup takes (background.py:66-70)."""
+    color = conf["model"]["background"]["color"]
+    if color not in BACKGROUND_COLORS:
+        raise ValueError(f"Background color must be one of 'white', 'black', 'random' (model.background.color is {color!r})")
+    return color
+
+
 def _stage(t, s):
     """(start, end, frequency) of a strategy block (utils/misc.check_step_condition's arguments)."""
     return (int(t[s]["start_iteration"]), int(t[s]["end_iteration"]), int(t[s]["frequency"]))
@@ -168,6 +181,7 @@ def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=No
     progressive = int(prog["init_n_features"]) < int(prog["max_n_features"])
     color = conf["model"]["background"]["color"]
     extra = {
+        # (zeros for `random` as well: BackgroundColor.setup stores black for it, the colour used when not training)
         "background": {"color": torch.full((3,), 1.0 if color == "white" else 0.0, dtype=torch.float32)},
         "progressive_training": progressive, "scene_extent": float(scene_extent), "config": _plain(conf),
         "optimizer": {"state": state, "param_groups": groups}, "global_step": int(global_step), "epoch": int(epoch),
@@ -221,6 +235,7 @@ class Trainer:
                  evaluator=None, tracer=None):
         self.conf = resolve_config(conf)
         c = self.conf
+        check_background_color(c)
         self.train_batches, self.val_batches, self.test_batches = list(train_batches), list(val_batches), list(test_batches)
         if not self.train_batches:
             raise ValueError("Trainer: no training views")
@@ -407,7 +422,7 @@ class Trainer:
         return dict(stats=stats, test=self.test_metrics)
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m 3dgrut_amd.trainer", description="Train a COLMAP scene and score its test split.")
     ap.add_argument("--path", required=True, help="COLMAP scene directory (sparse/0 + images[_F])")
     ap.add_argument("--out-dir", default=None)
@@ -417,7 +432,13 @@ def main(argv=None):
     ap.add_argument("--test-split-interval", type=int, default=8)
     ap.add_argument("--resume", default="")
     ap.add_argument("--seed", type=int, default=0)
-    a = ap.parse_args(argv)
+    ap.add_argument("--background", choices=BACKGROUND_COLORS, default=None,
+                    help="model.background.color (default: the config's, black); random = a uniform colour per training pixel")
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     from .io_colmap import ColmapScene
     conf = default_config("MCMCStrategy" if a.strategy == "mcmc" else "GSStrategy")
     if a.out_dir is not None:
@@ -425,6 +446,8 @@ def main(argv=None):
     if a.n_iterations is not None:
         conf["n_iterations"] = a.n_iterations
     conf["resume"], conf["seed"] = a.resume, a.seed
+    if a.background is not None:
+        conf["model"]["background"]["color"] = a.background
     train = ColmapScene(a.path, "train", a.downsample, a.test_split_interval)
     test = ColmapScene(a.path, "test", a.downsample, a.test_split_interval)
     # configs/initialization/colmap.yaml: observation-point scales, the model's default density / scale factor

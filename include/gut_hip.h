@@ -40,7 +40,8 @@ extern "C" {
  * unsorted backward clamps alpha with the reference's literal 0.99 whatever particle_kernel_max_alpha is; 6: GutRegularisation,
  * gut_set_regularisation, gut_sh_adam_step_regularised, gut_adam_unwalked_waves_regularised, gut_sync_moments_ex,
  * gut_regularisation_gradient, gut_regularisation_loss.  Added under 6 without a bump, nothing that was accepted changed meaning:
- * gut_photometric_loss_masked, a new entry point next to gut_photometric_loss, which is untouched). */
+ * gut_photometric_loss_masked and gut_photometric_loss_background, new entry points next to gut_photometric_loss, which is
+ * untouched). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -340,6 +341,20 @@ int gut_photometric_loss(void* stream, int32_t height, int32_t width, const floa
 int gut_photometric_loss_masked(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
                                 const float* d_mask, float background, float lambda_l1, float lambda_ssim, void* d_workspace,
                                 float* d_loss3, float* d_rgba_grad);
+
+/* The same loss over a background IMAGE: every pixel is composited over its own colour, as the reference's `random` background
+ * does in training (model/background.py:83-89: torch.rand_like(rays_d), per pixel), and as a constant RGB colour or an environment
+ * image need.  d_background: float32 [H,W,3], contiguous, interleaved like d_gt_rgb:
+ *     image = (rgb + B[y,x,:] * (1 - alpha)) * mask,  gt' = gt * mask          (d_mask == NULL: no mask, the factor is absent)
+ * d(loss)/d(rgb) = mask * d(loss)/d(image) and d(loss)/d(alpha) = -sum_c B_c * d(loss)/d(rgb_c); all four channels of every pixel
+ * of d_rgba_grad are written, and a pixel whose mask is 0 gets 0 in all four.  A pixel outside the image reads neither plane.
+ * Further compile-time variants of the same two kernels, which the constant-background entry points above do not launch: those
+ * return the bits they returned before.  An all-zero plane gives the values of background 0; an all-ones plane those of
+ * background 1 up to the rounding of the alpha sum.  Returns 1 for a null pointer other than d_mask (d_background included) or
+ * height / width <= 10.  Workspace (gut_photometric_workspace_bytes), launch count and stream behaviour as gut_photometric_loss. */
+int gut_photometric_loss_background(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
+                                    const float* d_mask, const float* d_background, float lambda_l1, float lambda_ssim,
+                                    void* d_workspace, float* d_loss3, float* d_rgba_grad);
 
 /* Evaluation metrics of one view (the reference's test-split scoring, threedgrut/render.py:137-285), forward only, no gradient:
  * d_out4 receives { MSE, PSNR, SSIM, L1 } of image = rgb + background * (1 - alpha) against d_gt_rgb, values unclamped.
