@@ -88,7 +88,7 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_set_position_gradient_statistics", "gut_mcmc_perturb", "gut_trace_raw_model_fields", "gut_set_regularisation",
            "gut_sh_adam_step_regularised", "gut_adam_unwalked_waves_regularised", "gut_sync_moments_ex", "gut_regularisation_gradient",
            "gut_regularisation_loss", "gut_image_metrics_workspace_bytes", "gut_image_metrics", "gut_photometric_loss_masked",
-           "gut_photometric_loss_background")
+           "gut_photometric_loss_background", "gut_set_pose_gradient", "gut_pose_adam_step")
 
 _lib = None
 
@@ -126,6 +126,8 @@ def load():
                                                f_p, f_p, f_p, f_p, f_p, f_p]
     lib.gut_position_gradient_statistics.argtypes = [vp, u32, f_p, u32, f_p, u32, f_p, f_p, vp]
     lib.gut_set_position_gradient_statistics.argtypes = [vp, f_p, vp]
+    lib.gut_set_pose_gradient.argtypes = [vp, f_p]
+    lib.gut_pose_adam_step.argtypes = [vp, f_p, f_p, f_p, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, f_p]
     lib.gut_mcmc_perturb.argtypes = [vp, u32, f_p, f_p, C.c_float, C.c_uint64, C.c_uint64, f_p]
     lib.gut_collect_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.gut_get_stats.argtypes = [vp, C.POINTER(GutStats)]

@@ -24,6 +24,7 @@ UNITS = [
     ("gut_sort.hip", ["-Wno-unused-parameter"]),
     ("gut_ssim.hip", ["-ffp-contract=fast"]),
     ("gut_train.hip", ["-ffp-contract=fast"]),
+    ("gut_pose.hip", ["-ffp-contract=off"]),
     ("gut_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 

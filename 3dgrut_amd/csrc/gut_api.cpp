@@ -137,6 +137,8 @@ struct gut_context {
     float* stat_accum = nullptr;    // gut_set_position_gradient_statistics: consumed by the next gut_optimize_after_bwd
     int32_t* stat_denom = nullptr;
     GutRegularisation reg{};        // gut_set_regularisation: consumed by the next optimiser step (both coefficients 0: none)
+    float* pose_out = nullptr;      // gut_set_pose_gradient: every backward reduces its gradient rows into these 8 floats (null: off)
+    DevBuf pose_partials;           // per-workgroup partials of that reduction
     DevBuf cam_pos;   // [3] floats: the sensor position of the cached forward (written by K1)
     DevBuf wave_sums, block_prefix, scan_total;   // two-level scan of the tile counts (K1 wave sums -> k_scan_wave_sums -> K3)
     bool timing_main_stream = true, timing_side_stream = true;   // GUT_OPT_KERNEL_TIMING_SET
@@ -430,7 +432,7 @@ void gut_destroy(gut_handle h) {
                       &h->sort_temp, &h->ranges, &h->trav_fwd, &h->trav_bwd, &h->tile_order, &h->counters, &h->ids_ordered,
                       &h->dbg_keys_sorted, &h->dbg_ids_sorted, &h->zero_word, &h->tile_ordered, &h->wave_walked, &h->packed12, &h->walk_sums,
                       &h->wave_sums, &h->block_prefix, &h->scan_total, &h->sph_widened, &h->sph_grad_wide, &h->cam_pos,
-                      &h->tile_entries, &h->tile_start, &h->tile_cursor};
+                      &h->tile_entries, &h->tile_start, &h->tile_cursor, &h->pose_partials};
     for (DevBuf* b : bufs) b->release();
     if (h->host_count) (void)hipHostFree(h->host_count);
     if (h->count_event) (void)hipEventDestroy(h->count_event);
@@ -957,13 +959,23 @@ static int trace_bwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
             return fail("gut_trace_bwd: particle_radiance_sph_degree=%d supports the packed radiance gradient only", h->cfg.particle_radiance_sph_degree);
         narrow_radiance_grad = d_particle_radiance_grad;
     }
+    // the pose gradient is the rigid-motion reduction of the gradient rows: it means something for ONE pose per view only
+    if (h->pose_out)
+        for (int k = 0; k < 7; ++k)
+            if (camera->pose_start[k] != camera->pose_end[k])
+                return fail("gut_trace_bwd: a pose gradient is set (gut_set_pose_gradient) and the view's start and end poses differ: "
+                            "the reduction is defined for pose_start == pose_end only");
     DeviceGuard dev_guard;
     HIP_TRY(dev_guard.set(h->device));
     gut::ViewParams v;
     if (build_view(camera, width, height, h->cfg.n_rolling_shutter_iterations, &v)) return 1;
     if (memcmp(&v, &h->view, sizeof(v)) != 0) return fail("gut_trace_bwd: camera differs from the cached forward");
     const uint32_t n = h->n;
-    if (n == 0) return 0;
+    if (n == 0) {
+        if (h->pose_out) HIP_TRY(hipMemsetAsync(h->pose_out, 0, 8 * sizeof(float), s));   // no rows: F = M = 0, none summed
+        return 0;
+    }
+    if (h->pose_out) HIP_TRY(h->pose_partials.ensure(gut::pose_gradient_scratch_bytes()));
     {
         const void* before = h->grad16.p;
         HIP_TRY(h->grad16.ensure(sizeof(float) * 16 * (size_t)n));
@@ -1005,6 +1017,11 @@ static int trace_bwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
                                h->trav_bwd.as<uint32_t>(), h->tile_order.as<uint32_t>(), h->trav_fwd.as<uint32_t>(), h->cfg.particle_kernel_degree);
     }
     mark(10);
+    // right behind the backward compositor and before any epilogue: the epilogues zero the gradient rows as they read them
+    // (behind the mark that ends render_bwd's timer: the two launches count towards project_bwd, not towards K7)
+    if (h->pose_out)
+        gut::launch_pose_gradient(s, n, h->tiles_count.as<uint32_t>(), h->grad16.as<float>(), d_particle_density, h->cam_pos.as<float>(),
+                                  h->pose_partials.as<float>(), h->pose_out);
     if (flags & GUT_BWD_SKIP_EPILOGUE) {
         // the caller folds the per-Gaussian epilogue into its optimiser step (gut_optimize_after_bwd)
     } else {
@@ -1106,6 +1123,23 @@ int gut_set_position_gradient_statistics(gut_handle h, float* d_norm_accum, int3
     std::lock_guard<std::mutex> lock(h->mu);
     h->stat_accum = d_norm_accum;
     h->stat_denom = d_norm_denom;
+    return 0;
+}
+
+int gut_set_pose_gradient(gut_handle h, float* d_out8) {
+    if (!h) return fail("gut_set_pose_gradient: null handle");
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->pose_out = d_out8;
+    return 0;
+}
+
+int gut_pose_adam_step(void* stream_, const float* d_grad8, float* d_m6, float* d_v6, int32_t* d_count, float lr_translation,
+                       float lr_rotation, float beta1, float beta2, float eps, float* d_delta6) {
+    if (!d_grad8 || !d_m6 || !d_v6 || !d_count || !d_delta6) return fail("gut_pose_adam_step: null pointer argument");
+    if (!(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f)) return fail("gut_pose_adam_step: betas must be in [0, 1)");
+    gut::launch_pose_adam(static_cast<hipStream_t>(stream_), d_grad8, d_m6, d_v6, d_count, lr_translation, lr_rotation, beta1, beta2, eps,
+                          d_delta6);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

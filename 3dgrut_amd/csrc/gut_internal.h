@@ -250,6 +250,13 @@ void launch_mark_walked_waves(hipStream_t s, uint32_t n, uint32_t tiles, const u
                               const uint32_t* ids, uint8_t* wave_walked);
 void launch_stats_reduce(hipStream_t s, uint32_t n, const uint32_t* tiles_count, uint32_t t, const uint32_t* trav_fwd,
                          const uint32_t* trav_bwd, Counters* out);
+// gut_pose.hip: out8 := {F, M, rows with a tile, 0}, the pose-gradient reduction of the gradient rows K7 left (read only; rows with
+// tiles_count != 0), around the sensor position cam_pos [3]; partials: pose_gradient_scratch_bytes() of scratch.  Two launches.
+size_t pose_gradient_scratch_bytes();
+void launch_pose_gradient(hipStream_t s, uint32_t n, const uint32_t* tiles_count, const float* grad16, const float* density12,
+                          const float* cam_pos, float* partials, float* out8);
+void launch_pose_adam(hipStream_t s, const float* grad8, float* m6, float* v6, int32_t* count, float lr_translation, float lr_rotation,
+                      float beta1, float beta2, float eps, float* delta6);
 
 // scan / sort (rocPRIM device-wide primitives; temp storage owned by the caller)
 size_t scan_temp_bytes(uint32_t n);

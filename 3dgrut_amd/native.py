@@ -141,7 +141,10 @@ class NativeTrainStep:
                  betas=(0.9, 0.999), eps=1e-15, fused_sh_adam=True, rank=0, fused_loss=True, lambda_l1=0.8, lambda_ssim=0.2,
                  dp_chunks=4, dp_chunk_min_rows=1 << 20, fuse_epilogue=True, schedule=None,
                  overlap_optimizer=None, dp_exchange="sparse", dp_side_stream=True, lazy_moments=True, lambda_opacity=0.0,
-                 lambda_scale=0.0):
+                 lambda_scale=0.0, pose_gradient=False):
+        if pose_gradient and world_size > 1:
+            raise ValueError("pose_gradient: the pose gradient belongs to ONE view per step; data-parallel pose refinement is out of scope "
+                             "(world_size must be 1)")
         self.model = model
         self.tracer = tracer
         self.raster: SplatRaster = tracer.tracer_wrapper
@@ -238,9 +241,29 @@ class NativeTrainStep:
         # called on the paths whose optimiser kernel does not see the view's own gradient (data-parallel exchange, unfused).
         self.fused_statistics = None
         self.row_listeners = []         # callables(perm): told when reorder() re-sorts the rows (strategy statistics follow)
+        # pose_gradient=True: every step leaves the camera-pose gradient of its view in `self.pose_gradient`, a device [8] tensor
+        # {F[3], M[3], rows summed, 0} (dL/d centre = -F, dL/d world-axis rotation about the centre = -M), valid after step(): the
+        # backward reduces its per-Gaussian gradient rows before any epilogue consumes them (SplatRaster.set_pose_gradient), on the
+        # one-pass fused path and the unfused one alike.  False: the tensor is None and the handle is left alone.
+        self._pose_buffer = torch.zeros(8, dtype=torch.float32, device=dev) if pose_gradient else None
+        self.pose_gradient = self._pose_buffer
         self.resize_workspace()
         self.phase_timing = False   # record HIP events around the phases of step() (bench / profiling)
         self._phase_events = []
+
+    def enable_pose_gradient(self, on):
+        """Switch the pose-gradient output of a stepper built with pose_gradient=True off and on again between steps (the trainer
+        does outside the refinement window): off, `pose_gradient` is None, the handle's output is cleared and the backward launches
+        nothing for it."""
+        if self._pose_buffer is None:
+            if on:
+                raise ValueError("enable_pose_gradient: the stepper was built without pose_gradient=True")
+            return
+        if bool(on) == (self.pose_gradient is not None):
+            return
+        self.pose_gradient = self._pose_buffer if on else None
+        if not on and getattr(self.raster, "_pose_out", None) is self._pose_buffer:
+            self.raster.set_pose_gradient(None)
 
     @property
     def probe_pending(self):
@@ -619,6 +642,10 @@ class NativeTrainStep:
         loss, pred_rgb, rgba_grad = self._loss(batch, rgba)
         self._mark(evs)                                  # mark 3: loss queued
         _, sensor, poses, _, _ = self._ctx
+        if self.pose_gradient is not None and getattr(self.raster, "_pose_out", None) is not self.pose_gradient:
+            # before the backward; the handle keeps it until someone else sets another (a second stepper on the same tracer).  A
+            # backward the library refuses for it (start pose != end pose) raises like any other: step()'s recovery applies as it is.
+            self.raster.set_pose_gradient(self.pose_gradient)
         bwd_args = (self.step_id, m.n_active_features, self.act, m.features, batch.rays_ori.contiguous(),
                     batch.rays_dir.contiguous(), None, sensor, poses.timestamps_us[0], poses.timestamps_us[1],
                     poses.T_world_sensors[0], poses.T_world_sensors[1], rgba, rgba_grad, dist_, None)

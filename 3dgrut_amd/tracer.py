@@ -432,6 +432,21 @@ class SplatRaster:
         _capi.check(self._lib.gut_set_position_gradient_statistics(self._handle, norm_accum.data_ptr(), norm_denom.data_ptr()),
                     "set_position_gradient_statistics")
 
+    def set_pose_gradient(self, out8):
+        """While set, every trace_bwd* on this handle also leaves the view's camera-pose gradient in `out8`, a contiguous float32
+        GPU tensor of 8 elements the caller keeps alive: {F[3], M[3], rows summed, 0} with dL/d(camera centre) = -F and dL/d(world-axis
+        rotation about the centre) = -M (gut_set_pose_gradient; pose.pose_gradient_from_rows is the definition).  None switches it
+        off.  Valid for views whose start and end poses are equal; the backward of any other view raises while it is set."""
+        if out8 is None:
+            self._pose_out = None
+            _capi.check(self._lib.gut_set_pose_gradient(self._handle, None), "set_pose_gradient")
+            return
+        if not (isinstance(out8, torch.Tensor) and out8.is_cuda and out8.dtype == torch.float32 and out8.is_contiguous()
+                and out8.numel() == 8 and out8.device.index == self.device_index):
+            raise RuntimeError("[3dgut] pose gradient output: a contiguous float32 tensor of 8 elements on the handle's GPU")
+        self._pose_out = out8   # (kept alive: the library holds its address)
+        _capi.check(self._lib.gut_set_pose_gradient(self._handle, out8.data_ptr()), "set_pose_gradient")
+
     def set_regularisation(self, reg):
         """The NEXT optimiser step on the handle (optimize_rows_without_gradient + optimize_after_bwd, or
         finish_optimizer_step_without_gradient) adds the MCMC regularisers' gradient to every row it updates and writes the loss

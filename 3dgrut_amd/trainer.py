@@ -20,8 +20,14 @@ strategy's densification buffers as 1-tuples (strategy/gs.py:42-48), and one key
 Everything in it is a tensor, number, string, list, tuple or dict: `torch.load(path, weights_only=True)` reads it.  Checkpoints
 written by the reference itself (an OmegaConf config inside) are not read.
 
+`pose_refinement.enabled` (default off; `--refine-poses`) refines the training views' camera poses while training
+(pose_refine.PoseRefiner): every step's backward leaves the view's pose gradient on the device, a per-view Adam turns it into an
+increment, and the view's next visit renders from the refined pose.  Held-out views (validation, test) are scored at their GIVEN
+poses.  The refiner's poses, moments and visit counts travel in the checkpoint's `native` block as tensors.
+
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
+                                 [--refine-poses [--pose-lr-translation X] [--pose-lr-rotation R]]
 """
 import argparse
 import copy
@@ -33,7 +39,7 @@ import time
 import numpy as np
 import torch
 
-from . import losses
+from . import losses, pose_refine
 from .evaluate import _check_batch, evaluate
 
 # configs/base_gs.yaml + configs/strategy/gs.yaml: the keys this trainer reads
@@ -52,6 +58,9 @@ GS_CONFIG = {
     "loss": {"use_l1": True, "lambda_l1": 0.8, "use_l2": False, "lambda_l2": 1.0, "use_ssim": True, "lambda_ssim": 0.2,
              "use_opacity": False, "lambda_opacity": 0.0, "use_scale": False, "lambda_scale": 0.0},
     "render": {"enable_kernel_timings": False},
+    # not a reference key: camera-pose refinement of the training views (pose_refine.py).  lr_translation is multiplied by the scene
+    # extent, lr_rotation is in radians; end_iteration -1 = to the end of the run.  The two rates are untuned on real captures.
+    "pose_refinement": dict(pose_refine.DEFAULTS),
     "strategy": {"method": "GSStrategy",
                  "densify": {"frequency": 300, "start_iteration": 500, "end_iteration": 15000, "clone_grad_threshold": 0.0002,
                              "split_grad_threshold": 0.0002, "relative_size_threshold": 0.01, "split": {"n_gaussians": 2}},
@@ -101,6 +110,7 @@ def resolve_config(conf):
     out = _merge(default_config(method), conf)
     if method == "GSStrategy" and out["strategy"]["reset_density"].get("end_iteration") is None:
         out["strategy"]["reset_density"]["end_iteration"] = out["strategy"]["densify"]["end_iteration"]
+    pose_refine.check_config(out["pose_refinement"])
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
         out["optimizer"]["params"]["features_specular"] = {"lr": float(out["optimizer"]["params"]["features_albedo"]["lr"]) / 20}
@@ -161,8 +171,8 @@ def _adam_group_template(betas, eps):
     return g
 
 
-def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=None):
-    """The checkpoint dictionary of a NativeTrainStep's state (see the module docstring)."""
+def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=None, refiner=None):
+    """The checkpoint dictionary of a NativeTrainStep's state (see the module docstring); refiner: the run's PoseRefiner or None."""
     from .io_ply import checkpoint_dict
     st = stepper.state_dict()   # moments brought up to date (sync_moments) and cloned
     m = stepper.model
@@ -192,6 +202,8 @@ def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=No
                    "permutation": None if getattr(m, "permutation", None) is None else m.permutation.detach().clone(),
                    "spatial_order": bool(getattr(m, "spatial_order", False))},
     }
+    if refiner is not None:
+        extra["native"]["pose_refinement"] = refiner.state_dict()   # tensors only: poses, moments, visit counts
     if progressive:
         extra["feature_dim_increase_interval"] = int(prog["increase_frequency"])
         extra["feature_dim_increase_step"] = int(prog["increase_step"])
@@ -261,6 +273,7 @@ class Trainer:
         self.stepper, self.tracer = stepper, tracer if tracer is not None else getattr(stepper, "tracer", None)
         self.model = stepper.model
         self.strategy = self._build_strategy(ckpt) if strategy is None else strategy
+        self.refiner = self._build_refiner(ckpt)
         if ckpt is not None:
             self.global_step = int(ckpt["global_step"])
 
@@ -296,7 +309,8 @@ class Trainer:
             sched.position_lr = float(nat["position_lr"])      # the schedule's state: current position rate and SH degree
             sched.n_active_features = int(ckpt["n_active_features"])
         stepper = NativeTrainStep(model, tracer, scene_extent=self.scene_extent, selective=c["optimizer"]["type"] == "selective_adam",
-                                  eps=float(c["optimizer"].get("eps", 1e-15)), schedule=sched, **losses.loss_weights(c["loss"]))
+                                  eps=float(c["optimizer"].get("eps", 1e-15)), schedule=sched,
+                                  pose_gradient=bool(c["pose_refinement"]["enabled"]), **losses.loss_weights(c["loss"]))
         stepper.lr12[0:3] = sched.position_lr
         stepper.lr12[3] = lr["density"]
         stepper.lr12[4:8] = lr["rotation"]
@@ -306,6 +320,36 @@ class Trainer:
         if state is not None:
             stepper.load_state_dict(state)   # moments, step counter (the lazy waves re-based on it), learning rates
         return stepper, tracer
+
+    def _build_refiner(self, ckpt):
+        """The PoseRefiner of a run with pose_refinement.enabled (else None), its state restored from a resumed checkpoint."""
+        pr = self.conf["pose_refinement"]
+        if not pr["enabled"]:
+            if ckpt is not None and ckpt.get("native", {}).get("pose_refinement") is not None:
+                # continuing at the GIVEN poses would silently drop the refined ones the Gaussians were trained against
+                raise ValueError("pose_refinement: the checkpoint holds refined poses and pose_refinement.enabled is off; resume with "
+                                 "--refine-poses (pose_refinement.enabled: true), with end_iteration 0 to keep the poses as they are")
+            return None
+        st = self.stepper
+        if int(getattr(st, "world_size", 1)) > 1:
+            raise ValueError("pose_refinement: data-parallel pose refinement is out of scope (the stepper's world_size must be 1)")
+        if getattr(st, "pose_gradient", None) is None:
+            raise ValueError(f"pose_refinement: {type(st).__name__} leaves no pose gradient (NativeTrainStep(..., pose_gradient=True) does)")
+        refiner = pose_refine.PoseRefiner([b.T_to_world for b in self.train_batches], st.pose_gradient.device,
+                                          lr_translation=float(pr["lr_translation"]) * self.scene_extent, lr_rotation=float(pr["lr_rotation"]),
+                                          betas=(float(pr["beta1"]), float(pr["beta2"])), eps=float(pr["eps"]),
+                                          start_iteration=int(pr["start_iteration"]), end_iteration=int(pr["end_iteration"]))
+        saved = None if ckpt is None else ckpt["native"].get("pose_refinement")
+        if saved is not None:
+            refiner.load_state_dict(saved)
+        return refiner
+
+    def refined_poses(self):
+        """[V,4,4] float64: the training views' current camera-to-world matrices, in train_batches order (the given ones when
+        pose refinement is off).  Held-out views keep their given poses and are scored there."""
+        if self.refiner is not None:
+            return self.refiner.refined_poses()
+        return torch.stack([b.T_to_world.detach().cpu().to(torch.float64).reshape(4, 4) for b in self.train_batches])
 
     def _build_strategy(self, ckpt):
         from .strategy import GSStrategy, MCMCStrategy
@@ -374,7 +418,7 @@ class Trainer:
 
     def checkpoint(self):
         return make_checkpoint(self.stepper, self.conf, self.global_step, self.epoch, self.scene_extent,
-                               self.strategy if self.method == "GSStrategy" else None)
+                               self.strategy if self.method == "GSStrategy" else None, self.refiner)
 
     def save_checkpoint(self, last=False):
         out = self._out_dir()
@@ -397,10 +441,19 @@ class Trainer:
         t0 = time.perf_counter()
         while self.global_step < n_iter:
             g = self.global_step
-            batch = self.train_batches[self.batch_index(g)]
+            view = self.batch_index(g)
+            batch = self.train_batches[view]
             if (g > 0 or c["validate_first"]) and g % val_freq == 0:
                 self.validate()
+            refiner = self.refiner
+            if refiner is not None:
+                batch = refiner.begin(view, batch)          # the view's refined pose (its pending increment applied first)
+                switch = getattr(self.stepper, "enable_pose_gradient", None)
+                if switch is not None:                      # outside [start_iteration, end_iteration) the backward reduces nothing
+                    switch(refiner.active(g))
             self._last_loss, _ = self.stepper.step(batch)   # scheduler + SH ramp run at the end of step()
+            if refiner is not None and refiner.active(g):
+                refiner.end(view, self.stepper.pose_gradient)   # queued on the device: no host synchronisation (V >= 2)
             self._post_optimizer_step(g)
             self.global_step = g + 1
             if self.global_step in ckpt_steps:
@@ -410,6 +463,9 @@ class Trainer:
         self.stats = dict(n_steps=self.global_step, n_epochs=-(-self.global_step // len(self.train_batches)), steps_run=self.global_step - start,
                           training_time=elapsed, iteration_speed=self.global_step / elapsed if elapsed > 0 else float("inf"),
                           n_gaussians=int(self.model.num_gaussians))
+        if self.refiner is not None:
+            ch = self.refiner.pose_change()
+            self.stats.update(pose_mean_translation=ch["mean_translation"], pose_mean_rotation_deg=ch["mean_rotation_deg"])
         return self.stats
 
     def run(self):
@@ -434,6 +490,10 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--background", choices=BACKGROUND_COLORS, default=None,
                     help="model.background.color (default: the config's, black); random = a uniform colour per training pixel")
+    ap.add_argument("--refine-poses", action="store_true",
+                    help="refine the training views' camera poses while training (pose_refinement.enabled); test views keep theirs")
+    ap.add_argument("--pose-lr-translation", type=float, default=None, help="pose_refinement.lr_translation (times the scene extent)")
+    ap.add_argument("--pose-lr-rotation", type=float, default=None, help="pose_refinement.lr_rotation (radians)")
     return ap
 
 
@@ -448,6 +508,11 @@ def main(argv=None):
     conf["resume"], conf["seed"] = a.resume, a.seed
     if a.background is not None:
         conf["model"]["background"]["color"] = a.background
+    conf["pose_refinement"]["enabled"] = bool(a.refine_poses)
+    if a.pose_lr_translation is not None:
+        conf["pose_refinement"]["lr_translation"] = a.pose_lr_translation
+    if a.pose_lr_rotation is not None:
+        conf["pose_refinement"]["lr_rotation"] = a.pose_lr_rotation
     train = ColmapScene(a.path, "train", a.downsample, a.test_split_interval)
     test = ColmapScene(a.path, "test", a.downsample, a.test_split_interval)
     # configs/initialization/colmap.yaml: observation-point scales, the model's default density / scale factor

@@ -41,7 +41,7 @@ extern "C" {
  * gut_set_regularisation, gut_sh_adam_step_regularised, gut_adam_unwalked_waves_regularised, gut_sync_moments_ex,
  * gut_regularisation_gradient, gut_regularisation_loss.  Added under 6 without a bump, nothing that was accepted changed meaning:
  * gut_photometric_loss_masked and gut_photometric_loss_background, new entry points next to gut_photometric_loss, which is
- * untouched). */
+ * untouched; gut_set_pose_gradient and gut_pose_adam_step, new entry points: while it is not set, every gut_trace_bwd* queues what it queued before). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -299,8 +299,9 @@ int gut_set_option(gut_handle h, int32_t option, int32_t value);
 /* per-kernel hipEvent timings of the last trace / trace_bwd (ms), for bench.py's roofline block.
  * Order: project, scan, expand, sort, ranges, render, render_bwd, project_bwd, optimizer (gut_optimize_after_bwd; -1 when
  * that call was not used), optimizer_early (gut_optimize_rows_without_gradient on its side stream, start of its first to end of
- * its second launch, idle gap included; -1 when not used), optimizer_early_2 (its second launch alone).  Requires
- * enable_kernel_timings; synchronises. */
+ * its second launch, idle gap included; -1 when not used), optimizer_early_2 (its second launch alone).  While a pose gradient
+ * is set (gut_set_pose_gradient) project_bwd also holds its two launches (with GUT_BWD_SKIP_EPILOGUE: nothing else); render_bwd stays
+ * the backward compositor alone.  Requires enable_kernel_timings; synchronises. */
 #define GUT_NUM_KERNEL_TIMERS 11
 int gut_kernel_times(gut_handle h, float* ms8);
 /* mean per-kernel time over the (at most 64 most recent) trace/trace_bwd calls since the previous call of this
@@ -581,6 +582,31 @@ int gut_position_gradient_statistics(void* stream, uint32_t num_particles, const
                                      const float* d_positions, uint32_t position_stride, const float* d_sensor_position,
                                      float* d_norm_accum, int32_t* d_norm_denom);
 int gut_set_position_gradient_statistics(gut_handle h, float* d_norm_accum, int32_t* d_norm_denom);
+
+/* ---- Camera-pose gradient of a view (new functionality, the reference keeps its poses fixed) ----
+ * The backward differentiates the per-ray 3-D evaluation only (the projection decides tile membership and is not differentiated, the SH
+ * view direction carries no gradient), and that evaluation depends on the relative placement of ray and Gaussian alone.  Moving a
+ * global-shutter camera rigidly therefore equals moving every Gaussian by the inverse motion with its colour held fixed, and the
+ * gradient w.r.t. the camera is a reduction of the per-Gaussian gradient rows the backward compositor has written anyway.  With
+ * g_mu / g_q a row's gradient w.r.t. its activated position / quaternion (wxyz), q that quaternion and c the sensor position:
+ *     F = sum_i g_mu_i,     M = sum_i (mu_i - c) x g_mu_i + tau_i,     tau_i,k = 1/2 g_q_i . ((0, e_k) (x) q_i),  k = x, y, z
+ * and for the world-axis twist  c' = c + rho,  R_c2w' = exp([phi]x) R_c2w  (rotation about the camera centre):
+ *     dL/d rho = -F,   dL/d phi = -M.
+ * gut_set_pose_gradient(h, d_out8): while d_out8 (device float[8], caller-owned, must stay valid) is set, EVERY gut_trace_bwd* on the
+ * handle queues the reduction on its stream right behind the backward compositor and before any epilogue (the epilogues, the fused
+ * optimiser and gut_compact_gradient_rows included, zero the rows as they read them) and leaves
+ *     d_out8 = { F[3], M[3], number of rows summed (the Gaussians with a tile), 0 }.
+ * The rows are only read.  c is the sensor position the forward's projection left on the device.  Two launches, fp32 accumulators,
+ * partial sums combined in a fixed order, no atomics: the numbers are a pure function of the rows.  A view whose start and end poses
+ * differ (a rolling shutter in motion) has no single rigid motion: gut_trace_bwd* then fails before it queues anything, and the handle
+ * stays as it was.  With num_particles == 0 the eight floats are set to zero.  NULL (the default) switches it off: nothing is
+ * launched and nothing else changes. */
+int gut_set_pose_gradient(gut_handle h, float* d_out8);
+/* Adam on the six pose coordinates of one view, from the eight floats above: gradient (-F, -M); d_m6 / d_v6 / d_count (one int32) are
+ * that view's own moments and visit count, which is advanced by one and used for the bias correction; lr_translation applies to rho,
+ * lr_rotation to phi.  d_delta6 receives the increment (d rho, d phi): c += d rho, R_c2w <- exp([d phi]x) R_c2w.  One launch. */
+int gut_pose_adam_step(void* stream, const float* d_grad8, float* d_m6, float* d_v6, int32_t* d_count, float lr_translation,
+                       float lr_rotation, float beta1, float beta2, float eps, float* d_delta6);
 
 /* ---- "next" row N3: MCMC relocation kernel (threedgrut/strategy/src/gaussian_mcmc.cu:33-73).
  * opacities [n], scales [n,3], ratios [n] (int32, 1..n_max), binoms [n_max,n_max] -> new_opacities [n], new_scales [n,3] */
