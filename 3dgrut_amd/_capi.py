@@ -88,7 +88,8 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_set_position_gradient_statistics", "gut_mcmc_perturb", "gut_trace_raw_model_fields", "gut_set_regularisation",
            "gut_sh_adam_step_regularised", "gut_adam_unwalked_waves_regularised", "gut_sync_moments_ex", "gut_regularisation_gradient",
            "gut_regularisation_loss", "gut_image_metrics_workspace_bytes", "gut_image_metrics", "gut_photometric_loss_masked",
-           "gut_photometric_loss_background", "gut_set_pose_gradient", "gut_pose_adam_step")
+           "gut_photometric_loss_background", "gut_set_pose_gradient", "gut_pose_adam_step",
+           "gut_photometric_exposure_workspace_bytes", "gut_photometric_loss_exposure", "gut_exposure_adam_step")
 
 _lib = None
 
@@ -145,6 +146,10 @@ def load():
     lib.gut_photometric_loss.argtypes = [vp, i32, i32, vp, vp, C.c_float, C.c_float, C.c_float, vp, vp, vp]
     lib.gut_photometric_loss_masked.argtypes = [vp, i32, i32, vp, vp, vp, C.c_float, C.c_float, C.c_float, vp, vp, vp]
     lib.gut_photometric_loss_background.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]
+    lib.gut_photometric_exposure_workspace_bytes.argtypes = [i32, i32]
+    lib.gut_photometric_exposure_workspace_bytes.restype = C.c_size_t
+    lib.gut_photometric_loss_exposure.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, vp, C.c_float, C.c_float, vp, vp, vp, vp]
+    lib.gut_exposure_adam_step.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float]
     lib.gut_image_metrics_workspace_bytes.argtypes = [i32, i32]
     lib.gut_image_metrics_workspace_bytes.restype = C.c_size_t
     lib.gut_image_metrics.argtypes = [vp, i32, i32, vp, vp, C.c_float, vp, vp]

@@ -17,6 +17,9 @@
 // Background image (gut_photometric_loss_background): further instantiations (kBgImage) composite every pixel over its own colour,
 // image = rgb + B[y,x,:] * (1 - alpha), for the reference's `random` background (model/background.py:83-89), a constant RGB colour or
 // an environment image; the constant-background instantiations do not read the plane.
+// Per-view exposure (gut_photometric_loss_exposure): further instantiations (kExposure) compare the AFFINE image
+// E [comp; 1], E = [A | b] a row-major 3x4 array in device memory, comp the composited pixel as above; the channels mix, so the rgb
+// gradient is finished by the per-pixel pass k_exposure_grad, which also reduces the 12 sums of dL/dE.  No other instantiation reads E.
 #include "gut_internal.h"
 
 namespace gut {
@@ -74,19 +77,48 @@ __device__ __forceinline__ float load_px_bg(const float* __restrict__ img, const
     return fmaf(bg[((size_t)y * v.W + x) * 3 + c], 1.0f - img[o + v.alpha_offset], img[o + (long long)c * v.sc]);
 }
 
+// kExposure: the three composited channels of a pixel, comp_k = rgb_k + B_k (1 - alpha), B the pixel's own background colour
+// (kBgImage) or the constant v.background — one definition for the forward, the backward and the per-pixel pass.
+template <bool kBgImage>
+__device__ __forceinline__ void composite3(const float* __restrict__ px /* the pixel's rgba */, long long sc, long long alpha_offset,
+                                           float background, const float* __restrict__ b3 /* the pixel's B, kBgImage only */,
+                                           float* __restrict__ comp) {
+    const float oma = 1.0f - px[alpha_offset];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float p = px[(long long)k * sc];
+        if constexpr (kBgImage) comp[k] = fmaf(b3[k], oma, p);
+        else comp[k] = background != 0.0f ? p + background * oma : p;
+    }
+}
+
+// kExposure: channel c of the affine image, A[c][0] comp_0 + A[c][1] comp_1 + A[c][2] comp_2 + b_c with e4 = row c of E (four
+// floats the workgroup holds in registers).  Outside the image 0, and nothing is read.
+template <bool kBgImage>
+__device__ __forceinline__ float load_px_exposure(const float* __restrict__ img, const ImgView& v, const float* __restrict__ bg,
+                                                  const float (&e4)[4], int y, int x) {
+    if (x < 0 || y < 0 || x >= v.W || y >= v.H) return 0.0f;
+    float comp[3];
+    composite3<kBgImage>(img + (long long)y * v.sh + (long long)x * v.sw, v.sc, v.alpha_offset, v.background,
+                         kBgImage ? bg + ((size_t)y * v.W + x) * 3 : nullptr, comp);
+    return fmaf(e4[0], comp[0], fmaf(e4[1], comp[1], fmaf(e4[2], comp[2], e4[3])));
+}
+
 // forward: partial sums of the valid-region SSIM map per workgroup + derivative maps (planar [C,H,W])
 // kMetrics (gut_image_metrics, no backward follows): the three derivative maps are not stored (their pointers may be null) and the
 // workgroup's sum of squared errors goes to partial_sq, next to the L1 partials.
 // kMasked: both patches are staged times the mask, so the SSIM statistics, the L1 partials and the derivative maps are those of the
 // two masked images; `mask` is not read otherwise.
 // kBgImage: img1 is staged through load_px_bg (v.background is not used); `bg` is not read otherwise.  Combines with kMasked.
-template <bool kMetrics, bool kMasked = false, bool kBgImage = false>
+// kExposure: img1 is staged through load_px_exposure, channel c with row c of `exposure`; combines with kMasked and kBgImage.
+template <bool kMetrics, bool kMasked = false, bool kBgImage = false, bool kExposure = false>
 __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const float* __restrict__ img1,
                                                  const float* __restrict__ img2, float* __restrict__ partial,
                                                  float* __restrict__ partial_l1, float* __restrict__ dm_dmu1,
                                                  float* __restrict__ dm_dsigma1_sq, float* __restrict__ dm_dsigma12,
                                                  uint32_t gx, uint32_t gy, float* __restrict__ partial_sq,
-                                                 const float* __restrict__ mask, const float* __restrict__ bg) {
+                                                 const float* __restrict__ mask, const float* __restrict__ bg,
+                                                 const float* __restrict__ exposure) {
     // row strides chosen for the two 16-lane rows a 32-lane LDS access group covers: 48 = 16 mod 32 for the patches (row r and
     // r + 1 fall on disjoint halves of the 32 banks while the 11-tap window slides), 16 for the filtered rows (ditto for the
     // column pass).  With the earlier 27 / 17 the window passes lost 46 % of their LDS cycles to 2-way conflicts.
@@ -98,9 +130,19 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const f
     xcd_tile(blockIdx.x, gx, gy, &tx, &ty);
     const int x0 = tx * kSTile, y0 = ty * kSTile;
     const int tid = threadIdx.x;
+    float e4[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (kExposure) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) e4[k] = exposure[4 * c + k];
+    }
     for (int i = tid; i < kPatch * kPatch; i += 256) {
         const int py = i / kPatch, pxx = i - py * kPatch;
-        if constexpr (kBgImage) {
+        if constexpr (kExposure) {
+            float mk = 1.0f;
+            if constexpr (kMasked) mk = mask_px(mask, v, y0 + py - kHalo, x0 + pxx - kHalo);
+            s1[py][pxx] = load_px_exposure<kBgImage>(img1, v, bg, e4, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
+            s2[py][pxx] = load_px(img2, v2, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
+        } else if constexpr (kBgImage) {
             float mk = 1.0f;
             if constexpr (kMasked) mk = mask_px(mask, v, y0 + py - kHalo, x0 + pxx - kHalo);
             s1[py][pxx] = load_px_bg(img1, v, bg, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
@@ -256,13 +298,16 @@ __global__ __launch_bounds__(256) void k_metrics_finish(const float* __restrict_
 // kMasked (fused photometric loss of a masked view): p and q are the masked pixels the forward saw, and the finished gradient, L1
 // term included, is multiplied by mask[y,x] (d image_masked / d rgb); where the mask is 0 it is written as 0.0f whatever g is.
 // kBgImage: p is the pixel over its own background colour, as the forward staged it; the alpha slot is written by k_alpha_grad_image.
-template <bool kMasked, bool kBgImage = false>
+// kExposure: p is channel c of the affine image, as the forward staged it, and slot c receives g_c = d loss / d image_c (mask factor
+// included), NOT yet the rgb gradient: k_exposure_grad turns the three into A^T g and writes the alpha slot of every pixel.
+template <bool kMasked, bool kBgImage = false, bool kExposure = false>
 __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const float* __restrict__ img1,
                                                  const float* __restrict__ img2, const float* __restrict__ dm_dmu1,
                                                  const float* __restrict__ dm_dsigma1_sq, const float* __restrict__ dm_dsigma12,
                                                  const float* __restrict__ upstream, float inv_count, float ssim_weight,
                                                  float l1_weight, float* __restrict__ grad, uint32_t gx, uint32_t gy, FinishArgs fin,
-                                                 const float* __restrict__ mask, const float* __restrict__ bg) {
+                                                 const float* __restrict__ mask, const float* __restrict__ bg,
+                                                 const float* __restrict__ exposure) {
     __shared__ float s[3][kPatch][kRowStride];
     __shared__ float h[3][kPatch][kSTile];
     if (fin.out3 && blockIdx.x == 0 && blockIdx.z == 0)   // (block-uniform)
@@ -307,7 +352,10 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const f
     if (x < v.W && y < v.H) {
         const long long o = (long long)c * v.sc + (long long)y * v.sh + (long long)x * v.sw;
         float p;
-        if constexpr (kBgImage) p = load_px_bg(img1, v, bg, c, y, x);
+        if constexpr (kExposure) {
+            const float e4[4] = {exposure[4 * c], exposure[4 * c + 1], exposure[4 * c + 2], exposure[4 * c + 3]};
+            p = load_px_exposure<kBgImage>(img1, v, bg, e4, y, x);
+        } else if constexpr (kBgImage) p = load_px_bg(img1, v, bg, c, y, x);
         else p = load_px(img1, v, c, y, x);
         float q = load_px(img2, v2, c, y, x);
         float mk = 1.0f;
@@ -319,7 +367,8 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const f
         if (l1_weight != 0.0f) g += l1_weight * (float)((p > q) - (p < q));
         if constexpr (kMasked) g = mk == 0.0f ? 0.0f : g * mk;
         grad[o] = g;
-        if (v.alpha_offset >= 0 && c == 0) grad[o + v.alpha_offset] = 0.0f;
+        if constexpr (!kExposure)
+            if (v.alpha_offset >= 0 && c == 0) grad[o + v.alpha_offset] = 0.0f;
     }
 }
 
@@ -345,6 +394,107 @@ __global__ __launch_bounds__(256) void k_alpha_grad_image(int pixels, const floa
         t.w = -(b[0] * t.x + b[1] * t.y + b[2] * t.z);
         *g = t;
     }
+}
+
+// Exposure, the per-pixel pass behind k_ssim_bwd<.., kExposure>: the pixel's float4 holds g = (g_r, g_g, g_b, unwritten).  Writes
+//     d loss / d rgb_k = sum_c A[c][k] g_c,      d loss / d alpha = -sum_k B_k d loss / d rgb_k     (exactly 0.0f for constant black)
+// into all four slots and, with `partials`, reduces the 12 sums of dL/dE = [sum g_c comp_k | sum g_c]: kExpPixels pixels per lane, a
+// wave butterfly, the four waves added in order, one row of 12 partials per workgroup.  A pixel whose mask is 0 gets four times
+// 0.0f and is left out of the sums (its rgba and background are not read).
+constexpr int kExpPixels = 4;   // pixels per lane: 1024 per workgroup, 12 partials per 1024 pixels
+
+template <bool kBgImage>
+__global__ __launch_bounds__(256) void k_exposure_grad(uint32_t pixels, const float* __restrict__ rgba, const float* __restrict__ bg,
+                                                      float background, const float* __restrict__ mask,
+                                                      const float* __restrict__ exposure, float* __restrict__ rgba_grad,
+                                                      float* __restrict__ partials) {
+    __shared__ float red[4][12];
+    float E[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) E[k] = exposure[k];
+    float acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kExpPixels; ++j) {
+        const uint32_t i = (blockIdx.x * kExpPixels + j) * 256u + threadIdx.x;
+        if (i >= pixels) break;
+        float4* gp = reinterpret_cast<float4*>(rgba_grad) + i;
+        if (mask && mask[i] == 0.0f) {   // (g is 0.0f there already; the alpha slot is not: every element is written)
+            *gp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            continue;
+        }
+        const float4 t = *gp;
+        const float g[3] = {t.x, t.y, t.z};
+        float d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) d[k] = E[k] * g[0] + E[4 + k] * g[1] + E[8 + k] * g[2];
+        const float* b3 = kBgImage ? bg + (size_t)i * 3 : nullptr;
+        float da = 0.0f;
+        if constexpr (kBgImage) da = -(b3[0] * d[0] + b3[1] * d[1] + b3[2] * d[2]);
+        else if (background != 0.0f) da = -background * (d[0] + d[1] + d[2]);
+        *gp = make_float4(d[0], d[1], d[2], da);
+        if (partials) {   // (block-uniform)
+            float comp[3];
+            composite3<kBgImage>(rgba + (size_t)i * 4, 1, 3, background, b3, comp);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) acc[4 * c + k] += g[c] * comp[k];
+                acc[4 * c + 3] += g[c];
+            }
+        }
+    }
+    if (!partials) return;
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+        for (int mk = 32; mk >= 1; mk >>= 1) acc[k] += __shfl_xor(acc[k], mk);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) red[threadIdx.x >> 6][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 12)
+        partials[(size_t)blockIdx.x * 12 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// deterministic final sum of the per-workgroup rows of 12 partials, in double: lane = component + 16 * slice; slice s adds the rows
+// s, s + 16, ... in order, then component k adds its 16 slices in order
+__global__ __launch_bounds__(256) void k_exposure_finish(uint32_t rows, const float* __restrict__ partials, float* __restrict__ out12) {
+    __shared__ double red[16][12];
+    const uint32_t k = threadIdx.x & 15u, slice = threadIdx.x >> 4;
+    if (k < 12) {
+        double acc = 0.0;
+        for (uint32_t j = slice; j < rows; j += 16u) acc += (double)partials[(size_t)j * 12 + k];
+        red[slice][k] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        double acc = red[0][threadIdx.x];
+        for (int s = 1; s < 16; ++s) acc += red[s][threadIdx.x];
+        out12[threadIdx.x] = (float)acc;
+    }
+}
+
+// Adam on the 12 exposure values of ONE view (3dgrut_amd/exposure.py): the view's own moments and visit count, which is advanced
+// first and gives the bias correction; betas held in float32, 1 - beta^t formed in double from them and rounded once (the host form
+// of ExposureCompensation.end does the same).  One launch of one wave; no contraction, so that the host form can follow it.
+__global__ __launch_bounds__(64) void k_exposure_adam(const float* __restrict__ grad12, float* __restrict__ e12, float* __restrict__ m12,
+                                                      float* __restrict__ v12, int32_t* __restrict__ count, float lr, float beta1,
+                                                      float beta2, float eps) {
+#pragma clang fp contract(off)
+    const uint32_t k = threadIdx.x;
+    const int32_t t = count[0] + 1;   // every lane reads the count before lane 0 stores it (one wave: the barrier below orders them)
+    __syncthreads();
+    if (k == 0) count[0] = t;
+    if (k >= 12) return;
+    const float g = grad12[k];
+    const float m = beta1 * m12[k] + (1.0f - beta1) * g;
+    const float v = beta2 * v12[k] + ((1.0f - beta2) * g) * g;
+    m12[k] = m;
+    v12[k] = v;
+    const float c1 = (float)(1.0 - pow((double)beta1, (double)t)), c2 = (float)(1.0 - pow((double)beta2, (double)t));
+    e12[k] = e12[k] - (lr * (m / c1)) / (sqrtf(v / c2) + eps);
 }
 
 }  // namespace gut
@@ -377,7 +527,8 @@ int gut_ssim_forward(void* stream, int32_t channels, int32_t height, int32_t wid
     const dim3 grid(gx * gy, 1, channels);
     const gut::ImgView v = make_view(channels, height, width, stride_c, stride_h, stride_w);
     hipLaunchKernelGGL(gut::k_ssim_fwd<false>, grid, dim3(256), 0, s, v, v, d_img1, d_img2, partial, (float*)nullptr, maps,
-                       maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+                       maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                       (const float*)nullptr);
     const double count = (double)channels * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     hipLaunchKernelGGL(gut::k_ssim_finish, dim3(1), dim3(256), 0, s, partial, (int)(grid.x * grid.z), (float)(1.0 / count),
                        d_mean_ssim);
@@ -396,7 +547,8 @@ int gut_ssim_backward(void* stream, int32_t channels, int32_t height, int32_t wi
     const gut::ImgView v = make_view(channels, height, width, stride_c, stride_h, stride_w);
     const double count = (double)channels * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     hipLaunchKernelGGL(gut::k_ssim_bwd<false>, grid, dim3(256), 0, s, v, v, d_img1, d_img2, maps, maps + plane, maps + 2 * plane, d_upstream,
-                       (float)(1.0 / count), 0.0f, 0.0f, d_grad_img1, gx, gy, gut::FinishArgs(), (const float*)nullptr, (const float*)nullptr);
+                       (float)(1.0 / count), 0.0f, 0.0f, d_grad_img1, gx, gy, gut::FinishArgs(), (const float*)nullptr, (const float*)nullptr,
+                       (const float*)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -405,11 +557,19 @@ size_t gut_photometric_workspace_bytes(int32_t height, int32_t width) {
     return gut_ssim_workspace_bytes(3, height, width) + tiles;
 }
 
+size_t gut_photometric_exposure_workspace_bytes(int32_t height, int32_t width) {
+    const size_t rows = ((size_t)height * width + 256 * gut::kExpPixels - 1) / (256 * gut::kExpPixels);
+    return gut_photometric_workspace_bytes(height, width) + rows * 12 * sizeof(float) + 256;
+}
+
 // d_mask == nullptr: the unmasked instantiations, the very kernels this launched before there was a mask; d_bg == nullptr: the
-// constant-background instantiations, likewise (`background` is not used with a plane)
+// constant-background instantiations, likewise (`background` is not used with a plane); d_exposure == nullptr: the instantiations
+// without an exposure, likewise.  With d_exposure the workspace is one of gut_photometric_exposure_workspace_bytes, the per-pixel pass
+// is k_exposure_grad for every background, and d_exposure_grad (may be nullptr) receives the 12 sums.
 static int photometric_loss_launch(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
                                    const float* d_mask, const float* d_bg, float background, float lambda_l1, float lambda_ssim,
-                                   void* d_workspace, float* d_loss3, float* d_rgba_grad) {
+                                   void* d_workspace, float* d_loss3, float* d_rgba_grad, const float* d_exposure = nullptr,
+                                   float* d_exposure_grad = nullptr) {
     if (!d_rgba || !d_gt_rgb || !d_workspace || !d_loss3 || !d_rgba_grad) return 1;
     if (height <= 2 * gut::kHalo || width <= 2 * gut::kHalo) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -427,8 +587,11 @@ static int photometric_loss_launch(void* stream, int32_t height, int32_t width, 
     const float* no_upstream = nullptr;   // the fused loss has no upstream gradient: the weights below
     auto fwd = d_bg ? (d_mask ? gut::k_ssim_fwd<false, true, true> : gut::k_ssim_fwd<false, false, true>)
                     : (d_mask ? gut::k_ssim_fwd<false, true> : gut::k_ssim_fwd<false>);
+    if (d_exposure)
+        fwd = d_bg ? (d_mask ? gut::k_ssim_fwd<false, true, true, true> : gut::k_ssim_fwd<false, false, true, true>)
+                   : (d_mask ? gut::k_ssim_fwd<false, true, false, true> : gut::k_ssim_fwd<false, false, false, true>);
     hipLaunchKernelGGL(fwd, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, maps, maps + plane, maps + 2 * plane, gx, gy,
-                       (float*)nullptr, d_mask, d_bg);
+                       (float*)nullptr, d_mask, d_bg, d_exposure);
     const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     const double numel = 3.0 * height * width;
     gut::FinishArgs fin;
@@ -437,10 +600,22 @@ static int photometric_loss_launch(void* stream, int32_t height, int32_t width, 
     fin.lambda_l1 = lambda_l1; fin.lambda_ssim = lambda_ssim; fin.out3 = d_loss3;
     auto bwd = d_bg ? (d_mask ? gut::k_ssim_bwd<true, true> : gut::k_ssim_bwd<false, true>)
                     : (d_mask ? gut::k_ssim_bwd<true> : gut::k_ssim_bwd<false>);
+    if (d_exposure)
+        bwd = d_bg ? (d_mask ? gut::k_ssim_bwd<true, true, true> : gut::k_ssim_bwd<false, true, true>)
+                   : (d_mask ? gut::k_ssim_bwd<true, false, true> : gut::k_ssim_bwd<false, false, true>);
     hipLaunchKernelGGL(bwd, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, maps, maps + plane, maps + 2 * plane, no_upstream,
-                       (float)(1.0 / count), -lambda_ssim, (float)(lambda_l1 / numel), d_rgba_grad, gx, gy, fin, d_mask, d_bg);
+                       (float)(1.0 / count), -lambda_ssim, (float)(lambda_l1 / numel), d_rgba_grad, gx, gy, fin, d_mask, d_bg, d_exposure);
     const int pixels = height * width;
-    if (d_bg)
+    if (d_exposure) {
+        // the partials follow everything gut_photometric_workspace_bytes covers (partial_l1 ends exactly there)
+        float* partial_e = d_exposure_grad ? partial_l1 + nblocks : nullptr;
+        const uint32_t rows = ((uint32_t)pixels + 256 * gut::kExpPixels - 1) / (256 * gut::kExpPixels);
+        auto px = d_bg ? gut::k_exposure_grad<true> : gut::k_exposure_grad<false>;
+        hipLaunchKernelGGL(px, dim3(rows), dim3(256), 0, s, (uint32_t)pixels, d_rgba, d_bg, v.background, d_mask, d_exposure, d_rgba_grad,
+                           partial_e);
+        if (d_exposure_grad)
+            hipLaunchKernelGGL(gut::k_exposure_finish, dim3(1), dim3(256), 0, s, rows, partial_e, d_exposure_grad);
+    } else if (d_bg)
         hipLaunchKernelGGL(gut::k_alpha_grad_image, dim3((pixels + 255) / 256), dim3(256), 0, s, pixels, d_bg, d_rgba_grad);
     else if (background != 0.0f)
         hipLaunchKernelGGL(gut::k_alpha_grad, dim3((pixels + 255) / 256), dim3(256), 0, s, pixels, background, d_rgba_grad);
@@ -468,6 +643,23 @@ int gut_photometric_loss_background(void* stream, int32_t height, int32_t width,
                                    d_workspace, d_loss3, d_rgba_grad);
 }
 
+int gut_photometric_loss_exposure(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
+                                  const float* d_mask, const float* d_background, float background, const float* d_exposure12,
+                                  float lambda_l1, float lambda_ssim, void* d_workspace, float* d_loss3, float* d_rgba_grad,
+                                  float* d_exposure_grad12) {
+    if (!d_exposure12) return 1;
+    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, d_mask, d_background, background, lambda_l1, lambda_ssim,
+                                   d_workspace, d_loss3, d_rgba_grad, d_exposure12, d_exposure_grad12);
+}
+
+int gut_exposure_adam_step(void* stream, const float* d_grad12, float* d_exposure12, float* d_m12, float* d_v12, int32_t* d_count,
+                           float lr, float beta1, float beta2, float eps) {
+    if (!d_grad12 || !d_exposure12 || !d_m12 || !d_v12 || !d_count) return 1;
+    hipLaunchKernelGGL(gut::k_exposure_adam, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), d_grad12, d_exposure12, d_m12,
+                       d_v12, d_count, lr, beta1, beta2, eps);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
 // three arrays of per-workgroup partials (SSIM, L1, squared error; 3 channels x tiles entries, 64 floats of slack after each)
 size_t gut_image_metrics_workspace_bytes(int32_t height, int32_t width) {
     const size_t blocks = (size_t)((width + 15) / 16) * ((height + 15) / 16) * 3;
@@ -490,7 +682,8 @@ int gut_image_metrics(void* stream, int32_t height, int32_t width, const float* 
     v.background = background;
     const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
     hipLaunchKernelGGL(gut::k_ssim_fwd<true>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, (float*)nullptr,
-                       (float*)nullptr, (float*)nullptr, gx, gy, partial_sq, (const float*)nullptr, (const float*)nullptr);
+                       (float*)nullptr, (float*)nullptr, gx, gy, partial_sq, (const float*)nullptr, (const float*)nullptr,
+                       (const float*)nullptr);
     const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     const double numel = 3.0 * height * width;
     hipLaunchKernelGGL(gut::k_metrics_finish, dim3(1), dim3(256), 0, s, partial, partial_l1, partial_sq, nblocks,

@@ -119,14 +119,30 @@ def image_metrics(rgba, gt_rgb, background="black", out=None):
     return out
 
 
-def photometric_loss(pred_rgb, gt_rgb, lambda_l1=0.8, lambda_ssim=0.2, mask=None):
+def apply_exposure(pred_rgb, exposure):
+    """The affine image of a view: pred_rgb [...,3] (composited over its background) -> A pred + b per pixel, with
+    exposure = [A | b] given as [3,4] or [12] (row-major), of pred_rgb's dtype and device; differentiable in both."""
+    E = exposure.reshape(3, 4)
+    return pred_rgb @ E[:, :3].transpose(0, 1) + E[:, 3]
+
+
+def photometric_loss(pred_rgb, gt_rgb, lambda_l1=0.8, lambda_ssim=0.2, mask=None, exposure=None):
     """pred/gt [B,H,W,3].  lambda_l1*L1 + lambda_ssim*(1-SSIM)  (configs/base_gs.yaml:111-119, trainer.py:425-449).
     mask [B,H,W,1] (Batch.mask) or None: both images are multiplied by it first, as the reference's get_losses does
-    (trainer.py:397-404); the means keep their full-image counts."""
+    (trainer.py:397-404); the means keep their full-image counts.
+    exposure [3,4] / [12] or None: the prediction is passed through apply_exposure first (before the mask).
+    float32 GPU tensors go through the HIP SSIM (fused_ssim); host or fp64 tensors through train.ssim, the same definition in torch."""
+    if exposure is not None:
+        pred_rgb = apply_exposure(pred_rgb, exposure)
     if mask is not None:
         mask = mask.to(device=pred_rgb.device, dtype=pred_rgb.dtype)
         pred_rgb, gt_rgb = pred_rgb * mask, gt_rgb * mask
-    s = fused_ssim(pred_rgb.permute(0, 3, 1, 2), gt_rgb.permute(0, 3, 1, 2), padding="valid")
+    if pred_rgb.is_cuda and pred_rgb.dtype == torch.float32:
+        s = fused_ssim(pred_rgb.permute(0, 3, 1, 2), gt_rgb.permute(0, 3, 1, 2), padding="valid")
+    else:
+        # host or fp64 tensors (the tests' references): the same SSIM in plain torch, in the tensors' own precision
+        from .train import ssim
+        s = ssim(pred_rgb.permute(0, 3, 1, 2), gt_rgb.to(pred_rgb.dtype).permute(0, 3, 1, 2))
     return lambda_l1 * l1_loss(pred_rgb, gt_rgb) + lambda_ssim * (1.0 - s)
 
 
@@ -151,7 +167,19 @@ def _plane_background(background, H, W, device):
     return background.reshape(H, W, 3).to(device=device, dtype=torch.float32).contiguous()
 
 
-def fused_photometric_loss(rgba, gt_rgb, background, lambda_l1=0.8, lambda_ssim=0.2, mask=None, workspace=None):
+def _exposure12(exposure, device):
+    """An exposure given as a float32 [12] or [3,4] tensor on `device`, as contiguous [12] (a view where it already is)."""
+    if not isinstance(exposure, torch.Tensor) or tuple(exposure.shape) not in ((12,), (3, 4)):
+        raise ValueError(f"fused_photometric_loss: exposure must be a [12] or [3,4] tensor, got "
+                         f"{tuple(exposure.shape) if isinstance(exposure, torch.Tensor) else type(exposure).__name__}")
+    if exposure.dtype != torch.float32 or exposure.device != device:
+        raise ValueError(f"fused_photometric_loss: exposure must be float32 on {device} (the kernels read it there), got "
+                         f"{exposure.dtype} on {exposure.device}")
+    return exposure.detach().reshape(12).contiguous()
+
+
+def fused_photometric_loss(rgba, gt_rgb, background, lambda_l1=0.8, lambda_ssim=0.2, mask=None, workspace=None, exposure=None,
+                           exposure_grad=True):
     """The train step's loss and its gradient without autograd (gut_photometric_loss / gut_photometric_loss_masked /
     gut_photometric_loss_background, csrc/gut_ssim.hip): image = rgb + background * (1 - alpha), loss = lambda_l1 * L1 +
     lambda_ssim * (1 - SSIM) against gt_rgb.
@@ -161,7 +189,11 @@ def fused_photometric_loss(rgba, gt_rgb, background, lambda_l1=0.8, lambda_ssim=
     mask: None, or [H,W] / [H,W,1] / [1,H,W,1] of any dtype — image and gt_rgb are both multiplied by it
     (trainer.py:397-404), the means keep their full-image counts, and a pixel whose mask is 0 gets a gradient of exactly zero.
     workspace: a float32 device tensor of at least gut_photometric_workspace_bytes(H, W) bytes to reuse, or None.
-    Returns (loss3, rgba_grad): a float32 device tensor (loss, L1, SSIM) and d(loss)/d(rgba) [H,W,4]."""
+    Returns (loss3, rgba_grad): a float32 device tensor (loss, L1, SSIM) and d(loss)/d(rgba) [H,W,4].
+    exposure: None, or the view's affine colour transform E = [A | b] as a float32 [12] / [3,4] tensor on the images' device
+    (gut_photometric_loss_exposure): the compared image is A image + b (before the mask), the workspace is one of
+    gut_photometric_exposure_workspace_bytes(H, W), and the call returns (loss3, rgba_grad, exposure_grad12) with d(loss)/dE laid
+    out like E — None with exposure_grad=False, which applies E and reduces nothing."""
     plane = isinstance(background, torch.Tensor)
     bg = background if plane else {"black": 0.0, "white": 1.0}.get(background, background)
     if isinstance(bg, str):
@@ -179,25 +211,39 @@ def fused_photometric_loss(rgba, gt_rgb, background, lambda_l1=0.8, lambda_ssim=
     if mask is not None:
         mask = _plane_mask(mask, H, W, rgba.device)
     bg = _plane_background(bg, H, W, rgba.device) if plane else float(bg)
-    need = lib.gut_photometric_workspace_bytes(H, W)
+    if exposure is not None:
+        exposure = _exposure12(exposure, rgba.device)
+    need = lib.gut_photometric_workspace_bytes(H, W) if exposure is None else lib.gut_photometric_exposure_workspace_bytes(H, W)
     if workspace is None:
         workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=rgba.device)
     elif workspace.dtype != torch.float32 or workspace.device != rgba.device or workspace.numel() * 4 < need or not workspace.is_contiguous():
         raise RuntimeError(f"[fused_photometric_loss] workspace must be a contiguous float32 tensor of at least {need} bytes on the images' device")
     with torch.cuda.device(rgba.device):
+        if exposure is not None:
+            grad12 = torch.empty((12,), dtype=torch.float32, device=rgba.device) if exposure_grad else None
+            return (*_photometric_loss_call(lib, H, W, rgba, gt_rgb, bg, lambda_l1, lambda_ssim, mask, workspace, exposure, grad12), grad12)
         return _photometric_loss_call(lib, H, W, rgba, gt_rgb, bg, lambda_l1, lambda_ssim, mask, workspace)
 
 
-def _photometric_loss_call(lib, H, W, rgba, gt_rgb, bg, lambda_l1, lambda_ssim, mask, workspace):
+def _photometric_loss_call(lib, H, W, rgba, gt_rgb, bg, lambda_l1, lambda_ssim, mask, workspace, exposure=None, exposure_grad=None):
     """The two C calls behind fused_photometric_loss, nothing checked: contiguous float32 device tensors (gt_rgb with or without a
     leading 1), bg a float or a float32 [H,W,3] device plane, mask a float32 [H,W] plane or None, a workspace of
     gut_photometric_workspace_bytes(H, W), the images' device current.
-    NativeTrainStep calls this directly every step, on buffers it sized itself."""
+    NativeTrainStep calls this directly every step, on buffers it sized itself.
+    exposure: None, or a contiguous float32 [12] device tensor — then the one call gut_photometric_loss_exposure, on a workspace of
+    gut_photometric_exposure_workspace_bytes(H, W); exposure_grad: the [12] device tensor that receives d(loss)/dE, or None."""
     # three fresh floats every call (the caching allocator, no kernel): callers return views of them
     loss3 = torch.empty((3,), dtype=torch.float32, device=rgba.device)
     rgba_grad = torch.empty_like(rgba)
     stream = torch.cuda.current_stream(rgba.device).cuda_stream
-    if isinstance(bg, torch.Tensor):
+    plane = isinstance(bg, torch.Tensor)
+    if exposure is not None:
+        rc = lib.gut_photometric_loss_exposure(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(),
+                                               None if mask is None else mask.data_ptr(), bg.data_ptr() if plane else None,
+                                               0.0 if plane else bg, exposure.data_ptr(), lambda_l1, lambda_ssim, workspace.data_ptr(),
+                                               loss3.data_ptr(), rgba_grad.data_ptr(),
+                                               None if exposure_grad is None else exposure_grad.data_ptr())
+    elif plane:
         rc = lib.gut_photometric_loss_background(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(),
                                                  None if mask is None else mask.data_ptr(), bg.data_ptr(), lambda_l1, lambda_ssim,
                                                  workspace.data_ptr(), loss3.data_ptr(), rgba_grad.data_ptr())

@@ -22,7 +22,7 @@ import torch
 from . import _capi, optim_calls
 from .dp import (RecordExchange, allgather_rows_, allgather_rows_async, allreduce_max_, allreduce_max_async, allreduce_mean_, allreduce_sum_async,
                  assert_replicas_identical)
-from .losses import _photometric_loss_call, _plane_background, _plane_mask, photometric_loss
+from .losses import _exposure12, _photometric_loss_call, _plane_background, _plane_mask, photometric_loss
 from .tracer import SplatRaster, Tracer
 
 # column layout of the raw [N,12] tensor and the reference's Adam learning rates (configs/base_gs.yaml:81-109)
@@ -141,7 +141,10 @@ class NativeTrainStep:
                  betas=(0.9, 0.999), eps=1e-15, fused_sh_adam=True, rank=0, fused_loss=True, lambda_l1=0.8, lambda_ssim=0.2,
                  dp_chunks=4, dp_chunk_min_rows=1 << 20, fuse_epilogue=True, schedule=None,
                  overlap_optimizer=None, dp_exchange="sparse", dp_side_stream=True, lazy_moments=True, lambda_opacity=0.0,
-                 lambda_scale=0.0, pose_gradient=False):
+                 lambda_scale=0.0, pose_gradient=False, exposure_gradient=False):
+        if exposure_gradient and world_size > 1:
+            raise ValueError("exposure_gradient: the exposure belongs to ONE view per step; data-parallel exposure compensation is out of "
+                             "scope (world_size must be 1)")
         if pose_gradient and world_size > 1:
             raise ValueError("pose_gradient: the pose gradient belongs to ONE view per step; data-parallel pose refinement is out of scope "
                              "(world_size must be 1)")
@@ -247,6 +250,13 @@ class NativeTrainStep:
         # one-pass fused path and the unfused one alike.  False: the tensor is None and the handle is left alone.
         self._pose_buffer = torch.zeros(8, dtype=torch.float32, device=dev) if pose_gradient else None
         self.pose_gradient = self._pose_buffer
+        # exposure_gradient=True: a batch with `.exposure` (a float32 [12] / [3,4] device tensor E = [A | b], exposure.py) is compared
+        # through A image + b in BOTH loss branches and every such step leaves d(loss)/dE in `self.exposure_gradient`,
+        # a device [12] tensor laid out like E, valid after step().  A batch without `.exposure` trains as without the switch.
+        # False: `.exposure` is not looked at and the tensor is None.
+        self._exposure_on = bool(exposure_gradient)
+        self._exposure_buffer = torch.zeros(12, dtype=torch.float32, device=dev) if exposure_gradient else None
+        self.exposure_gradient = self._exposure_buffer
         self.resize_workspace()
         self.phase_timing = False   # record HIP events around the phases of step() (bench / profiling)
         self._phase_events = []
@@ -264,6 +274,16 @@ class NativeTrainStep:
         self.pose_gradient = self._pose_buffer if on else None
         if not on and getattr(self.raster, "_pose_out", None) is self._pose_buffer:
             self.raster.set_pose_gradient(None)
+
+    def enable_exposure_gradient(self, on):
+        """Switch the exposure-gradient output of a stepper built with exposure_gradient=True off and on again between steps (the
+        trainer does outside the compensation window): off, `exposure_gradient` is None, the batch's exposure is still applied and
+        the loss reduces nothing for it."""
+        if self._exposure_buffer is None:
+            if on:
+                raise ValueError("enable_exposure_gradient: the stepper was built without exposure_gradient=True")
+            return
+        self.exposure_gradient = self._exposure_buffer if on else None
 
     @property
     def probe_pending(self):
@@ -692,11 +712,15 @@ class NativeTrainStep:
         # Batch.mask [1,H,W,1] or None: prediction and ground truth are multiplied by it inside the loss (trainer.py:397-404); the
         # pred_rgb returned stays unmasked, as the reference masks only the locals of get_losses
         mask = getattr(batch, "mask", None)
+        # Batch.exposure (ExposureCompensation.begin) or None: the prediction goes through A image + b inside the loss, before the
+        # mask; the pred_rgb returned stays the uncompensated render
+        exposure = getattr(batch, "exposure", None) if self._exposure_on else None
         if self.fused_loss and m.background_color in ("black", "white", "random") and gt.dtype == torch.float32 and gt.is_contiguous() \
                 and gt.numel() == rgba.shape[0] * rgba.shape[1] * 3:
-            # loss value and d(loss)/d(rgba) in two HIP launches (csrc/gut_ssim.hip: gut_photometric_loss[_masked | _background])
+            # loss value and d(loss)/d(rgba) in two HIP launches (csrc/gut_ssim.hip: gut_photometric_loss[_masked | _background]; with an exposure gut_photometric_loss_exposure)
             H, W = rgba.shape[0], rgba.shape[1]
-            need = self._lib.gut_photometric_workspace_bytes(H, W)
+            need = self._lib.gut_photometric_workspace_bytes(H, W) if exposure is None \
+                else self._lib.gut_photometric_exposure_workspace_bytes(H, W)
             if self._loss_ws is None or self._loss_ws.numel() * 4 < need:
                 self._loss_ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=rgba.device)
             # three fresh floats every step (the caching allocator, no kernel): the loss returned below is a VIEW of them — a
@@ -708,8 +732,11 @@ class NativeTrainStep:
                 bg = _plane_background(m.draw_background(batch.rays_dir), H, W, rgba.device)   # (a view: float32 [H,W,3] already)
             else:
                 bg = 1.0 if m.background_color == "white" else 0.0
+            # (an exposure: one more argument pair, E read on the device from the caller's row, and the entry point of the affine form)
             self._loss3, rgba_grad = _photometric_loss_call(self._lib, H, W, rgba, gt, bg, self.lambda_l1, self.lambda_ssim,
-                                                            None if mask is None else _plane_mask(mask, H, W, rgba.device), self._loss_ws)
+                                                            None if mask is None else _plane_mask(mask, H, W, rgba.device), self._loss_ws,
+                                                            None if exposure is None else _exposure12(exposure, rgba.device),
+                                                            None if exposure is None else self.exposure_gradient)
             pred_rgb = rgba[..., :3].unsqueeze(0)
             if m.background_color == "white":
                 pred_rgb = pred_rgb + (1.0 - rgba[..., 3:].unsqueeze(0))
@@ -720,8 +747,13 @@ class NativeTrainStep:
         pred_rgb = rgba_leaf[..., :3].unsqueeze(0)
         pred_opacity = rgba_leaf[..., 3:].unsqueeze(0)
         pred_rgb, pred_opacity = m.background(batch.T_to_world, batch.rays_dir, pred_rgb, pred_opacity, True)
-        loss = photometric_loss(pred_rgb, gt, self.lambda_l1, self.lambda_ssim, mask=mask)
+        E = None
+        if exposure is not None:   # a leaf copy: autograd leaves d(loss)/dE on it, the caller's row is not touched
+            E = _exposure12(exposure, rgba.device).clone().requires_grad_(self.exposure_gradient is not None)
+        loss = photometric_loss(pred_rgb, gt, self.lambda_l1, self.lambda_ssim, mask=mask, exposure=E)
         loss.backward()  # image-sized autograd only
+        if E is not None and self.exposure_gradient is not None:
+            self.exposure_gradient.copy_(E.grad)
         return loss, pred_rgb, rgba_leaf.grad
 
     def _act_written(self):

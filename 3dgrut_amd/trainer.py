@@ -25,9 +25,15 @@ written by the reference itself (an OmegaConf config inside) are not read.
 increment, and the view's next visit renders from the refined pose.  Held-out views (validation, test) are scored at their GIVEN
 poses.  The refiner's poses, moments and visit counts travel in the checkpoint's `native` block as tensors.
 
+`exposure.enabled` (default off; `--exposure`) learns an affine colour transform per training view (exposure.ExposureCompensation,
+DESIGN.md §10): the loss compares A image + b with the photo, its backward leaves d(loss)/d[A | b] on the device, and a per-view
+Adam updates the view's twelve floats there.  Held-out views (validation, test) have no learnt transform and are scored with the
+identity.  The transforms, moments and visit counts travel in the checkpoint's `native` block as tensors.
+
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
                                  [--refine-poses [--pose-lr-translation X] [--pose-lr-rotation R]]
+                                 [--exposure [--exposure-lr X]]
 """
 import argparse
 import copy
@@ -39,6 +45,7 @@ import time
 import numpy as np
 import torch
 
+from . import exposure as exposure_mod
 from . import losses, pose_refine
 from .evaluate import _check_batch, evaluate
 
@@ -61,6 +68,9 @@ GS_CONFIG = {
     # not a reference key: camera-pose refinement of the training views (pose_refine.py).  lr_translation is multiplied by the scene
     # extent, lr_rotation is in radians; end_iteration -1 = to the end of the run.  The two rates are untuned on real captures.
     "pose_refinement": dict(pose_refine.DEFAULTS),
+    # not a reference key: a learnt affine colour transform per training view (exposure.py).  end_iteration -1 = to the end of the run.
+    # The rate is untuned on real captures.
+    "exposure": dict(exposure_mod.DEFAULTS),
     "strategy": {"method": "GSStrategy",
                  "densify": {"frequency": 300, "start_iteration": 500, "end_iteration": 15000, "clone_grad_threshold": 0.0002,
                              "split_grad_threshold": 0.0002, "relative_size_threshold": 0.01, "split": {"n_gaussians": 2}},
@@ -111,6 +121,7 @@ def resolve_config(conf):
     if method == "GSStrategy" and out["strategy"]["reset_density"].get("end_iteration") is None:
         out["strategy"]["reset_density"]["end_iteration"] = out["strategy"]["densify"]["end_iteration"]
     pose_refine.check_config(out["pose_refinement"])
+    exposure_mod.check_config(out["exposure"])
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
         out["optimizer"]["params"]["features_specular"] = {"lr": float(out["optimizer"]["params"]["features_albedo"]["lr"]) / 20}
@@ -171,8 +182,9 @@ def _adam_group_template(betas, eps):
     return g
 
 
-def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=None, refiner=None):
-    """The checkpoint dictionary of a NativeTrainStep's state (see the module docstring); refiner: the run's PoseRefiner or None."""
+def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=None, refiner=None, exposures=None):
+    """The checkpoint dictionary of a NativeTrainStep's state (see the module docstring); refiner: the run's PoseRefiner or None;
+    exposures: its ExposureCompensation or None."""
     from .io_ply import checkpoint_dict
     st = stepper.state_dict()   # moments brought up to date (sync_moments) and cloned
     m = stepper.model
@@ -204,6 +216,8 @@ def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=No
     }
     if refiner is not None:
         extra["native"]["pose_refinement"] = refiner.state_dict()   # tensors only: poses, moments, visit counts
+    if exposures is not None:
+        extra["native"]["exposure"] = exposures.state_dict()        # tensors only: transforms, moments, visit counts
     if progressive:
         extra["feature_dim_increase_interval"] = int(prog["increase_frequency"])
         extra["feature_dim_increase_step"] = int(prog["increase_step"])
@@ -274,6 +288,7 @@ class Trainer:
         self.model = stepper.model
         self.strategy = self._build_strategy(ckpt) if strategy is None else strategy
         self.refiner = self._build_refiner(ckpt)
+        self.exposure = self._build_exposure(ckpt)
         if ckpt is not None:
             self.global_step = int(ckpt["global_step"])
 
@@ -310,7 +325,8 @@ class Trainer:
             sched.n_active_features = int(ckpt["n_active_features"])
         stepper = NativeTrainStep(model, tracer, scene_extent=self.scene_extent, selective=c["optimizer"]["type"] == "selective_adam",
                                   eps=float(c["optimizer"].get("eps", 1e-15)), schedule=sched,
-                                  pose_gradient=bool(c["pose_refinement"]["enabled"]), **losses.loss_weights(c["loss"]))
+                                  pose_gradient=bool(c["pose_refinement"]["enabled"]),
+                                  exposure_gradient=bool(c["exposure"]["enabled"]), **losses.loss_weights(c["loss"]))
         stepper.lr12[0:3] = sched.position_lr
         stepper.lr12[3] = lr["density"]
         stepper.lr12[4:8] = lr["rotation"]
@@ -343,6 +359,35 @@ class Trainer:
         if saved is not None:
             refiner.load_state_dict(saved)
         return refiner
+
+    def _build_exposure(self, ckpt):
+        """The ExposureCompensation of a run with exposure.enabled (else None), its state restored from a resumed checkpoint."""
+        ex = self.conf["exposure"]
+        if not ex["enabled"]:
+            if ckpt is not None and ckpt.get("native", {}).get("exposure") is not None:
+                # continuing without them would silently drop the transforms the Gaussians were trained against
+                raise ValueError("exposure: the checkpoint holds learnt exposures and exposure.enabled is off; resume with --exposure "
+                                 "(exposure.enabled: true), with end_iteration 0 to keep the exposures as they are")
+            return None
+        st = self.stepper
+        if int(getattr(st, "world_size", 1)) > 1:
+            raise ValueError("exposure: data-parallel exposure compensation is out of scope (the stepper's world_size must be 1)")
+        if getattr(st, "exposure_gradient", None) is None:
+            raise ValueError(f"exposure: {type(st).__name__} leaves no exposure gradient (NativeTrainStep(..., exposure_gradient=True) does)")
+        comp = exposure_mod.ExposureCompensation(len(self.train_batches), st.exposure_gradient.device, lr=float(ex["lr"]),
+                                                 betas=(float(ex["beta1"]), float(ex["beta2"])), eps=float(ex["eps"]),
+                                                 start_iteration=int(ex["start_iteration"]), end_iteration=int(ex["end_iteration"]))
+        saved = None if ckpt is None else ckpt["native"].get("exposure")
+        if saved is not None:
+            comp.load_state_dict(saved)
+        return comp
+
+    def exposures(self):
+        """[V,3,4] float32: the training views' current colour transforms [A | b], in train_batches order (identities when exposure
+        compensation is off).  Held-out views have none and are scored with the identity."""
+        if self.exposure is not None:
+            return self.exposure.exposures()
+        return torch.tensor(exposure_mod.IDENTITY, dtype=torch.float32).reshape(1, 3, 4).repeat(len(self.train_batches), 1, 1)
 
     def refined_poses(self):
         """[V,4,4] float64: the training views' current camera-to-world matrices, in train_batches order (the given ones when
@@ -418,7 +463,7 @@ class Trainer:
 
     def checkpoint(self):
         return make_checkpoint(self.stepper, self.conf, self.global_step, self.epoch, self.scene_extent,
-                               self.strategy if self.method == "GSStrategy" else None, self.refiner)
+                               self.strategy if self.method == "GSStrategy" else None, self.refiner, self.exposure)
 
     def save_checkpoint(self, last=False):
         out = self._out_dir()
@@ -451,7 +496,15 @@ class Trainer:
                 switch = getattr(self.stepper, "enable_pose_gradient", None)
                 if switch is not None:                      # outside [start_iteration, end_iteration) the backward reduces nothing
                     switch(refiner.active(g))
+            comp = self.exposure
+            if comp is not None:
+                batch = comp.begin(view, batch)             # batch.exposure: the view's row of the device state
+                switch = getattr(self.stepper, "enable_exposure_gradient", None)
+                if switch is not None:                      # outside [start_iteration, end_iteration) the loss reduces nothing
+                    switch(comp.active(g))
             self._last_loss, _ = self.stepper.step(batch)   # scheduler + SH ramp run at the end of step()
+            if comp is not None and comp.active(g):
+                comp.end(view, self.stepper.exposure_gradient)   # twelve-float Adam on the device: nothing waits
             if refiner is not None and refiner.active(g):
                 refiner.end(view, self.stepper.pose_gradient)   # queued on the device: no host synchronisation (V >= 2)
             self._post_optimizer_step(g)
@@ -466,6 +519,9 @@ class Trainer:
         if self.refiner is not None:
             ch = self.refiner.pose_change()
             self.stats.update(pose_mean_translation=ch["mean_translation"], pose_mean_rotation_deg=ch["mean_rotation_deg"])
+        if self.exposure is not None:
+            sm = self.exposure.summary()
+            self.stats.update(exposure_mean_gain=sm["mean_gain"], exposure_mean_offset=sm["mean_offset"])
         return self.stats
 
     def run(self):
@@ -494,12 +550,14 @@ def build_parser():
                     help="refine the training views' camera poses while training (pose_refinement.enabled); test views keep theirs")
     ap.add_argument("--pose-lr-translation", type=float, default=None, help="pose_refinement.lr_translation (times the scene extent)")
     ap.add_argument("--pose-lr-rotation", type=float, default=None, help="pose_refinement.lr_rotation (radians)")
+    ap.add_argument("--exposure", action="store_true",
+                    help="learn an affine colour transform per training view (exposure.enabled); test views are scored with the identity")
+    ap.add_argument("--exposure-lr", type=float, default=None, help="exposure.lr")
     return ap
 
 
-def main(argv=None):
-    a = build_parser().parse_args(argv)
-    from .io_colmap import ColmapScene
+def config_from_args(a):
+    """The plain conf dict of parsed command-line arguments (build_parser().parse_args(...))."""
     conf = default_config("MCMCStrategy" if a.strategy == "mcmc" else "GSStrategy")
     if a.out_dir is not None:
         conf["out_dir"] = a.out_dir
@@ -513,6 +571,16 @@ def main(argv=None):
         conf["pose_refinement"]["lr_translation"] = a.pose_lr_translation
     if a.pose_lr_rotation is not None:
         conf["pose_refinement"]["lr_rotation"] = a.pose_lr_rotation
+    conf["exposure"]["enabled"] = bool(a.exposure)
+    if a.exposure_lr is not None:
+        conf["exposure"]["lr"] = a.exposure_lr
+    return conf
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    from .io_colmap import ColmapScene
+    conf = config_from_args(a)
     train = ColmapScene(a.path, "train", a.downsample, a.test_split_interval)
     test = ColmapScene(a.path, "test", a.downsample, a.test_split_interval)
     # configs/initialization/colmap.yaml: observation-point scales, the model's default density / scale factor

@@ -41,7 +41,9 @@ extern "C" {
  * gut_set_regularisation, gut_sh_adam_step_regularised, gut_adam_unwalked_waves_regularised, gut_sync_moments_ex,
  * gut_regularisation_gradient, gut_regularisation_loss.  Added under 6 without a bump, nothing that was accepted changed meaning:
  * gut_photometric_loss_masked and gut_photometric_loss_background, new entry points next to gut_photometric_loss, which is
- * untouched; gut_set_pose_gradient and gut_pose_adam_step, new entry points: while it is not set, every gut_trace_bwd* queues what it queued before). */
+ * untouched; gut_set_pose_gradient and gut_pose_adam_step, new entry points: while it is not set, every gut_trace_bwd* queues what it queued before;
+ * gut_photometric_exposure_workspace_bytes, gut_photometric_loss_exposure and gut_exposure_adam_step, new entry points next to the
+ * other forms of the fused loss, which launch what they launched before). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -607,6 +609,32 @@ int gut_set_pose_gradient(gut_handle h, float* d_out8);
  * lr_rotation to phi.  d_delta6 receives the increment (d rho, d phi): c += d rho, R_c2w <- exp([d phi]x) R_c2w.  One launch. */
 int gut_pose_adam_step(void* stream, const float* d_grad8, float* d_m6, float* d_v6, int32_t* d_count, float lr_translation,
                        float lr_rotation, float beta1, float beta2, float eps, float* d_delta6);
+
+/* ---- Per-view exposure in the fused loss (new functionality, the reference has none) ----
+ * gut_photometric_loss_exposure is the fused loss of gut_photometric_loss[_masked | _background] on the AFFINE image of a view:
+ *     comp_k  = rgb_k + B_k (1 - alpha)                    B: `background` (d_background NULL) or the [H,W,3] plane d_background
+ *     image_c = (sum_k A[c][k] comp_k + b_c) * mask        E = [A | b]: d_exposure12, a row-major 3x4 float array in DEVICE memory,
+ *                                                          read by the kernels (no host copy, no synchronisation); identity [I | 0]
+ * against gt * mask, counts as in the other forms.  With g_c = d loss / d image_c (mask factor included):
+ *     d loss / d rgb_k = sum_c A[c][k] g_c,   d loss / d alpha = -sum_k B_k d loss / d rgb_k,
+ *     d loss / d A[c][k] = sum_pixels g_c comp_k,   d loss / d b_c = sum_pixels g_c      -> d_exposure_grad12, laid out like E.
+ * d_exposure_grad12 NULL: E is applied and nothing is reduced (one launch less).  The 12 sums are deterministic: a wave butterfly,
+ * one row of partials per workgroup of 1024 pixels in the workspace, a final sum in double in a fixed order; no atomics.  Every
+ * element of d_rgba_grad, d_loss3 and d_exposure_grad12 is written; a pixel whose mask is 0 gets four times 0.0f and adds nothing to
+ * the sums.  The workspace is one of gut_photometric_exposure_workspace_bytes.  Launches: forward, backward, the per-pixel pass (for
+ * every background, black included: the channels mix), the finish of the sums.  Returns 1 for a null pointer other than d_mask,
+ * d_background and d_exposure_grad12 or an image of 10 pixels or less either way, 2 for a launch failure.
+ * gut_exposure_adam_step: one Adam step on the 12 values of one view, in place: *d_count (the view's visit count) is advanced first
+ * and gives the bias correction; d_m12 / d_v12 are the view's own moments; the betas are held in float32.  One launch. */
+size_t gut_photometric_exposure_workspace_bytes(int32_t height, int32_t width);
+int gut_photometric_loss_exposure(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
+                                  const float* d_mask        /* [H,W] or NULL */,
+                                  const float* d_background  /* [H,W,3] or NULL: then `background` is the constant */,
+                                  float background, const float* d_exposure12, float lambda_l1, float lambda_ssim,
+                                  void* d_workspace, float* d_loss3, float* d_rgba_grad,
+                                  float* d_exposure_grad12   /* NULL: E is applied, nothing is reduced */);
+int gut_exposure_adam_step(void* stream, const float* d_grad12, float* d_exposure12, float* d_m12, float* d_v12,
+                           int32_t* d_count, float lr, float beta1, float beta2, float eps);
 
 /* ---- "next" row N3: MCMC relocation kernel (threedgrut/strategy/src/gaussian_mcmc.cu:33-73).
  * opacities [n], scales [n,3], ratios [n] (int32, 1..n_max), binoms [n_max,n_max] -> new_opacities [n], new_scales [n,3] */
