@@ -89,7 +89,8 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_sh_adam_step_regularised", "gut_adam_unwalked_waves_regularised", "gut_sync_moments_ex", "gut_regularisation_gradient",
            "gut_regularisation_loss", "gut_image_metrics_workspace_bytes", "gut_image_metrics", "gut_photometric_loss_masked",
            "gut_photometric_loss_background", "gut_set_pose_gradient", "gut_pose_adam_step",
-           "gut_photometric_exposure_workspace_bytes", "gut_photometric_loss_exposure", "gut_exposure_adam_step")
+           "gut_photometric_exposure_workspace_bytes", "gut_photometric_loss_exposure", "gut_exposure_adam_step",
+           "gut_image_metrics_cc_workspace_bytes", "gut_image_metrics_cc")
 
 _lib = None
 
@@ -153,6 +154,10 @@ def load():
     lib.gut_image_metrics_workspace_bytes.argtypes = [i32, i32]
     lib.gut_image_metrics_workspace_bytes.restype = C.c_size_t
     lib.gut_image_metrics.argtypes = [vp, i32, i32, vp, vp, C.c_float, vp, vp]
+    lib.gut_image_metrics_cc_workspace_bytes.argtypes = [i32, i32]
+    lib.gut_image_metrics_cc_workspace_bytes.restype = C.c_size_t
+    lib.gut_image_metrics_cc.argtypes = [vp, i32, i32, vp, vp, C.c_float, C.c_float, vp, vp, vp]
+    lib.gut_image_metrics_cc.restype = C.c_int
     lib.gut_trace_bwd_ex.argtypes = [vp, vp, u32, i32, u32, f_p, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera),
                                      f_p, f_p, f_p, f_p, f_p, f_p, u32]
     lib.gut_activate_pack.argtypes = [vp, u32, vp, vp]

@@ -20,6 +20,10 @@
 // Per-view exposure (gut_photometric_loss_exposure): further instantiations (kExposure) compare the AFFINE image
 // E [comp; 1], E = [A | b] a row-major 3x4 array in device memory, comp the composited pixel as above; the channels mix, so the rgb
 // gradient is finished by the per-pixel pass k_exposure_grad, which also reduces the 12 sums of dL/dE.  No other instantiation reads E.
+// Colour-corrected metrics (gut_image_metrics_cc): k_cc_moments / k_cc_solve fit the affine E that maps the composited
+// image best onto the ground truth, and the metrics forward runs once more with kMetrics AND kExposure, reading that E.
+#include <cmath>
+
 #include "gut_internal.h"
 
 namespace gut {
@@ -497,6 +501,143 @@ __global__ __launch_bounds__(64) void k_exposure_adam(const float* __restrict__ 
     e12[k] = e12[k] - (lr * (m / c1)) / (sqrtf(v / c2) + eps);
 }
 
+// Colour-corrected metrics (gut_image_metrics_cc), pass 1: the 22 moments of the ridge-regularised affine fit of the
+// composited image to the ground truth.  With x = (comp_0, comp_1, comp_2, 1) and y = gt: the 10 distinct sums of x x^T (row-major
+// upper triangle: 00 01 02 03 11 12 13 22 23 33) and the 12 sums of x y^T ([4][3], row-major).  The partition of k_exposure_grad
+// (kExpPixels pixels per lane, 1024 per workgroup), accumulated in DOUBLE from the first product: fp32 sums move an entry of the
+// fitted E by up to 6e-4 on images whose channels correlate.  A wave butterfly, the four waves added in order, one row of 22
+// doubles per workgroup; every row is written and nothing is atomic: the sums are a pure function of the inputs.
+constexpr int kCcTerms = 22;
+constexpr uint32_t kCcBatch = 16;   // k_cc_solve: rows a lane fetches before it adds them, so that the loads overlap
+
+__global__ __launch_bounds__(256) void k_cc_moments(uint32_t pixels, const float* __restrict__ rgba, const float* __restrict__ gt,
+                                                   float background, double* __restrict__ partials) {
+    __shared__ double red[4][kCcTerms];
+    double acc[kCcTerms];
+#pragma unroll
+    for (int k = 0; k < kCcTerms; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int j = 0; j < kExpPixels; ++j) {
+        const uint32_t i = (blockIdx.x * kExpPixels + j) * 256u + threadIdx.x;
+        if (i >= pixels) break;
+        const float4 t = reinterpret_cast<const float4*>(rgba)[i];
+        const float px[4] = {t.x, t.y, t.z, t.w};
+        float comp[3];
+        composite3<false>(px, 1, 3, background, nullptr, comp);
+        const double x[4] = {(double)comp[0], (double)comp[1], (double)comp[2], 1.0};
+        const float* g = gt + (size_t)i * 3;
+        const double y[3] = {(double)g[0], (double)g[1], (double)g[2]};
+        int n = 0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+#pragma unroll
+            for (int b = a; b < 4; ++b) acc[n++] += x[a] * x[b];
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[10 + 3 * a + c] += x[a] * y[c];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kCcTerms; ++k)
+        for (int mk = 32; mk >= 1; mk >>= 1) acc[k] += __shfl_xor(acc[k], mk);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kCcTerms; ++k) red[threadIdx.x >> 6][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kCcTerms)
+        partials[(size_t)blockIdx.x * kCcTerms + threadIdx.x] =
+            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// ... pass 2, one workgroup: the rows are summed in a fixed order (lane = term + 32 * slice; slice s adds the rows s, s + 8, ... in
+// order, then term k adds its 8 slices in order, as k_exposure_finish does), then one lane adds the ridge, ridge_p = ridge * pixels on
+// the diagonal of G = sum x x^T and on the identity part of C = sum x y^T, factors G = L L^T and solves the three right-hand sides, all
+// in double: E^T = G^-1 C, written as 12 floats (row-major 3x4) to e_ws and, if given, to e_out.  With finite inputs and ridge > 0 G is
+// positive definite and no pivot can be <= 0; non-finite inputs give non-finite outputs.
+__global__ __launch_bounds__(256) void k_cc_solve(uint32_t rows, const double* __restrict__ partials, double ridge_p,
+                                                 float* __restrict__ e_ws, float* __restrict__ e_out) {
+    __shared__ double red[8][32];
+    __shared__ double sum[kCcTerms];
+    const uint32_t k = threadIdx.x & 31u, slice = threadIdx.x >> 5;
+    if (k < (uint32_t)kCcTerms) {
+        double acc = 0.0;
+        for (uint32_t j = slice; j < rows; j += 8u * kCcBatch) {   // kCcBatch loads in flight, added in row order (+ 0.0 past the end)
+            double v[kCcBatch];
+#pragma unroll
+            for (uint32_t u = 0; u < kCcBatch; ++u) {
+                const uint32_t r = j + 8u * u;
+                v[u] = r < rows ? partials[(size_t)r * kCcTerms + k] : 0.0;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < kCcBatch; ++u) acc += v[u];
+        }
+        red[slice][k] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x < kCcTerms) {
+        double acc = red[0][threadIdx.x];
+        for (int s = 1; s < 8; ++s) acc += red[s][threadIdx.x];
+        sum[threadIdx.x] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double G[4][4], C[4][3], L[4][4];
+    int n = 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+#pragma unroll
+        for (int b = a; b < 4; ++b) {
+            G[a][b] = G[b][a] = sum[n++] + (a == b ? ridge_p : 0.0);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) C[a][c] = sum[10 + 3 * a + c] + (a == c ? ridge_p : 0.0);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double d = G[j][j];
+#pragma unroll
+        for (int m = 0; m < j; ++m) d -= L[j][m] * L[j][m];
+        L[j][j] = sqrt(d);
+#pragma unroll
+        for (int i = j + 1; i < 4; ++i) {
+            double s = G[i][j];
+#pragma unroll
+            for (int m = 0; m < j; ++m) s -= L[i][m] * L[j][m];
+            L[i][j] = s / L[j][j];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double z[4], w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {   // L z = C[:, c]
+            double s = C[i][c];
+#pragma unroll
+            for (int m = 0; m < i; ++m) s -= L[i][m] * z[m];
+            z[i] = s / L[i][i];
+        }
+#pragma unroll
+        for (int i = 3; i >= 0; --i) {  // L^T w = z
+            double s = z[i];
+#pragma unroll
+            for (int m = i + 1; m < 4; ++m) s -= L[m][i] * w[m];
+            w[i] = s / L[i][i];
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const float e = (float)w[a];
+            e_ws[4 * c + a] = e;
+            if (e_out) e_out[4 * c + a] = e;
+        }
+    }
+}
+
 }  // namespace gut
 
 extern "C" {
@@ -684,6 +825,53 @@ int gut_image_metrics(void* stream, int32_t height, int32_t width, const float* 
     hipLaunchKernelGGL(gut::k_ssim_fwd<true>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, (float*)nullptr,
                        (float*)nullptr, (float*)nullptr, gx, gy, partial_sq, (const float*)nullptr, (const float*)nullptr,
                        (const float*)nullptr);
+    const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
+    const double numel = 3.0 * height * width;
+    hipLaunchKernelGGL(gut::k_metrics_finish, dim3(1), dim3(256), 0, s, partial, partial_l1, partial_sq, nblocks,
+                       (float)(1.0 / count), (float)(1.0 / numel), d_out4);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// the workspace of gut_image_metrics (rounded up to 16 bytes), then one row of 22 doubles per 1024 pixels, then the fitted E (12 floats)
+static size_t cc_rows(int32_t height, int32_t width) {
+    return ((size_t)height * width + 256 * gut::kExpPixels - 1) / (256 * gut::kExpPixels);
+}
+static size_t cc_moments_offset(int32_t height, int32_t width) {
+    return (gut_image_metrics_workspace_bytes(height, width) + 15) / 16 * 16;
+}
+
+size_t gut_image_metrics_cc_workspace_bytes(int32_t height, int32_t width) {
+    if (height <= 0 || width <= 0) return 0;
+    return cc_moments_offset(height, width) + cc_rows(height, width) * gut::kCcTerms * sizeof(double) + 64;
+}
+
+int gut_image_metrics_cc(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
+                         float ridge, void* d_workspace, float* d_out4, float* d_exposure12) {
+    if (!d_rgba || !d_gt_rgb || !d_workspace || !d_out4) return 1;
+    if (height <= 2 * gut::kHalo || width <= 2 * gut::kHalo) return 1;
+    if (!(ridge > 0.0f) || !std::isfinite(ridge)) return 1;
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 8 != 0) return 1;   // (the rows of doubles)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t gx = (width + 15) / 16, gy = (height + 15) / 16;
+    const dim3 grid(gx * gy, 1, 3);
+    const int nblocks = (int)(grid.x * grid.z);
+    float* partial = static_cast<float*>(d_workspace);
+    float* partial_l1 = partial + nblocks + 64;
+    float* partial_sq = partial_l1 + nblocks + 64;
+    const uint32_t rows = (uint32_t)cc_rows(height, width);
+    double* moments = reinterpret_cast<double*>(static_cast<char*>(d_workspace) + cc_moments_offset(height, width));
+    float* fitted = reinterpret_cast<float*>(moments + (size_t)rows * gut::kCcTerms);
+    const uint32_t pixels = (uint32_t)height * (uint32_t)width;
+    hipLaunchKernelGGL(gut::k_cc_moments, dim3(rows), dim3(256), 0, s, pixels, d_rgba, d_gt_rgb, background, moments);
+    hipLaunchKernelGGL(gut::k_cc_solve, dim3(1), dim3(256), 0, s, rows, (const double*)moments, (double)ridge * (double)pixels, fitted,
+                       d_exposure12);
+    gut::ImgView v = make_view(3, height, width, 1, 4 * (int64_t)width, 4);   // rgba, interleaved
+    v.alpha_offset = 3;
+    v.background = background;
+    const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
+    hipLaunchKernelGGL((gut::k_ssim_fwd<true, false, false, true>), grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1,
+                       (float*)nullptr, (float*)nullptr, (float*)nullptr, gx, gy, partial_sq, (const float*)nullptr, (const float*)nullptr,
+                       (const float*)fitted);
     const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
     const double numel = 3.0 * height * width;
     hipLaunchKernelGGL(gut::k_metrics_finish, dim3(1), dim3(256), 0, s, partial, partial_l1, partial_sq, nblocks,

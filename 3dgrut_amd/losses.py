@@ -119,6 +119,72 @@ def image_metrics(rgba, gt_rgb, background="black", out=None):
     return out
 
 
+def colour_correction(comp, gt_rgb, ridge=1e-6):
+    """The affine colour transform that fits an image best to its photo, in float64 torch on the tensors' device: the
+    documented restatement of what gut_image_metrics_cc fits, for host tensors and tests.  comp [...,3] (the image composited over its
+    background) and gt_rgb of the same shape; with x = (comp, 1) per pixel and P pixels, E = [A | b] minimises
+        sum |A comp + b - gt|^2 + ridge * P * |[A | b] - [I | 0]|_F^2,
+    i.e. G = sum x x^T + ridge P I_4, C = sum x gt^T + ridge P [I_3; 0], E^T = G^-1 C.  ridge > 0 belongs to the definition: G is
+    positive definite whatever the image, and what the data do not show stays at the identity.  Returns E [3,4] float64."""
+    ridge = float(ridge)
+    if not (0.0 < ridge < float("inf")):
+        raise ValueError(f"colour_correction: ridge must be finite and > 0, got {ridge!r}")
+    if comp.shape[-1] != 3 or tuple(gt_rgb.shape) != tuple(comp.shape):
+        raise ValueError(f"colour_correction: expected two [...,3] tensors of one shape, got {tuple(comp.shape)} and {tuple(gt_rgb.shape)}")
+    x = comp.detach().reshape(-1, 3).to(torch.float64)
+    y = gt_rgb.detach().reshape(-1, 3).to(device=x.device, dtype=torch.float64)
+    x = torch.cat([x, torch.ones((x.shape[0], 1), dtype=torch.float64, device=x.device)], dim=1)
+    eye = torch.eye(4, dtype=torch.float64, device=x.device)
+    rp = ridge * x.shape[0]
+    G = x.transpose(0, 1) @ x + rp * eye
+    Cm = x.transpose(0, 1) @ y + rp * eye[:, :3]
+    return torch.cholesky_solve(Cm, torch.linalg.cholesky(G)).transpose(0, 1).contiguous()
+
+
+def image_metrics_colour_corrected(rgba, gt_rgb, background="black", ridge=1e-6, out=None, exposure_out=None):
+    """Colour-corrected evaluation metrics of one view on the GPU (gut_image_metrics_cc, csrc/gut_ssim.hip): the
+    affine E of colour_correction is fitted to image = rgb + background * (1 - alpha) against gt_rgb on the device (moments and solve
+    in double), and (MSE, PSNR, SSIM, L1) are those of E [image; 1], unclamped, with image_metrics' counts.  Arguments as
+    image_metrics; ridge: finite and > 0.  out: a contiguous float32 device tensor of 4 elements to write into; exposure_out: one of
+    12 (a [12] or [3,4] tensor, e.g. row i of an evaluation pass's [V,12]) that receives E.  Returns (out, E [3,4]), both on the
+    device; nothing is read back."""
+    bg = {"black": 0.0, "white": 1.0}.get(background, background)
+    if isinstance(bg, str):
+        raise ValueError(f"image_metrics_colour_corrected: background must be 'black', 'white' or a number, got {background!r}")
+    ridge = float(ridge)
+    if not (0.0 < ridge < float("inf")):
+        raise ValueError(f"image_metrics_colour_corrected: ridge must be finite and > 0, got {ridge!r}")
+    rgba = rgba.reshape(rgba.shape[-3:]) if rgba.dim() == 4 and rgba.shape[0] == 1 else rgba
+    gt_rgb = gt_rgb.reshape(gt_rgb.shape[-3:]) if gt_rgb.dim() == 4 and gt_rgb.shape[0] == 1 else gt_rgb
+    if rgba.dim() != 3 or rgba.shape[2] != 4 or tuple(gt_rgb.shape) != (rgba.shape[0], rgba.shape[1], 3):
+        raise RuntimeError(f"[image_metrics_colour_corrected] expected rgba [H,W,4] and gt [H,W,3], got {tuple(rgba.shape)} and "
+                           f"{tuple(gt_rgb.shape)}")
+    if not rgba.is_cuda or rgba.dtype != torch.float32 or gt_rgb.dtype != torch.float32 or gt_rgb.device != rgba.device:
+        raise RuntimeError("[image_metrics_colour_corrected] expected float32 GPU tensors on one device (there is no CPU path)")
+    rgba, gt_rgb = rgba.contiguous(), gt_rgb.contiguous()
+    if out is None:
+        out = torch.empty((4,), dtype=torch.float32, device=rgba.device)
+    elif out.dtype != torch.float32 or out.device != rgba.device or out.numel() != 4 or not out.is_contiguous():
+        raise RuntimeError("[image_metrics_colour_corrected] out must be a contiguous float32 tensor of 4 elements on the images' device")
+    if exposure_out is None:
+        exposure_out = torch.empty((3, 4), dtype=torch.float32, device=rgba.device)
+    elif exposure_out.dtype != torch.float32 or exposure_out.device != rgba.device or tuple(exposure_out.shape) not in ((12,), (3, 4)) \
+            or not exposure_out.is_contiguous():
+        raise RuntimeError("[image_metrics_colour_corrected] exposure_out must be a contiguous float32 [12] or [3,4] tensor on the "
+                           "images' device")
+    lib = _capi.load()
+    H, W = int(rgba.shape[0]), int(rgba.shape[1])
+    # (float64 elements: the rows of moments in the workspace are doubles, and the allocation is aligned for them)
+    ws = torch.empty(((lib.gut_image_metrics_cc_workspace_bytes(H, W) + 7) // 8,), dtype=torch.float64, device=rgba.device)
+    stream = torch.cuda.current_stream(rgba.device).cuda_stream
+    with torch.cuda.device(rgba.device):
+        rc = lib.gut_image_metrics_cc(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(), float(bg), ridge, ws.data_ptr(),
+                                      out.data_ptr(), exposure_out.data_ptr())
+    if rc:
+        raise RuntimeError(f"[image_metrics_colour_corrected] failed ({rc})" + ("; images must exceed 10x10" if rc == 1 else ""))
+    return out, exposure_out.reshape(3, 4)
+
+
 def apply_exposure(pred_rgb, exposure):
     """The affine image of a view: pred_rgb [...,3] (composited over its background) -> A pred + b per pixel, with
     exposure = [A | b] given as [3,4] or [12] (row-major), of pred_rgb's dtype and device; differentiable in both."""

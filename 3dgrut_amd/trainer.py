@@ -30,10 +30,15 @@ DESIGN.md §10): the loss compares A image + b with the photo, its backward leav
 Adam updates the view's twelve floats there.  Held-out views (validation, test) have no learnt transform and are scored with the
 identity.  The transforms, moments and visit counts travel in the checkpoint's `native` block as tensors.
 
+`evaluation.colour_corrected` (default off; `--cc-metrics`) additionally scores every held-out view COLOUR-CORRECTED:
+before scoring, the render is mapped through the affine colour transform that fits it best to the photo, fitted on the device, so
+that a held-out photo's own exposure is not charged to the model — the number to compare an `--exposure` run with a run without it.
+The plain metrics are unchanged; it needs nothing from the checkpoint and composes with every other option.
+
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
                                  [--refine-poses [--pose-lr-translation X] [--pose-lr-rotation R]]
-                                 [--exposure [--exposure-lr X]]
+                                 [--exposure [--exposure-lr X]] [--cc-metrics]
 """
 import argparse
 import copy
@@ -71,6 +76,9 @@ GS_CONFIG = {
     # not a reference key: a learnt affine colour transform per training view (exposure.py).  end_iteration -1 = to the end of the run.
     # The rate is untuned on real captures.
     "exposure": dict(exposure_mod.DEFAULTS),
+    # not a reference key: colour-corrected held-out metrics next to the plain ones (evaluate.py).  ridge is the regulariser of the
+    # per-view affine fit, a parameter of the metric's definition (> 0), not a tolerance.
+    "evaluation": {"colour_corrected": False, "ridge": 1e-6},
     "strategy": {"method": "GSStrategy",
                  "densify": {"frequency": 300, "start_iteration": 500, "end_iteration": 15000, "clone_grad_threshold": 0.0002,
                              "split_grad_threshold": 0.0002, "relative_size_threshold": 0.01, "split": {"n_gaussians": 2}},
@@ -122,10 +130,24 @@ def resolve_config(conf):
         out["strategy"]["reset_density"]["end_iteration"] = out["strategy"]["densify"]["end_iteration"]
     pose_refine.check_config(out["pose_refinement"])
     exposure_mod.check_config(out["exposure"])
+    check_evaluation_config(out["evaluation"])
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
         out["optimizer"]["params"]["features_specular"] = {"lr": float(out["optimizer"]["params"]["features_albedo"]["lr"]) / 20}
     return out
+
+
+def check_evaluation_config(block):
+    """The resolved `evaluation` block: colour_corrected true or false, ridge finite and > 0."""
+    unknown = set(block) - set(GS_CONFIG["evaluation"])
+    if unknown:
+        raise ValueError(f"evaluation: unknown keys {sorted(unknown)}")
+    if not isinstance(block["colour_corrected"], bool):   # (a string such as "false" would be truthy)
+        raise ValueError(f"evaluation.colour_corrected must be true or false, got {block['colour_corrected']!r}")
+    ridge = block["ridge"]
+    if isinstance(ridge, (bool, str)) or not (0.0 < float(ridge) < float("inf")):
+        raise ValueError(f"evaluation.ridge must be finite and > 0, got {ridge!r}")
+    return block
 
 
 BACKGROUND_COLORS = ("black", "white", "random")   # configs/base_gs.yaml:72-74
@@ -442,14 +464,21 @@ class Trainer:
         if raw is not None and raw.is_cuda:
             torch.cuda.synchronize(raw.device)
 
+    def _evaluation_options(self):
+        """The evaluator's keyword arguments: none with evaluation.colour_corrected off (an injected evaluator is then called with
+        the five positional arguments alone)."""
+        ev = self.conf["evaluation"]
+        return dict(colour_corrected=True, ridge=float(ev["ridge"])) if ev["colour_corrected"] else {}
+
     def validate(self):
         """Validation pass on val_batches (trainer.py:805-842): held-out metrics and the last training loss."""
         if not self.val_batches:
             return None
-        res = self.evaluator(self.model, self.tracer, self.val_batches, None, self.global_step)
+        res = self.evaluator(self.model, self.tracer, self.val_batches, None, self.global_step, **self._evaluation_options())
         loss = getattr(self, "_last_loss", None)
         entry = dict(step=self.global_step, loss=None if loss is None else float(loss), mean_psnr=res["mean_psnr"],
                      mean_ssim=res["mean_ssim"], n_gaussians=int(self.model.num_gaussians))
+        entry.update({k: res[k] for k in ("mean_cc_psnr", "mean_cc_ssim") if k in res})
         self.validations.append(entry)
         if self.conf.get("verbose", False):
             print(f"[trainer] step {entry['step']}: loss {entry['loss']} val psnr {entry['mean_psnr']:.3f} ssim {entry['mean_ssim']:.4f} "
@@ -530,7 +559,8 @@ class Trainer:
         print("Training Statistics: " + json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in stats.items()}), flush=True)
         if self.conf["test_last"] and self.test_batches:
             self.save_checkpoint(last=True)
-            self.test_metrics = self.evaluator(self.model, self.tracer, self.test_batches, self._out_dir(), self.global_step)
+            self.test_metrics = self.evaluator(self.model, self.tracer, self.test_batches, self._out_dir(), self.global_step,
+                                               **self._evaluation_options())
         return dict(stats=stats, test=self.test_metrics)
 
 
@@ -551,8 +581,12 @@ def build_parser():
     ap.add_argument("--pose-lr-translation", type=float, default=None, help="pose_refinement.lr_translation (times the scene extent)")
     ap.add_argument("--pose-lr-rotation", type=float, default=None, help="pose_refinement.lr_rotation (radians)")
     ap.add_argument("--exposure", action="store_true",
-                    help="learn an affine colour transform per training view (exposure.enabled); test views are scored with the identity")
+                    help="learn an affine colour transform per training view (exposure.enabled); test views are scored with the "
+                         "identity (--cc-metrics adds colour-corrected scores)")
     ap.add_argument("--exposure-lr", type=float, default=None, help="exposure.lr")
+    ap.add_argument("--cc-metrics", action="store_true",
+                    help="also score held-out views colour-corrected: through the affine colour transform fitted per view "
+                         "(evaluation.colour_corrected)")
     return ap
 
 
@@ -574,6 +608,7 @@ def config_from_args(a):
     conf["exposure"]["enabled"] = bool(a.exposure)
     if a.exposure_lr is not None:
         conf["exposure"]["lr"] = a.exposure_lr
+    conf["evaluation"]["colour_corrected"] = bool(a.cc_metrics)
     return conf
 
 
@@ -593,7 +628,8 @@ def main(argv=None):
     test_res = res["test"]
     out = dict(stats=res["stats"])
     if test_res is not None:
-        out["test"] = {k: test_res[k] for k in ("mean_psnr", "std_psnr", "mean_ssim", "n_views", "mean_inference_time") if k in test_res}
+        out["test"] = {k: test_res[k] for k in ("mean_psnr", "std_psnr", "mean_ssim", "n_views", "mean_inference_time", "mean_cc_psnr", "std_cc_psnr",
+                                                   "mean_cc_ssim") if k in test_res}
     print(json.dumps(out), flush=True)
     return 0
 

@@ -43,7 +43,8 @@ extern "C" {
  * gut_photometric_loss_masked and gut_photometric_loss_background, new entry points next to gut_photometric_loss, which is
  * untouched; gut_set_pose_gradient and gut_pose_adam_step, new entry points: while it is not set, every gut_trace_bwd* queues what it queued before;
  * gut_photometric_exposure_workspace_bytes, gut_photometric_loss_exposure and gut_exposure_adam_step, new entry points next to the
- * other forms of the fused loss, which launch what they launched before). */
+ * other forms of the fused loss, which launch what they launched before; gut_image_metrics_cc_workspace_bytes and gut_image_metrics_cc,
+ * new entry points next to gut_image_metrics, which launches what it launched before). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -369,6 +370,29 @@ int gut_photometric_loss_background(void* stream, int32_t height, int32_t width,
 size_t gut_image_metrics_workspace_bytes(int32_t height, int32_t width);
 int gut_image_metrics(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
                       void* d_workspace, float* d_out4);
+
+/* COLOUR-CORRECTED evaluation metrics of one view (new functionality): the metrics above of the image mapped through
+ * the affine colour transform that fits it best to the photo, so that a held-out photo's own exposure and white balance are not
+ * charged to the model.  With comp_k = rgb_k + background (1 - alpha) in fp32 and x = (comp_0, comp_1, comp_2, 1), over the
+ * P = height * width pixels (no mask, nothing clamped), E = [A | b] (3x4) minimises
+ *     sum_pixels |A comp + b - gt|^2  +  ridge * P * |[A | b] - [I | 0]|_F^2 :
+ *     G = sum x x^T + ridge P I_4,   C = sum x gt^T + ridge P [I_3; 0],   E^T = G^-1 C.
+ * ridge > 0 is part of the definition (1e-6 in the Python surface): G is positive definite for every finite input (a constant or grey
+ * image, an all-black render), directions the data do not show stay at the identity, SSE(E) <= SSE(identity), and for gt = A* comp + b*
+ * exactly the corrected MSE is at most ridge |[A* | b*] - [I | 0]|_F^2 / 3.
+ * d_out4 receives { MSE, PSNR, SSIM, L1 } of image_c = fma(E[c][0], comp_0, fma(E[c][1], comp_1, fma(E[c][2], comp_2, E[c][3])))
+ * against d_gt_rgb, counts and definitions as gut_image_metrics; d_exposure12 (may be NULL) receives the fitted E, row-major 3x4; both
+ * may point into a caller's [V,4] / [V,12] device tensors.  Four launches on `stream`, nothing copied to the host, nothing
+ * synchronised: the 22 moments (10 of G, 12 of C) accumulated in double from the first product, one row of 22 doubles per 1024
+ * pixels, no atomics; one workgroup that sums the rows in a fixed order, adds the ridge, factors G by Cholesky and solves, in double;
+ * the metrics forward on E [comp; 1], reading E from the workspace; the finish of gut_image_metrics.  Identical inputs, identical
+ * bits.  Non-finite inputs give non-finite outputs.  d_rgba must be 16-byte and d_workspace 8-byte aligned (torch allocations are).
+ * Returns 1 — on the host, before anything is queued — for a null pointer other than d_exposure12, height / width <= 10, a ridge that
+ * is not finite or not > 0, or a misaligned workspace; 2 for a launch failure.  Workspace: gut_image_metrics_cc_workspace_bytes(). */
+size_t gut_image_metrics_cc_workspace_bytes(int32_t height, int32_t width);
+int gut_image_metrics_cc(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
+                         float background, float ridge, void* d_workspace, float* d_out4,
+                         float* d_exposure12 /* receives the fitted E, row-major 3x4; may be NULL */);
 
 /* ---- "next" row N2: parameter activation + fused Adam ----
  * gut_activate_pack: raw rows [N,12] (pos3, density logit, quat4, log-scale3, unused) -> activated rows
