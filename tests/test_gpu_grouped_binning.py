@@ -52,8 +52,10 @@ def _compare(sc, view, rgba_grad):
 @pytest.mark.parametrize("order", ["given", "morton"])
 @pytest.mark.parametrize("name", ["c1_pinhole_128", "ragged_100x70", "fisheye_144x96", "inside_cloud", "dense_big_splats"])
 def test_grouped_binning_matches_the_full_sort(name, order):
-    """"given": random storage order, the workgroups' tile windows are mostly too large (per-entry global atomics);
-    "morton": the trainer's order, the LDS bins of the window take most entries."""
+    """"given": random storage order, every workgroup's window spans most of the grid; "morton": the trainer's order, compact
+    windows.  At these sizes (at most 81 tiles) every window fits its 1536 LDS bins: the entries outside a window (per-entry
+    global atomics) come only from large footprints.  Windows that do not fit, and workgroups without one, are
+    tests/test_gpu_capacity_edges.py."""
     mk, kind, W, H, (eye, tgt), kw = CASES[name]
     sc = mk()
     if order == "morton":
