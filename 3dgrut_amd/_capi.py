@@ -77,6 +77,13 @@ class GutRegularisation(C.Structure):
     _fields_ = [("density_coeff", C.c_float), ("scale_coeff", C.c_float), ("d_partials", C.c_void_p)]
 
 
+class GutPhotometricLoss(C.Structure):
+    """The fused loss by descriptor (gut_hip.h, gut_photometric_loss_run): device pointers, None = that operand is absent."""
+    _fields_ = [("d_rgba", C.c_void_p), ("d_gt_rgb", C.c_void_p), ("d_mask", C.c_void_p), ("d_background", C.c_void_p),
+                ("d_exposure12", C.c_void_p), ("d_workspace", C.c_void_p), ("d_loss3", C.c_void_p), ("d_rgba_grad", C.c_void_p),
+                ("d_exposure_grad12", C.c_void_p), ("background", C.c_float), ("lambda_l1", C.c_float), ("lambda_ssim", C.c_float)]
+
+
 EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_trace_bwd", "gut_collect_times",
            "gut_get_stats", "gut_debug_buffer", "gut_debug_copy", "gut_kernel_times", "gut_kernel_times_mean", "gut_last_error", "gut_abi_version",
            "gut_ssim_workspace_bytes", "gut_ssim_forward", "gut_ssim_backward",
@@ -90,7 +97,7 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_regularisation_loss", "gut_image_metrics_workspace_bytes", "gut_image_metrics", "gut_photometric_loss_masked",
            "gut_photometric_loss_background", "gut_set_pose_gradient", "gut_pose_adam_step",
            "gut_photometric_exposure_workspace_bytes", "gut_photometric_loss_exposure", "gut_exposure_adam_step",
-           "gut_image_metrics_cc_workspace_bytes", "gut_image_metrics_cc")
+           "gut_image_metrics_cc_workspace_bytes", "gut_image_metrics_cc", "gut_photometric_loss_run")
 
 _lib = None
 
@@ -150,6 +157,7 @@ def load():
     lib.gut_photometric_exposure_workspace_bytes.argtypes = [i32, i32]
     lib.gut_photometric_exposure_workspace_bytes.restype = C.c_size_t
     lib.gut_photometric_loss_exposure.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, vp, C.c_float, C.c_float, vp, vp, vp, vp]
+    lib.gut_photometric_loss_run.argtypes = [vp, i32, i32, C.POINTER(GutPhotometricLoss)]
     lib.gut_exposure_adam_step.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float]
     lib.gut_image_metrics_workspace_bytes.argtypes = [i32, i32]
     lib.gut_image_metrics_workspace_bytes.restype = C.c_size_t

@@ -1,28 +1,34 @@
-// gut_ssim.hip — fused SSIM (forward + backward) for gfx950.
+// gut_ssim.hip — the image losses and metrics for gfx950: fused SSIM (forward + backward), the fused photometric loss, the
+// evaluation metrics.
 //
-// "Next" row N1 of SURVEY §8f: the reference's loss calls the external CUDA-only `fused_ssim` package
-// (threedgrut/model/losses.py:17-33, requirements.txt:23) right after every render
-// (trainer.py:425-430): mean SSIM with an 11x11 Gaussian window (sigma 1.5), C1 = 0.01^2, C2 = 0.03^2,
-// padding="valid" (the 5-pixel border of the SSIM map is excluded from the mean).
+// The model.  The reference's loss calls the external CUDA-only `fused_ssim` package (threedgrut/model/losses.py:17-33,
+// requirements.txt:23) right after every render (trainer.py:425-430): mean SSIM with an 11x11 Gaussian window
+// (sigma 1.5), C1 = 0.01^2, C2 = 0.03^2, padding="valid" (the 5-pixel border of the SSIM map is excluded from the mean).  Two kernels
+// do all of it.  k_ssim_fwd: one 256-thread workgroup per 16x16 output tile and channel stages the (16+10)^2 patch of the PREDICTION
+// and of the ground truth in LDS once, runs the separable window horizontally into LDS and vertically in registers, and writes its
+// partial sums (SSIM, L1, for the metrics the squared error) and the three derivative maps d(ssim)/d(mu1), d(ssim)/d(sigma1^2),
+// d(ssim)/d(sigma12) (the scheme of fused-ssim).  k_ssim_bwd convolves those maps with the window and writes the gradient.  Images are
+// addressed through (channel, row, pixel) element strides (ImgView), so the tracer's [1,H,W,3] / [H,W,4] tensors are consumed in place.
 //
-// Layout-agnostic: images are addressed through (channel, row, pixel) element strides so the [1,H,W,3]
-// tensor the tracer produces is consumed in place (no permute/contiguous copies).
-// One 256-thread workgroup per 16x16 output tile and channel; the (16+10)^2 input patch of both images is
-// staged in LDS once, the separable window runs horizontally into LDS and vertically in registers.
-// Forward also stores the three partial-derivative maps d(ssim)/d(mu1), d(ssim)/d(sigma1^2),
-// d(ssim)/d(sigma12) the backward needs (same scheme as fused-ssim); backward convolves them with the window.
-// The evaluation metrics (gut_image_metrics: MSE, PSNR, SSIM, L1) run the same forward without those maps.
-// Masked views (gut_photometric_loss_masked): a second instantiation of the forward and the backward (kMasked) multiplies both
-// images by a per-pixel mask where they are loaded; the unmasked instantiations do not see the mask at all.
-// Background image (gut_photometric_loss_background): further instantiations (kBgImage) composite every pixel over its own colour,
-// image = rgb + B[y,x,:] * (1 - alpha), for the reference's `random` background (model/background.py:83-89), a constant RGB colour or
-// an environment image; the constant-background instantiations do not read the plane.
-// Per-view exposure (gut_photometric_loss_exposure): further instantiations (kExposure) compare the AFFINE image
-// E [comp; 1], E = [A | b] a row-major 3x4 array in device memory, comp the composited pixel as above; the channels mix, so the rgb
-// gradient is finished by the per-pixel pass k_exposure_grad, which also reduces the 12 sums of dL/dE.  No other instantiation reads E.
-// Colour-corrected metrics (gut_image_metrics_cc): k_cc_moments / k_cc_solve fit the affine E that maps the composited
-// image best onto the ground truth, and the metrics forward runs once more with kMetrics AND kExposure, reading that E.
+// Operands.  What the prediction IS is decided where a pixel is loaded (load_pred) and by nothing else:
+//     comp_k = rgb_k + B_k (1 - alpha)      B: the view's constant background, or the pixel's own colour in the plane `bg` (kBgImage:
+//                                           the reference's `random` background, model/background.py:83-89, a colour, an environment image)
+//     pred_c = E [comp; 1]                  kExposure: E = [A | b], a row-major 3x4 array in device memory
+//     pred_c, gt_c times mask[y,x]          kMasked (trainer.py:397-404): both images, a halo pixel with ITS OWN mask value
+// An operand is one pointer of LossOperands and one template flag of both kernels; an instantiation reads exactly the operands its
+// flags name (the others may be null), so a combination without an operand runs code that has never heard of it.  loss_kernels() maps
+// the operands a call brings to the instantiation pair.
+//
+// Post-passes of the fused loss, per pixel on the float4 gradient:
+//     k_alpha_grad<kBgImage>     d loss / d alpha = -sum_k B_k g_k, for a background other than constant black (there the backward's 0 stands)
+//     k_exposure_grad<kBgImage>  with an exposure the channels mix: the backward leaves g_c = d loss / d pred_c, this turns the three into
+//                                A^T g, writes the alpha slot and reduces the 12 sums of dL/dE (k_exposure_finish adds the rows)
+// The loss value itself has no pass: workgroup 0 of the backward finishes it (photometric_finish).  The metrics run the forward alone
+// (kMetrics: no maps), then k_metrics_finish; the colour-corrected metrics first fit E (k_cc_moments, k_cc_solve) and
+// run the same forward with kExposure on it.
+#include <array>
 #include <cmath>
+#include <utility>
 
 #include "gut_internal.h"
 
@@ -72,14 +78,15 @@ __device__ __forceinline__ float mask_px(const float* __restrict__ mask, const I
     return mask[(size_t)y * v.W + x];
 }
 
-// kBgImage: the rgba pixel composited over ITS OWN background colour, bg[y,x,c] ([H,W,3] floats, interleaved like the ground truth):
-// rgb + B * (1 - alpha) as one fma, the same in the forward and the backward.  Outside the image 0, and nothing is read.
-__device__ __forceinline__ float load_px_bg(const float* __restrict__ img, const ImgView& v, const float* __restrict__ bg, int c, int y,
-                                            int x) {
-    if (x < 0 || y < 0 || x >= v.W || y >= v.H) return 0.0f;
-    const long long o = (long long)y * v.sh + (long long)x * v.sw;
-    return fmaf(bg[((size_t)y * v.W + x) * 3 + c], 1.0f - img[o + v.alpha_offset], img[o + (long long)c * v.sc]);
-}
+// The optional operands of the fused loss, device pointers: mask [H,W], bg [H,W,3] (interleaved like the ground truth), exposure
+// (E, 12 floats).  A kernel instantiation reads only those its template flags name; the others may be null.
+struct LossOperands {
+    const float* __restrict__ mask = nullptr;
+    const float* __restrict__ bg = nullptr;
+    const float* __restrict__ exposure = nullptr;
+    static constexpr int kCount = 3;
+    unsigned present() const { return (mask ? 1u : 0u) | (bg ? 2u : 0u) | (exposure ? 4u : 0u); }   // bit i: operand i is there
+};
 
 // kExposure: the three composited channels of a pixel, comp_k = rgb_k + B_k (1 - alpha), B the pixel's own background colour
 // (kBgImage) or the constant v.background — one definition for the forward, the backward and the per-pixel pass.
@@ -96,33 +103,45 @@ __device__ __forceinline__ void composite3(const float* __restrict__ px /* the p
     }
 }
 
-// kExposure: channel c of the affine image, A[c][0] comp_0 + A[c][1] comp_1 + A[c][2] comp_2 + b_c with e4 = row c of E (four
-// floats the workgroup holds in registers).  Outside the image 0, and nothing is read.
-template <bool kBgImage>
-__device__ __forceinline__ float load_px_exposure(const float* __restrict__ img, const ImgView& v, const float* __restrict__ bg,
-                                                  const float (&e4)[4], int y, int x) {
-    if (x < 0 || y < 0 || x >= v.W || y >= v.H) return 0.0f;
-    float comp[3];
-    composite3<kBgImage>(img + (long long)y * v.sh + (long long)x * v.sw, v.sc, v.alpha_offset, v.background,
-                         kBgImage ? bg + ((size_t)y * v.W + x) * 3 : nullptr, comp);
-    return fmaf(e4[0], comp[0], fmaf(e4[1], comp[1], fmaf(e4[2], comp[2], e4[3])));
+// kExposure: row c of E, the four floats a workgroup holds in registers (zeros, and nothing read, without an exposure)
+template <bool kExposure>
+__device__ __forceinline__ void exposure_row(const LossOperands& ops, int c, float (&e4)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) e4[k] = kExposure ? ops.exposure[4 * c + k] : 0.0f;
+}
+
+// Channel c of the prediction at (y, x), before the mask factor — the one place that knows what the prediction is, for the forward
+// and the backward alike.  Outside the image 0, and nothing is read.
+//   neither flag: the rgba pixel over the constant v.background (load_px)
+//   kBgImage:     over ITS OWN background colour bg[y,x,c]: rgb + B * (1 - alpha) as one fma (v.background is not used)
+//   kExposure:    A[c][0] comp_0 + A[c][1] comp_1 + A[c][2] comp_2 + b_c of the composited pixel, e4 = row c of E
+template <bool kBgImage, bool kExposure>
+__device__ __forceinline__ float load_pred(const float* __restrict__ img, const ImgView& v, const LossOperands& ops, const float (&e4)[4],
+                                           int c, int y, int x) {
+    if constexpr (!kBgImage && !kExposure) return load_px(img, v, c, y, x);
+    else {
+        if (x < 0 || y < 0 || x >= v.W || y >= v.H) return 0.0f;
+        const long long o = (long long)y * v.sh + (long long)x * v.sw;
+        if constexpr (kExposure) {
+            float comp[3];
+            composite3<kBgImage>(img + o, v.sc, v.alpha_offset, v.background, kBgImage ? ops.bg + ((size_t)y * v.W + x) * 3 : nullptr, comp);
+            return fmaf(e4[0], comp[0], fmaf(e4[1], comp[1], fmaf(e4[2], comp[2], e4[3])));
+        } else return fmaf(ops.bg[((size_t)y * v.W + x) * 3 + c], 1.0f - img[o + v.alpha_offset], img[o + (long long)c * v.sc]);
+    }
 }
 
 // forward: partial sums of the valid-region SSIM map per workgroup + derivative maps (planar [C,H,W])
 // kMetrics (gut_image_metrics, no backward follows): the three derivative maps are not stored (their pointers may be null) and the
 // workgroup's sum of squared errors goes to partial_sq, next to the L1 partials.
+// kBgImage / kExposure: img1 is staged through load_pred<kBgImage, kExposure>, channel c with row c of E.
 // kMasked: both patches are staged times the mask, so the SSIM statistics, the L1 partials and the derivative maps are those of the
-// two masked images; `mask` is not read otherwise.
-// kBgImage: img1 is staged through load_px_bg (v.background is not used); `bg` is not read otherwise.  Combines with kMasked.
-// kExposure: img1 is staged through load_px_exposure, channel c with row c of `exposure`; combines with kMasked and kBgImage.
+// two masked images.  The three flags combine freely.
 template <bool kMetrics, bool kMasked = false, bool kBgImage = false, bool kExposure = false>
 __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const float* __restrict__ img1,
                                                  const float* __restrict__ img2, float* __restrict__ partial,
                                                  float* __restrict__ partial_l1, float* __restrict__ dm_dmu1,
                                                  float* __restrict__ dm_dsigma1_sq, float* __restrict__ dm_dsigma12,
-                                                 uint32_t gx, uint32_t gy, float* __restrict__ partial_sq,
-                                                 const float* __restrict__ mask, const float* __restrict__ bg,
-                                                 const float* __restrict__ exposure) {
+                                                 uint32_t gx, uint32_t gy, float* __restrict__ partial_sq, LossOperands ops) {
     // row strides chosen for the two 16-lane rows a 32-lane LDS access group covers: 48 = 16 mod 32 for the patches (row r and
     // r + 1 fall on disjoint halves of the 32 banks while the 11-tap window slides), 16 for the filtered rows (ditto for the
     // column pass).  With the earlier 27 / 17 the window passes lost 46 % of their LDS cycles to 2-way conflicts.
@@ -134,31 +153,15 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(ImgView v, ImgView v2, const f
     xcd_tile(blockIdx.x, gx, gy, &tx, &ty);
     const int x0 = tx * kSTile, y0 = ty * kSTile;
     const int tid = threadIdx.x;
-    float e4[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (kExposure) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) e4[k] = exposure[4 * c + k];
-    }
+    float e4[4];
+    exposure_row<kExposure>(ops, c, e4);
     for (int i = tid; i < kPatch * kPatch; i += 256) {
         const int py = i / kPatch, pxx = i - py * kPatch;
-        if constexpr (kExposure) {
-            float mk = 1.0f;
-            if constexpr (kMasked) mk = mask_px(mask, v, y0 + py - kHalo, x0 + pxx - kHalo);
-            s1[py][pxx] = load_px_exposure<kBgImage>(img1, v, bg, e4, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
-            s2[py][pxx] = load_px(img2, v2, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
-        } else if constexpr (kBgImage) {
-            float mk = 1.0f;
-            if constexpr (kMasked) mk = mask_px(mask, v, y0 + py - kHalo, x0 + pxx - kHalo);
-            s1[py][pxx] = load_px_bg(img1, v, bg, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
-            s2[py][pxx] = load_px(img2, v2, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
-        } else if constexpr (kMasked) {
-            const float mk = mask_px(mask, v, y0 + py - kHalo, x0 + pxx - kHalo);
-            s1[py][pxx] = load_px(img1, v, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
-            s2[py][pxx] = load_px(img2, v2, c, y0 + py - kHalo, x0 + pxx - kHalo) * mk;
-        } else {
-            s1[py][pxx] = load_px(img1, v, c, y0 + py - kHalo, x0 + pxx - kHalo);
-            s2[py][pxx] = load_px(img2, v2, c, y0 + py - kHalo, x0 + pxx - kHalo);
-        }
+        const int y = y0 + py - kHalo, x = x0 + pxx - kHalo;
+        float mk = 1.0f;
+        if constexpr (kMasked) mk = mask_px(ops.mask, v, y, x);
+        s1[py][pxx] = load_pred<kBgImage, kExposure>(img1, v, ops, e4, c, y, x) * mk;
+        s2[py][pxx] = load_px(img2, v2, c, y, x) * mk;
     }
     __syncthreads();
     for (int i = tid; i < kPatch * kSTile; i += 256) {
@@ -250,15 +253,12 @@ struct FinishArgs {
 // kMetrics (k_metrics_finish): the squared-error partials are summed as well, in the same order, and the output is the four
 // floats { MSE, PSNR, SSIM, L1 } (MSE over the same numel as L1); lambda_l1 / lambda_ssim are not used then.
 template <bool kMetrics>
-__device__ __forceinline__ void photometric_finish(const float* __restrict__ partial, const float* __restrict__ partial_l1,
-                                                   int n, float inv_count_ssim, float inv_count_l1, float lambda_l1,
-                                                   float lambda_ssim, float* __restrict__ out3,
-                                                   const float* __restrict__ partial_sq = nullptr) {
+__device__ __forceinline__ void photometric_finish(const FinishArgs& fin, const float* __restrict__ partial_sq = nullptr) {
     __shared__ double red[kMetrics ? 3 : 2][4];
     double a = 0.0, b = 0.0, q = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        a += (double)partial[i];
-        b += (double)partial_l1[i];
+    for (int i = threadIdx.x; i < fin.n; i += 256) {
+        a += (double)fin.partial[i];
+        b += (double)fin.partial_l1[i];
         if constexpr (kMetrics) q += (double)partial_sq[i];
     }
     for (int mk = 32; mk >= 1; mk >>= 1) {
@@ -273,26 +273,24 @@ __device__ __forceinline__ void photometric_finish(const float* __restrict__ par
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const float ssim = (float)((red[0][0] + red[0][1] + red[0][2] + red[0][3]) * (double)inv_count_ssim);
-        const float l1 = (float)((red[1][0] + red[1][1] + red[1][2] + red[1][3]) * (double)inv_count_l1);
+        const float ssim = (float)((red[0][0] + red[0][1] + red[0][2] + red[0][3]) * (double)fin.inv_count_ssim);
+        const float l1 = (float)((red[1][0] + red[1][1] + red[1][2] + red[1][3]) * (double)fin.inv_count_l1);
         if constexpr (kMetrics) {
-            const double mse = (red[2][0] + red[2][1] + red[2][2] + red[2][3]) * (double)inv_count_l1;
-            out3[0] = (float)mse;
-            out3[1] = mse > 0.0 ? (float)(10.0 * log10(1.0 / mse)) : __builtin_huge_valf();   // PSNR for a data range of 1
-            out3[2] = ssim;
-            out3[3] = l1;
+            const double mse = (red[2][0] + red[2][1] + red[2][2] + red[2][3]) * (double)fin.inv_count_l1;
+            fin.out3[0] = (float)mse;
+            fin.out3[1] = mse > 0.0 ? (float)(10.0 * log10(1.0 / mse)) : __builtin_huge_valf();   // PSNR for a data range of 1
+            fin.out3[2] = ssim;
+            fin.out3[3] = l1;
         } else {
-            out3[0] = lambda_l1 * l1 + lambda_ssim * (1.0f - ssim);
-            out3[1] = l1;
-            out3[2] = ssim;
+            fin.out3[0] = fin.lambda_l1 * l1 + fin.lambda_ssim * (1.0f - ssim);
+            fin.out3[1] = l1;
+            fin.out3[2] = ssim;
         }
     }
 }
 
-__global__ __launch_bounds__(256) void k_metrics_finish(const float* __restrict__ partial, const float* __restrict__ partial_l1,
-                                                       const float* __restrict__ partial_sq, int n, float inv_count_ssim,
-                                                       float inv_numel, float* __restrict__ out4) {
-    photometric_finish<true>(partial, partial_l1, n, inv_count_ssim, inv_numel, 0.f, 0.f, out4, partial_sq);
+__global__ __launch_bounds__(256) void k_metrics_finish(FinishArgs fin /* out3: the four floats */, const float* __restrict__ partial_sq) {
+    photometric_finish<true>(fin, partial_sq);
 }
 
 // backward: d(mean ssim)/d(img1) * upstream, written through the same strides as img1
@@ -301,7 +299,7 @@ __global__ __launch_bounds__(256) void k_metrics_finish(const float* __restrict_
 // k_alpha_grad for a non-black background; zero for black).
 // kMasked (fused photometric loss of a masked view): p and q are the masked pixels the forward saw, and the finished gradient, L1
 // term included, is multiplied by mask[y,x] (d image_masked / d rgb); where the mask is 0 it is written as 0.0f whatever g is.
-// kBgImage: p is the pixel over its own background colour, as the forward staged it; the alpha slot is written by k_alpha_grad_image.
+// kBgImage: p is the pixel over its own background colour, as the forward staged it; the alpha slot is written by k_alpha_grad<true>.
 // kExposure: p is channel c of the affine image, as the forward staged it, and slot c receives g_c = d loss / d image_c (mask factor
 // included), NOT yet the rgb gradient: k_exposure_grad turns the three into A^T g and writes the alpha slot of every pixel.
 template <bool kMasked, bool kBgImage = false, bool kExposure = false>
@@ -310,14 +308,13 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const f
                                                  const float* __restrict__ dm_dsigma1_sq, const float* __restrict__ dm_dsigma12,
                                                  const float* __restrict__ upstream, float inv_count, float ssim_weight,
                                                  float l1_weight, float* __restrict__ grad, uint32_t gx, uint32_t gy, FinishArgs fin,
-                                                 const float* __restrict__ mask, const float* __restrict__ bg,
-                                                 const float* __restrict__ exposure) {
+                                                 LossOperands ops) {
     __shared__ float s[3][kPatch][kRowStride];
     __shared__ float h[3][kPatch][kSTile];
-    if (fin.out3 && blockIdx.x == 0 && blockIdx.z == 0)   // (block-uniform)
-        photometric_finish<false>(fin.partial, fin.partial_l1, fin.n, fin.inv_count_ssim, fin.inv_count_l1, fin.lambda_l1,
-                                  fin.lambda_ssim, fin.out3);
     const int c = blockIdx.z;
+    float e4[4];
+    exposure_row<kExposure>(ops, c, e4);   // before the finish's stores: a load the compiler can prove unclobbered stays scalar
+    if (fin.out3 && blockIdx.x == 0 && blockIdx.z == 0) photometric_finish<false>(fin);   // (block-uniform)
     int tx, ty;
     xcd_tile(blockIdx.x, gx, gy, &tx, &ty);
     const int x0 = tx * kSTile, y0 = ty * kSTile;
@@ -355,16 +352,10 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const f
     const int x = x0 + ox, y = y0 + oy;
     if (x < v.W && y < v.H) {
         const long long o = (long long)c * v.sc + (long long)y * v.sh + (long long)x * v.sw;
-        float p;
-        if constexpr (kExposure) {
-            const float e4[4] = {exposure[4 * c], exposure[4 * c + 1], exposure[4 * c + 2], exposure[4 * c + 3]};
-            p = load_px_exposure<kBgImage>(img1, v, bg, e4, y, x);
-        } else if constexpr (kBgImage) p = load_px_bg(img1, v, bg, c, y, x);
-        else p = load_px(img1, v, c, y, x);
-        float q = load_px(img2, v2, c, y, x);
+        float p = load_pred<kBgImage, kExposure>(img1, v, ops, e4, c, y, x), q = load_px(img2, v2, c, y, x);
         float mk = 1.0f;
         if constexpr (kMasked) {
-            mk = mask_px(mask, v, y, x);
+            mk = mask_px(ops.mask, v, y, x);
             p *= mk; q *= mk;
         }
         float g = scale * (a + 2.0f * p * b + q * d);
@@ -376,26 +367,20 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(ImgView v, ImgView v2, const f
     }
 }
 
-// d(loss)/d(alpha) = -background * (g_r + g_g + g_b) for rgb_out = rgb + background * (1 - alpha)
-__global__ __launch_bounds__(256) void k_alpha_grad(int pixels, float background, float* __restrict__ rgba_grad) {
+// d(loss)/d(alpha) for rgb_out = rgb + B * (1 - alpha): -background * (g_r + g_g + g_b) over a constant colour, and with kBgImage
+// -(B_r g_r + B_g g_g + B_b g_b), B = bg[pixel] ([H,W,3]; `background` is not used).  The colour gradients of a masked view are
+// already multiplied by the mask.
+template <bool kBgImage>
+__global__ __launch_bounds__(256) void k_alpha_grad(int pixels, float background, const float* __restrict__ bg,
+                                                   float* __restrict__ rgba_grad) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < pixels) {
         float4* g = reinterpret_cast<float4*>(rgba_grad) + i;
         float4 t = *g;
-        t.w = -background * (t.x + t.y + t.z);
-        *g = t;
-    }
-}
-
-// the same for a background image: d(loss)/d(alpha) = -(B_r g_r + B_g g_g + B_b g_b), B = bg[pixel] ([H,W,3]); the colour gradients of
-// a masked view are already multiplied by the mask
-__global__ __launch_bounds__(256) void k_alpha_grad_image(int pixels, const float* __restrict__ bg, float* __restrict__ rgba_grad) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < pixels) {
-        float4* g = reinterpret_cast<float4*>(rgba_grad) + i;
-        float4 t = *g;
-        const float* b = bg + (size_t)i * 3;
-        t.w = -(b[0] * t.x + b[1] * t.y + b[2] * t.z);
+        if constexpr (kBgImage) {
+            const float* b = bg + (size_t)i * 3;
+            t.w = -(b[0] * t.x + b[1] * t.y + b[2] * t.z);
+        } else t.w = -background * (t.x + t.y + t.z);
         *g = t;
     }
 }
@@ -638,6 +623,56 @@ __global__ __launch_bounds__(256) void k_cc_solve(uint32_t rows, const double* _
     }
 }
 
+// The fused loss's instantiation pair for every set of operands, indexed by LossOperands::present().  One more operand is one more
+// flag in loss_pair (and its field and bit in LossOperands).
+struct LossKernels {
+    decltype(&k_ssim_fwd<false>) fwd;
+    decltype(&k_ssim_bwd<false>) bwd;
+};
+template <size_t B>
+constexpr LossKernels loss_pair = {k_ssim_fwd<false, (B & 1) != 0, (B & 2) != 0, (B & 4) != 0>, k_ssim_bwd<(B & 1) != 0, (B & 2) != 0, (B & 4) != 0>};
+template <size_t... B>
+constexpr std::array<LossKernels, sizeof...(B)> loss_table(std::index_sequence<B...>) { return {{loss_pair<B>...}}; }
+
+static LossKernels loss_kernels(const LossOperands& ops) {
+    static constexpr auto table = loss_table(std::make_index_sequence<(1 << LossOperands::kCount)>());
+    return table[ops.present()];
+}
+
+// What every entry point derives from (channels, height, width): the tile grid, the two interleaved views of the fused loss, the
+// means' denominators and where the partial arrays lie (nblocks floats each, 64 floats of slack after the first two).
+struct LossGeometry {
+    int32_t C, H, W;
+    uint32_t gx, gy;
+    dim3 grid;
+    int nblocks;
+    size_t plane;          // elements of one derivative map
+    double count, numel;   // valid-region SSIM values, image elements
+    LossGeometry(int32_t channels, int32_t height, int32_t width)
+        : C(channels), H(height), W(width), gx((width + 15) / 16), gy((height + 15) / 16), grid(gx * gy, 1, channels),
+          nblocks((int)(grid.x * grid.z)), plane((size_t)channels * height * width),
+          count((double)channels * (height - 2 * kHalo) * (width - 2 * kHalo)), numel((double)channels * height * width) {}
+    static bool too_small(int32_t height, int32_t width) { return height <= 2 * kHalo || width <= 2 * kHalo; }
+    ImgView view(int64_t sc, int64_t sh, int64_t sw, long long alpha_offset = -1, float background = 0.0f) const {
+        ImgView v;
+        v.C = C; v.H = H; v.W = W; v.sc = sc; v.sh = sh; v.sw = sw;
+        v.alpha_offset = alpha_offset;
+        v.background = background;
+        return v;
+    }
+    ImgView rgba(float background) const { return view(1, 4 * (int64_t)W, 4, 3, background); }   // the tracer's [H,W,4], interleaved
+    ImgView rgb() const { return view(1, 3 * (int64_t)W, 3); }                                    // ground truth [H,W,3], interleaved
+    float* partial_l1(float* partial) const { return partial + nblocks + 64; }
+    float* partial_sq(float* partial) const { return partial_l1(partial) + nblocks + 64; }
+    FinishArgs finish(float* partial, float lambda_l1, float lambda_ssim, float* out) const {
+        FinishArgs fin;
+        fin.partial = partial; fin.partial_l1 = partial_l1(partial); fin.n = nblocks;
+        fin.inv_count_ssim = (float)(1.0 / count); fin.inv_count_l1 = (float)(1.0 / numel);
+        fin.lambda_l1 = lambda_l1; fin.lambda_ssim = lambda_ssim; fin.out3 = out;
+        return fin;
+    }
+};
+
 }  // namespace gut
 
 extern "C" {
@@ -648,31 +683,18 @@ size_t gut_ssim_workspace_bytes(int32_t channels, int32_t height, int32_t width)
     return maps + tiles + 256;
 }
 
-static gut::ImgView make_view(int32_t C, int32_t H, int32_t W, int64_t sc, int64_t sh, int64_t sw) {
-    gut::ImgView v;
-    v.C = C; v.H = H; v.W = W; v.sc = sc; v.sh = sh; v.sw = sw;
-    v.alpha_offset = -1;
-    v.background = 0.0f;
-    return v;
-}
-
 int gut_ssim_forward(void* stream, int32_t channels, int32_t height, int32_t width, int64_t stride_c, int64_t stride_h,
                      int64_t stride_w, const float* d_img1, const float* d_img2, void* d_workspace, float* d_mean_ssim) {
     if (!d_img1 || !d_img2 || !d_workspace || !d_mean_ssim || channels <= 0) return 1;
-    if (height <= 2 * gut::kHalo || width <= 2 * gut::kHalo) return 1;
+    if (gut::LossGeometry::too_small(height, width)) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t plane = (size_t)channels * height * width;
+    const gut::LossGeometry geo(channels, height, width);
     float* maps = static_cast<float*>(d_workspace);
-    float* partial = maps + 3 * plane;
-    const uint32_t gx = (width + 15) / 16, gy = (height + 15) / 16;
-    const dim3 grid(gx * gy, 1, channels);
-    const gut::ImgView v = make_view(channels, height, width, stride_c, stride_h, stride_w);
-    hipLaunchKernelGGL(gut::k_ssim_fwd<false>, grid, dim3(256), 0, s, v, v, d_img1, d_img2, partial, (float*)nullptr, maps,
-                       maps + plane, maps + 2 * plane, gx, gy, (float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr);
-    const double count = (double)channels * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
-    hipLaunchKernelGGL(gut::k_ssim_finish, dim3(1), dim3(256), 0, s, partial, (int)(grid.x * grid.z), (float)(1.0 / count),
-                       d_mean_ssim);
+    float* partial = maps + 3 * geo.plane;
+    const gut::ImgView v = geo.view(stride_c, stride_h, stride_w);
+    hipLaunchKernelGGL(gut::k_ssim_fwd<false>, geo.grid, dim3(256), 0, s, v, v, d_img1, d_img2, partial, (float*)nullptr, maps,
+                       maps + geo.plane, maps + 2 * geo.plane, geo.gx, geo.gy, (float*)nullptr, gut::LossOperands{});
+    hipLaunchKernelGGL(gut::k_ssim_finish, dim3(1), dim3(256), 0, s, partial, geo.nblocks, (float)(1.0 / geo.count), d_mean_ssim);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -681,15 +703,11 @@ int gut_ssim_backward(void* stream, int32_t channels, int32_t height, int32_t wi
                       const float* d_upstream /* 1 float */, float* d_grad_img1) {
     if (!d_img1 || !d_img2 || !d_workspace || !d_upstream || !d_grad_img1) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t plane = (size_t)channels * height * width;
+    const gut::LossGeometry geo(channels, height, width);
     const float* maps = static_cast<const float*>(d_workspace);
-    const uint32_t gx = (width + 15) / 16, gy = (height + 15) / 16;
-    const dim3 grid(gx * gy, 1, channels);
-    const gut::ImgView v = make_view(channels, height, width, stride_c, stride_h, stride_w);
-    const double count = (double)channels * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
-    hipLaunchKernelGGL(gut::k_ssim_bwd<false>, grid, dim3(256), 0, s, v, v, d_img1, d_img2, maps, maps + plane, maps + 2 * plane, d_upstream,
-                       (float)(1.0 / count), 0.0f, 0.0f, d_grad_img1, gx, gy, gut::FinishArgs(), (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr);
+    const gut::ImgView v = geo.view(stride_c, stride_h, stride_w);
+    hipLaunchKernelGGL(gut::k_ssim_bwd<false>, geo.grid, dim3(256), 0, s, v, v, d_img1, d_img2, maps, maps + geo.plane, maps + 2 * geo.plane,
+                       d_upstream, (float)(1.0 / geo.count), 0.0f, 0.0f, d_grad_img1, geo.gx, geo.gy, gut::FinishArgs(), gut::LossOperands{});
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -703,85 +721,62 @@ size_t gut_photometric_exposure_workspace_bytes(int32_t height, int32_t width) {
     return gut_photometric_workspace_bytes(height, width) + rows * 12 * sizeof(float) + 256;
 }
 
-// d_mask == nullptr: the unmasked instantiations, the very kernels this launched before there was a mask; d_bg == nullptr: the
-// constant-background instantiations, likewise (`background` is not used with a plane); d_exposure == nullptr: the instantiations
-// without an exposure, likewise.  With d_exposure the workspace is one of gut_photometric_exposure_workspace_bytes, the per-pixel pass
-// is k_exposure_grad for every background, and d_exposure_grad (may be nullptr) receives the 12 sums.
-static int photometric_loss_launch(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
-                                   const float* d_mask, const float* d_bg, float background, float lambda_l1, float lambda_ssim,
-                                   void* d_workspace, float* d_loss3, float* d_rgba_grad, const float* d_exposure = nullptr,
-                                   float* d_exposure_grad = nullptr) {
-    if (!d_rgba || !d_gt_rgb || !d_workspace || !d_loss3 || !d_rgba_grad) return 1;
-    if (height <= 2 * gut::kHalo || width <= 2 * gut::kHalo) return 1;
+// The fused loss of one view.  The operands the descriptor brings choose the instantiation pair (loss_kernels) and the post-pass:
+// with an exposure k_exposure_grad for every background (the channels mix) and, if the 12 sums are wanted, k_exposure_finish on the
+// rows of partials, which follow everything gut_photometric_workspace_bytes covers (partial_l1 ends exactly there); without one
+// k_alpha_grad, unless the background is constant black.  The loss value is finished in the backward (FinishArgs).
+int gut_photometric_loss_run(void* stream, int32_t height, int32_t width, const GutPhotometricLoss* d) {
+    static_assert(sizeof(GutPhotometricLoss) == 88, "GutPhotometricLoss: nine pointers, three floats (include/gut_hip.h)");
+    if (!d || !d->d_rgba || !d->d_gt_rgb || !d->d_workspace || !d->d_loss3 || !d->d_rgba_grad) return 1;
+    if (d->d_exposure_grad12 && !d->d_exposure12) return 1;
+    if (gut::LossGeometry::too_small(height, width)) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t plane = (size_t)3 * height * width;
-    float* maps = static_cast<float*>(d_workspace);
-    float* partial = maps + 3 * plane;
-    const uint32_t gx = (width + 15) / 16, gy = (height + 15) / 16;
-    const dim3 grid(gx * gy, 1, 3);
-    const int nblocks = (int)(grid.x * grid.z);
-    float* partial_l1 = partial + nblocks + 64;
-    gut::ImgView v = make_view(3, height, width, 1, 4 * (int64_t)width, 4);   // rgba, interleaved
-    v.alpha_offset = 3;
-    v.background = d_bg ? 0.0f : background;
-    const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
+    const gut::LossGeometry geo(3, height, width);
+    const gut::LossOperands ops{d->d_mask, d->d_background, d->d_exposure12};
+    const float background = ops.bg ? 0.0f : d->background;   // (not used with a plane)
+    float* maps = static_cast<float*>(d->d_workspace);
+    float* partial = maps + 3 * geo.plane;
+    const gut::ImgView v = geo.rgba(background), g = geo.rgb();
+    const gut::LossKernels k = gut::loss_kernels(ops);
+    hipLaunchKernelGGL(k.fwd, geo.grid, dim3(256), 0, s, v, g, d->d_rgba, d->d_gt_rgb, partial, geo.partial_l1(partial), maps,
+                       maps + geo.plane, maps + 2 * geo.plane, geo.gx, geo.gy, (float*)nullptr, ops);
     const float* no_upstream = nullptr;   // the fused loss has no upstream gradient: the weights below
-    auto fwd = d_bg ? (d_mask ? gut::k_ssim_fwd<false, true, true> : gut::k_ssim_fwd<false, false, true>)
-                    : (d_mask ? gut::k_ssim_fwd<false, true> : gut::k_ssim_fwd<false>);
-    if (d_exposure)
-        fwd = d_bg ? (d_mask ? gut::k_ssim_fwd<false, true, true, true> : gut::k_ssim_fwd<false, false, true, true>)
-                   : (d_mask ? gut::k_ssim_fwd<false, true, false, true> : gut::k_ssim_fwd<false, false, false, true>);
-    hipLaunchKernelGGL(fwd, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, maps, maps + plane, maps + 2 * plane, gx, gy,
-                       (float*)nullptr, d_mask, d_bg, d_exposure);
-    const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
-    const double numel = 3.0 * height * width;
-    gut::FinishArgs fin;
-    fin.partial = partial; fin.partial_l1 = partial_l1; fin.n = nblocks;
-    fin.inv_count_ssim = (float)(1.0 / count); fin.inv_count_l1 = (float)(1.0 / numel);
-    fin.lambda_l1 = lambda_l1; fin.lambda_ssim = lambda_ssim; fin.out3 = d_loss3;
-    auto bwd = d_bg ? (d_mask ? gut::k_ssim_bwd<true, true> : gut::k_ssim_bwd<false, true>)
-                    : (d_mask ? gut::k_ssim_bwd<true> : gut::k_ssim_bwd<false>);
-    if (d_exposure)
-        bwd = d_bg ? (d_mask ? gut::k_ssim_bwd<true, true, true> : gut::k_ssim_bwd<false, true, true>)
-                   : (d_mask ? gut::k_ssim_bwd<true, false, true> : gut::k_ssim_bwd<false, false, true>);
-    hipLaunchKernelGGL(bwd, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, maps, maps + plane, maps + 2 * plane, no_upstream,
-                       (float)(1.0 / count), -lambda_ssim, (float)(lambda_l1 / numel), d_rgba_grad, gx, gy, fin, d_mask, d_bg, d_exposure);
+    hipLaunchKernelGGL(k.bwd, geo.grid, dim3(256), 0, s, v, g, d->d_rgba, d->d_gt_rgb, maps, maps + geo.plane, maps + 2 * geo.plane, no_upstream,
+                       (float)(1.0 / geo.count), -d->lambda_ssim, (float)(d->lambda_l1 / geo.numel), d->d_rgba_grad, geo.gx, geo.gy,
+                       geo.finish(partial, d->lambda_l1, d->lambda_ssim, d->d_loss3), ops);
     const int pixels = height * width;
-    if (d_exposure) {
-        // the partials follow everything gut_photometric_workspace_bytes covers (partial_l1 ends exactly there)
-        float* partial_e = d_exposure_grad ? partial_l1 + nblocks : nullptr;
+    if (ops.exposure) {
+        float* partial_e = d->d_exposure_grad12 ? geo.partial_l1(partial) + geo.nblocks : nullptr;
         const uint32_t rows = ((uint32_t)pixels + 256 * gut::kExpPixels - 1) / (256 * gut::kExpPixels);
-        auto px = d_bg ? gut::k_exposure_grad<true> : gut::k_exposure_grad<false>;
-        hipLaunchKernelGGL(px, dim3(rows), dim3(256), 0, s, (uint32_t)pixels, d_rgba, d_bg, v.background, d_mask, d_exposure, d_rgba_grad,
-                           partial_e);
-        if (d_exposure_grad)
-            hipLaunchKernelGGL(gut::k_exposure_finish, dim3(1), dim3(256), 0, s, rows, partial_e, d_exposure_grad);
-    } else if (d_bg)
-        hipLaunchKernelGGL(gut::k_alpha_grad_image, dim3((pixels + 255) / 256), dim3(256), 0, s, pixels, d_bg, d_rgba_grad);
-    else if (background != 0.0f)
-        hipLaunchKernelGGL(gut::k_alpha_grad, dim3((pixels + 255) / 256), dim3(256), 0, s, pixels, background, d_rgba_grad);
+        hipLaunchKernelGGL(ops.bg ? gut::k_exposure_grad<true> : gut::k_exposure_grad<false>, dim3(rows), dim3(256), 0, s, (uint32_t)pixels,
+                           d->d_rgba, ops.bg, background, ops.mask, ops.exposure, d->d_rgba_grad, partial_e);
+        if (partial_e) hipLaunchKernelGGL(gut::k_exposure_finish, dim3(1), dim3(256), 0, s, rows, partial_e, d->d_exposure_grad12);
+    } else if (ops.bg || background != 0.0f)
+        hipLaunchKernelGGL(ops.bg ? gut::k_alpha_grad<true> : gut::k_alpha_grad<false>, dim3((pixels + 255) / 256), dim3(256), 0, s, pixels,
+                           background, ops.bg, d->d_rgba_grad);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
+// The four positional forms: each fills the descriptor with what it has.
 int gut_photometric_loss(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
                          float lambda_l1, float lambda_ssim, void* d_workspace, float* d_loss3, float* d_rgba_grad) {
-    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, nullptr, nullptr, background, lambda_l1, lambda_ssim,
-                                   d_workspace, d_loss3, d_rgba_grad);
+    const GutPhotometricLoss d{d_rgba, d_gt_rgb, nullptr, nullptr, nullptr, d_workspace, d_loss3, d_rgba_grad, nullptr, background, lambda_l1, lambda_ssim};
+    return gut_photometric_loss_run(stream, height, width, &d);
 }
 
 int gut_photometric_loss_masked(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
                                 const float* d_mask, float background, float lambda_l1, float lambda_ssim, void* d_workspace,
                                 float* d_loss3, float* d_rgba_grad) {
-    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, d_mask, nullptr, background, lambda_l1, lambda_ssim,
-                                   d_workspace, d_loss3, d_rgba_grad);
+    const GutPhotometricLoss d{d_rgba, d_gt_rgb, d_mask, nullptr, nullptr, d_workspace, d_loss3, d_rgba_grad, nullptr, background, lambda_l1, lambda_ssim};
+    return gut_photometric_loss_run(stream, height, width, &d);
 }
 
 int gut_photometric_loss_background(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
                                     const float* d_mask, const float* d_background, float lambda_l1, float lambda_ssim,
                                     void* d_workspace, float* d_loss3, float* d_rgba_grad) {
     if (!d_background) return 1;
-    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, d_mask, d_background, 0.0f, lambda_l1, lambda_ssim,
-                                   d_workspace, d_loss3, d_rgba_grad);
+    const GutPhotometricLoss d{d_rgba, d_gt_rgb, d_mask, d_background, nullptr, d_workspace, d_loss3, d_rgba_grad, nullptr, 0.0f, lambda_l1, lambda_ssim};
+    return gut_photometric_loss_run(stream, height, width, &d);
 }
 
 int gut_photometric_loss_exposure(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
@@ -789,8 +784,9 @@ int gut_photometric_loss_exposure(void* stream, int32_t height, int32_t width, c
                                   float lambda_l1, float lambda_ssim, void* d_workspace, float* d_loss3, float* d_rgba_grad,
                                   float* d_exposure_grad12) {
     if (!d_exposure12) return 1;
-    return photometric_loss_launch(stream, height, width, d_rgba, d_gt_rgb, d_mask, d_background, background, lambda_l1, lambda_ssim,
-                                   d_workspace, d_loss3, d_rgba_grad, d_exposure12, d_exposure_grad12);
+    const GutPhotometricLoss d{d_rgba, d_gt_rgb, d_mask, d_background, d_exposure12, d_workspace, d_loss3, d_rgba_grad, d_exposure_grad12,
+                               background, lambda_l1, lambda_ssim};
+    return gut_photometric_loss_run(stream, height, width, &d);
 }
 
 int gut_exposure_adam_step(void* stream, const float* d_grad12, float* d_exposure12, float* d_m12, float* d_v12, int32_t* d_count,
@@ -807,29 +803,27 @@ size_t gut_image_metrics_workspace_bytes(int32_t height, int32_t width) {
     return 3 * (blocks + 64) * sizeof(float) + 256;
 }
 
+// The metrics forward and its finish: the three partial arrays lie at the start of the workspace.  d_exposure: null, or the E the
+// image is mapped through first (the kExposure instantiation).
+static int metrics_forward_finish(hipStream_t s, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
+                                  const float* d_exposure, void* d_workspace, float* d_out4) {
+    const gut::LossGeometry geo(3, height, width);
+    float* partial = static_cast<float*>(d_workspace);
+    gut::LossOperands ops;
+    ops.exposure = d_exposure;
+    hipLaunchKernelGGL((d_exposure ? gut::k_ssim_fwd<true, false, false, true> : gut::k_ssim_fwd<true>), geo.grid, dim3(256), 0, s,
+                       geo.rgba(background), geo.rgb(), d_rgba, d_gt_rgb, partial, geo.partial_l1(partial), (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr, geo.gx, geo.gy, geo.partial_sq(partial), ops);
+    hipLaunchKernelGGL(gut::k_metrics_finish, dim3(1), dim3(256), 0, s, geo.finish(partial, 0.f, 0.f, d_out4),
+                       (const float*)geo.partial_sq(partial));
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
 int gut_image_metrics(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
                       void* d_workspace, float* d_out4) {
     if (!d_rgba || !d_gt_rgb || !d_workspace || !d_out4) return 1;
-    if (height <= 2 * gut::kHalo || width <= 2 * gut::kHalo) return 1;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t gx = (width + 15) / 16, gy = (height + 15) / 16;
-    const dim3 grid(gx * gy, 1, 3);
-    const int nblocks = (int)(grid.x * grid.z);
-    float* partial = static_cast<float*>(d_workspace);
-    float* partial_l1 = partial + nblocks + 64;
-    float* partial_sq = partial_l1 + nblocks + 64;
-    gut::ImgView v = make_view(3, height, width, 1, 4 * (int64_t)width, 4);   // rgba, interleaved
-    v.alpha_offset = 3;
-    v.background = background;
-    const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
-    hipLaunchKernelGGL(gut::k_ssim_fwd<true>, grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1, (float*)nullptr,
-                       (float*)nullptr, (float*)nullptr, gx, gy, partial_sq, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr);
-    const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
-    const double numel = 3.0 * height * width;
-    hipLaunchKernelGGL(gut::k_metrics_finish, dim3(1), dim3(256), 0, s, partial, partial_l1, partial_sq, nblocks,
-                       (float)(1.0 / count), (float)(1.0 / numel), d_out4);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    if (gut::LossGeometry::too_small(height, width)) return 1;
+    return metrics_forward_finish(static_cast<hipStream_t>(stream), height, width, d_rgba, d_gt_rgb, background, nullptr, d_workspace, d_out4);
 }
 
 // the workspace of gut_image_metrics (rounded up to 16 bytes), then one row of 22 doubles per 1024 pixels, then the fitted E (12 floats)
@@ -848,16 +842,10 @@ size_t gut_image_metrics_cc_workspace_bytes(int32_t height, int32_t width) {
 int gut_image_metrics_cc(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, float background,
                          float ridge, void* d_workspace, float* d_out4, float* d_exposure12) {
     if (!d_rgba || !d_gt_rgb || !d_workspace || !d_out4) return 1;
-    if (height <= 2 * gut::kHalo || width <= 2 * gut::kHalo) return 1;
+    if (gut::LossGeometry::too_small(height, width)) return 1;
     if (!(ridge > 0.0f) || !std::isfinite(ridge)) return 1;
     if (reinterpret_cast<uintptr_t>(d_workspace) % 8 != 0) return 1;   // (the rows of doubles)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t gx = (width + 15) / 16, gy = (height + 15) / 16;
-    const dim3 grid(gx * gy, 1, 3);
-    const int nblocks = (int)(grid.x * grid.z);
-    float* partial = static_cast<float*>(d_workspace);
-    float* partial_l1 = partial + nblocks + 64;
-    float* partial_sq = partial_l1 + nblocks + 64;
     const uint32_t rows = (uint32_t)cc_rows(height, width);
     double* moments = reinterpret_cast<double*>(static_cast<char*>(d_workspace) + cc_moments_offset(height, width));
     float* fitted = reinterpret_cast<float*>(moments + (size_t)rows * gut::kCcTerms);
@@ -865,18 +853,7 @@ int gut_image_metrics_cc(void* stream, int32_t height, int32_t width, const floa
     hipLaunchKernelGGL(gut::k_cc_moments, dim3(rows), dim3(256), 0, s, pixels, d_rgba, d_gt_rgb, background, moments);
     hipLaunchKernelGGL(gut::k_cc_solve, dim3(1), dim3(256), 0, s, rows, (const double*)moments, (double)ridge * (double)pixels, fitted,
                        d_exposure12);
-    gut::ImgView v = make_view(3, height, width, 1, 4 * (int64_t)width, 4);   // rgba, interleaved
-    v.alpha_offset = 3;
-    v.background = background;
-    const gut::ImgView g = make_view(3, height, width, 1, 3 * (int64_t)width, 3);  // ground truth, interleaved rgb
-    hipLaunchKernelGGL((gut::k_ssim_fwd<true, false, false, true>), grid, dim3(256), 0, s, v, g, d_rgba, d_gt_rgb, partial, partial_l1,
-                       (float*)nullptr, (float*)nullptr, (float*)nullptr, gx, gy, partial_sq, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)fitted);
-    const double count = 3.0 * (height - 2 * gut::kHalo) * (width - 2 * gut::kHalo);
-    const double numel = 3.0 * height * width;
-    hipLaunchKernelGGL(gut::k_metrics_finish, dim3(1), dim3(256), 0, s, partial, partial_l1, partial_sq, nblocks,
-                       (float)(1.0 / count), (float)(1.0 / numel), d_out4);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    return metrics_forward_finish(s, height, width, d_rgba, d_gt_rgb, background, fitted, d_workspace, d_out4);
 }
 
 }  // extern "C"

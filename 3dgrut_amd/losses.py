@@ -88,21 +88,34 @@ def loss_weights(loss_conf):
     return dict(lambda_l1=weight("l1"), lambda_ssim=weight("ssim"), lambda_opacity=weight("opacity"), lambda_scale=weight("scale"))
 
 
+def _constant_background(background, who, forms="'black', 'white' or a number"):
+    """A constant background given as "black", "white" or a number, as the number."""
+    bg = {"black": 0.0, "white": 1.0}.get(background, background)
+    if isinstance(bg, str):
+        raise ValueError(f"{who}: background must be {forms}, got {background!r}")
+    return bg
+
+
+def _view_images(rgba, gt_rgb, who):
+    """The images of one view as every GPU entry point here takes them: a leading 1 squeezed, rgba [H,W,4] against gt_rgb [H,W,3],
+    both float32 on one GPU."""
+    rgba = rgba.reshape(rgba.shape[-3:]) if rgba.dim() == 4 and rgba.shape[0] == 1 else rgba
+    gt_rgb = gt_rgb.reshape(gt_rgb.shape[-3:]) if gt_rgb.dim() == 4 and gt_rgb.shape[0] == 1 else gt_rgb
+    if rgba.dim() != 3 or rgba.shape[2] != 4 or tuple(gt_rgb.shape) != (rgba.shape[0], rgba.shape[1], 3):
+        raise RuntimeError(f"[{who}] expected rgba [H,W,4] and gt [H,W,3], got {tuple(rgba.shape)} and {tuple(gt_rgb.shape)}")
+    if not rgba.is_cuda or rgba.dtype != torch.float32 or gt_rgb.dtype != torch.float32 or gt_rgb.device != rgba.device:
+        raise RuntimeError(f"[{who}] expected float32 GPU tensors on one device (there is no CPU path)")
+    return rgba, gt_rgb
+
+
 def image_metrics(rgba, gt_rgb, background="black", out=None):
     """Evaluation metrics of one view on the GPU (gut_image_metrics, csrc/gut_ssim.hip): a float32 device tensor [4] = (MSE, PSNR,
     SSIM, L1) of image = rgb + background * (1 - alpha) against gt_rgb, unclamped, as the reference scores outputs["pred_rgb"]
     (render.py:137-285; PSNR for a data range of 1, SSIM the valid-region mean of the training loss).  rgba: [H,W,4] (or [1,H,W,4]),
     gt_rgb: [H,W,3] (or [1,H,W,3]), both float32 on the GPU; background: "black", "white" or 0.0 / 1.0.  out: a float32 device
     tensor of 4 contiguous elements to write into (e.g. row i of an evaluation pass's [V,4] tensor); nothing is read back."""
-    bg = {"black": 0.0, "white": 1.0}.get(background, background)
-    if isinstance(bg, str):
-        raise ValueError(f"image_metrics: background must be 'black', 'white' or a number, got {background!r}")
-    rgba = rgba.reshape(rgba.shape[-3:]) if rgba.dim() == 4 and rgba.shape[0] == 1 else rgba
-    gt_rgb = gt_rgb.reshape(gt_rgb.shape[-3:]) if gt_rgb.dim() == 4 and gt_rgb.shape[0] == 1 else gt_rgb
-    if rgba.dim() != 3 or rgba.shape[2] != 4 or tuple(gt_rgb.shape) != (rgba.shape[0], rgba.shape[1], 3):
-        raise RuntimeError(f"[image_metrics] expected rgba [H,W,4] and gt [H,W,3], got {tuple(rgba.shape)} and {tuple(gt_rgb.shape)}")
-    if not rgba.is_cuda or rgba.dtype != torch.float32 or gt_rgb.dtype != torch.float32 or gt_rgb.device != rgba.device:
-        raise RuntimeError("[image_metrics] expected float32 GPU tensors on one device (there is no CPU path)")
+    bg = _constant_background(background, "image_metrics")
+    rgba, gt_rgb = _view_images(rgba, gt_rgb, "image_metrics")
     rgba, gt_rgb = rgba.contiguous(), gt_rgb.contiguous()
     if out is None:
         out = torch.empty((4,), dtype=torch.float32, device=rgba.device)
@@ -148,19 +161,11 @@ def image_metrics_colour_corrected(rgba, gt_rgb, background="black", ridge=1e-6,
     image_metrics; ridge: finite and > 0.  out: a contiguous float32 device tensor of 4 elements to write into; exposure_out: one of
     12 (a [12] or [3,4] tensor, e.g. row i of an evaluation pass's [V,12]) that receives E.  Returns (out, E [3,4]), both on the
     device; nothing is read back."""
-    bg = {"black": 0.0, "white": 1.0}.get(background, background)
-    if isinstance(bg, str):
-        raise ValueError(f"image_metrics_colour_corrected: background must be 'black', 'white' or a number, got {background!r}")
+    bg = _constant_background(background, "image_metrics_colour_corrected")
     ridge = float(ridge)
     if not (0.0 < ridge < float("inf")):
         raise ValueError(f"image_metrics_colour_corrected: ridge must be finite and > 0, got {ridge!r}")
-    rgba = rgba.reshape(rgba.shape[-3:]) if rgba.dim() == 4 and rgba.shape[0] == 1 else rgba
-    gt_rgb = gt_rgb.reshape(gt_rgb.shape[-3:]) if gt_rgb.dim() == 4 and gt_rgb.shape[0] == 1 else gt_rgb
-    if rgba.dim() != 3 or rgba.shape[2] != 4 or tuple(gt_rgb.shape) != (rgba.shape[0], rgba.shape[1], 3):
-        raise RuntimeError(f"[image_metrics_colour_corrected] expected rgba [H,W,4] and gt [H,W,3], got {tuple(rgba.shape)} and "
-                           f"{tuple(gt_rgb.shape)}")
-    if not rgba.is_cuda or rgba.dtype != torch.float32 or gt_rgb.dtype != torch.float32 or gt_rgb.device != rgba.device:
-        raise RuntimeError("[image_metrics_colour_corrected] expected float32 GPU tensors on one device (there is no CPU path)")
+    rgba, gt_rgb = _view_images(rgba, gt_rgb, "image_metrics_colour_corrected")
     rgba, gt_rgb = rgba.contiguous(), gt_rgb.contiguous()
     if out is None:
         out = torch.empty((4,), dtype=torch.float32, device=rgba.device)
@@ -246,30 +251,22 @@ def _exposure12(exposure, device):
 
 def fused_photometric_loss(rgba, gt_rgb, background, lambda_l1=0.8, lambda_ssim=0.2, mask=None, workspace=None, exposure=None,
                            exposure_grad=True):
-    """The train step's loss and its gradient without autograd (gut_photometric_loss / gut_photometric_loss_masked /
-    gut_photometric_loss_background, csrc/gut_ssim.hip): image = rgb + background * (1 - alpha), loss = lambda_l1 * L1 +
-    lambda_ssim * (1 - SSIM) against gt_rgb.
-    rgba [H,W,4] (or [1,H,W,4]) and gt_rgb [H,W,3] (or [1,H,W,3]): contiguous float32 on one GPU; background: "black", "white"
-    or 0.0 / 1.0, or a tensor — [H,W,3] / [1,H,W,3], every pixel over its own colour (the reference's `random` background,
-    model/background.py:83-89, or an environment image), or [3], one RGB colour; any dtype or device.
-    mask: None, or [H,W] / [H,W,1] / [1,H,W,1] of any dtype — image and gt_rgb are both multiplied by it
-    (trainer.py:397-404), the means keep their full-image counts, and a pixel whose mask is 0 gets a gradient of exactly zero.
-    workspace: a float32 device tensor of at least gut_photometric_workspace_bytes(H, W) bytes to reuse, or None.
-    Returns (loss3, rgba_grad): a float32 device tensor (loss, L1, SSIM) and d(loss)/d(rgba) [H,W,4].
+    """The train step's loss and its gradient without autograd (gut_photometric_loss_run, csrc/gut_ssim.hip):
+    loss = lambda_l1 * L1 + lambda_ssim * (1 - SSIM) of image = mask * (A (rgb + B * (1 - alpha)) + b) against mask * gt_rgb.
+    rgba [H,W,4] (or [1,H,W,4]) and gt_rgb [H,W,3] (or [1,H,W,3]): contiguous float32 on one GPU.  The operands:
+    background (B): "black", "white" or 0.0 / 1.0, or a tensor of any dtype or device — [H,W,3] / [1,H,W,3], every pixel over its own
+    colour (the reference's `random` background, model/background.py:83-89, or an environment image), or [3], one RGB colour.
+    mask: None, or [H,W] / [H,W,1] / [1,H,W,1] of any dtype (trainer.py:397-404); the means keep their full-image counts, and a
+    pixel whose mask is 0 gets a gradient of exactly zero.
     exposure: None, or the view's affine colour transform E = [A | b] as a float32 [12] / [3,4] tensor on the images' device
-    (gut_photometric_loss_exposure): the compared image is A image + b (before the mask), the workspace is one of
-    gut_photometric_exposure_workspace_bytes(H, W), and the call returns (loss3, rgba_grad, exposure_grad12) with d(loss)/dE laid
-    out like E — None with exposure_grad=False, which applies E and reduces nothing."""
+    (DESIGN.md §10), applied before the mask.
+    workspace: a float32 device tensor to reuse, or None: at least gut_photometric_workspace_bytes(H, W) bytes, with an exposure
+    gut_photometric_exposure_workspace_bytes(H, W).
+    Returns (loss3, rgba_grad): a float32 device tensor (loss, L1, SSIM) and d(loss)/d(rgba) [H,W,4]; with an exposure (loss3,
+    rgba_grad, exposure_grad12), d(loss)/dE laid out like E — None with exposure_grad=False, which applies E and reduces nothing."""
     plane = isinstance(background, torch.Tensor)
-    bg = background if plane else {"black": 0.0, "white": 1.0}.get(background, background)
-    if isinstance(bg, str):
-        raise ValueError(f"fused_photometric_loss: background must be 'black', 'white', a number or a tensor, got {background!r}")
-    rgba = rgba.reshape(rgba.shape[-3:]) if rgba.dim() == 4 and rgba.shape[0] == 1 else rgba
-    gt_rgb = gt_rgb.reshape(gt_rgb.shape[-3:]) if gt_rgb.dim() == 4 and gt_rgb.shape[0] == 1 else gt_rgb
-    if rgba.dim() != 3 or rgba.shape[2] != 4 or tuple(gt_rgb.shape) != (rgba.shape[0], rgba.shape[1], 3):
-        raise RuntimeError(f"[fused_photometric_loss] expected rgba [H,W,4] and gt [H,W,3], got {tuple(rgba.shape)} and {tuple(gt_rgb.shape)}")
-    if not rgba.is_cuda or rgba.dtype != torch.float32 or gt_rgb.dtype != torch.float32 or gt_rgb.device != rgba.device:
-        raise RuntimeError("[fused_photometric_loss] expected float32 GPU tensors on one device (there is no CPU path)")
+    bg = background if plane else _constant_background(background, "fused_photometric_loss", "'black', 'white', a number or a tensor")
+    rgba, gt_rgb = _view_images(rgba, gt_rgb, "fused_photometric_loss")
     if not rgba.is_contiguous() or not gt_rgb.is_contiguous():
         raise RuntimeError("[fused_photometric_loss] expected contiguous tensors")
     lib = _capi.load()
@@ -292,33 +289,21 @@ def fused_photometric_loss(rgba, gt_rgb, background, lambda_l1=0.8, lambda_ssim=
 
 
 def _photometric_loss_call(lib, H, W, rgba, gt_rgb, bg, lambda_l1, lambda_ssim, mask, workspace, exposure=None, exposure_grad=None):
-    """The two C calls behind fused_photometric_loss, nothing checked: contiguous float32 device tensors (gt_rgb with or without a
-    leading 1), bg a float or a float32 [H,W,3] device plane, mask a float32 [H,W] plane or None, a workspace of
-    gut_photometric_workspace_bytes(H, W), the images' device current.
-    NativeTrainStep calls this directly every step, on buffers it sized itself.
-    exposure: None, or a contiguous float32 [12] device tensor — then the one call gut_photometric_loss_exposure, on a workspace of
-    gut_photometric_exposure_workspace_bytes(H, W); exposure_grad: the [12] device tensor that receives d(loss)/dE, or None."""
+    """The one C call behind fused_photometric_loss (gut_photometric_loss_run), nothing checked: contiguous float32 device tensors
+    (gt_rgb with or without a leading 1), the images' device current.  NativeTrainStep calls this directly every step, on buffers
+    it sized itself.  The operands: bg a float or a float32 [H,W,3] device plane; mask a float32 [H,W] plane or None; exposure a
+    contiguous float32 [12] device tensor or None, and exposure_grad the [12] device tensor that receives d(loss)/dE, or None.
+    workspace: gut_photometric_workspace_bytes(H, W), with an exposure gut_photometric_exposure_workspace_bytes(H, W)."""
     # three fresh floats every call (the caching allocator, no kernel): callers return views of them
     loss3 = torch.empty((3,), dtype=torch.float32, device=rgba.device)
     rgba_grad = torch.empty_like(rgba)
     stream = torch.cuda.current_stream(rgba.device).cuda_stream
     plane = isinstance(bg, torch.Tensor)
-    if exposure is not None:
-        rc = lib.gut_photometric_loss_exposure(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(),
-                                               None if mask is None else mask.data_ptr(), bg.data_ptr() if plane else None,
-                                               0.0 if plane else bg, exposure.data_ptr(), lambda_l1, lambda_ssim, workspace.data_ptr(),
-                                               loss3.data_ptr(), rgba_grad.data_ptr(),
-                                               None if exposure_grad is None else exposure_grad.data_ptr())
-    elif plane:
-        rc = lib.gut_photometric_loss_background(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(),
-                                                 None if mask is None else mask.data_ptr(), bg.data_ptr(), lambda_l1, lambda_ssim,
-                                                 workspace.data_ptr(), loss3.data_ptr(), rgba_grad.data_ptr())
-    elif mask is None:
-        rc = lib.gut_photometric_loss(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(), bg, lambda_l1, lambda_ssim,
-                                      workspace.data_ptr(), loss3.data_ptr(), rgba_grad.data_ptr())
-    else:
-        rc = lib.gut_photometric_loss_masked(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(), mask.data_ptr(), bg,
-                                             lambda_l1, lambda_ssim, workspace.data_ptr(), loss3.data_ptr(), rgba_grad.data_ptr())
+    ptr = lambda t: None if t is None else t.data_ptr()
+    desc = _capi.GutPhotometricLoss(rgba.data_ptr(), gt_rgb.data_ptr(), ptr(mask), bg.data_ptr() if plane else None, ptr(exposure),
+                                    workspace.data_ptr(), loss3.data_ptr(), rgba_grad.data_ptr(), ptr(exposure_grad),
+                                    0.0 if plane else bg, lambda_l1, lambda_ssim)
+    rc = lib.gut_photometric_loss_run(C.c_void_p(stream), H, W, C.byref(desc))
     if rc:
         raise RuntimeError(f"[3dgut] photometric_loss failed ({rc}): " + ("a null pointer, or an image of 10x10 pixels or less"
                                                                          if rc == 1 else "the kernel launch failed"))

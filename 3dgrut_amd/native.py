@@ -717,7 +717,7 @@ class NativeTrainStep:
         exposure = getattr(batch, "exposure", None) if self._exposure_on else None
         if self.fused_loss and m.background_color in ("black", "white", "random") and gt.dtype == torch.float32 and gt.is_contiguous() \
                 and gt.numel() == rgba.shape[0] * rgba.shape[1] * 3:
-            # loss value and d(loss)/d(rgba) in two HIP launches (csrc/gut_ssim.hip: gut_photometric_loss[_masked | _background]; with an exposure gut_photometric_loss_exposure)
+            # loss value and d(loss)/d(rgba) in two HIP launches plus the per-pixel post-pass (csrc/gut_ssim.hip: gut_photometric_loss_run)
             H, W = rgba.shape[0], rgba.shape[1]
             need = self._lib.gut_photometric_workspace_bytes(H, W) if exposure is None \
                 else self._lib.gut_photometric_exposure_workspace_bytes(H, W)

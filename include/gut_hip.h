@@ -44,7 +44,8 @@ extern "C" {
  * untouched; gut_set_pose_gradient and gut_pose_adam_step, new entry points: while it is not set, every gut_trace_bwd* queues what it queued before;
  * gut_photometric_exposure_workspace_bytes, gut_photometric_loss_exposure and gut_exposure_adam_step, new entry points next to the
  * other forms of the fused loss, which launch what they launched before; gut_image_metrics_cc_workspace_bytes and gut_image_metrics_cc,
- * new entry points next to gut_image_metrics, which launches what it launched before). */
+ * new entry points next to gut_image_metrics, which launches what it launched before; GutPhotometricLoss and gut_photometric_loss_run,
+ * the descriptor form of the fused loss: the four positional forms keep their signatures and call it). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -659,6 +660,29 @@ int gut_photometric_loss_exposure(void* stream, int32_t height, int32_t width, c
                                   float* d_exposure_grad12   /* NULL: E is applied, nothing is reduced */);
 int gut_exposure_adam_step(void* stream, const float* d_grad12, float* d_exposure12, float* d_m12, float* d_v12,
                            int32_t* d_count, float lr, float beta1, float beta2, float eps);
+
+/* ---- The fused loss by descriptor: the form new callers should use ----
+ * One struct names everything the four positional forms above take; gut_photometric_loss_run is the function all four call, so
+ * values, launches, workspace and stream behaviour are theirs.  An optional pointer that is NULL means "that operand is absent":
+ *     d_mask NULL            no mask                                   (gut_photometric_loss_masked otherwise)
+ *     d_background NULL      the constant `background`; non-NULL: the [H,W,3] plane, and `background` is not used
+ *     d_exposure12 NULL      no exposure; non-NULL: d_workspace is one of gut_photometric_exposure_workspace_bytes (else
+ *                            gut_photometric_workspace_bytes) and d_exposure_grad12 (may be NULL) receives d(loss)/dE
+ * Returns 1 — on the host, nothing is launched — for a NULL descriptor, a NULL d_rgba, d_gt_rgb, d_workspace, d_loss3 or d_rgba_grad,
+ * d_exposure_grad12 without d_exposure12, or height / width <= 10; 2 for a launch failure.  88 bytes: nine pointers, three floats. */
+typedef struct GutPhotometricLoss {
+    const float* d_rgba;          /* [H,W,4] */
+    const float* d_gt_rgb;        /* [H,W,3] */
+    const float* d_mask;          /* [H,W] or NULL */
+    const float* d_background;    /* [H,W,3] or NULL */
+    const float* d_exposure12;    /* E, row-major 3x4, or NULL */
+    void* d_workspace;
+    float* d_loss3;               /* receives {loss, L1, SSIM} */
+    float* d_rgba_grad;           /* [H,W,4], receives d(loss)/d(rgba) */
+    float* d_exposure_grad12;     /* receives d(loss)/dE, or NULL */
+    float background, lambda_l1, lambda_ssim;
+} GutPhotometricLoss;
+int gut_photometric_loss_run(void* stream, int32_t height, int32_t width, const GutPhotometricLoss* loss);
 
 /* ---- "next" row N3: MCMC relocation kernel (threedgrut/strategy/src/gaussian_mcmc.cu:33-73).
  * opacities [n], scales [n,3], ratios [n] (int32, 1..n_max), binoms [n_max,n_max] -> new_opacities [n], new_scales [n,3] */
