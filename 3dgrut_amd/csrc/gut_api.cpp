@@ -787,6 +787,8 @@ static int trace_bwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
                           const float* d_ray_radiance_density, const float* d_ray_radiance_density_grad,
                           const float* d_ray_hit_distance, const float* d_ray_hit_distance_grad, float* d_particle_density_grad,
                           float* d_particle_radiance_grad, uint32_t flags, const gut::GradFields& fields);
+// internal flag of trace_bwd_impl (never taken from a caller): gut_trace_bwd_pose, the compositor and the consuming reduction alone
+static constexpr uint32_t kBwdPoseOnly = 0x80000000u;
 
 int gut_trace_bwd_ex(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
                      const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
@@ -796,8 +798,25 @@ int gut_trace_bwd_ex(gut_handle h, void* stream_, uint32_t frame_number, int32_t
                      float* d_particle_radiance_grad, uint32_t flags) {
     return trace_bwd_impl(h, stream_, frame_number, num_active_features, num_particles, d_particle_density, d_particle_radiance, width,
                           height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density, d_ray_radiance_density_grad,
-                          d_ray_hit_distance, d_ray_hit_distance_grad, d_particle_density_grad, d_particle_radiance_grad, flags,
-                          gut::GradFields());
+                          d_ray_hit_distance, d_ray_hit_distance_grad, d_particle_density_grad, d_particle_radiance_grad,
+                          flags & ~kBwdPoseOnly, gut::GradFields());
+}
+
+// The backward for the pose gradient alone: the compositor as in every other backward, then the CONSUMING form of the
+// reduction, which leaves the rows it read zero, and no epilogue: nothing of size N is written besides the handle's own gradient rows.
+int gut_trace_bwd_pose(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+                       const float* d_particle_density, int32_t width, int32_t height, const float* d_ray_origin,
+                       const float* d_ray_direction, const GutCamera* camera, const float* d_ray_radiance_density,
+                       const float* d_ray_radiance_density_grad, const float* d_ray_hit_distance, const float* d_ray_hit_distance_grad) {
+    if (!h) return fail("gut_trace_bwd_pose: null handle");
+    if (!d_particle_density) {
+        if (!h->packed_valid && num_particles)
+            return fail("gut_trace_bwd_pose: d_particle_density is NULL and the last forward on this handle packed no rows (not a *_fields one)");
+        d_particle_density = h->packed12.as<float>();
+    }
+    return trace_bwd_impl(h, stream_, frame_number, num_active_features, num_particles, d_particle_density, nullptr, width, height,
+                          d_ray_origin, d_ray_direction, camera, d_ray_radiance_density, d_ray_radiance_density_grad, d_ray_hit_distance,
+                          d_ray_hit_distance_grad, nullptr, nullptr, kBwdPoseOnly | GUT_BWD_SKIP_EPILOGUE, gut::GradFields());
 }
 
 // The [N,12] rows of the *_fields forwards: packed (or activated and packed) from the caller's four tensors into handle scratch by
@@ -926,6 +945,16 @@ int gut_trace_bwd_model_fields(gut_handle h, void* stream_, uint32_t frame_numbe
                           h->packed_raw ? GUT_BWD_RAW_PARAMETER_GRADS : 0u, f);
 }
 
+// how the consuming reduction zeroes: it reads the whole row and stores only where a word is set (the default, the faster form on the
+// 6 M-Gaussian workload), or GUT_POSE_CONSUME=store for measurements: four unconditional zero stores per visited row
+static bool pose_consume_tests() {
+    static const bool tests = [] {
+        const char* e = getenv("GUT_POSE_CONSUME");
+        return !(e && strcmp(e, "store") == 0);
+    }();
+    return tests;
+}
+
 static int trace_bwd_impl(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
                           const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
                           const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
@@ -950,9 +979,13 @@ static int trace_bwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
         return fail("gut_trace_bwd: null pointer argument");
     if (num_particles && (!d_particle_density || (!(flags & GUT_BWD_SKIP_EPILOGUE) && (!d_particle_density_grad || !d_particle_radiance_grad))))
         return fail("gut_trace_bwd: null particle buffers");
-    if (h->early_ran && !(flags & GUT_BWD_SKIP_EPILOGUE))
+    if (h->early_ran && (!(flags & GUT_BWD_SKIP_EPILOGUE) || (flags & kBwdPoseOnly)))
         return fail("gut_trace_bwd: gut_optimize_rows_without_gradient was called for this forward: the backward must be "
                     "gut_trace_bwd_ex(..., GUT_BWD_SKIP_EPILOGUE) followed by gut_optimize_after_bwd");
+    if (flags & kBwdPoseOnly) {
+        if (!h->pose_out) return fail("gut_trace_bwd_pose: no pose output is set (gut_set_pose_gradient)");
+        if (h->m && h->cfg.k_buffer_size > 0 && !d_ray_hit_distance) return fail("gut_trace_bwd: the sorted variant needs d_ray_hit_distance");
+    }
     float* narrow_radiance_grad = nullptr;   // particle_radiance_sph_degree < 3: the caller's [N, 3 (degree + 1)^2] gradient
     if (h->cfg.particle_radiance_sph_degree != 3 && !(flags & GUT_BWD_SKIP_EPILOGUE)) {
         if ((flags & GUT_BWD_COMPACT_RADIANCE_GRADS) || fields.alb)
@@ -1019,10 +1052,15 @@ static int trace_bwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
     mark(10);
     // right behind the backward compositor and before any epilogue: the epilogues zero the gradient rows as they read them
     // (behind the mark that ends render_bwd's timer: the two launches count towards project_bwd, not towards K7)
-    if (h->pose_out)
+    if (flags & kBwdPoseOnly)
+        gut::launch_pose_gradient_consume(s, n, h->tiles_count.as<uint32_t>(), h->grad16.as<float>(), d_particle_density,
+                                          h->cam_pos.as<float>(), h->pose_partials.as<float>(), h->pose_out, pose_consume_tests());
+    else if (h->pose_out)
         gut::launch_pose_gradient(s, n, h->tiles_count.as<uint32_t>(), h->grad16.as<float>(), d_particle_density, h->cam_pos.as<float>(),
                                   h->pose_partials.as<float>(), h->pose_out);
-    if (flags & GUT_BWD_SKIP_EPILOGUE) {
+    if (flags & kBwdPoseOnly) {
+        h->grad16_zero = true;  // the reduction zeroed every row K7 could have touched (the rows with tiles): nothing is left to consume
+    } else if (flags & GUT_BWD_SKIP_EPILOGUE) {
         // the caller folds the per-Gaussian epilogue into its optimiser step (gut_optimize_after_bwd)
     } else {
         if (flags & GUT_BWD_COMPACT_RADIANCE_GRADS)
@@ -1046,7 +1084,7 @@ static int trace_bwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
     }
     h->kev_bwd_valid = timing;
     if (timing) h->ring[h->ring_cur].bwd = true;
-    h->have_backward = true;
+    h->have_backward = !(flags & kBwdPoseOnly);   // (gut_optimize_after_bwd / gut_compact_gradient_rows have nothing to follow a pose-only one)
     return 0;
 }
 
@@ -1564,7 +1602,8 @@ int gut_debug_buffer(gut_handle h, int32_t which, void** d_ptr, size_t* bytes) {
         *d_ptr = h->packed12.p; *bytes = 48 * n; break;
     case GUT_BUF_TILE_RANGES: *d_ptr = h->ranges.p; *bytes = 8 * t; break;
     case GUT_BUF_GRAD_SCRATCH:
-        if (!h->have_backward) return fail("gut_debug_buffer: no backward yet");
+        // (also while the rows are known to be zero, after gut_trace_bwd_pose or any consumer: the view then shows whether they are)
+        if (!h->have_backward && !(h->grad16_zero && h->grad16.p && h->grad16.cap >= 64 * n)) return fail("gut_debug_buffer: no backward yet");
         *d_ptr = h->grad16.p; *bytes = 64 * n; break;
     case GUT_BUF_TILE_TRAVERSED_FWD: *d_ptr = h->trav_fwd.p; *bytes = 4 * t; break;
     case GUT_BUF_TILE_TRAVERSED_BWD:

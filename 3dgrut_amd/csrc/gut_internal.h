@@ -255,6 +255,11 @@ void launch_stats_reduce(hipStream_t s, uint32_t n, const uint32_t* tiles_count,
 size_t pose_gradient_scratch_bytes();
 void launch_pose_gradient(hipStream_t s, uint32_t n, const uint32_t* tiles_count, const float* grad16, const float* density12,
                           const float* cam_pos, float* partials, float* out8);
+// the consuming form (gut_trace_bwd_pose): the same numbers, and every row with a tile is left as 64 zero bytes.  test_before_store:
+// read the whole row and store only where a word is set (what the library launches); false: four unconditional zero stores per
+// visited row (kept for measurements)
+void launch_pose_gradient_consume(hipStream_t s, uint32_t n, const uint32_t* tiles_count, float* grad16, const float* density12,
+                                  const float* cam_pos, float* partials, float* out8, bool test_before_store);
 void launch_pose_adam(hipStream_t s, const float* grad8, float* m6, float* v6, int32_t* count, float lr_translation, float lr_rotation,
                       float beta1, float beta2, float eps, float* delta6);
 

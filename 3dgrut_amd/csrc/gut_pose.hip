@@ -11,15 +11,27 @@
 // Two launches, no float atomics: k_pose_partials keeps six fp32 accumulators per lane over a grid-stride loop of 64-row waves,
 // reduces them across the wave and the workgroup in a fixed order and writes one partial per workgroup; k_pose_finish (one wave)
 // sums the partials in a fixed order.  The grid depends on N alone, so the six numbers are a pure function of the rows.
+// gut_trace_bwd_pose launches a CONSUMING form of k_pose_partials: the same numbers, and the rows it read are left zero.
 #include "gut_internal.h"
 
 namespace gut {
 
 constexpr uint32_t kPoseMaxBlocks = 1024;   // partials of one reduction (handle scratch: 32 bytes each)
 
-// rows are read, never written: the epilogue that follows (K8 / the fused optimiser / the compaction) consumes and zeroes them
+// kPoseRead: rows are read, never written: the epilogue that follows (K8 / the fused optimiser / the compaction) consumes and zeroes
+// them.  The two consuming forms (gut_trace_bwd_pose: no epilogue follows) leave every row they visited, the rows with a tile, as 64
+// zero bytes, the scale and colour slots K7 also writes included: kPoseConsumeStore stores four zero float4 per visited row whatever
+// it held, kPoseConsumeTest reads the whole row and stores only where a word is set.  Arithmetic, grid and summation order are those
+// of the reading form.
+enum PoseRows { kPoseRead = 0, kPoseConsumeStore = 1, kPoseConsumeTest = 2 };
+
+template <int kRows> struct PoseRowPointer { typedef const float4* __restrict__ type; };
+template <> struct PoseRowPointer<kPoseConsumeStore> { typedef float4* __restrict__ type; };
+template <> struct PoseRowPointer<kPoseConsumeTest> { typedef float4* __restrict__ type; };
+
+template <int kRows>
 __global__ __launch_bounds__(kBlock) void k_pose_partials(uint32_t n, const uint32_t* __restrict__ tiles_count,
-                                                         const float4* __restrict__ grad16, const float4* __restrict__ density12,
+                                                         typename PoseRowPointer<kRows>::type grad16, const float4* __restrict__ density12,
                                                          const float* __restrict__ cam_pos, float* __restrict__ partials) {
     __shared__ float wave_part[kBlock / 64][8];
     const float cx = cam_pos[0], cy = cam_pos[1], cz = cam_pos[2];
@@ -31,6 +43,19 @@ __global__ __launch_bounds__(kBlock) void k_pose_partials(uint32_t n, const uint
         ++rows;
         const float4 g0 = grad16[4 * i + 0];   // d pos3, d density
         const float4 g1 = grad16[4 * i + 1];   // d quat wxyz
+        if constexpr (kRows == kPoseConsumeStore) {
+            const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+            grad16[4 * i + 0] = zero; grad16[4 * i + 1] = zero; grad16[4 * i + 2] = zero; grad16[4 * i + 3] = zero;
+        } else if constexpr (kRows == kPoseConsumeTest) {
+            const float4 g2 = grad16[4 * i + 2], g3 = grad16[4 * i + 3];   // d scale3 and the colour slots: not summed, zeroed
+            const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+            // bit tests: a word that holds -0.f or a NaN is rewritten as well
+            auto set = [](const float4& v) { return (__float_as_uint(v.x) | __float_as_uint(v.y) | __float_as_uint(v.z) | __float_as_uint(v.w)) != 0u; };
+            if (set(g0)) grad16[4 * i + 0] = zero;
+            if (set(g1)) grad16[4 * i + 1] = zero;
+            if (set(g2)) grad16[4 * i + 2] = zero;
+            if (set(g3)) grad16[4 * i + 3] = zero;
+        }
         // A row K7 gave nothing contributes exactly zero; its activated row is not fetched.  (Under the two-pass optimiser the
         // side stream rewrites the activated rows of waves the forward walked nothing of while this kernel runs: those rows have
         // zero gradients, so they are never read here.)
@@ -96,12 +121,29 @@ __global__ __launch_bounds__(64) void k_pose_finish(uint32_t num_partials, const
 
 size_t pose_gradient_scratch_bytes() { return sizeof(float) * 8 * kPoseMaxBlocks; }
 
+static uint32_t pose_blocks(uint32_t n) {
+    return (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock < kPoseMaxBlocks ? ((uint64_t)n + kBlock - 1) / kBlock : kPoseMaxBlocks);
+}
+
 void launch_pose_gradient(hipStream_t s, uint32_t n, const uint32_t* tiles_count, const float* grad16, const float* density12,
                           const float* cam_pos, float* partials, float* out8) {
     if (n == 0) return;
-    const uint32_t blocks = (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock < kPoseMaxBlocks ? ((uint64_t)n + kBlock - 1) / kBlock : kPoseMaxBlocks);
-    hipLaunchKernelGGL(k_pose_partials, dim3(blocks), dim3(kBlock), 0, s, n, tiles_count, reinterpret_cast<const float4*>(grad16),
+    const uint32_t blocks = pose_blocks(n);
+    hipLaunchKernelGGL(k_pose_partials<kPoseRead>, dim3(blocks), dim3(kBlock), 0, s, n, tiles_count, reinterpret_cast<const float4*>(grad16),
                        reinterpret_cast<const float4*>(density12), cam_pos, partials);
+    hipLaunchKernelGGL(k_pose_finish, dim3(1), dim3(64), 0, s, blocks, partials, out8);
+}
+
+void launch_pose_gradient_consume(hipStream_t s, uint32_t n, const uint32_t* tiles_count, float* grad16, const float* density12,
+                                  const float* cam_pos, float* partials, float* out8, bool test_before_store) {
+    if (n == 0) return;
+    const uint32_t blocks = pose_blocks(n);
+    if (test_before_store)
+        hipLaunchKernelGGL(k_pose_partials<kPoseConsumeTest>, dim3(blocks), dim3(kBlock), 0, s, n, tiles_count, reinterpret_cast<float4*>(grad16),
+                           reinterpret_cast<const float4*>(density12), cam_pos, partials);
+    else
+        hipLaunchKernelGGL(k_pose_partials<kPoseConsumeStore>, dim3(blocks), dim3(kBlock), 0, s, n, tiles_count, reinterpret_cast<float4*>(grad16),
+                           reinterpret_cast<const float4*>(density12), cam_pos, partials);
     hipLaunchKernelGGL(k_pose_finish, dim3(1), dim3(64), 0, s, blocks, partials, out8);
 }
 

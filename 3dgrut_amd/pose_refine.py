@@ -17,7 +17,8 @@ completed, so `begin` does not wait; with ONE view it waits for the step before 
 
 Rays stay as they are: they are in camera space.  Only views with a single pose (pose_start == pose_end) can be refined; the
 backward refuses any other while the gradient output is set.  Data-parallel refinement does not exist (ValueError in
-NativeTrainStep).  Held-out views are scored at their given poses: nothing here touches validation or test batches.
+NativeTrainStep).  Held-out views are scored at their given poses unless `pose_alignment` is on
+(pose_align.py): nothing here touches validation or test batches.
 """
 import copy
 import ctypes as C

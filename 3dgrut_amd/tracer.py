@@ -447,6 +447,36 @@ class SplatRaster:
         self._pose_out = out8   # (kept alive: the library holds its address)
         _capi.check(self._lib.gut_set_pose_gradient(self._handle, out8.data_ptr()), "set_pose_gradient")
 
+    def trace_bwd_pose(self, frame_number, num_active_features, particle_density, ray_ori, ray_dir, sensor_params, ts_start, ts_end,
+                       pose_start, pose_end, ray_radiance_density, ray_radiance_density_grd, ray_hit_distance, ray_hit_distance_grd=None):
+        """The backward for the pose gradient ALONE (gut_trace_bwd_pose): follows any forward on this handle, fills the tensor given
+        to set_pose_gradient (which must be set) and returns nothing: no per-Gaussian gradient exists afterwards, in a tensor or in the
+        handle (the reduction leaves the handle's rows zero), and optimize_after_bwd / compact_gradient_rows have nothing to follow.
+        particle_density: the [N,12] rows of the forward, or an int N after a *_fields forward (the rows that forward packed)."""
+        ray_ori = _check_f32_cuda(ray_ori, "rayOrigin", (3,))
+        ray_dir = _check_f32_cuda(ray_dir, "rayDirection", (3,))
+        H, W = int(ray_ori.shape[1]), int(ray_ori.shape[2])
+        dev = ray_ori.device
+        rgba = _check_f32_cuda(ray_radiance_density, "rayRadianceDensity", (4,))
+        rgba_g = _check_f32_cuda(ray_radiance_density_grd, "rayRadianceDensityGradient", (4,))
+        dist = _check_f32_cuda(ray_hit_distance, "rayHitDistance")
+        dist_g = None if ray_hit_distance_grd is None else _check_f32_cuda(ray_hit_distance_grd, "rayHitDistanceGradient")
+        rows = None
+        if isinstance(particle_density, torch.Tensor):
+            n = int(particle_density.shape[0])
+            if n:
+                rows = _check_f32_cuda(particle_density, "particleDensity", (12,))
+        else:
+            n = int(particle_density)
+        cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            rc = self._lib.gut_trace_bwd_pose(self._handle, C.c_void_p(stream), int(frame_number) & 0xFFFFFFFF, int(num_active_features), n,
+                                              None if rows is None else rows.data_ptr(), W, H, ray_ori.data_ptr(), ray_dir.data_ptr(),
+                                              C.byref(cam), rgba.data_ptr(), rgba_g.data_ptr(), dist.data_ptr(),
+                                              None if dist_g is None else dist_g.data_ptr())
+        _capi.check(rc, "trace_bwd_pose")
+
     def set_regularisation(self, reg):
         """The NEXT optimiser step on the handle (optimize_rows_without_gradient + optimize_after_bwd, or
         finish_optimizer_step_without_gradient) adds the MCMC regularisers' gradient to every row it updates and writes the loss

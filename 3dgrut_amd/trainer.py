@@ -23,7 +23,7 @@ written by the reference itself (an OmegaConf config inside) are not read.
 `pose_refinement.enabled` (default off; `--refine-poses`) refines the training views' camera poses while training
 (pose_refine.PoseRefiner): every step's backward leaves the view's pose gradient on the device, a per-view Adam turns it into an
 increment, and the view's next visit renders from the refined pose.  Held-out views (validation, test) are scored at their GIVEN
-poses.  The refiner's poses, moments and visit counts travel in the checkpoint's `native` block as tensors.
+poses unless `pose_alignment` is on.  The refiner's poses, moments and visit counts travel in the checkpoint's `native` block as tensors.
 
 `exposure.enabled` (default off; `--exposure`) learns an affine colour transform per training view (exposure.ExposureCompensation,
 DESIGN.md §10): the loss compares A image + b with the photo, its backward leaves d(loss)/d[A | b] on the device, and a per-view
@@ -35,10 +35,17 @@ before scoring, the render is mapped through the affine colour transform that fi
 that a held-out photo's own exposure is not charged to the model — the number to compare an `--exposure` run with a run without it.
 The plain metrics are unchanged; it needs nothing from the checkpoint and composes with every other option.
 
+`pose_alignment.enabled` (default off; `--aligned-metrics`) additionally scores every held-out view POSE-ALIGNED (DESIGN.md §12,
+pose_align.PoseAligner): after a view has been scored at its given pose, that pose is optimised against the photo with the model
+frozen (`iterations` steps of the six-float Adam on the pose-only backward) and the render at the best pose found is scored next to
+the plain one — the number to compare a `--refine-poses` run with a run without it.  It applies to the final test pass, and with
+`validation: true` to the validation passes too; `lr_translation` is multiplied by the scene extent, the loss weights are the run's.
+The rates and the iteration count are untuned on real captures.  It needs nothing from the checkpoint and writes nothing into it.
+
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
                                  [--refine-poses [--pose-lr-translation X] [--pose-lr-rotation R]]
-                                 [--exposure [--exposure-lr X]] [--cc-metrics]
+                                 [--exposure [--exposure-lr X]] [--cc-metrics] [--aligned-metrics [--align-iterations K]]
 """
 import argparse
 import copy
@@ -51,7 +58,7 @@ import numpy as np
 import torch
 
 from . import exposure as exposure_mod
-from . import losses, pose_refine
+from . import losses, pose_align, pose_refine
 from .evaluate import _check_batch, evaluate
 
 # configs/base_gs.yaml + configs/strategy/gs.yaml: the keys this trainer reads
@@ -79,6 +86,10 @@ GS_CONFIG = {
     # not a reference key: colour-corrected held-out metrics next to the plain ones (evaluate.py).  ridge is the regulariser of the
     # per-view affine fit, a parameter of the metric's definition (> 0), not a tolerance.
     "evaluation": {"colour_corrected": False, "ridge": 1e-6},
+    # not a reference key: pose-aligned held-out metrics next to the plain ones (pose_align.py).  lr_translation is multiplied by the
+    # scene extent, lr_rotation is in radians; validation: the validation passes too, not only the final test pass.  The two rates and
+    # the iteration count are untuned on real captures.
+    "pose_alignment": dict(pose_align.DEFAULTS),
     "strategy": {"method": "GSStrategy",
                  "densify": {"frequency": 300, "start_iteration": 500, "end_iteration": 15000, "clone_grad_threshold": 0.0002,
                              "split_grad_threshold": 0.0002, "relative_size_threshold": 0.01, "split": {"n_gaussians": 2}},
@@ -131,6 +142,7 @@ def resolve_config(conf):
     pose_refine.check_config(out["pose_refinement"])
     exposure_mod.check_config(out["exposure"])
     check_evaluation_config(out["evaluation"])
+    pose_align.check_config(out["pose_alignment"])
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
         out["optimizer"]["params"]["features_specular"] = {"lr": float(out["optimizer"]["params"]["features_albedo"]["lr"]) / 20}
@@ -149,6 +161,10 @@ def check_evaluation_config(block):
         raise ValueError(f"evaluation.ridge must be finite and > 0, got {ridge!r}")
     return block
 
+
+# what a pose-aligned evaluation adds to the validation entries and to main()'s final JSON, where the evaluator returned it
+PA_SUMMARY_KEYS = ("mean_pa_psnr", "std_pa_psnr", "mean_pa_ssim", "mean_pa_translation", "mean_pa_rotation_deg", "mean_pa_cc_psnr",
+                   "std_pa_cc_psnr", "mean_pa_cc_ssim")
 
 BACKGROUND_COLORS = ("black", "white", "random")   # configs/base_gs.yaml:72-74
 
@@ -464,21 +480,29 @@ class Trainer:
         if raw is not None and raw.is_cuda:
             torch.cuda.synchronize(raw.device)
 
-    def _evaluation_options(self):
-        """The evaluator's keyword arguments: none with evaluation.colour_corrected off (an injected evaluator is then called with
-        the five positional arguments alone)."""
+    def _evaluation_options(self, validation=False):
+        """The evaluator's keyword arguments: none with evaluation.colour_corrected and pose_alignment.enabled off (an injected
+        evaluator is then called with the five positional arguments alone).  pose_aligned: the aligner's settings with the translation
+        rate in world units and the run's loss weights; on validation passes only with pose_alignment.validation."""
         ev = self.conf["evaluation"]
-        return dict(colour_corrected=True, ridge=float(ev["ridge"])) if ev["colour_corrected"] else {}
+        opts = dict(colour_corrected=True, ridge=float(ev["ridge"])) if ev["colour_corrected"] else {}
+        pa = self.conf["pose_alignment"]
+        if pa["enabled"] and (not validation or pa["validation"]):
+            w = losses.loss_weights(self.conf["loss"])
+            opts["pose_aligned"] = dict(iterations=int(pa["iterations"]), lr_translation=float(pa["lr_translation"]) * float(self.scene_extent),
+                                        lr_rotation=float(pa["lr_rotation"]), beta1=float(pa["beta1"]), beta2=float(pa["beta2"]),
+                                        eps=float(pa["eps"]), lambda_l1=w["lambda_l1"], lambda_ssim=w["lambda_ssim"])
+        return opts
 
     def validate(self):
         """Validation pass on val_batches (trainer.py:805-842): held-out metrics and the last training loss."""
         if not self.val_batches:
             return None
-        res = self.evaluator(self.model, self.tracer, self.val_batches, None, self.global_step, **self._evaluation_options())
+        res = self.evaluator(self.model, self.tracer, self.val_batches, None, self.global_step, **self._evaluation_options(validation=True))
         loss = getattr(self, "_last_loss", None)
         entry = dict(step=self.global_step, loss=None if loss is None else float(loss), mean_psnr=res["mean_psnr"],
                      mean_ssim=res["mean_ssim"], n_gaussians=int(self.model.num_gaussians))
-        entry.update({k: res[k] for k in ("mean_cc_psnr", "mean_cc_ssim") if k in res})
+        entry.update({k: res[k] for k in ("mean_cc_psnr", "mean_cc_ssim") + PA_SUMMARY_KEYS if k in res})
         self.validations.append(entry)
         if self.conf.get("verbose", False):
             print(f"[trainer] step {entry['step']}: loss {entry['loss']} val psnr {entry['mean_psnr']:.3f} ssim {entry['mean_ssim']:.4f} "
@@ -587,6 +611,10 @@ def build_parser():
     ap.add_argument("--cc-metrics", action="store_true",
                     help="also score held-out views colour-corrected: through the affine colour transform fitted per view "
                          "(evaluation.colour_corrected)")
+    ap.add_argument("--aligned-metrics", action="store_true",
+                    help="also score held-out views pose-aligned: each test view's pose is optimised against its photo with the model "
+                         "frozen before it is scored again (pose_alignment.enabled); the plain scores stay")
+    ap.add_argument("--align-iterations", type=int, default=None, help="pose_alignment.iterations")
     return ap
 
 
@@ -609,6 +637,9 @@ def config_from_args(a):
     if a.exposure_lr is not None:
         conf["exposure"]["lr"] = a.exposure_lr
     conf["evaluation"]["colour_corrected"] = bool(a.cc_metrics)
+    conf["pose_alignment"]["enabled"] = bool(a.aligned_metrics)
+    if a.align_iterations is not None:
+        conf["pose_alignment"]["iterations"] = a.align_iterations
     return conf
 
 
@@ -629,7 +660,7 @@ def main(argv=None):
     out = dict(stats=res["stats"])
     if test_res is not None:
         out["test"] = {k: test_res[k] for k in ("mean_psnr", "std_psnr", "mean_ssim", "n_views", "mean_inference_time", "mean_cc_psnr", "std_cc_psnr",
-                                                   "mean_cc_ssim") if k in test_res}
+                                                   "mean_cc_ssim") + PA_SUMMARY_KEYS if k in test_res}
     print(json.dumps(out), flush=True)
     return 0
 

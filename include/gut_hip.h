@@ -42,6 +42,7 @@ extern "C" {
  * gut_regularisation_gradient, gut_regularisation_loss.  Added under 6 without a bump, nothing that was accepted changed meaning:
  * gut_photometric_loss_masked and gut_photometric_loss_background, new entry points next to gut_photometric_loss, which is
  * untouched; gut_set_pose_gradient and gut_pose_adam_step, new entry points: while it is not set, every gut_trace_bwd* queues what it queued before;
+ * gut_trace_bwd_pose, a new entry point: the backward for the pose gradient alone, every other backward launches what it launched;
  * gut_photometric_exposure_workspace_bytes, gut_photometric_loss_exposure and gut_exposure_adam_step, new entry points next to the
  * other forms of the fused loss, which launch what they launched before; gut_image_metrics_cc_workspace_bytes and gut_image_metrics_cc,
  * new entry points next to gut_image_metrics, which launches what it launched before; GutPhotometricLoss and gut_photometric_loss_run,
@@ -132,7 +133,7 @@ enum {
     GUT_BUF_SORTED_KEYS = 9,   /* u64 [M]  (SORTED_*: the reference's fully sorted lists; built on request, see ORDERED_IDS) */
     GUT_BUF_SORTED_IDS = 10,   /* u32 [M] */
     GUT_BUF_TILE_RANGES = 11,  /* u32 [T,2] */
-    GUT_BUF_GRAD_SCRATCH = 12, /* f32 [N,16] per-Gaussian gradient rows of the last trace_bwd */
+    GUT_BUF_GRAD_SCRATCH = 12, /* f32 [N,16] per-Gaussian gradient rows of the last trace_bwd (also while the library holds them to be all zero) */
     GUT_BUF_TILE_TRAVERSED_FWD = 13, /* u32 [T] list entries each tile walked before all its rays terminated */
     GUT_BUF_TILE_TRAVERSED_BWD = 14, /* u32 [T] same, last trace_bwd */
     GUT_BUF_ORDERED_IDS = 15,  /* u32 [M] what the compositors actually walked: per tile, the ids in final order for the chunks the
@@ -634,6 +635,21 @@ int gut_set_pose_gradient(gut_handle h, float* d_out8);
  * lr_rotation to phi.  d_delta6 receives the increment (d rho, d phi): c += d rho, R_c2w <- exp([d phi]x) R_c2w.  One launch. */
 int gut_pose_adam_step(void* stream, const float* d_grad8, float* d_m6, float* d_v6, int32_t* d_count, float lr_translation,
                        float lr_rotation, float beta1, float beta2, float eps, float* d_delta6);
+/* The backward for the pose gradient ALONE (pose alignment of held-out views with the Gaussians frozen).  Arguments as
+ * gut_trace_bwd_ex without the gradient outputs and without flags; d_particle_density may be NULL after a *_fields forward (the rows
+ * that forward packed).  Follows any forward on the same handle and stream, runs the backward compositor as every other backward
+ * does (both variants) and then the CONSUMING form of the reduction above: the same arithmetic, grid and summation order, so d_out8
+ * is the same pure function of the rows, and every gradient row with a tile is left as 64 zero bytes.  No epilogue runs and nothing
+ * of size N is written besides the handle's own gradient rows.  Afterwards the rows are known to be zero (the next backward queues
+ * no clear), NO backward context is pending (gut_optimize_after_bwd and gut_compact_gradient_rows refuse) and the next gut_trace
+ * is accepted.  Refused before anything is queued, the handle left as it was: no pose output set, pose_start != pose_end,
+ * gut_optimize_rows_without_gradient was called for this forward, arguments that differ from the cached forward.  With
+ * num_particles == 0 the eight floats are set to zero.  Timers: the two launches count towards project_bwd. */
+int gut_trace_bwd_pose(gut_handle h, void* stream, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+                       const float* d_particle_density, int32_t width, int32_t height, const float* d_ray_origin,
+                       const float* d_ray_direction, const GutCamera* camera, const float* d_ray_radiance_density,
+                       const float* d_ray_radiance_density_grad, const float* d_ray_hit_distance,
+                       const float* d_ray_hit_distance_grad /* may be NULL */);
 
 /* ---- Per-view exposure in the fused loss (new functionality, the reference has none) ----
  * gut_photometric_loss_exposure is the fused loss of gut_photometric_loss[_masked | _background] on the AFFINE image of a view:
