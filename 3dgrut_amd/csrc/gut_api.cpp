@@ -448,79 +448,82 @@ void gut_destroy(gut_handle h) {
     delete h;
 }
 
-static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
-                          const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
-                          const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
-                          float* d_ray_radiance_density, float* d_ray_hit_distance, float* d_ray_hit_count,
-                          float* d_particle_visibility, const float* d_features_albedo);
+}  // extern "C"
 
-// host_count[2], [3]: sum of the traversal depths / of the list lengths of the last frame that had a backward (copied with the count)
-static void update_fwd_order(gut_handle h) {
-    if (!h->walk_sums.p) return;
-    const uint32_t walked = h->host_count[2], listed = h->host_count[3];
-    if (listed) h->fwd_longest_first = (double)walked > 0.25 * (double)listed;
+namespace {
+
+// ---- the trace call path: the records the exported entry points (below) fill for trace_fwd_impl / trace_bwd_impl ----
+struct TraceView {   // one view, as every forward and backward names it
+    hipStream_t stream;
+    int32_t sh_degree;   // num_active_features
+    uint32_t n;
+    int32_t width, height;
+    const float *ray_origin, *ray_direction;
+    const GutCamera* camera;
+};
+TraceView view_of(void* stream_, int32_t num_active_features, uint32_t num_particles, int32_t width, int32_t height,
+                  const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera) {
+    return TraceView{static_cast<hipStream_t>(stream_), num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera};
+}
+struct FwdOutputs { float *rgba, *hit_distance, *hit_count, *visibility; };
+struct BwdUpstream { const float *rgba, *rgba_grad, *hit_distance, *hit_distance_grad /* may be NULL (= all zeros) */; };
+// what follows the backward compositor: the per-Gaussian epilogue in one of its two forms, nothing, or the consuming pose reduction alone
+enum class BwdMode { kDense, kCompact, kSkipEpilogue, kPoseOnly };
+struct BwdArgs {
+    BwdMode mode;
+    bool raw_grads;           // kDense: GUT_BWD_RAW_PARAMETER_GRADS
+    const float* density;     // [N,12] rows of the forward
+    float* density_grad;      // [N,12]; unused when fields.pos is set
+    float* radiance_grad;     // [N,48] ([N,3] compact); unused when fields.spec is set
+    gut::GradFields fields;   // where the split gradients go (the *_fields backwards), all NULL otherwise
+};
+bool has_epilogue(BwdMode mode) { return mode == BwdMode::kDense || mode == BwdMode::kCompact; }
+
+// kernel-timer boundary i of the frame's ring set; the end of a call's total timer (arm_timer began it)
+void mark(gut_handle h, hipStream_t s, bool timing, int i) {
+    if (timing && h->kev[i]) (void)hipEventRecord(h->kev[i], s);
+}
+void end_timer(EventPair* total, hipStream_t s) {
+    if (!total) return;
+    (void)hipEventRecord(total->b, s);
+    total->armed = true;
 }
 
-int gut_trace(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
-              const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
-              const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
-              float* d_ray_radiance_density, float* d_ray_hit_distance, float* d_ray_hit_count,
-              float* d_particle_visibility) {
-    return trace_fwd_impl(h, stream_, frame_number, num_active_features, num_particles, d_particle_density, d_particle_radiance, width,
-                          height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density, d_ray_hit_distance, d_ray_hit_count,
-                          d_particle_visibility, nullptr);
-}
+// what the steps of one forward share
+struct FwdFrame {
+    gut::ViewParams v;
+    int tiles = 0, end_bit = 0;
+    const uint32_t* d_count = nullptr;   // device-side intersection count
+    bool timing = false;                 // the kernel-timer marks are live
+    EventPair* total = nullptr;
+    bool early_after_project = false;    // GUT_EARLY_AFTER_PROJECT
+};
 
 // d_features_albedo != NULL: d_particle_radiance is features_specular [N,45] (gut_trace_model_fields)
-static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
-                          const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
-                          const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
-                          float* d_ray_radiance_density, float* d_ray_hit_distance, float* d_ray_hit_count,
-                          float* d_particle_visibility, const float* d_features_albedo) {
-    (void)frame_number;
+int check_forward_args(gut_handle h, const TraceView& view, const float* d_particle_density, const float* d_particle_radiance,
+                       const float* d_features_albedo, const FwdOutputs& out) {
     if (!h) return fail("gut_trace: null handle");
-    if (!camera || !d_ray_origin || !d_ray_direction || !d_ray_radiance_density || !d_ray_hit_distance || !d_ray_hit_count)
+    if (!view.camera || !view.ray_origin || !view.ray_direction || !out.rgba || !out.hit_distance || !out.hit_count)
         return fail("gut_trace: null pointer argument");
-    if (width <= 0 || height <= 0) return fail("gut_trace: bad resolution %dx%d", width, height);
-    if (num_active_features < 0 || num_active_features > 3) return fail("gut_trace: SH degree %d outside 0..3", num_active_features);
-    if (num_particles && (!d_particle_density || !d_particle_radiance || !d_particle_visibility))
-        return fail("gut_trace: null particle buffers with %u particles", num_particles);
-    if (h->cfg.particle_radiance_sph_degree != 3) {
-        if (num_active_features > h->cfg.particle_radiance_sph_degree)
-            return fail("gut_trace: %d active SH degrees, the handle was created for particle_radiance_sph_degree=%d", num_active_features,
-                        h->cfg.particle_radiance_sph_degree);
-        if (d_features_albedo)
-            return fail("gut_trace_model_fields: features_specular [N,45] belongs to particle_radiance_sph_degree=3; this handle has %d "
-                        "(use gut_trace / gut_trace_fields with the concatenated rows)", h->cfg.particle_radiance_sph_degree);
-    }
-    std::lock_guard<std::mutex> lock(h->mu);
-    hipStream_t s = static_cast<hipStream_t>(stream_);
-    DeviceGuard dev_guard;
-    HIP_TRY(dev_guard.set(h->device));
-    gut::ViewParams v;
-    if (build_view(camera, width, height, h->cfg.n_rolling_shutter_iterations, &v)) return 1;
-    const uint32_t n = num_particles;
-    const int tiles = v.grid_x * v.grid_y;
-    if ((uint64_t)tiles >= 0xFFFFFFFFull) return fail("gut_trace: too many tiles");
-    if (h->early_ran)
-        return fail("gut_trace: gut_optimize_rows_without_gradient was called for the previous forward but gut_optimize_after_bwd "
-                    "was not: that optimiser step is half applied");
-    if (h->early_wait_pending) {  // (only reachable after an error path; the optimiser call normally orders the streams)
-        HIP_TRY(hipStreamWaitEvent(s, h->ev_early_done, 0));
-        h->early_wait_pending = false;
-    }
-    h->have_forward = false;
-    h->have_backward = false;
-    h->marks_valid = false;
-    h->packed_valid = false;   // (gut_trace_fields sets it again once this call has succeeded)
+    if (view.width <= 0 || view.height <= 0) return fail("gut_trace: bad resolution %dx%d", view.width, view.height);
+    if (view.sh_degree < 0 || view.sh_degree > 3) return fail("gut_trace: SH degree %d outside 0..3", view.sh_degree);
+    if (view.n && (!d_particle_density || !d_particle_radiance || !out.visibility))
+        return fail("gut_trace: null particle buffers with %u particles", view.n);
+    const int rows_degree = h->cfg.particle_radiance_sph_degree;
+    if (rows_degree != 3 && view.sh_degree > rows_degree)
+        return fail("gut_trace: %d active SH degrees, the handle was created for particle_radiance_sph_degree=%d", view.sh_degree, rows_degree);
+    if (rows_degree != 3 && d_features_albedo)
+        return fail("gut_trace_model_fields: features_specular [N,45] belongs to particle_radiance_sph_degree=3; this handle has %d "
+                    "(use gut_trace / gut_trace_fields with the concatenated rows)", rows_degree);
+    return 0;
+}
 
+int ensure_frame_scratch(gut_handle h, hipStream_t s, uint32_t n, int tiles) {
+    const size_t blocks = ((size_t)n + gut::kBlock - 1) / gut::kBlock;
     HIP_TRY(h->tiles_count.ensure(sizeof(uint32_t) * (size_t)n));
-    {
-        const size_t blocks = ((size_t)n + gut::kBlock - 1) / gut::kBlock;
-        HIP_TRY(h->wave_sums.ensure(sizeof(uint32_t) * (gut::kBlock / 64) * (blocks + 1)));
-        HIP_TRY(h->block_prefix.ensure(sizeof(uint32_t) * (blocks + 1)));
-        HIP_TRY(h->scan_total.ensure(64));
-    }
+    HIP_TRY(h->wave_sums.ensure(sizeof(uint32_t) * (gut::kBlock / 64) * (blocks + 1)));
+    HIP_TRY(h->block_prefix.ensure(sizeof(uint32_t) * (blocks + 1)));
+    HIP_TRY(h->scan_total.ensure(64));
     HIP_TRY(h->proj_pos.ensure(sizeof(float) * 2 * (size_t)n));
     HIP_TRY(h->conic_opacity.ensure(sizeof(float) * 4 * (size_t)n));
     HIP_TRY(h->extent.ensure(sizeof(float) * 2 * (size_t)n));
@@ -535,25 +538,29 @@ static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
         HIP_TRY(h->zero_word.ensure(64));
         HIP_TRY(hipMemsetAsync(h->zero_word.p, 0, 64, s));
     }
+    return 0;
+}
 
-    const bool timing = h->cfg.enable_kernel_timings != 0 && h->timing_main_stream;
-    EventPair* total = timing ? arm_timer(h->fwd_timers, s) : nullptr;
+// the frame's total timer and a fresh set of per-kernel events (the next slot of the ring)
+void begin_frame_timing(gut_handle h, hipStream_t s, FwdFrame* f) {
+    f->timing = h->cfg.enable_kernel_timings != 0 && h->timing_main_stream;
+    f->total = f->timing ? arm_timer(h->fwd_timers, s) : nullptr;
     h->kev_fwd_valid = false;
-    if (h->cfg.enable_kernel_timings != 0 && (h->timing_main_stream || h->timing_side_stream)) {   // (a fresh set of events per frame)
+    if (h->cfg.enable_kernel_timings != 0 && (h->timing_main_stream || h->timing_side_stream)) {
         h->ring_cur = (h->ring_cur + 1) % gut_context::kRing;
         h->kev = h->ring[h->ring_cur].e;
-        h->ring[h->ring_cur].fwd = false;
-        h->ring[h->ring_cur].bwd = false;
-        h->ring[h->ring_cur].opt = false;
-        h->ring[h->ring_cur].early = false;
-        h->ring[h->ring_cur].early2 = false;
+        gut_context::KevSet& set = h->ring[h->ring_cur];
+        set.fwd = set.bwd = set.opt = set.early = set.early2 = false;
     }
-    auto mark = [&](int i) {
-        if (timing && h->kev[i]) (void)hipEventRecord(h->kev[i], s);
-    };
+}
 
+// frame clears, K1 (projection), the scan of the tile counts and the event behind the count's read-back
+int queue_projection_and_scan(gut_handle h, const TraceView& view, const float* d_particle_density, const float* d_particle_radiance,
+                              const float* d_features_albedo, float* d_particle_visibility, FwdFrame* f) {
+    const hipStream_t s = view.stream;
+    const uint32_t n = view.n;
+    const int tiles = f->tiles;
     // per-tile ranges / backward traversal depths and the per-wave "walked" bytes start every frame at zero: K1 clears them on its way
-    // (three fill launches on the step's critical chain until round 4); without Gaussians there is no K1
     gut::FrameClears clears;
     clears.ranges = h->ranges.as<uint2>();
     clears.trav_bwd = h->trav_bwd.as<uint32_t>();
@@ -575,11 +582,11 @@ static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
             }
             clears.tile_entries = h->tile_entries.as<uint32_t>();
         }
-    } else {
+    } else {   // without Gaussians there is no K1
         HIP_TRY(hipMemsetAsync(h->trav_bwd.p, 0, sizeof(uint32_t) * (size_t)tiles, s));
         HIP_TRY(hipMemsetAsync(h->ranges.p, 0, sizeof(uint32_t) * 2 * (size_t)tiles, s));
     }
-    mark(0);
+    mark(h, s, f->timing, 0);
     if (h->cfg.particle_radiance_sph_degree != 3 && n) {
         // rows of 3 (degree + 1)^2 floats (gaussianParticles.cuh:208-216 reads PARTICLE_RADIANCE_NUM_COEFFS coefficients per particle):
         // zero-extended to the 16 coefficients the projection kernel is laid out for; the coefficients above the active degree are
@@ -589,25 +596,20 @@ static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
         gut::launch_resize_sph_rows(s, n, w, 48u, d_particle_radiance, h->sph_widened.as<float>());
         d_particle_radiance = h->sph_widened.as<float>();
     }
-    gut::launch_project(s, v, h->consts, n, num_active_features, d_particle_density, d_particle_radiance,
-                        h->tiles_count.as<uint32_t>(), h->proj_pos.as<float>(), h->conic_opacity.as<float>(),
-                        h->extent.as<float>(), h->depth.as<float>(), h->feat.as<float>(), d_particle_visibility,
-                        h->wave_sums.as<uint32_t>(), d_features_albedo, clears);
-    mark(1);
+    gut::launch_project(s, f->v, h->consts, n, view.sh_degree, d_particle_density, d_particle_radiance, h->tiles_count.as<uint32_t>(),
+                        h->proj_pos.as<float>(), h->conic_opacity.as<float>(), h->extent.as<float>(), h->depth.as<float>(),
+                        h->feat.as<float>(), d_particle_visibility, h->wave_sums.as<uint32_t>(), d_features_albedo, clears);
+    mark(h, s, f->timing, 1);
     static const bool early_after_project = getenv("GUT_EARLY_AFTER_PROJECT") != nullptr;  // tuning experiments only
+    f->early_after_project = early_after_project;
     if (early_after_project) {
         if (!h->ev_projected) HIP_TRY(hipEventCreateWithFlags(&h->ev_projected, kOrderingEvent));
         HIP_TRY(hipEventRecord(h->ev_projected, s));
     }
-    const int end_bit = 32 + (int)bit_width_u32((uint32_t)tiles);
-    h->dbg_sorted_valid = false;
-    h->dbg_unsorted_valid = false;
-    h->dbg_ordered_valid = false;
+    f->end_bit = 32 + (int)bit_width_u32((uint32_t)tiles);
+    h->dbg_sorted_valid = h->dbg_unsorted_valid = h->dbg_ordered_valid = h->dbg_offset_valid = false;
     // device-side intersection count: written by the scan of the block sums (a zero word when there are no particles)
-    const uint32_t* d_count = n ? h->scan_total.as<uint32_t>() : h->zero_word.as<uint32_t>();
-    h->dbg_offset_valid = false;
-    uint32_t m = 0;
-    bool count_pending = false;
+    f->d_count = n ? h->scan_total.as<uint32_t>() : h->zero_word.as<uint32_t>();
     if (n) {
         // K2 (gutRenderer.cu:300-311: a device-wide cub scan of the [N] counts): two levels here — K1 left one sum per wave, one
         // workgroup scans the per-block sums (and writes the count), K3 finishes inside each wave.  One 5 us launch instead of three
@@ -615,159 +617,373 @@ static int trace_fwd_impl(gut_handle h, void* stream_, uint32_t frame_number, in
         gut::launch_scan_wave_sums(s, n, h->wave_sums.as<uint32_t>(), h->block_prefix.as<uint32_t>(), h->scan_total.as<uint32_t>(),
                                    h->host_count_dev, h->walk_sums.as<uint32_t>(), clears.tile_entries, (uint32_t)tiles,
                                    h->tile_start.as<uint32_t>(), h->tile_cursor.as<uint32_t>());
-        // intersection count read-back (gutRenderer.cu:313-321).  The reference blocks on it before it can size the
-        // binning buffers; here the copy is queued and the host only waits for it AFTER the rest of the forward has been
-        // queued against a capacity taken from the previous frames (m_capacity), so the GPU never idles on the host.
-        // The scan kernel writes the count — and with it the walked share of the last frame that had a backward (k_tile_order's
-        // walk_sums; see launch_render below) — straight into the pinned host words; the event below orders the host's read.
+        // intersection count read-back (gutRenderer.cu:313-321).  The reference blocks on it before it can size the binning buffers;
+        // here the host only waits for it (wait_for_count) AFTER the rest of the forward has been queued against a capacity taken
+        // from the previous frames (m_capacity), so the GPU never idles on the host.  The scan kernel writes the count — and with it
+        // the walked share of the last frame that had a backward — straight into the pinned host words; the event orders the host's read.
         if (!h->count_event) HIP_TRY(hipEventCreateWithFlags(&h->count_event, kOrderingEvent));
         HIP_TRY(hipEventRecord(h->count_event, s));
-        count_pending = true;
     }
-    mark(2);
-    // One binning + compositing pass over `sort_n` list slots (>= the real count, the tail is padding).  Returns through
-    // the lambda so that the rare overflow can run it a second time.
-    auto bin_and_render = [&](uint32_t sort_n, bool lazy) -> int {
-        h->lazy_order = lazy;
-        if (sort_n && lazy) {
+    mark(h, s, f->timing, 2);
+    return 0;
+}
+
+// The forward's single host synchronisation: the frame's intersection count.  host_count[2], [3] came with it: sum of the traversal
+// depths / of the list lengths of the last frame that had a backward.
+int wait_for_count(gut_handle h, uint32_t* m) {
+    HIP_TRY(hipEventSynchronize(h->count_event));
+    *m = h->host_count[0];
+    const uint32_t walked = h->host_count[2], listed = h->host_count[3];
+    if (h->walk_sums.p && listed) h->fwd_longest_first = (double)walked > 0.25 * (double)listed;
+    return 0;
+}
+
+// (the k-buffer variant walks whole lists: it keeps the full sort, as do frames whose lists are too long on average to re-scan per 512 entries)
+bool want_lazy(gut_handle h, int tiles, uint64_t count) {
+    return h->lazy_enabled && h->cfg.k_buffer_size == 0 && count != 0 && count < (uint64_t)tiles * 16384ull;
+}
+
+// One binning + compositing pass over `sort_n` list slots (>= the real count, the tail is padding); the rare overflow runs it twice.
+int bin_and_render(gut_handle h, const TraceView& view, const FwdFrame& f, const float* d_particle_density, const FwdOutputs& out,
+                   uint32_t sort_n) {
+    const hipStream_t s = view.stream;
+    const int tiles = f.tiles;
+    const bool lazy = h->lazy_order = want_lazy(h, tiles, sort_n);
+    if (sort_n && !lazy) {
+        HIP_TRY(h->keys_unsorted.ensure(sizeof(uint64_t) * (size_t)sort_n));
+        HIP_TRY(h->keys_sorted.ensure(sizeof(uint64_t) * (size_t)sort_n));
+        HIP_TRY(h->ids_unsorted.ensure(sizeof(uint32_t) * (size_t)sort_n));
+        HIP_TRY(h->ids_sorted.ensure(sizeof(uint32_t) * (size_t)sort_n));
+        gut::launch_expand(s, f.v, h->consts, view.n, h->tiles_count.as<uint32_t>(), h->wave_sums.as<uint32_t>(),
+                           h->block_prefix.as<uint32_t>(), f.d_count, h->proj_pos.as<float>(), h->conic_opacity.as<float>(),
+                           h->extent.as<float>(), h->depth.as<float>(), h->keys_unsorted.as<uint64_t>(), h->ids_unsorted.as<uint32_t>(), sort_n);
+        mark(h, s, f.timing, 3);
+        HIP_TRY(h->sort_temp.ensure(gut::sort_temp_bytes(sort_n, f.end_bit)));
+        HIP_TRY(gut::run_sort(s, h->sort_temp.p, h->sort_temp.cap, h->keys_unsorted.as<uint64_t>(), h->keys_sorted.as<uint64_t>(),
+                              h->ids_unsorted.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), sort_n, f.end_bit));
+        mark(h, s, f.timing, 4);
+        gut::launch_tile_ranges(s, sort_n, h->keys_sorted.as<uint64_t>(), h->ranges.as<uint32_t>());
+    } else {
+        if (lazy) {   // (then sort_n != 0)
             // grouped binning: each entry goes straight into its tile's slice (slices from K1's per-tile counts and the scan), the
             // compositor orders every tile itself — no expansion into (tile | depth) keys, no sort, no K5.  The kernel-timer marks
             // of the sort and the ranges follow at once.
             HIP_TRY(h->keys_sorted.ensure(sizeof(uint64_t) * (size_t)sort_n));
             HIP_TRY(h->ids_ordered.ensure(sizeof(uint32_t) * (size_t)sort_n));
-            gut::launch_expand_grouped(s, v, h->consts, n, h->proj_pos.as<float>(), h->conic_opacity.as<float>(), h->extent.as<float>(),
+            gut::launch_expand_grouped(s, f.v, h->consts, view.n, h->proj_pos.as<float>(), h->conic_opacity.as<float>(), h->extent.as<float>(),
                                        h->depth.as<float>(), (uint32_t)tiles, h->tile_start.as<uint32_t>(), h->tile_cursor.as<uint32_t>(),
                                        h->ranges.as<uint32_t>(), h->keys_sorted.as<uint64_t>(), sort_n);
-            mark(3);
-            mark(4);
-        } else if (sort_n) {
-            HIP_TRY(h->keys_unsorted.ensure(sizeof(uint64_t) * (size_t)sort_n));
-            HIP_TRY(h->keys_sorted.ensure(sizeof(uint64_t) * (size_t)sort_n));
-            HIP_TRY(h->ids_unsorted.ensure(sizeof(uint32_t) * (size_t)sort_n));
-            HIP_TRY(h->ids_sorted.ensure(sizeof(uint32_t) * (size_t)sort_n));
-            gut::launch_expand(s, v, h->consts, n, h->tiles_count.as<uint32_t>(), h->wave_sums.as<uint32_t>(),
-                               h->block_prefix.as<uint32_t>(), d_count, h->proj_pos.as<float>(),
-                               h->conic_opacity.as<float>(), h->extent.as<float>(), h->depth.as<float>(),
-                               h->keys_unsorted.as<uint64_t>(), h->ids_unsorted.as<uint32_t>(), sort_n);
-            mark(3);
-            HIP_TRY(h->sort_temp.ensure(gut::sort_temp_bytes(sort_n, end_bit)));
-            HIP_TRY(gut::run_sort(s, h->sort_temp.p, h->sort_temp.cap, h->keys_unsorted.as<uint64_t>(), h->keys_sorted.as<uint64_t>(),
-                                  h->ids_unsorted.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), sort_n, end_bit));
-            mark(4);
-            gut::launch_tile_ranges(s, sort_n, h->keys_sorted.as<uint64_t>(), h->ranges.as<uint32_t>());
-        } else {
-            mark(3);
-            mark(4);
         }
-        mark(5);
-        // the side-stream optimiser pass may start here: tiles_count is final and the HBM-bound part of the forward
-        // (projection, scan, expansion, sort) is over — what follows on this stream is VALU-bound compositing
-        if (!early_after_project) {
-            if (!h->ev_projected) HIP_TRY(hipEventCreateWithFlags(&h->ev_projected, kOrderingEvent));
-            HIP_TRY(hipEventRecord(h->ev_projected, s));
-        }
-        // with zero intersections the reference returns its freshly initialised outputs (gutRenderer.cu:323-325);
-        // running the compositor over empty ranges writes exactly those values
-        if (h->cfg.k_buffer_size > 0) {
-            HIP_TRY(hipMemsetAsync(h->trav_fwd.p, 0, sizeof(uint32_t) * (size_t)tiles, s));
-            gut::launch_render_sorted(s, v, h->consts, h->cfg.k_buffer_size, d_particle_density, h->feat.as<float>(), d_ray_origin,
-                                      d_ray_direction, h->ranges.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), d_count,
-                                      d_ray_radiance_density, d_ray_hit_distance, d_ray_hit_count, h->cfg.particle_kernel_degree);
-        } else {
-            // Longest lists first (as the backward launches its deepest tiles first), when the frames before this one walked a good part
-            // of their lists — then a tile's list length says how long it will run, and the few long ones must not form the tail of
-            // the grid: surface-like stand-in (E/M = 0.46) K6 1.36 -> 1.15 ms; where whole-tile termination leaves most of every list
-            // untouched (headline stand-in, E/M = 0.12) the length says little and the natural order keeps neighbouring tiles, which
-            // share Gaussians, together in time (0.52 -> 0.53 ms with the order, plus its 8 us launch).  The walked share comes from
-            // the backward's own ordering kernel (walk_sums), read back with the intersection count: no extra synchronisation.
-            const bool fwd_order = h->fwd_order_mode >= 0 ? h->fwd_order_mode != 0 : h->fwd_longest_first;   // GUT_OPT_FORWARD_TILE_ORDER
-            if (fwd_order && sort_n)
-                gut::launch_tile_order(s, (uint32_t)tiles, nullptr, h->tile_order.as<uint32_t>(), h->ranges.as<uint32_t>(), true);
-            gut::launch_render(s, v, h->consts, d_particle_density, h->feat.as<float>(), d_ray_origin, d_ray_direction,
-                               h->ranges.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), d_count, d_ray_radiance_density,
-                               d_ray_hit_distance, d_ray_hit_count, h->trav_fwd.as<uint32_t>(),
-                               lazy ? h->keys_sorted.as<uint64_t>() : nullptr, lazy ? h->ids_ordered.as<uint32_t>() : nullptr,
-                               lazy ? h->tile_ordered.as<uint32_t>() : nullptr,
-                               (fwd_order && sort_n) ? h->tile_order.as<uint32_t>() : nullptr, h->cfg.particle_kernel_degree);
-        }
-        // render.enable_hitcounts = false: the reference compiles the counter out (rayPayload.cuh:44-46,69-73,126-128) and its
-        // output tensor keeps the zeros it was created with (splatRaster.cpp:198).  Not a configuration worth a kernel variant.
-        if (!h->cfg.enable_hitcounts) HIP_TRY(hipMemsetAsync(d_ray_hit_count, 0, sizeof(float) * (size_t)width * (size_t)height, s));
-        return 0;
-    };
-    // the k-buffer variant walks whole lists: it keeps the full sort
-    // ... and frames whose tile lists are so long on average that re-scanning them per 512 ordered entries cannot pay
-    auto want_lazy = [&](uint64_t count) {
-        return h->lazy_enabled && h->cfg.k_buffer_size == 0 && count != 0 && count < (uint64_t)tiles * 16384ull;
-    };
-    if (n && h->m_capacity == 0) {
-        // first frame on this handle (or after a reset): nothing to size from, wait for the count like the reference
-        HIP_TRY(hipEventSynchronize(h->count_event));
-        count_pending = false;
-        m = *h->host_count;
-        update_fwd_order(h);
-        if (bin_and_render(m, want_lazy(m))) return 1;
+        mark(h, s, f.timing, 3);
+        mark(h, s, f.timing, 4);
+    }
+    mark(h, s, f.timing, 5);
+    // the side-stream optimiser pass may start here: tiles_count is final and the HBM-bound part of the forward
+    // (projection, scan, expansion, sort) is over — what follows on this stream is VALU-bound compositing
+    if (!f.early_after_project) {
+        if (!h->ev_projected) HIP_TRY(hipEventCreateWithFlags(&h->ev_projected, kOrderingEvent));
+        HIP_TRY(hipEventRecord(h->ev_projected, s));
+    }
+    // with zero intersections the reference returns its freshly initialised outputs (gutRenderer.cu:323-325);
+    // running the compositor over empty ranges writes exactly those values
+    if (h->cfg.k_buffer_size > 0) {
+        HIP_TRY(hipMemsetAsync(h->trav_fwd.p, 0, sizeof(uint32_t) * (size_t)tiles, s));
+        gut::launch_render_sorted(s, f.v, h->consts, h->cfg.k_buffer_size, d_particle_density, h->feat.as<float>(), view.ray_origin,
+                                  view.ray_direction, h->ranges.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), f.d_count,
+                                  out.rgba, out.hit_distance, out.hit_count, h->cfg.particle_kernel_degree);
     } else {
-        const uint32_t sort_n = n ? h->m_capacity : 0u;
-        if (bin_and_render(sort_n, want_lazy(sort_n))) return 1;
-        if (count_pending) {
-            HIP_TRY(hipEventSynchronize(h->count_event));  // everything is queued: the GPU keeps working while the host waits here
-            count_pending = false;
-            m = *h->host_count;
-            update_fwd_order(h);
-        update_fwd_order(h);
-        }
-        if (m > sort_n) {
-            // the frame has more intersections than the capacity assumed: entries beyond it were dropped by the expansion.
-            // Redo binning and compositing with the real count (same stream: the second pass simply overwrites the first).  The
-            // grouped binning (lazy order; then the first pass had it too) restarts its slots, K5 its ranges.
-            if (want_lazy(m))
-                HIP_TRY(hipMemcpyAsync(h->tile_cursor.p, h->tile_start.p, sizeof(uint32_t) * (size_t)tiles, hipMemcpyDeviceToDevice, s));
-            else
-                HIP_TRY(hipMemsetAsync(h->ranges.p, 0, sizeof(uint32_t) * 2 * (size_t)tiles, s));
-            h->overflows++;
-            if (bin_and_render(m, want_lazy(m))) return 1;
-            h->sort_n = m;
-        } else {
-            h->sort_n = sort_n;
-        }
+        // Longest lists first (as the backward launches its deepest tiles first), when the frames before this one walked a good part
+        // of their lists: then a tile's list length says how long it will run, and the few long ones must not form the tail of the
+        // grid; otherwise the natural order, which keeps neighbouring tiles together in time (DESIGN.md has the measurements).  The
+        // walked share comes from the backward's own ordering kernel (walk_sums), read back with the intersection count.
+        const bool fwd_order = h->fwd_order_mode >= 0 ? h->fwd_order_mode != 0 : h->fwd_longest_first;   // GUT_OPT_FORWARD_TILE_ORDER
+        if (fwd_order && sort_n)
+            gut::launch_tile_order(s, (uint32_t)tiles, nullptr, h->tile_order.as<uint32_t>(), h->ranges.as<uint32_t>(), true);
+        gut::launch_render(s, f.v, h->consts, d_particle_density, h->feat.as<float>(), view.ray_origin, view.ray_direction,
+                           h->ranges.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), f.d_count, out.rgba, out.hit_distance, out.hit_count,
+                           h->trav_fwd.as<uint32_t>(), lazy ? h->keys_sorted.as<uint64_t>() : nullptr,
+                           lazy ? h->ids_ordered.as<uint32_t>() : nullptr, lazy ? h->tile_ordered.as<uint32_t>() : nullptr,
+                           (fwd_order && sort_n) ? h->tile_order.as<uint32_t>() : nullptr, h->cfg.particle_kernel_degree);
     }
-    if (n && h->m_capacity == 0) h->sort_n = m;
-    // capacity for the next frame: a little above the largest recent count (slowly forgetting old peaks), multiple of 4096
-    {
-        const double decayed = (double)h->m_peak * 0.999;
-        h->m_peak = (uint32_t)((double)m > decayed ? (double)m : decayed);
-        const uint64_t want = (uint64_t)((double)h->m_peak * 1.03) + 4096ull;
-        h->m_capacity = m || h->m_peak ? (uint32_t)(((want + 4095ull) / 4096ull) * 4096ull) : 0u;
-    }
-    mark(6);
-    HIP_TRY(hipGetLastError());
-    if (total) {
-        (void)hipEventRecord(total->b, s);
-        total->armed = true;
-    }
-    h->kev_fwd_valid = timing;
-    if (timing) h->ring[h->ring_cur].fwd = true;
-    if (h->cfg.enable_kernel_timings != 0 && (h->timing_main_stream || h->timing_side_stream) && h->ring_count < gut_context::kRing) h->ring_count++;
-    h->have_forward = true;
-    h->fwd_stream = s;
-    h->n = n;
-    h->m = m;
-    h->width = width;
-    h->height = height;
-    h->tiles = tiles;
-    h->sh_degree = num_active_features;
-    h->end_bit = end_bit;
-    h->view = v;
+    // render.enable_hitcounts = false: the reference compiles the counter out (rayPayload.cuh:44-46,69-73,126-128) and its
+    // output tensor keeps the zeros it was created with (splatRaster.cpp:198).  Not a configuration worth a kernel variant.
+    if (!h->cfg.enable_hitcounts)
+        HIP_TRY(hipMemsetAsync(out.hit_count, 0, sizeof(float) * (size_t)view.width * (size_t)view.height, s));
     return 0;
 }
 
+// The frame has more intersections (m) than the capacity it was binned into: entries beyond it were dropped by the expansion.  Before
+// bin_and_render runs again with the real count (same stream: the second pass simply overwrites the first), the grouped binning (lazy
+// order; then the first pass had it too) restarts its slots, K5 its ranges.
+int restart_overflowed_binning(gut_handle h, hipStream_t s, int tiles, uint32_t m) {
+    if (want_lazy(h, tiles, m))
+        HIP_TRY(hipMemcpyAsync(h->tile_cursor.p, h->tile_start.p, sizeof(uint32_t) * (size_t)tiles, hipMemcpyDeviceToDevice, s));
+    else
+        HIP_TRY(hipMemsetAsync(h->ranges.p, 0, sizeof(uint32_t) * 2 * (size_t)tiles, s));
+    h->overflows++;
+    return 0;
+}
+
+// the capacity for the next frame, the end of the frame's timers and the context the backward is checked against
+int finish_forward(gut_handle h, const TraceView& view, const FwdFrame& f, uint32_t m) {
+    // a little above the largest recent count (slowly forgetting old peaks), multiple of 4096
+    const double decayed = (double)h->m_peak * 0.999;
+    h->m_peak = (uint32_t)((double)m > decayed ? (double)m : decayed);
+    const uint64_t want = (uint64_t)((double)h->m_peak * 1.03) + 4096ull;
+    h->m_capacity = m || h->m_peak ? (uint32_t)(((want + 4095ull) / 4096ull) * 4096ull) : 0u;
+    mark(h, view.stream, f.timing, 6);
+    HIP_TRY(hipGetLastError());
+    end_timer(f.total, view.stream);
+    h->kev_fwd_valid = f.timing;
+    if (f.timing) h->ring[h->ring_cur].fwd = true;
+    if (h->cfg.enable_kernel_timings != 0 && (h->timing_main_stream || h->timing_side_stream) && h->ring_count < gut_context::kRing) h->ring_count++;
+    h->have_forward = true; h->fwd_stream = view.stream;
+    h->n = view.n; h->m = m; h->sh_degree = view.sh_degree;
+    h->width = view.width; h->height = view.height; h->tiles = f.tiles; h->end_bit = f.end_bit;
+    h->view = f.v;
+    return 0;
+}
+
+int trace_fwd_impl(gut_handle h, const TraceView& view, const float* d_particle_density, const float* d_particle_radiance,
+                   const float* d_features_albedo, const FwdOutputs& out) {
+    if (check_forward_args(h, view, d_particle_density, d_particle_radiance, d_features_albedo, out)) return 1;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dev_guard;
+    HIP_TRY(dev_guard.set(h->device));
+    FwdFrame f;
+    if (build_view(view.camera, view.width, view.height, h->cfg.n_rolling_shutter_iterations, &f.v)) return 1;
+    f.tiles = f.v.grid_x * f.v.grid_y;
+    if ((uint64_t)f.tiles >= 0xFFFFFFFFull) return fail("gut_trace: too many tiles");
+    if (h->early_ran)
+        return fail("gut_trace: gut_optimize_rows_without_gradient was called for the previous forward but gut_optimize_after_bwd "
+                    "was not: that optimiser step is half applied");
+    if (h->early_wait_pending) {  // (only reachable after an error path; the optimiser call normally orders the streams)
+        HIP_TRY(hipStreamWaitEvent(view.stream, h->ev_early_done, 0));
+        h->early_wait_pending = false;
+    }
+    h->have_forward = h->have_backward = h->marks_valid = h->packed_valid = false;   // (trace_fwd_packed sets packed_valid again on success)
+    if (ensure_frame_scratch(h, view.stream, view.n, f.tiles)) return 1;
+    begin_frame_timing(h, view.stream, &f);
+    if (queue_projection_and_scan(h, view, d_particle_density, d_particle_radiance, d_features_albedo, out.visibility, &f)) return 1;
+    uint32_t m = 0, sort_n = 0;   // the frame's intersection count, the list slots it was binned into
+    if (view.n && h->m_capacity == 0) {
+        // first frame on this handle (or after a reset): nothing to size from, wait for the count like the reference
+        if (wait_for_count(h, &m)) return 1;
+        sort_n = m;
+        if (bin_and_render(h, view, f, d_particle_density, out, sort_n)) return 1;
+    } else {
+        sort_n = view.n ? h->m_capacity : 0u;
+        if (bin_and_render(h, view, f, d_particle_density, out, sort_n)) return 1;
+        if (view.n && wait_for_count(h, &m)) return 1;  // everything is queued: the GPU keeps working while the host waits here
+        if (m > sort_n) {
+            sort_n = m;
+            if (restart_overflowed_binning(h, view.stream, f.tiles, m) || bin_and_render(h, view, f, d_particle_density, out, sort_n)) return 1;
+        }
+    }
+    h->sort_n = sort_n;
+    return finish_forward(h, view, f, m);
+}
+
+// The three *_fields forwards (`name` in their messages).  The [N,12] rows are packed (`raw`: activated and packed) from the caller's four
+// tensors into handle scratch by `pack`, where they stay for the backward; then the forward runs on them.  split_sh: d_particle_radiance
+// is features_specular [N,45] and goes with d_features_albedo [N,3]; otherwise it is the [N,48] rows and d_features_albedo is unused.
+using PackLauncher = void (*)(hipStream_t, uint32_t, const float*, const float*, const float*, const float*, float*);
+int trace_fwd_packed(gut_handle h, const char* name, PackLauncher pack, bool raw, const TraceView& view, const float* d_positions,
+                     const float* d_density, const float* d_rotation, const float* d_scale, const float* d_particle_radiance,
+                     const float* d_features_albedo, bool split_sh, const FwdOutputs& out) {
+    if (!h) return fail("%s: null handle", name);
+    if (view.n && (!d_positions || !d_density || !d_rotation || !d_scale || (split_sh && (!d_features_albedo || !d_particle_radiance))))
+        return fail("%s: null particle buffers with %u particles", name, view.n);
+    if ((((uintptr_t)d_rotation | (split_sh ? (uintptr_t)d_particle_radiance : 0u)) & 15u) != 0)
+        return fail("%s: the rotation %s must be 16-byte aligned", name, split_sh ? "and features_specular tensors" : "tensor");
+    {   // invalidates whatever the scratch held; it is valid again once the forward has succeeded
+        std::lock_guard<std::mutex> lock(h->mu);
+        DeviceGuard dev_guard;
+        HIP_TRY(dev_guard.set(h->device));
+        h->packed_valid = h->packed_raw = false;
+        HIP_TRY(h->packed12.ensure(sizeof(float) * 12 * (size_t)view.n + 64));
+        pack(view.stream, view.n, d_positions, d_density, d_rotation, d_scale, h->packed12.as<float>());
+        HIP_TRY(hipGetLastError());
+    }
+    if (trace_fwd_impl(h, view, h->packed12.as<float>(), d_particle_radiance, split_sh && view.n ? d_features_albedo : nullptr, out)) return 1;
+    h->packed_valid = true; h->packed_raw = raw;
+    return 0;
+}
+
+// how the consuming reduction zeroes: it reads the whole row and stores only where a word is set (the default, the faster form on the
+// 6 M-Gaussian workload, DESIGN.md §12), or GUT_POSE_CONSUME=store for measurements: four unconditional zero stores per visited row
+bool pose_consume_tests() {
+    static const bool tests = [] {
+        const char* e = getenv("GUT_POSE_CONSUME");
+        return !(e && strcmp(e, "store") == 0);
+    }();
+    return tests;
+}
+
+// every refusal of a backward that needs no view parameters; under the handle's lock, nothing is queued or changed
+int check_backward_args(gut_handle h, const TraceView& view, const BwdUpstream& up, const BwdArgs& a) {
+    // same contract as the reference: backward needs the forward's cached context on the same stream (gutRenderer.cu:413-417)
+    if (!h->have_forward || h->fwd_stream != view.stream)
+        return fail("gut_trace_bwd: no forward context on this stream (call gut_trace first, same stream)");
+    if (view.n != h->n || view.width != h->width || view.height != h->height || view.sh_degree != h->sh_degree)
+        return fail("gut_trace_bwd: arguments differ from the cached forward (N %u vs %u, %dx%d vs %dx%d)", view.n, h->n,
+                    view.width, view.height, h->width, h->height);
+    // (up.hit_distance_grad == NULL: no loss on pred_dist, the reference trainer's default; its terms are compiled out of the kernel)
+    if (!view.camera || !view.ray_origin || !view.ray_direction || !up.rgba || !up.rgba_grad)
+        return fail("gut_trace_bwd: null pointer argument");
+    if (view.n && (!a.density || (has_epilogue(a.mode) && !a.fields.pos && (!a.density_grad || !a.radiance_grad))))
+        return fail("gut_trace_bwd: null particle buffers");
+    if (h->early_ran && a.mode != BwdMode::kSkipEpilogue)
+        return fail("gut_trace_bwd: gut_optimize_rows_without_gradient was called for this forward: the backward must be "
+                    "gut_trace_bwd_ex(..., GUT_BWD_SKIP_EPILOGUE) followed by gut_optimize_after_bwd");
+    if (a.mode == BwdMode::kPoseOnly) {
+        if (!h->pose_out) return fail("gut_trace_bwd_pose: no pose output is set (gut_set_pose_gradient)");
+        if (h->m && h->cfg.k_buffer_size > 0 && !up.hit_distance) return fail("gut_trace_bwd: the sorted variant needs d_ray_hit_distance");
+    }
+    if (h->cfg.particle_radiance_sph_degree != 3 && has_epilogue(a.mode) && (a.mode == BwdMode::kCompact || a.fields.alb))
+        return fail("gut_trace_bwd: particle_radiance_sph_degree=%d supports the packed radiance gradient only", h->cfg.particle_radiance_sph_degree);
+    // the pose gradient is the rigid-motion reduction of the gradient rows: it means something for ONE pose per view only
+    if (h->pose_out)
+        for (int k = 0; k < 7; ++k)
+            if (view.camera->pose_start[k] != view.camera->pose_end[k])
+                return fail("gut_trace_bwd: a pose gradient is set (gut_set_pose_gradient) and the view's start and end poses differ: "
+                            "the reduction is defined for pose_start == pose_end only");
+    return 0;
+}
+
+// K7, the backward compositor of the cached forward's variant: adds to the handle's gradient rows
+int queue_bwd_compositor(gut_handle h, const TraceView& view, const gut::ViewParams& v, const BwdUpstream& up, const float* d_particle_density) {
+    const hipStream_t s = view.stream;
+    if (h->m && h->cfg.k_buffer_size > 0) {
+        if (!up.hit_distance) return fail("gut_trace_bwd: the sorted variant needs d_ray_hit_distance");
+        HIP_TRY(hipMemsetAsync(h->trav_bwd.p, 0, sizeof(uint32_t) * (size_t)h->tiles, s));
+        gut::launch_render_sorted_bwd(s, v, h->consts, h->cfg.k_buffer_size, d_particle_density, h->feat.as<float>(), view.ray_origin,
+                                      view.ray_direction, h->ranges.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), up.rgba, up.hit_distance,
+                                      up.rgba_grad, up.hit_distance_grad, h->grad16.as<float>(), h->sorted_reference_bwd, h->cfg.particle_kernel_degree);
+    } else if (h->m) {
+        HIP_TRY(h->walk_sums.ensure(2 * sizeof(uint32_t)));
+        gut::launch_tile_order(s, (uint32_t)h->tiles, h->trav_fwd.as<uint32_t>(), h->tile_order.as<uint32_t>(), h->ranges.as<uint32_t>(), false,
+                               h->walk_sums.as<uint32_t>());
+        gut::launch_render_bwd(s, v, h->consts, d_particle_density, h->feat.as<float>(), view.ray_origin, view.ray_direction,
+                               h->ranges.as<uint32_t>(), (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(),
+                               up.rgba, up.rgba_grad, up.hit_distance_grad, h->grad16.as<float>(),
+                               h->trav_bwd.as<uint32_t>(), h->tile_order.as<uint32_t>(), h->trav_fwd.as<uint32_t>(), h->cfg.particle_kernel_degree);
+    }
+    return 0;
+}
+
+// the per-Gaussian epilogue (K8) in its dense or compact form; leaves the gradient rows it read zero
+void queue_bwd_epilogue(gut_handle h, hipStream_t s, const gut::ViewParams& v, const BwdArgs& a, float* narrow_radiance_grad) {
+    float* const d_radiance_grad = narrow_radiance_grad ? h->sph_grad_wide.as<float>() : a.radiance_grad;
+    if (a.mode == BwdMode::kCompact)
+        gut::launch_project_bwd_compact(s, h->n, a.density, h->tiles_count.as<uint32_t>(), h->feat.as<float>(),
+                                        h->grad16.as<float>(), a.density_grad, d_radiance_grad);
+    else
+        gut::launch_project_bwd(s, v, h->n, h->sh_degree, a.density, h->tiles_count.as<uint32_t>(), h->feat.as<float>(),
+                                h->grad16.as<float>(), a.density_grad, d_radiance_grad, a.raw_grads, a.fields);
+    if (narrow_radiance_grad) {
+        const uint32_t w = 3u * (uint32_t)((h->cfg.particle_radiance_sph_degree + 1) * (h->cfg.particle_radiance_sph_degree + 1));
+        gut::launch_resize_sph_rows(s, h->n, 48u, w, h->sph_grad_wide.as<float>(), narrow_radiance_grad);
+    }
+}
+
+int trace_bwd_impl(gut_handle h, const TraceView& view, const BwdUpstream& up, const BwdArgs& a) {
+    if (!h) return fail("gut_trace_bwd: null handle");
+    std::lock_guard<std::mutex> lock(h->mu);
+    const hipStream_t s = view.stream;
+    if (check_backward_args(h, view, up, a)) return 1;
+    DeviceGuard dev_guard;
+    HIP_TRY(dev_guard.set(h->device));
+    gut::ViewParams v;
+    if (build_view(view.camera, view.width, view.height, h->cfg.n_rolling_shutter_iterations, &v)) return 1;
+    if (memcmp(&v, &h->view, sizeof(v)) != 0) return fail("gut_trace_bwd: camera differs from the cached forward");
+    const uint32_t n = h->n;
+    if (n == 0) {
+        if (h->pose_out) HIP_TRY(hipMemsetAsync(h->pose_out, 0, 8 * sizeof(float), s));   // no rows: F = M = 0, none summed
+        return 0;
+    }
+    if (h->pose_out) HIP_TRY(h->pose_partials.ensure(gut::pose_gradient_scratch_bytes()));
+    const void* const grad16_before = h->grad16.p;
+    HIP_TRY(h->grad16.ensure(sizeof(float) * 16 * (size_t)n));
+    if (h->grad16.p != grad16_before) h->grad16_zero = false;  // fresh allocation
+    // particle_radiance_sph_degree < 3: the epilogue writes [N,48] scratch, narrowed to the caller's [N, 3 (degree + 1)^2] gradient
+    float* const narrow_radiance_grad = h->cfg.particle_radiance_sph_degree != 3 && has_epilogue(a.mode) ? a.radiance_grad : nullptr;
+    if (narrow_radiance_grad) HIP_TRY(h->sph_grad_wide.ensure(sizeof(float) * 48 * (size_t)n));
+    const bool timing = h->cfg.enable_kernel_timings != 0 && h->timing_main_stream;
+    EventPair* total = timing ? arm_timer(h->bwd_timers, s) : nullptr;
+    h->kev_bwd_valid = false;
+    mark(h, s, timing, 8);
+    // the gradient rows are zero already unless this is the first backward or the previous one was never consumed (every
+    // per-Gaussian consumer below zeroes the rows it reads, so there is no 64 N-byte clear per step)
+    if (!h->grad16_zero) HIP_TRY(hipMemsetAsync(h->grad16.p, 0, h->grad16.cap, s));
+    h->grad16_zero = false;
+    if (launch_early_part2(h, s)) return 1;
+    mark(h, s, timing, 9);
+    if (queue_bwd_compositor(h, view, v, up, a.density)) return 1;
+    mark(h, s, timing, 10);
+    // right behind the backward compositor and before any epilogue: the epilogues zero the gradient rows as they read them
+    // (behind the mark that ends render_bwd's timer: the two launches count towards project_bwd, not towards K7)
+    if (a.mode == BwdMode::kPoseOnly)
+        gut::launch_pose_gradient_consume(s, n, h->tiles_count.as<uint32_t>(), h->grad16.as<float>(), a.density,
+                                          h->cam_pos.as<float>(), h->pose_partials.as<float>(), h->pose_out, pose_consume_tests());
+    else if (h->pose_out)
+        gut::launch_pose_gradient(s, n, h->tiles_count.as<uint32_t>(), h->grad16.as<float>(), a.density, h->cam_pos.as<float>(),
+                                  h->pose_partials.as<float>(), h->pose_out);
+    if (has_epilogue(a.mode)) queue_bwd_epilogue(h, s, v, a, narrow_radiance_grad);
+    // the reduction or the epilogue zeroed every row K7 could have touched (the rows with tiles); kSkipEpilogue leaves them to the caller
+    if (a.mode != BwdMode::kSkipEpilogue) h->grad16_zero = true;
+    mark(h, s, timing, 11);
+    HIP_TRY(hipGetLastError());
+    end_timer(total, s);
+    h->kev_bwd_valid = timing;
+    if (timing) h->ring[h->ring_cur].bwd = true;
+    h->have_backward = a.mode != BwdMode::kPoseOnly;   // (gut_optimize_after_bwd / gut_compact_gradient_rows have nothing to follow a pose-only one)
+    return 0;
+}
+
+// The two *_fields backwards (`name` and `forwards` in their messages): the forward must have packed the rows, the split gradient
+// tensors of `f` (and d_particle_radiance_grad [N,48] unless f carries the SH gradient as f.alb / f.spec: split_sh) must be there.
+int trace_bwd_packed(gut_handle h, const char* name, const char* forwards, const TraceView& view, const BwdUpstream& up,
+                     const gut::GradFields& f, float* d_particle_radiance_grad, bool split_sh) {
+    if (!h) return fail("%s: null handle", name);
+    if (!h->packed_valid) return fail("%s: no %s forward on this handle", name, forwards);
+    if (view.n && (!f.pos || !f.dns || !f.rot || !f.scl || (split_sh ? (!f.alb || !f.spec) : !d_particle_radiance_grad)))
+        return fail("%s: null gradient buffers", name);
+    if ((((uintptr_t)f.rot | (split_sh ? (uintptr_t)f.spec : 0u)) & 15u) != 0)
+        return fail("%s: the rotation %s must be 16-byte aligned", name, split_sh ? "and features_specular gradients" : "gradient");
+    // (after gut_trace_raw_model_fields the rows carry |quat| in the pad column and the gradients are chained to the raw tensors)
+    return trace_bwd_impl(h, view, up, BwdArgs{BwdMode::kDense, split_sh && h->packed_raw, h->packed12.as<float>(), nullptr,
+                                               d_particle_radiance_grad, f});
+}
+
+}  // namespace
+
+extern "C" {
+
+int gut_trace(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+              const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
+              const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
+              float* d_ray_radiance_density, float* d_ray_hit_distance, float* d_ray_hit_count,
+              float* d_particle_visibility) {
+    return trace_fwd_impl(h, view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                          d_particle_density, d_particle_radiance, nullptr,
+                          FwdOutputs{d_ray_radiance_density, d_ray_hit_distance, d_ray_hit_count, d_particle_visibility});
+}
+
+// (of several flags, GUT_BWD_SKIP_EPILOGUE goes before GUT_BWD_COMPACT_RADIANCE_GRADS, and that before GUT_BWD_RAW_PARAMETER_GRADS)
 int gut_trace_bwd_ex(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
                      const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
                      const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
                      const float* d_ray_radiance_density, const float* d_ray_radiance_density_grad,
                      const float* d_ray_hit_distance, const float* d_ray_hit_distance_grad, float* d_particle_density_grad,
-                     float* d_particle_radiance_grad, uint32_t flags);
+                     float* d_particle_radiance_grad, uint32_t flags) {
+    const BwdMode mode = (flags & GUT_BWD_SKIP_EPILOGUE) ? BwdMode::kSkipEpilogue
+                         : (flags & GUT_BWD_COMPACT_RADIANCE_GRADS) ? BwdMode::kCompact : BwdMode::kDense;
+    return trace_bwd_impl(h, view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                          BwdUpstream{d_ray_radiance_density, d_ray_radiance_density_grad, d_ray_hit_distance, d_ray_hit_distance_grad},
+                          BwdArgs{mode, (flags & GUT_BWD_RAW_PARAMETER_GRADS) != 0, d_particle_density, d_particle_density_grad,
+                                  d_particle_radiance_grad, gut::GradFields()});
+}
 
 int gut_trace_bwd(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
                   const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
@@ -779,27 +995,6 @@ int gut_trace_bwd(gut_handle h, void* stream_, uint32_t frame_number, int32_t nu
                             width, height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density,
                             d_ray_radiance_density_grad, d_ray_hit_distance, d_ray_hit_distance_grad, d_particle_density_grad,
                             d_particle_radiance_grad, 0u);
-}
-
-static int trace_bwd_impl(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
-                          const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
-                          const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
-                          const float* d_ray_radiance_density, const float* d_ray_radiance_density_grad,
-                          const float* d_ray_hit_distance, const float* d_ray_hit_distance_grad, float* d_particle_density_grad,
-                          float* d_particle_radiance_grad, uint32_t flags, const gut::GradFields& fields);
-// internal flag of trace_bwd_impl (never taken from a caller): gut_trace_bwd_pose, the compositor and the consuming reduction alone
-static constexpr uint32_t kBwdPoseOnly = 0x80000000u;
-
-int gut_trace_bwd_ex(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
-                     const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
-                     const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
-                     const float* d_ray_radiance_density, const float* d_ray_radiance_density_grad,
-                     const float* d_ray_hit_distance, const float* d_ray_hit_distance_grad, float* d_particle_density_grad,
-                     float* d_particle_radiance_grad, uint32_t flags) {
-    return trace_bwd_impl(h, stream_, frame_number, num_active_features, num_particles, d_particle_density, d_particle_radiance, width,
-                          height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density, d_ray_radiance_density_grad,
-                          d_ray_hit_distance, d_ray_hit_distance_grad, d_particle_density_grad, d_particle_radiance_grad,
-                          flags & ~kBwdPoseOnly, gut::GradFields());
 }
 
 // The backward for the pose gradient alone: the compositor as in every other backward, then the CONSUMING form of the
@@ -814,25 +1009,9 @@ int gut_trace_bwd_pose(gut_handle h, void* stream_, uint32_t frame_number, int32
             return fail("gut_trace_bwd_pose: d_particle_density is NULL and the last forward on this handle packed no rows (not a *_fields one)");
         d_particle_density = h->packed12.as<float>();
     }
-    return trace_bwd_impl(h, stream_, frame_number, num_active_features, num_particles, d_particle_density, nullptr, width, height,
-                          d_ray_origin, d_ray_direction, camera, d_ray_radiance_density, d_ray_radiance_density_grad, d_ray_hit_distance,
-                          d_ray_hit_distance_grad, nullptr, nullptr, kBwdPoseOnly | GUT_BWD_SKIP_EPILOGUE, gut::GradFields());
-}
-
-// The [N,12] rows of the *_fields forwards: packed (or activated and packed) from the caller's four tensors into handle scratch by
-// `pack`, where they stay for the backward.  Invalidates whatever the scratch held; the caller marks it valid once its forward succeeded.
-using PackLauncher = void (*)(hipStream_t, uint32_t, const float*, const float*, const float*, const float*, float*);
-static int pack_rows(gut_handle h, void* stream_, uint32_t num_particles, PackLauncher pack, const float* d_positions,
-                     const float* d_density, const float* d_rotation, const float* d_scale) {
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dev_guard;
-    HIP_TRY(dev_guard.set(h->device));
-    h->packed_valid = false;
-    h->packed_raw = false;
-    HIP_TRY(h->packed12.ensure(sizeof(float) * 12 * (size_t)num_particles + 64));
-    pack(static_cast<hipStream_t>(stream_), num_particles, d_positions, d_density, d_rotation, d_scale, h->packed12.as<float>());
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return trace_bwd_impl(h, view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                          BwdUpstream{d_ray_radiance_density, d_ray_radiance_density_grad, d_ray_hit_distance, d_ray_hit_distance_grad},
+                          BwdArgs{BwdMode::kPoseOnly, false, d_particle_density, nullptr, nullptr, gut::GradFields()});
 }
 
 // SplatRaster::trace with the four activated tensors the reference's Tracer hands to _Autograd (tracer.py:317-327) instead of
@@ -843,16 +1022,10 @@ int gut_trace_fields(gut_handle h, void* stream_, uint32_t frame_number, int32_t
                      const float* d_particle_radiance, int32_t width, int32_t height, const float* d_ray_origin,
                      const float* d_ray_direction, const GutCamera* camera, float* d_ray_radiance_density,
                      float* d_ray_hit_distance, float* d_ray_hit_count, float* d_particle_visibility) {
-    if (!h) return fail("gut_trace_fields: null handle");
-    if (num_particles && (!d_positions || !d_density || !d_rotation || !d_scale))
-        return fail("gut_trace_fields: null particle buffers with %u particles", num_particles);
-    if (((uintptr_t)d_rotation & 15u) != 0) return fail("gut_trace_fields: the rotation tensor must be 16-byte aligned");
-    if (pack_rows(h, stream_, num_particles, gut::launch_pack_fields, d_positions, d_density, d_rotation, d_scale)) return 1;
-    const int rc = gut_trace(h, stream_, frame_number, num_active_features, num_particles, h->packed12.as<float>(), d_particle_radiance,
-                             width, height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density, d_ray_hit_distance,
-                             d_ray_hit_count, d_particle_visibility);
-    if (rc == 0) h->packed_valid = true;
-    return rc;
+    return trace_fwd_packed(h, "gut_trace_fields", gut::launch_pack_fields, false,
+                            view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                            d_positions, d_density, d_rotation, d_scale, d_particle_radiance, nullptr, false,
+                            FwdOutputs{d_ray_radiance_density, d_ray_hit_distance, d_ray_hit_count, d_particle_visibility});
 }
 
 // SplatRaster::traceBwd for the forward above; the density gradient is written as the four tensors of _Autograd.backward's
@@ -863,16 +1036,10 @@ int gut_trace_bwd_fields(gut_handle h, void* stream_, uint32_t frame_number, int
                          const float* d_ray_radiance_density_grad, const float* d_ray_hit_distance,
                          const float* d_ray_hit_distance_grad, float* d_positions_grad, float* d_density_grad, float* d_rotation_grad,
                          float* d_scale_grad, float* d_particle_radiance_grad) {
-    if (!h) return fail("gut_trace_bwd_fields: null handle");
-    if (!h->packed_valid) return fail("gut_trace_bwd_fields: no gut_trace_fields forward on this handle");
-    if (num_particles && (!d_positions_grad || !d_density_grad || !d_rotation_grad || !d_scale_grad || !d_particle_radiance_grad))
-        return fail("gut_trace_bwd_fields: null gradient buffers");
-    if (((uintptr_t)d_rotation_grad & 15u) != 0) return fail("gut_trace_bwd_fields: the rotation gradient must be 16-byte aligned");
-    gut::GradFields f;
-    f.pos = d_positions_grad; f.dns = d_density_grad; f.rot = d_rotation_grad; f.scl = d_scale_grad;
-    return trace_bwd_impl(h, stream_, frame_number, num_active_features, num_particles, h->packed12.as<float>(), d_particle_radiance, width,
-                          height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density, d_ray_radiance_density_grad,
-                          d_ray_hit_distance, d_ray_hit_distance_grad, d_positions_grad /* non-null marker */, d_particle_radiance_grad, 0u, f);
+    return trace_bwd_packed(h, "gut_trace_bwd_fields", "gut_trace_fields",
+                            view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                            BwdUpstream{d_ray_radiance_density, d_ray_radiance_density_grad, d_ray_hit_distance, d_ray_hit_distance_grad},
+                            gut::GradFields{d_positions_grad, d_density_grad, d_rotation_grad, d_scale_grad}, d_particle_radiance_grad, false);
 }
 
 // gut_trace_fields / gut_trace_bwd_fields with the SH coefficients as the model's two tensors too (features_albedo [N,3],
@@ -884,18 +1051,10 @@ int gut_trace_model_fields(gut_handle h, void* stream_, uint32_t frame_number, i
                            const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
                            float* d_ray_radiance_density, float* d_ray_hit_distance, float* d_ray_hit_count,
                            float* d_particle_visibility) {
-    if (!h) return fail("gut_trace_model_fields: null handle");
-    if (num_particles && (!d_positions || !d_density || !d_rotation || !d_scale || !d_features_albedo || !d_features_specular))
-        return fail("gut_trace_model_fields: null particle buffers with %u particles", num_particles);
-    if ((((uintptr_t)d_rotation | (uintptr_t)d_features_specular) & 15u) != 0)
-        return fail("gut_trace_model_fields: the rotation and features_specular tensors must be 16-byte aligned");
-    if (pack_rows(h, stream_, num_particles, gut::launch_pack_fields, d_positions, d_density, d_rotation, d_scale)) return 1;
-    const int rc = trace_fwd_impl(h, stream_, frame_number, num_active_features, num_particles, h->packed12.as<float>(),
-                                  d_features_specular, width, height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density,
-                                  d_ray_hit_distance, d_ray_hit_count, d_particle_visibility,
-                                  num_particles ? d_features_albedo : nullptr);
-    if (rc == 0) h->packed_valid = true;
-    return rc;
+    return trace_fwd_packed(h, "gut_trace_model_fields", gut::launch_pack_fields, false,
+                            view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                            d_positions, d_density, d_rotation, d_scale, d_features_specular, d_features_albedo, true,
+                            FwdOutputs{d_ray_radiance_density, d_ray_hit_distance, d_ray_hit_count, d_particle_visibility});
 }
 
 // gut_trace_model_fields on the model's PRE-ACTIVATION tensors (model.py:74-93: density logit, un-normalised quaternion, log-scale):
@@ -908,18 +1067,10 @@ int gut_trace_raw_model_fields(gut_handle h, void* stream_, uint32_t frame_numbe
                                const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
                                float* d_ray_radiance_density, float* d_ray_hit_distance, float* d_ray_hit_count,
                                float* d_particle_visibility) {
-    if (!h) return fail("gut_trace_raw_model_fields: null handle");
-    if (num_particles && (!d_positions || !d_density_logit || !d_rotation_raw || !d_log_scale || !d_features_albedo || !d_features_specular))
-        return fail("gut_trace_raw_model_fields: null particle buffers with %u particles", num_particles);
-    if ((((uintptr_t)d_rotation_raw | (uintptr_t)d_features_specular) & 15u) != 0)
-        return fail("gut_trace_raw_model_fields: the rotation and features_specular tensors must be 16-byte aligned");
-    if (pack_rows(h, stream_, num_particles, gut::launch_pack_activate_fields, d_positions, d_density_logit, d_rotation_raw, d_log_scale)) return 1;
-    const int rc = trace_fwd_impl(h, stream_, frame_number, num_active_features, num_particles, h->packed12.as<float>(),
-                                  d_features_specular, width, height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density,
-                                  d_ray_hit_distance, d_ray_hit_count, d_particle_visibility,
-                                  num_particles ? d_features_albedo : nullptr);
-    if (rc == 0) { h->packed_valid = true; h->packed_raw = true; }
-    return rc;
+    return trace_fwd_packed(h, "gut_trace_raw_model_fields", gut::launch_pack_activate_fields, true,
+                            view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                            d_positions, d_density_logit, d_rotation_raw, d_log_scale, d_features_specular, d_features_albedo, true,
+                            FwdOutputs{d_ray_radiance_density, d_ray_hit_distance, d_ray_hit_count, d_particle_visibility});
 }
 
 int gut_trace_bwd_model_fields(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
@@ -928,164 +1079,12 @@ int gut_trace_bwd_model_fields(gut_handle h, void* stream_, uint32_t frame_numbe
                                const float* d_ray_hit_distance, const float* d_ray_hit_distance_grad, float* d_positions_grad,
                                float* d_density_grad, float* d_rotation_grad, float* d_scale_grad, float* d_features_albedo_grad,
                                float* d_features_specular_grad) {
-    if (!h) return fail("gut_trace_bwd_model_fields: null handle");
-    if (!h->packed_valid) return fail("gut_trace_bwd_model_fields: no gut_trace_fields / gut_trace_model_fields forward on this handle");
-    if (num_particles && (!d_positions_grad || !d_density_grad || !d_rotation_grad || !d_scale_grad || !d_features_albedo_grad ||
-                          !d_features_specular_grad))
-        return fail("gut_trace_bwd_model_fields: null gradient buffers");
-    if ((((uintptr_t)d_rotation_grad | (uintptr_t)d_features_specular_grad) & 15u) != 0)
-        return fail("gut_trace_bwd_model_fields: the rotation and features_specular gradients must be 16-byte aligned");
-    gut::GradFields f;
-    f.pos = d_positions_grad; f.dns = d_density_grad; f.rot = d_rotation_grad; f.scl = d_scale_grad;
-    f.alb = d_features_albedo_grad; f.spec = d_features_specular_grad;
-    // (after gut_trace_raw_model_fields the rows carry |quat| in the pad column and the gradients are chained to the raw tensors)
-    return trace_bwd_impl(h, stream_, frame_number, num_active_features, num_particles, h->packed12.as<float>(), nullptr, width,
-                          height, d_ray_origin, d_ray_direction, camera, d_ray_radiance_density, d_ray_radiance_density_grad,
-                          d_ray_hit_distance, d_ray_hit_distance_grad, d_positions_grad /* non-null markers */, d_features_specular_grad,
-                          h->packed_raw ? GUT_BWD_RAW_PARAMETER_GRADS : 0u, f);
-}
-
-// how the consuming reduction zeroes: it reads the whole row and stores only where a word is set (the default, the faster form on the
-// 6 M-Gaussian workload, DESIGN.md §12), or GUT_POSE_CONSUME=store for measurements: four unconditional zero stores per visited row
-static bool pose_consume_tests() {
-    static const bool tests = [] {
-        const char* e = getenv("GUT_POSE_CONSUME");
-        return !(e && strcmp(e, "store") == 0);
-    }();
-    return tests;
-}
-
-static int trace_bwd_impl(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
-                          const float* d_particle_density, const float* d_particle_radiance, int32_t width, int32_t height,
-                          const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
-                          const float* d_ray_radiance_density, const float* d_ray_radiance_density_grad,
-                          const float* d_ray_hit_distance, const float* d_ray_hit_distance_grad, float* d_particle_density_grad,
-                          float* d_particle_radiance_grad, uint32_t flags, const gut::GradFields& fields) {
-    (void)frame_number;
-    (void)d_particle_radiance;
-    if (!h) return fail("gut_trace_bwd: null handle");
-    std::lock_guard<std::mutex> lock(h->mu);
-    hipStream_t s = static_cast<hipStream_t>(stream_);
-    // same contract as the reference: backward needs the forward's cached context on the same stream
-    // (gutRenderer.cu:413-417)
-    if (!h->have_forward || h->fwd_stream != s)
-        return fail("gut_trace_bwd: no forward context on this stream (call gut_trace first, same stream)");
-    if (num_particles != h->n || width != h->width || height != h->height || num_active_features != h->sh_degree)
-        return fail("gut_trace_bwd: arguments differ from the cached forward (N %u vs %u, %dx%d vs %dx%d)", num_particles, h->n,
-                    width, height, h->width, h->height);
-    // d_ray_hit_distance_grad may be NULL (= all zeros: no loss on pred_dist, the default of the reference's trainer);
-    // the hit-distance gradient terms are then compiled out of the backward kernel
-    if (!camera || !d_ray_origin || !d_ray_direction || !d_ray_radiance_density || !d_ray_radiance_density_grad)
-        return fail("gut_trace_bwd: null pointer argument");
-    if (num_particles && (!d_particle_density || (!(flags & GUT_BWD_SKIP_EPILOGUE) && (!d_particle_density_grad || !d_particle_radiance_grad))))
-        return fail("gut_trace_bwd: null particle buffers");
-    if (h->early_ran && (!(flags & GUT_BWD_SKIP_EPILOGUE) || (flags & kBwdPoseOnly)))
-        return fail("gut_trace_bwd: gut_optimize_rows_without_gradient was called for this forward: the backward must be "
-                    "gut_trace_bwd_ex(..., GUT_BWD_SKIP_EPILOGUE) followed by gut_optimize_after_bwd");
-    if (flags & kBwdPoseOnly) {
-        if (!h->pose_out) return fail("gut_trace_bwd_pose: no pose output is set (gut_set_pose_gradient)");
-        if (h->m && h->cfg.k_buffer_size > 0 && !d_ray_hit_distance) return fail("gut_trace_bwd: the sorted variant needs d_ray_hit_distance");
-    }
-    float* narrow_radiance_grad = nullptr;   // particle_radiance_sph_degree < 3: the caller's [N, 3 (degree + 1)^2] gradient
-    if (h->cfg.particle_radiance_sph_degree != 3 && !(flags & GUT_BWD_SKIP_EPILOGUE)) {
-        if ((flags & GUT_BWD_COMPACT_RADIANCE_GRADS) || fields.alb)
-            return fail("gut_trace_bwd: particle_radiance_sph_degree=%d supports the packed radiance gradient only", h->cfg.particle_radiance_sph_degree);
-        narrow_radiance_grad = d_particle_radiance_grad;
-    }
-    // the pose gradient is the rigid-motion reduction of the gradient rows: it means something for ONE pose per view only
-    if (h->pose_out)
-        for (int k = 0; k < 7; ++k)
-            if (camera->pose_start[k] != camera->pose_end[k])
-                return fail("gut_trace_bwd: a pose gradient is set (gut_set_pose_gradient) and the view's start and end poses differ: "
-                            "the reduction is defined for pose_start == pose_end only");
-    DeviceGuard dev_guard;
-    HIP_TRY(dev_guard.set(h->device));
-    gut::ViewParams v;
-    if (build_view(camera, width, height, h->cfg.n_rolling_shutter_iterations, &v)) return 1;
-    if (memcmp(&v, &h->view, sizeof(v)) != 0) return fail("gut_trace_bwd: camera differs from the cached forward");
-    const uint32_t n = h->n;
-    if (n == 0) {
-        if (h->pose_out) HIP_TRY(hipMemsetAsync(h->pose_out, 0, 8 * sizeof(float), s));   // no rows: F = M = 0, none summed
-        return 0;
-    }
-    if (h->pose_out) HIP_TRY(h->pose_partials.ensure(gut::pose_gradient_scratch_bytes()));
-    {
-        const void* before = h->grad16.p;
-        HIP_TRY(h->grad16.ensure(sizeof(float) * 16 * (size_t)n));
-        if (h->grad16.p != before) h->grad16_zero = false;  // fresh allocation
-    }
-    if (narrow_radiance_grad) {
-        HIP_TRY(h->sph_grad_wide.ensure(sizeof(float) * 48 * (size_t)n));
-        d_particle_radiance_grad = h->sph_grad_wide.as<float>();
-    }
-
-    const bool timing = h->cfg.enable_kernel_timings != 0 && h->timing_main_stream;
-    EventPair* total = timing ? arm_timer(h->bwd_timers, s) : nullptr;
-    h->kev_bwd_valid = false;
-    auto mark = [&](int i) {
-        if (timing && h->kev[i]) (void)hipEventRecord(h->kev[i], s);
-    };
-    mark(8);
-    // the gradient rows are zero already unless this is the first backward or the previous one was never consumed (every
-    // per-Gaussian consumer below zeroes the rows it reads, so there is no 64 N-byte clear per step)
-    if (!h->grad16_zero) HIP_TRY(hipMemsetAsync(h->grad16.p, 0, h->grad16.cap, s));
-    h->grad16_zero = false;
-    if (launch_early_part2(h, s)) return 1;
-    mark(9);
-    if (h->m && h->cfg.k_buffer_size > 0) {
-        if (!d_ray_hit_distance) return fail("gut_trace_bwd: the sorted variant needs d_ray_hit_distance");
-        HIP_TRY(hipMemsetAsync(h->trav_bwd.p, 0, sizeof(uint32_t) * (size_t)h->tiles, s));
-        gut::launch_render_sorted_bwd(s, v, h->consts, h->cfg.k_buffer_size, d_particle_density, h->feat.as<float>(), d_ray_origin,
-                                      d_ray_direction, h->ranges.as<uint32_t>(), h->ids_sorted.as<uint32_t>(),
-                                      d_ray_radiance_density, d_ray_hit_distance, d_ray_radiance_density_grad,
-                                      d_ray_hit_distance_grad, h->grad16.as<float>(), h->sorted_reference_bwd, h->cfg.particle_kernel_degree);
-    } else if (h->m) {
-        HIP_TRY(h->walk_sums.ensure(2 * sizeof(uint32_t)));
-        gut::launch_tile_order(s, (uint32_t)h->tiles, h->trav_fwd.as<uint32_t>(), h->tile_order.as<uint32_t>(), h->ranges.as<uint32_t>(), false,
-                               h->walk_sums.as<uint32_t>());
-        gut::launch_render_bwd(s, v, h->consts, d_particle_density, h->feat.as<float>(), d_ray_origin, d_ray_direction,
-                               h->ranges.as<uint32_t>(), (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(),
-                               d_ray_radiance_density,
-                               d_ray_radiance_density_grad, d_ray_hit_distance_grad, h->grad16.as<float>(),
-                               h->trav_bwd.as<uint32_t>(), h->tile_order.as<uint32_t>(), h->trav_fwd.as<uint32_t>(), h->cfg.particle_kernel_degree);
-    }
-    mark(10);
-    // right behind the backward compositor and before any epilogue: the epilogues zero the gradient rows as they read them
-    // (behind the mark that ends render_bwd's timer: the two launches count towards project_bwd, not towards K7)
-    if (flags & kBwdPoseOnly)
-        gut::launch_pose_gradient_consume(s, n, h->tiles_count.as<uint32_t>(), h->grad16.as<float>(), d_particle_density,
-                                          h->cam_pos.as<float>(), h->pose_partials.as<float>(), h->pose_out, pose_consume_tests());
-    else if (h->pose_out)
-        gut::launch_pose_gradient(s, n, h->tiles_count.as<uint32_t>(), h->grad16.as<float>(), d_particle_density, h->cam_pos.as<float>(),
-                                  h->pose_partials.as<float>(), h->pose_out);
-    if (flags & kBwdPoseOnly) {
-        h->grad16_zero = true;  // the reduction zeroed every row K7 could have touched (the rows with tiles): nothing is left to consume
-    } else if (flags & GUT_BWD_SKIP_EPILOGUE) {
-        // the caller folds the per-Gaussian epilogue into its optimiser step (gut_optimize_after_bwd)
-    } else {
-        if (flags & GUT_BWD_COMPACT_RADIANCE_GRADS)
-            gut::launch_project_bwd_compact(s, n, d_particle_density, h->tiles_count.as<uint32_t>(), h->feat.as<float>(),
-                                            h->grad16.as<float>(), d_particle_density_grad, d_particle_radiance_grad);
-        else
-            gut::launch_project_bwd(s, v, n, h->sh_degree, d_particle_density, h->tiles_count.as<uint32_t>(), h->feat.as<float>(),
-                                    h->grad16.as<float>(), d_particle_density_grad, d_particle_radiance_grad,
-                                    (flags & GUT_BWD_RAW_PARAMETER_GRADS) != 0, fields);
-        if (narrow_radiance_grad) {
-            const uint32_t w = 3u * (uint32_t)((h->cfg.particle_radiance_sph_degree + 1) * (h->cfg.particle_radiance_sph_degree + 1));
-            gut::launch_resize_sph_rows(s, n, 48u, w, h->sph_grad_wide.as<float>(), narrow_radiance_grad);
-        }
-        h->grad16_zero = true;  // the epilogue zeroed every row K7 could have touched (the rows with tiles)
-    }
-    mark(11);
-    HIP_TRY(hipGetLastError());
-    if (total) {
-        (void)hipEventRecord(total->b, s);
-        total->armed = true;
-    }
-    h->kev_bwd_valid = timing;
-    if (timing) h->ring[h->ring_cur].bwd = true;
-    h->have_backward = !(flags & kBwdPoseOnly);   // (gut_optimize_after_bwd / gut_compact_gradient_rows have nothing to follow a pose-only one)
-    return 0;
+    return trace_bwd_packed(h, "gut_trace_bwd_model_fields", "gut_trace_fields / gut_trace_model_fields",
+                            view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                            BwdUpstream{d_ray_radiance_density, d_ray_radiance_density_grad, d_ray_hit_distance, d_ray_hit_distance_grad},
+                            gut::GradFields{d_positions_grad, d_density_grad, d_rotation_grad, d_scale_grad, d_features_albedo_grad,
+                                            d_features_specular_grad},
+                            nullptr, true);
 }
 
 int gut_optimize_after_bwd(gut_handle h, void* stream_, int32_t num_active_features, const float* d_camera_position,
@@ -1528,7 +1527,7 @@ int gut_debug_buffer(gut_handle h, int32_t which, void** d_ptr, size_t* bytes) {
     switch (which) {
     case GUT_BUF_TILES_COUNT: *d_ptr = h->tiles_count.p; *bytes = 4 * n; break;
     case GUT_BUF_TILES_OFFSET:
-        // debug view: the product path never materialises the [N] inclusive scan (see K2 in trace_fwd_impl); built here on request
+        // debug view: the product path never materialises the [N] inclusive scan (see K2 in queue_projection_and_scan); built here on request
         if (!h->dbg_offset_valid && n) {
             DeviceGuard dev_guard;
             HIP_TRY(dev_guard.set(h->device));

@@ -175,6 +175,27 @@ def _check_f32_cuda(t, name, shape_tail=None):
     return t.contiguous()
 
 
+def _ptr(t, n=1):
+    """The device address of t; None (NULL) for no tensor and for the rows of n == 0 Gaussians."""
+    return t.data_ptr() if (n and t is not None) else None
+
+
+_F32P = C.POINTER(C.c_float)
+
+
+def _optimiser_args(raw12, raw_m, raw_v, sh48, sh_m, sh_v, lr12, lr48, betas, eps, step):
+    """The optimiser state and Adam settings as the run of ctypes arguments gut_optimize_after_bwd and
+    gut_optimize_rows_without_gradient share.  lr12 / lr48: float32 numpy arrays."""
+    return (raw12.data_ptr(), raw_m.data_ptr(), raw_v.data_ptr(), sh48.data_ptr(), sh_m.data_ptr(), sh_v.data_ptr(),
+            lr12.ctypes.data_as(_F32P), lr48.ctypes.data_as(_F32P), betas[0], betas[1], eps, int(step))
+
+
+def _pose_args(sensor_poses):
+    """(ts_start, ts_end, pose_start, pose_end): the tail every SplatRaster.trace* takes, from a SensorPose3D."""
+    return (sensor_poses.timestamps_us[0], sensor_poses.timestamps_us[1], sensor_poses.T_world_sensors[0],
+            sensor_poses.T_world_sensors[1])
+
+
 class SplatRaster:
     """Drop-in for the pybind class of the same name (splatRaster.h:47-89)."""
 
@@ -220,73 +241,75 @@ class SplatRaster:
         cam.timestamp_end_us = int(ts_end)
         return cam
 
-    def trace(self, frame_number, num_active_features, particle_density, particle_radiance, ray_ori, ray_dir, ray_time,
-              sensor_params, ts_start, ts_end, pose_start, pose_end):
+    # ---- what the eight trace methods share ----
+    @staticmethod
+    def _rays(ray_ori, ray_dir, single_view=False):
+        """Checked rays -> (ray_ori, ray_dir, H, W, device); single_view: the forward's [1,H,W,3] test."""
         ray_ori = _check_f32_cuda(ray_ori, "rayOrigin", (3,))
         ray_dir = _check_f32_cuda(ray_dir, "rayDirection", (3,))
-        if ray_ori.dim() != 4 or ray_ori.shape[0] != 1:
+        if single_view and (ray_ori.dim() != 4 or ray_ori.shape[0] != 1):
             raise RuntimeError("[3dgut] rays must be [1,H,W,3] (the reference renders one view per call)")
-        H, W = int(ray_ori.shape[1]), int(ray_ori.shape[2])
+        return ray_ori, ray_dir, int(ray_ori.shape[1]), int(ray_ori.shape[2]), ray_ori.device
+
+    @staticmethod
+    def _upstream(ray_radiance_density, ray_radiance_density_grd, ray_hit_distance, ray_hit_distance_grd):
+        """The four upstream tensors of a backward, checked; the hit-distance gradient may be None (= all zeros)."""
+        return (_check_f32_cuda(ray_radiance_density, "rayRadianceDensity", (4,)),
+                _check_f32_cuda(ray_radiance_density_grd, "rayRadianceDensityGradient", (4,)),
+                _check_f32_cuda(ray_hit_distance, "rayHitDistance"),
+                None if ray_hit_distance_grd is None else _check_f32_cuda(ray_hit_distance_grd, "rayHitDistanceGradient"))
+
+    @staticmethod
+    def _forward_outputs(H, W, n, dev):
+        """(rgba, dist, hits, vis): fully written by the kernels (no zero-fill passes)."""
+        return (torch.empty((H, W, 4), dtype=torch.float32, device=dev), torch.empty((H, W, 1), dtype=torch.float32, device=dev),
+                torch.empty((H, W, 1), dtype=torch.float32, device=dev), torch.empty((n, 1), dtype=torch.float32, device=dev))
+
+    def _call(self, what, entry, dev, frame_number, *args):
+        """entry(handle, current stream of dev, frame number, *args) on dev; raises with the library's message."""
+        stream = torch.cuda.current_stream(dev).cuda_stream  # splatRaster.cpp:186-187
+        with torch.cuda.device(dev):
+            rc = entry(self._handle, C.c_void_p(stream), int(frame_number) & 0xFFFFFFFF, *args)
+        _capi.check(rc, what)
+
+    def trace(self, frame_number, num_active_features, particle_density, particle_radiance, ray_ori, ray_dir, ray_time,
+              sensor_params, ts_start, ts_end, pose_start, pose_end):
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir, single_view=True)
         n = int(particle_density.shape[0])
-        dev = ray_ori.device
         if n:
             particle_density = _check_f32_cuda(particle_density, "particleDensity", (12,))
             particle_radiance = _check_f32_cuda(particle_radiance, "particleRadiance", (self._radiance_width,))
-        opts = dict(dtype=torch.float32, device=dev)
-        rgba = torch.empty((H, W, 4), **opts)   # fully written by the kernels (no zero-fill passes)
-        dist = torch.empty((H, W, 1), **opts)
-        hits = torch.empty((H, W, 1), **opts)
-        vis = torch.empty((n, 1), **opts)
+        rgba, dist, hits, vis = self._forward_outputs(H, W, n, dev)
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
-        stream = torch.cuda.current_stream(dev).cuda_stream  # splatRaster.cpp:186-187
-        with torch.cuda.device(dev):
-            rc = self._lib.gut_trace(self._handle, C.c_void_p(stream), int(frame_number) & 0xFFFFFFFF,
-                                     int(num_active_features), n,
-                                     particle_density.data_ptr() if n else None, particle_radiance.data_ptr() if n else None,
-                                     W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam),
-                                     rgba.data_ptr(), dist.data_ptr(), hits.data_ptr(), vis.data_ptr() if n else None)
-        _capi.check(rc, "trace")
+        self._call("trace", self._lib.gut_trace, dev, frame_number, int(num_active_features), n, _ptr(particle_density, n),
+                   _ptr(particle_radiance, n), W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(),
+                   dist.data_ptr(), hits.data_ptr(), _ptr(vis, n))
         return rgba, dist, hits, vis
 
     def trace_bwd(self, frame_number, num_active_features, particle_density, particle_radiance, ray_ori, ray_dir, ray_time,
                   sensor_params, ts_start, ts_end, pose_start, pose_end, ray_radiance_density, ray_radiance_density_grd,
                   ray_hit_distance, ray_hit_distance_grd, raw_parameter_grads=False, compact_radiance_grads=False, out=None,
                   skip_epilogue=False):
-        ray_ori = _check_f32_cuda(ray_ori, "rayOrigin", (3,))
-        ray_dir = _check_f32_cuda(ray_dir, "rayDirection", (3,))
-        H, W = int(ray_ori.shape[1]), int(ray_ori.shape[2])
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
         n = int(particle_density.shape[0])
-        dev = ray_ori.device
-        rgba = _check_f32_cuda(ray_radiance_density, "rayRadianceDensity", (4,))
-        rgba_g = _check_f32_cuda(ray_radiance_density_grd, "rayRadianceDensityGradient", (4,))
-        dist = _check_f32_cuda(ray_hit_distance, "rayHitDistance")
-        dist_g = None if ray_hit_distance_grd is None else _check_f32_cuda(ray_hit_distance_grd, "rayHitDistanceGradient")
-        opts = dict(dtype=torch.float32, device=dev)
+        rgba, rgba_g, dist, dist_g = self._upstream(ray_radiance_density, ray_radiance_density_grd, ray_hit_distance, ray_hit_distance_grd)
         if skip_epilogue:   # gradient rows stay in the handle for optimize_after_bwd (native trainer, one view)
             dens_g = sph_g = None
         elif out is not None:
             dens_g, sph_g = out
         else:
-            dens_g = torch.empty((n, 12), **opts)  # fully written by the per-Gaussian epilogue kernel
-            sph_g = torch.empty((n, 3 if compact_radiance_grads else self._radiance_width), **opts)
+            dens_g = torch.empty((n, 12), dtype=torch.float32, device=dev)  # fully written by the per-Gaussian epilogue kernel
+            sph_g = torch.empty((n, 3 if compact_radiance_grads else self._radiance_width), dtype=torch.float32, device=dev)
         if n:
             particle_density = _check_f32_cuda(particle_density, "particleDensity", (12,))
             particle_radiance = _check_f32_cuda(particle_radiance, "particleRadiance", (self._radiance_width,))
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            rc = self._lib.gut_trace_bwd_ex(self._handle, C.c_void_p(stream), int(frame_number) & 0xFFFFFFFF,
-                                         int(num_active_features), n,
-                                         particle_density.data_ptr() if n else None,
-                                         particle_radiance.data_ptr() if n else None, W, H, ray_ori.data_ptr(),
-                                         ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(), rgba_g.data_ptr(),
-                                         dist.data_ptr(), None if dist_g is None else dist_g.data_ptr(),
-                                         dens_g.data_ptr() if (n and dens_g is not None) else None,
-                                         sph_g.data_ptr() if (n and sph_g is not None) else None,
-                                         (_capi.BWD_RAW_PARAMETER_GRADS if raw_parameter_grads else 0) |
-                                         (_capi.BWD_COMPACT_RADIANCE_GRADS if compact_radiance_grads else 0) |
-                                         (_capi.BWD_SKIP_EPILOGUE if skip_epilogue else 0))
-        _capi.check(rc, "trace_bwd")
+        self._call("trace_bwd", self._lib.gut_trace_bwd_ex, dev, frame_number, int(num_active_features), n, _ptr(particle_density, n),
+                   _ptr(particle_radiance, n), W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(),
+                   rgba_g.data_ptr(), dist.data_ptr(), _ptr(dist_g), _ptr(dens_g, n), _ptr(sph_g, n),
+                   (_capi.BWD_RAW_PARAMETER_GRADS if raw_parameter_grads else 0) |
+                   (_capi.BWD_COMPACT_RADIANCE_GRADS if compact_radiance_grads else 0) |
+                   (_capi.BWD_SKIP_EPILOGUE if skip_epilogue else 0))
         return dens_g, sph_g
 
     def trace_fields(self, frame_number, num_active_features, mog_pos, mog_dns, mog_rot, mog_scl, particle_radiance, ray_ori, ray_dir,
@@ -294,28 +317,17 @@ class SplatRaster:
         """trace() on the four activated tensors Tracer.render hands to _Autograd (positions [N,3], density [N,1], rotation [N,4],
         scale [N,3]) instead of their [N,12] concatenation: gut_trace_fields packs the rows inside the library (extension of the
         reference's surface; a wrapper without it gets the reference's torch.cat + trace())."""
-        ray_ori = _check_f32_cuda(ray_ori, "rayOrigin", (3,))
-        ray_dir = _check_f32_cuda(ray_dir, "rayDirection", (3,))
-        if ray_ori.dim() != 4 or ray_ori.shape[0] != 1:
-            raise RuntimeError("[3dgut] rays must be [1,H,W,3] (the reference renders one view per call)")
-        H, W = int(ray_ori.shape[1]), int(ray_ori.shape[2])
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir, single_view=True)
         n = int(mog_pos.shape[0])
-        dev = ray_ori.device
         if n:
             mog_pos = _check_f32_cuda(mog_pos, "positions", (3,)); mog_dns = _check_f32_cuda(mog_dns, "density", (1,))
             mog_rot = _check_f32_cuda(mog_rot, "rotation", (4,)); mog_scl = _check_f32_cuda(mog_scl, "scale", (3,))
             particle_radiance = _check_f32_cuda(particle_radiance, "particleRadiance", (self._radiance_width,))
-        opts = dict(dtype=torch.float32, device=dev)
-        rgba, dist, hits, vis = torch.empty((H, W, 4), **opts), torch.empty((H, W, 1), **opts), torch.empty((H, W, 1), **opts), torch.empty((n, 1), **opts)
+        rgba, dist, hits, vis = self._forward_outputs(H, W, n, dev)
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: t.data_ptr() if n else None
-        with torch.cuda.device(dev):
-            rc = self._lib.gut_trace_fields(self._handle, C.c_void_p(stream), int(frame_number) & 0xFFFFFFFF, int(num_active_features), n,
-                                            ptr(mog_pos), ptr(mog_dns), ptr(mog_rot), ptr(mog_scl), ptr(particle_radiance), W, H,
-                                            ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(), dist.data_ptr(),
-                                            hits.data_ptr(), ptr(vis))
-        _capi.check(rc, "trace_fields")
+        self._call("trace_fields", self._lib.gut_trace_fields, dev, frame_number, int(num_active_features), n, _ptr(mog_pos, n),
+                   _ptr(mog_dns, n), _ptr(mog_rot, n), _ptr(mog_scl, n), _ptr(particle_radiance, n), W, H, ray_ori.data_ptr(),
+                   ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(), dist.data_ptr(), hits.data_ptr(), _ptr(vis, n))
         return rgba, dist, hits, vis
 
     def trace_bwd_fields(self, frame_number, num_active_features, num_particles, particle_radiance, ray_ori, ray_dir, sensor_params, ts_start,
@@ -323,31 +335,17 @@ class SplatRaster:
                          ray_hit_distance_grd):
         """Backward of trace_fields: returns (positions, density, rotation, scale, radiance) gradients as five fresh tensors —
         what _Autograd.backward hands to autograd, with no [N,12] intermediate, split or copies."""
-        ray_ori = _check_f32_cuda(ray_ori, "rayOrigin", (3,))
-        ray_dir = _check_f32_cuda(ray_dir, "rayDirection", (3,))
-        H, W = int(ray_ori.shape[1]), int(ray_ori.shape[2])
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
         n = int(num_particles)
-        dev = ray_ori.device
-        rgba = _check_f32_cuda(ray_radiance_density, "rayRadianceDensity", (4,))
-        rgba_g = _check_f32_cuda(ray_radiance_density_grd, "rayRadianceDensityGradient", (4,))
-        dist = _check_f32_cuda(ray_hit_distance, "rayHitDistance")
-        dist_g = None if ray_hit_distance_grd is None else _check_f32_cuda(ray_hit_distance_grd, "rayHitDistanceGradient")
-        opts = dict(dtype=torch.float32, device=dev)
-        pos_g, dns_g, rot_g, scl_g = (torch.empty((n, c), **opts) for c in (3, 1, 4, 3))
-        sph_g = torch.empty((n, self._radiance_width), **opts)
+        rgba, rgba_g, dist, dist_g = self._upstream(ray_radiance_density, ray_radiance_density_grd, ray_hit_distance, ray_hit_distance_grd)
+        grads = tuple(torch.empty((n, c), dtype=torch.float32, device=dev) for c in (3, 1, 4, 3, self._radiance_width))
         if n:
             particle_radiance = _check_f32_cuda(particle_radiance, "particleRadiance", (self._radiance_width,))
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: t.data_ptr() if n else None
-        with torch.cuda.device(dev):
-            rc = self._lib.gut_trace_bwd_fields(self._handle, C.c_void_p(stream), int(frame_number) & 0xFFFFFFFF, int(num_active_features), n,
-                                                ptr(particle_radiance), W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam),
-                                                rgba.data_ptr(), rgba_g.data_ptr(), dist.data_ptr(),
-                                                None if dist_g is None else dist_g.data_ptr(), ptr(pos_g), ptr(dns_g), ptr(rot_g),
-                                                ptr(scl_g), ptr(sph_g))
-        _capi.check(rc, "trace_bwd_fields")
-        return pos_g, dns_g, rot_g, scl_g, sph_g
+        self._call("trace_bwd_fields", self._lib.gut_trace_bwd_fields, dev, frame_number, int(num_active_features), n,
+                   _ptr(particle_radiance, n), W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(),
+                   rgba_g.data_ptr(), dist.data_ptr(), _ptr(dist_g), *(_ptr(g, n) for g in grads))
+        return grads
 
     def trace_raw_model_fields(self, *args):
         """trace_model_fields() on the model's PRE-ACTIVATION density / rotation / scale tensors (gut_trace_raw_model_fields): the
@@ -358,13 +356,8 @@ class SplatRaster:
                            ray_dir, sensor_params, ts_start, ts_end, pose_start, pose_end, _raw=False):
         """trace_fields() with the SH coefficients as the model's two tensors (features_albedo [N,3], features_specular [N,45]; model.py:
         68-75) instead of get_features()'s [N,48] torch.cat (gut_trace_model_fields)."""
-        ray_ori = _check_f32_cuda(ray_ori, "rayOrigin", (3,))
-        ray_dir = _check_f32_cuda(ray_dir, "rayDirection", (3,))
-        if ray_ori.dim() != 4 or ray_ori.shape[0] != 1:
-            raise RuntimeError("[3dgut] rays must be [1,H,W,3] (the reference renders one view per call)")
-        H, W = int(ray_ori.shape[1]), int(ray_ori.shape[2])
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir, single_view=True)
         n = int(mog_pos.shape[0])
-        dev = ray_ori.device
         if n:
             mog_pos = _check_f32_cuda(mog_pos, "positions", (3,)); mog_dns = _check_f32_cuda(mog_dns, "density", (1,))
             mog_rot = _check_f32_cuda(mog_rot, "rotation", (4,)); mog_scl = _check_f32_cuda(mog_scl, "scale", (3,))
@@ -372,18 +365,12 @@ class SplatRaster:
             sph_specular = _check_f32_cuda(sph_specular, "featuresSpecular", (45,))
             if sph_albedo.shape[0] != n or sph_specular.shape[0] != n:
                 raise RuntimeError("[3dgut] feature tensors and positions differ in their number of rows")
-        opts = dict(dtype=torch.float32, device=dev)
-        rgba, dist, hits, vis = torch.empty((H, W, 4), **opts), torch.empty((H, W, 1), **opts), torch.empty((H, W, 1), **opts), torch.empty((n, 1), **opts)
+        rgba, dist, hits, vis = self._forward_outputs(H, W, n, dev)
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: t.data_ptr() if n else None
         entry = self._lib.gut_trace_raw_model_fields if _raw else self._lib.gut_trace_model_fields
-        with torch.cuda.device(dev):
-            rc = entry(self._handle, C.c_void_p(stream), int(frame_number) & 0xFFFFFFFF, int(num_active_features), n,
-                                                  ptr(mog_pos), ptr(mog_dns), ptr(mog_rot), ptr(mog_scl), ptr(sph_albedo), ptr(sph_specular),
-                                                  W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(),
-                                                  dist.data_ptr(), hits.data_ptr(), ptr(vis))
-        _capi.check(rc, "trace_model_fields")
+        self._call("trace_model_fields", entry, dev, frame_number, int(num_active_features), n, _ptr(mog_pos, n), _ptr(mog_dns, n),
+                   _ptr(mog_rot, n), _ptr(mog_scl, n), _ptr(sph_albedo, n), _ptr(sph_specular, n), W, H, ray_ori.data_ptr(),
+                   ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(), dist.data_ptr(), hits.data_ptr(), _ptr(vis, n))
         return rgba, dist, hits, vis
 
     def trace_bwd_model_fields(self, frame_number, num_active_features, num_particles, ray_ori, ray_dir, sensor_params, ts_start, ts_end,
@@ -391,32 +378,20 @@ class SplatRaster:
                                out=None):
         """Backward of trace_model_fields: (positions, density, rotation, scale, features_albedo, features_specular) gradients as six
         fresh tensors (or the six of `out`), each written in full by the kernels."""
-        ray_ori = _check_f32_cuda(ray_ori, "rayOrigin", (3,))
-        ray_dir = _check_f32_cuda(ray_dir, "rayDirection", (3,))
-        H, W = int(ray_ori.shape[1]), int(ray_ori.shape[2])
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
         n = int(num_particles)
-        dev = ray_ori.device
-        rgba = _check_f32_cuda(ray_radiance_density, "rayRadianceDensity", (4,))
-        rgba_g = _check_f32_cuda(ray_radiance_density_grd, "rayRadianceDensityGradient", (4,))
-        dist = _check_f32_cuda(ray_hit_distance, "rayHitDistance")
-        dist_g = None if ray_hit_distance_grd is None else _check_f32_cuda(ray_hit_distance_grd, "rayHitDistanceGradient")
-        opts = dict(dtype=torch.float32, device=dev)
+        rgba, rgba_g, dist, dist_g = self._upstream(ray_radiance_density, ray_radiance_density_grd, ray_hit_distance, ray_hit_distance_grd)
         if out is not None:
-            pos_g, dns_g, rot_g, scl_g, alb_g, spec_g = (_check_f32_cuda(t, "gradient output", (c,)) for t, c in zip(out, (3, 1, 4, 3, 3, 45)))
-            if any(t.shape[0] != n or not o.is_contiguous() for t, o in zip((pos_g, dns_g, rot_g, scl_g, alb_g, spec_g), out)):
+            grads = tuple(_check_f32_cuda(t, "gradient output", (c,)) for t, c in zip(out, (3, 1, 4, 3, 3, 45)))
+            if any(t.shape[0] != n or not o.is_contiguous() for t, o in zip(grads, out)):
                 raise RuntimeError("[3dgut] gradient outputs must be contiguous [N,c] tensors with the forward's number of rows")
         else:
-            pos_g, dns_g, rot_g, scl_g, alb_g, spec_g = (torch.empty((n, c), **opts) for c in (3, 1, 4, 3, 3, 45))
+            grads = tuple(torch.empty((n, c), dtype=torch.float32, device=dev) for c in (3, 1, 4, 3, 3, 45))
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: t.data_ptr() if n else None
-        with torch.cuda.device(dev):
-            rc = self._lib.gut_trace_bwd_model_fields(self._handle, C.c_void_p(stream), int(frame_number) & 0xFFFFFFFF, int(num_active_features),
-                                                      n, W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(),
-                                                      rgba_g.data_ptr(), dist.data_ptr(), None if dist_g is None else dist_g.data_ptr(),
-                                                      ptr(pos_g), ptr(dns_g), ptr(rot_g), ptr(scl_g), ptr(alb_g), ptr(spec_g))
-        _capi.check(rc, "trace_bwd_model_fields")
-        return pos_g, dns_g, rot_g, scl_g, alb_g, spec_g
+        self._call("trace_bwd_model_fields", self._lib.gut_trace_bwd_model_fields, dev, frame_number, int(num_active_features), n, W, H,
+                   ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(), rgba_g.data_ptr(), dist.data_ptr(),
+                   _ptr(dist_g), *(_ptr(g, n) for g in grads))
+        return grads
 
     def set_position_gradient_statistics(self, norm_accum, norm_denom):
         """The NEXT optimize_after_bwd also accumulates GSStrategy.update_gradient_buffer's statistics (gs.py:106-115) into these two
@@ -453,14 +428,8 @@ class SplatRaster:
         to set_pose_gradient (which must be set) and returns nothing: no per-Gaussian gradient exists afterwards, in a tensor or in the
         handle (the reduction leaves the handle's rows zero), and optimize_after_bwd / compact_gradient_rows have nothing to follow.
         particle_density: the [N,12] rows of the forward, or an int N after a *_fields forward (the rows that forward packed)."""
-        ray_ori = _check_f32_cuda(ray_ori, "rayOrigin", (3,))
-        ray_dir = _check_f32_cuda(ray_dir, "rayDirection", (3,))
-        H, W = int(ray_ori.shape[1]), int(ray_ori.shape[2])
-        dev = ray_ori.device
-        rgba = _check_f32_cuda(ray_radiance_density, "rayRadianceDensity", (4,))
-        rgba_g = _check_f32_cuda(ray_radiance_density_grd, "rayRadianceDensityGradient", (4,))
-        dist = _check_f32_cuda(ray_hit_distance, "rayHitDistance")
-        dist_g = None if ray_hit_distance_grd is None else _check_f32_cuda(ray_hit_distance_grd, "rayHitDistanceGradient")
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
+        rgba, rgba_g, dist, dist_g = self._upstream(ray_radiance_density, ray_radiance_density_grd, ray_hit_distance, ray_hit_distance_grd)
         rows = None
         if isinstance(particle_density, torch.Tensor):
             n = int(particle_density.shape[0])
@@ -469,13 +438,8 @@ class SplatRaster:
         else:
             n = int(particle_density)
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            rc = self._lib.gut_trace_bwd_pose(self._handle, C.c_void_p(stream), int(frame_number) & 0xFFFFFFFF, int(num_active_features), n,
-                                              None if rows is None else rows.data_ptr(), W, H, ray_ori.data_ptr(), ray_dir.data_ptr(),
-                                              C.byref(cam), rgba.data_ptr(), rgba_g.data_ptr(), dist.data_ptr(),
-                                              None if dist_g is None else dist_g.data_ptr())
-        _capi.check(rc, "trace_bwd_pose")
+        self._call("trace_bwd_pose", self._lib.gut_trace_bwd_pose, dev, frame_number, int(num_active_features), n, _ptr(rows), W, H,
+                   ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(), rgba_g.data_ptr(), dist.data_ptr(), _ptr(dist_g))
 
     def set_regularisation(self, reg):
         """The NEXT optimiser step on the handle (optimize_rows_without_gradient + optimize_after_bwd, or
@@ -488,27 +452,21 @@ class SplatRaster:
         """Per-Gaussian backward epilogue + SH-gradient rebuild + Adam in one pass (gut_optimize_after_bwd); follows a
         trace_bwd(..., skip_epilogue=True) on the same stream.  lr12 / lr48: float32 numpy arrays.  camera_position None: the sensor
         position of the cached forward, which the library keeps on the device (no host-to-device copy in the step)."""
-        f32p = C.POINTER(C.c_float)
         stream = torch.cuda.current_stream(raw12.device).cuda_stream
         with torch.cuda.device(raw12.device):
-            rc = self._lib.gut_optimize_after_bwd(self._handle, C.c_void_p(stream), int(num_active_features),
-                                                  None if camera_position is None else camera_position.data_ptr(),
-                                                  raw12.data_ptr(), raw_m.data_ptr(), raw_v.data_ptr(), sh48.data_ptr(), sh_m.data_ptr(),
-                                                  sh_v.data_ptr(), lr12.ctypes.data_as(f32p), lr48.ctypes.data_as(f32p), betas[0],
-                                                  betas[1], eps, int(step), None if visibility is None else visibility.data_ptr(),
-                                                  None if act_out is None else act_out.data_ptr(), None if lazy is None else C.byref(lazy))
+            rc = self._lib.gut_optimize_after_bwd(self._handle, C.c_void_p(stream), int(num_active_features), _ptr(camera_position),
+                                                  *_optimiser_args(raw12, raw_m, raw_v, sh48, sh_m, sh_v, lr12, lr48, betas, eps, step),
+                                                  _ptr(visibility), _ptr(act_out), None if lazy is None else C.byref(lazy))
         _capi.check(rc, "optimize_after_bwd")
 
     def optimize_rows_without_gradient(self, raw12, raw_m, raw_v, sh48, sh_m, sh_v, lr12, lr48, betas, eps, step, act_out=None, lazy=None):
         """Adam step of the rows the projection gave no tile, on the handle's low-priority side stream, between trace and
         trace_bwd(..., skip_epilogue=True) (gut_optimize_rows_without_gradient); optimize_after_bwd must follow."""
-        f32p = C.POINTER(C.c_float)
         stream = torch.cuda.current_stream(raw12.device).cuda_stream
         with torch.cuda.device(raw12.device):
             rc = self._lib.gut_optimize_rows_without_gradient(
-                self._handle, C.c_void_p(stream), raw12.data_ptr(), raw_m.data_ptr(), raw_v.data_ptr(), sh48.data_ptr(),
-                sh_m.data_ptr(), sh_v.data_ptr(), lr12.ctypes.data_as(f32p), lr48.ctypes.data_as(f32p), betas[0], betas[1], eps,
-                int(step), None if act_out is None else act_out.data_ptr(), None if lazy is None else C.byref(lazy))
+                self._handle, C.c_void_p(stream), *_optimiser_args(raw12, raw_m, raw_v, sh48, sh_m, sh_v, lr12, lr48, betas, eps, step),
+                _ptr(act_out), None if lazy is None else C.byref(lazy))
         _capi.check(rc, "optimize_rows_without_gradient")
 
     def finish_optimizer_step_without_gradient(self):
@@ -627,8 +585,7 @@ class Tracer:
                 trace = tracer_wrapper.trace_raw_model_fields if raw_parameters else tracer_wrapper.trace_model_fields
                 rgba, dist, hits, vis = trace(
                     frame_id, n_active_features, mog_pos, mog_dns, mog_rot, mog_scl, mog_sph.contiguous(), mog_sph_specular.contiguous(),
-                    ray_ori.contiguous(), ray_dir.contiguous(), sensor_params, sensor_poses.timestamps_us[0],
-                    sensor_poses.timestamps_us[1], sensor_poses.T_world_sensors[0], sensor_poses.T_world_sensors[1])
+                    ray_ori.contiguous(), ray_dir.contiguous(), sensor_params, *_pose_args(sensor_poses))
                 ctx.fields = True
                 ctx.num_particles = int(mog_pos.shape[0])
                 ctx.save_for_backward(ray_ori, ray_dir, rgba, dist)
@@ -641,8 +598,7 @@ class Tracer:
                 # four gradients as four tensors: no torch.cat here (0.43 ms at 6 M Gaussians), no split + four copies in backward
                 rgba, dist, hits, vis = tracer_wrapper.trace_fields(
                     frame_id, n_active_features, mog_pos, mog_dns, mog_rot, mog_scl, particle_radiance, ray_ori.contiguous(),
-                    ray_dir.contiguous(), sensor_params, sensor_poses.timestamps_us[0], sensor_poses.timestamps_us[1],
-                    sensor_poses.T_world_sensors[0], sensor_poses.T_world_sensors[1])
+                    ray_dir.contiguous(), sensor_params, *_pose_args(sensor_poses))
                 ctx.num_particles = int(mog_pos.shape[0])
                 ctx.save_for_backward(ray_ori, ray_dir, rgba, dist, particle_radiance)
                 ctx.mark_non_differentiable(hits, vis)
@@ -653,8 +609,7 @@ class Tracer:
             ray_time = None  # the reference allocates an int64 [1,H,W,1] tensor that no kernel reads (tracer.py:181-186)
             rgba, dist, hits, vis = tracer_wrapper.trace(
                 frame_id, n_active_features, particle_density, particle_radiance, ray_ori.contiguous(),
-                ray_dir.contiguous(), ray_time, sensor_params, sensor_poses.timestamps_us[0], sensor_poses.timestamps_us[1],
-                sensor_poses.T_world_sensors[0], sensor_poses.T_world_sensors[1])
+                ray_dir.contiguous(), ray_time, sensor_params, *_pose_args(sensor_poses))
             ctx.save_for_backward(ray_ori, ray_dir, rgba, dist, particle_density, particle_radiance)
             ctx.mark_non_differentiable(hits, vis)
             return rgba, dist, hits, vis
@@ -667,9 +622,8 @@ class Tracer:
                 if rgba_grd is None:
                     rgba_grd = torch.zeros_like(rgba)
                 pos_g, dns_g, rot_g, scl_g, alb_g, spec_g = ctx.tracer_wrapper.trace_bwd_model_fields(
-                    ctx.frame_id, ctx.n_active_features, ctx.num_particles, ray_ori, ray_dir, ctx.sensor_params, poses.timestamps_us[0],
-                    poses.timestamps_us[1], poses.T_world_sensors[0], poses.T_world_sensors[1], rgba, rgba_grd.contiguous(), dist,
-                    None if dist_grd is None else dist_grd.contiguous())
+                    ctx.frame_id, ctx.n_active_features, ctx.num_particles, ray_ori, ray_dir, ctx.sensor_params, *_pose_args(poses), rgba,
+                    rgba_grd.contiguous(), dist, None if dist_grd is None else dist_grd.contiguous())
                 return (None, None, None, None, None, pos_g, rot_g, scl_g, dns_g, alb_g, None, None, spec_g, None)
             if ctx.fields:
                 ray_ori, ray_dir, rgba, dist, particle_radiance = ctx.saved_tensors
@@ -677,16 +631,14 @@ class Tracer:
                     rgba_grd = torch.zeros_like(rgba)
                 pos_g, dns_g, rot_g, scl_g, sph_grd = ctx.tracer_wrapper.trace_bwd_fields(
                     ctx.frame_id, ctx.n_active_features, ctx.num_particles, particle_radiance, ray_ori, ray_dir, ctx.sensor_params,
-                    poses.timestamps_us[0], poses.timestamps_us[1], poses.T_world_sensors[0], poses.T_world_sensors[1], rgba,
-                    rgba_grd.contiguous(), dist, None if dist_grd is None else dist_grd.contiguous())
+                    *_pose_args(poses), rgba, rgba_grd.contiguous(), dist, None if dist_grd is None else dist_grd.contiguous())
                 return (None, None, None, None, None, pos_g, rot_g, scl_g, dns_g, sph_grd, None, None, None, None)
             ray_ori, ray_dir, rgba, dist, particle_density, particle_radiance = ctx.saved_tensors
             if rgba_grd is None:
                 rgba_grd = torch.zeros_like(rgba)
             dens_grd, sph_grd = ctx.tracer_wrapper.trace_bwd(
-                ctx.frame_id, ctx.n_active_features, particle_density, particle_radiance, ray_ori, ray_dir, None,
-                ctx.sensor_params, poses.timestamps_us[0], poses.timestamps_us[1], poses.T_world_sensors[0],
-                poses.T_world_sensors[1], rgba, rgba_grd.contiguous(), dist, None if dist_grd is None else dist_grd.contiguous())
+                ctx.frame_id, ctx.n_active_features, particle_density, particle_radiance, ray_ori, ray_dir, None, ctx.sensor_params,
+                *_pose_args(poses), rgba, rgba_grd.contiguous(), dist, None if dist_grd is None else dist_grd.contiguous())
             pos_g, dns_g, rot_g, scl_g, _ = torch.split(dens_grd, [3, 1, 4, 3, 1], dim=1)  # tracer.py:268-270
             return (None, None, None, None, None, pos_g.contiguous(), rot_g.contiguous(), scl_g.contiguous(),
                     dns_g.contiguous(), sph_grd, None, None, None, None)
