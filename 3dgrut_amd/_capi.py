@@ -84,6 +84,11 @@ class GutPhotometricLoss(C.Structure):
                 ("d_exposure_grad12", C.c_void_p), ("background", C.c_float), ("lambda_l1", C.c_float), ("lambda_ssim", C.c_float)]
 
 
+class GutContribution(C.Structure):
+    """One Gaussian's contribution record (gut_hip.h, gut_trace_contribution): 16 bytes, accumulated into."""
+    _fields_ = [("weight_sum_q32", C.c_uint64), ("max_weight_bits", C.c_uint32), ("pixels", C.c_uint32)]
+
+
 EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_trace_bwd", "gut_collect_times",
            "gut_get_stats", "gut_debug_buffer", "gut_debug_copy", "gut_kernel_times", "gut_kernel_times_mean", "gut_last_error", "gut_abi_version",
            "gut_ssim_workspace_bytes", "gut_ssim_forward", "gut_ssim_backward",
@@ -97,7 +102,8 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_regularisation_loss", "gut_image_metrics_workspace_bytes", "gut_image_metrics", "gut_photometric_loss_masked",
            "gut_photometric_loss_background", "gut_set_pose_gradient", "gut_pose_adam_step",
            "gut_photometric_exposure_workspace_bytes", "gut_photometric_loss_exposure", "gut_exposure_adam_step",
-           "gut_image_metrics_cc_workspace_bytes", "gut_image_metrics_cc", "gut_photometric_loss_run", "gut_trace_bwd_pose")
+           "gut_image_metrics_cc_workspace_bytes", "gut_image_metrics_cc", "gut_photometric_loss_run", "gut_trace_bwd_pose",
+           "gut_trace_contribution")
 
 _lib = None
 
@@ -138,6 +144,7 @@ def load():
     lib.gut_set_pose_gradient.argtypes = [vp, f_p]
     lib.gut_pose_adam_step.argtypes = [vp, f_p, f_p, f_p, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, f_p]
     lib.gut_trace_bwd_pose.argtypes = [vp, vp, u32, i32, u32, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera), f_p, f_p, f_p, f_p]
+    lib.gut_trace_contribution.argtypes = [vp, vp, u32, i32, u32, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera), vp]
     lib.gut_mcmc_perturb.argtypes = [vp, u32, f_p, f_p, C.c_float, C.c_uint64, C.c_uint64, f_p]
     lib.gut_collect_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.gut_get_stats.argtypes = [vp, C.POINTER(GutStats)]

@@ -20,6 +20,7 @@ UNITS = [
     ("gut_project.hip", ["-ffp-contract=off"]),
     ("gut_render.hip", ["-ffp-contract=fast", "-munsafe-fp-atomics", "-fno-slp-vectorize"]),
     ("gut_render_general.hip", ["-ffp-contract=fast", "-munsafe-fp-atomics", "-fno-slp-vectorize"]),
+    ("gut_contrib.hip", ["-ffp-contract=fast", "-munsafe-fp-atomics", "-fno-slp-vectorize"]),   # gut_render.hip's flags: same contractions
     ("gut_render_sorted.hip", ["-ffp-contract=fast", "-munsafe-fp-atomics", "-fno-slp-vectorize"]),
     ("gut_sort.hip", ["-Wno-unused-parameter"]),
     ("gut_ssim.hip", ["-ffp-contract=fast"]),

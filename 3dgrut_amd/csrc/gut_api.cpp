@@ -821,13 +821,25 @@ bool pose_consume_tests() {
 }
 
 // every refusal of a backward that needs no view parameters; under the handle's lock, nothing is queued or changed
-int check_backward_args(gut_handle h, const TraceView& view, const BwdUpstream& up, const BwdArgs& a) {
+// what every call that follows a forward (`name` in the messages) checks first: the cached context and the view it was made for
+int check_follows_forward(gut_handle h, const TraceView& view, const char* name) {
     // same contract as the reference: backward needs the forward's cached context on the same stream (gutRenderer.cu:413-417)
     if (!h->have_forward || h->fwd_stream != view.stream)
-        return fail("gut_trace_bwd: no forward context on this stream (call gut_trace first, same stream)");
+        return fail("%s: no forward context on this stream (call gut_trace first, same stream)", name);
     if (view.n != h->n || view.width != h->width || view.height != h->height || view.sh_degree != h->sh_degree)
-        return fail("gut_trace_bwd: arguments differ from the cached forward (N %u vs %u, %dx%d vs %dx%d)", view.n, h->n,
+        return fail("%s: arguments differ from the cached forward (N %u vs %u, %dx%d vs %dx%d)", name, view.n, h->n,
                     view.width, view.height, h->width, h->height);
+    return 0;
+}
+// the view of a following call rebuilt and compared with the forward's
+int check_same_camera(gut_handle h, const TraceView& view, const char* name, gut::ViewParams* v) {
+    if (build_view(view.camera, view.width, view.height, h->cfg.n_rolling_shutter_iterations, v)) return 1;
+    if (memcmp(v, &h->view, sizeof(*v)) != 0) return fail("%s: camera differs from the cached forward", name);
+    return 0;
+}
+
+int check_backward_args(gut_handle h, const TraceView& view, const BwdUpstream& up, const BwdArgs& a) {
+    if (check_follows_forward(h, view, "gut_trace_bwd")) return 1;
     // (up.hit_distance_grad == NULL: no loss on pred_dist, the reference trainer's default; its terms are compiled out of the kernel)
     if (!view.camera || !view.ray_origin || !view.ray_direction || !up.rgba || !up.rgba_grad)
         return fail("gut_trace_bwd: null pointer argument");
@@ -895,8 +907,7 @@ int trace_bwd_impl(gut_handle h, const TraceView& view, const BwdUpstream& up, c
     DeviceGuard dev_guard;
     HIP_TRY(dev_guard.set(h->device));
     gut::ViewParams v;
-    if (build_view(view.camera, view.width, view.height, h->cfg.n_rolling_shutter_iterations, &v)) return 1;
-    if (memcmp(&v, &h->view, sizeof(v)) != 0) return fail("gut_trace_bwd: camera differs from the cached forward");
+    if (check_same_camera(h, view, "gut_trace_bwd", &v)) return 1;
     const uint32_t n = h->n;
     if (n == 0) {
         if (h->pose_out) HIP_TRY(hipMemsetAsync(h->pose_out, 0, 8 * sizeof(float), s));   // no rows: F = M = 0, none summed
@@ -1012,6 +1023,44 @@ int gut_trace_bwd_pose(gut_handle h, void* stream_, uint32_t frame_number, int32
     return trace_bwd_impl(h, view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
                           BwdUpstream{d_ray_radiance_density, d_ray_radiance_density_grad, d_ray_hit_distance, d_ray_hit_distance_grad},
                           BwdArgs{BwdMode::kPoseOnly, false, d_particle_density, nullptr, nullptr, gut::GradFields()});
+}
+
+// The contribution scores of the cached forward's view: the forward's walk once more, without colours, into the
+// caller's accumulating records.  Reads the forward's lists and depths, writes tile_order (every backward rebuilds it) and d_scores.
+int gut_trace_contribution(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+                           const float* d_particle_density, int32_t width, int32_t height, const float* d_ray_origin,
+                           const float* d_ray_direction, const GutCamera* camera, GutContribution* d_scores) {
+    const char* const name = "gut_trace_contribution";
+    if (!h) return fail("%s: null handle", name);
+    const TraceView view = view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera);
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (h->cfg.k_buffer_size > 0 || h->cfg.particle_kernel_degree != 2)
+        return fail("%s: supported on the unsorted variant (k_buffer_size=0) at particle_kernel_degree=2 only; this handle has "
+                    "k_buffer_size=%d, particle_kernel_degree=%d", name, h->cfg.k_buffer_size, h->cfg.particle_kernel_degree);
+    if (check_follows_forward(h, view, name)) return 1;
+    if (!view.camera || !view.ray_origin || !view.ray_direction) return fail("%s: null pointer argument", name);
+    if (!d_particle_density) {
+        if (!h->packed_valid && view.n)
+            return fail("%s: d_particle_density is NULL and the last forward on this handle packed no rows (not a *_fields one)", name);
+        d_particle_density = h->packed12.as<float>();
+    }
+    if (view.n && !d_scores) return fail("%s: d_scores is NULL with %u particles", name, view.n);
+    if (((uintptr_t)d_scores & 7u) != 0) return fail("%s: d_scores must be 8-byte aligned", name);
+    if (h->early_ran)
+        return fail("%s: gut_optimize_rows_without_gradient was called for this forward: that optimiser step is half applied "
+                    "(gut_trace_bwd_ex(..., GUT_BWD_SKIP_EPILOGUE) and gut_optimize_after_bwd come first)", name);
+    DeviceGuard dev_guard;
+    HIP_TRY(dev_guard.set(h->device));
+    gut::ViewParams v;
+    if (check_same_camera(h, view, name, &v)) return 1;
+    if (h->n == 0 || h->m == 0) return 0;   // nothing was walked
+    const hipStream_t s = view.stream;
+    gut::launch_tile_order(s, (uint32_t)h->tiles, h->trav_fwd.as<uint32_t>(), h->tile_order.as<uint32_t>());
+    gut::launch_contribution(s, v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
+                             (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
+                             h->trav_fwd.as<uint32_t>(), h->n, d_scores);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // SplatRaster::trace with the four activated tensors the reference's Tracer hands to _Autograd (tracer.py:317-327) instead of

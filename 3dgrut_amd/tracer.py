@@ -441,6 +441,28 @@ class SplatRaster:
         self._call("trace_bwd_pose", self._lib.gut_trace_bwd_pose, dev, frame_number, int(num_active_features), n, _ptr(rows), W, H,
                    ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(), rgba_g.data_ptr(), dist.data_ptr(), _ptr(dist_g))
 
+    def trace_contribution(self, frame_number, num_active_features, particle_density, ray_ori, ray_dir, sensor_params, ts_start, ts_end,
+                           pose_start, pose_end, scores):
+        """Adds the cached forward's per-Gaussian contribution to `scores` (gut_trace_contribution): an int64 [N,2] GPU tensor of
+        GutContribution records the caller zeroed once (column 0: the weight sum in units of 2^-32; column 1: the float bits of the
+        largest weight in the low word, the composited-pixel count in the high word; contribution.unpack_scores reads it).  Follows any
+        forward on this handle, consumes nothing, and may be followed by any backward.  Unsorted variant at kernel degree 2 only.
+        particle_density: the [N,12] rows of the forward, or an int N after a *_fields forward (the rows that forward packed)."""
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
+        rows = None
+        if isinstance(particle_density, torch.Tensor):
+            n = int(particle_density.shape[0])
+            if n:
+                rows = _check_f32_cuda(particle_density, "particleDensity", (12,))
+        else:
+            n = int(particle_density)
+        if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.int64 and scores.is_contiguous()
+                and tuple(scores.shape) == (n, 2) and scores.device == dev):
+            raise RuntimeError(f"[3dgut] contribution scores: a contiguous int64 tensor [{n}, 2] on the rays' GPU")
+        cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
+        self._call("trace_contribution", self._lib.gut_trace_contribution, dev, frame_number, int(num_active_features), n, _ptr(rows), W, H,
+                   ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), _ptr(scores, n))
+
     def set_regularisation(self, reg):
         """The NEXT optimiser step on the handle (optimize_rows_without_gradient + optimize_after_bwd, or
         finish_optimizer_step_without_gradient) adds the MCMC regularisers' gradient to every row it updates and writes the loss

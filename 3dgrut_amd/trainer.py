@@ -42,10 +42,18 @@ the plain one — the number to compare a `--refine-poses` run with a run withou
 `validation: true` to the validation passes too; `lr_translation` is multiplied by the scene extent, the loss weights are the run's.
 The rates and the iteration count are untuned on real captures.  It needs nothing from the checkpoint and writes nothing into it.
 
+`compaction.enabled` (default off; `--compact-to FRACTION`) compacts the trained model (contribution.py): after the
+last training iteration every training view is rendered once more and each Gaussian's contribution to them is accumulated on the
+device (ContributionScores); the best `keep_fraction` of the rows by `score` stay (rows composited in fewer than `min_pixels` pixels
+go first), the others leave with their optimiser state; `finetune_iterations` further steps follow with the strategy detached (no
+densification, the learning-rate schedule continuing); then the usual final checkpoint and test pass.  The test split is scored
+once more BEFORE the pruning, so that both sides of the trade are printed.  One GPU only.
+
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
                                  [--refine-poses [--pose-lr-translation X] [--pose-lr-rotation R]]
                                  [--exposure [--exposure-lr X]] [--cc-metrics] [--aligned-metrics [--align-iterations K]]
+                                 [--compact-to FRACTION [--compact-score weight_sum|max_weight] [--compact-finetune K]]
 """
 import argparse
 import copy
@@ -57,6 +65,7 @@ import time
 import numpy as np
 import torch
 
+from . import contribution as contribution_mod
 from . import exposure as exposure_mod
 from . import losses, pose_align, pose_refine
 from .evaluate import _check_batch, evaluate
@@ -90,6 +99,10 @@ GS_CONFIG = {
     # scene extent, lr_rotation is in radians; validation: the validation passes too, not only the final test pass.  The two rates and
     # the iteration count are untuned on real captures.
     "pose_alignment": dict(pose_align.DEFAULTS),
+    # not a reference key: compaction of the trained model by per-Gaussian contribution scores (contribution.py), after the last
+    # training iteration.  keep_fraction of the rows stay (the best by `score`; rows composited in fewer than min_pixels pixels of the
+    # training views go first), then finetune_iterations further steps without the strategy.
+    "compaction": dict(contribution_mod.DEFAULTS),
     "strategy": {"method": "GSStrategy",
                  "densify": {"frequency": 300, "start_iteration": 500, "end_iteration": 15000, "clone_grad_threshold": 0.0002,
                              "split_grad_threshold": 0.0002, "relative_size_threshold": 0.01, "split": {"n_gaussians": 2}},
@@ -143,6 +156,7 @@ def resolve_config(conf):
     exposure_mod.check_config(out["exposure"])
     check_evaluation_config(out["evaluation"])
     pose_align.check_config(out["pose_alignment"])
+    contribution_mod.check_config(out["compaction"])
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
         out["optimizer"]["params"]["features_specular"] = {"lr": float(out["optimizer"]["params"]["features_albedo"]["lr"]) / 20}
@@ -329,6 +343,8 @@ class Trainer:
         self.exposure = self._build_exposure(ckpt)
         if ckpt is not None:
             self.global_step = int(ckpt["global_step"])
+        if c["compaction"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
+            raise ValueError("compaction: data-parallel compaction is out of scope (the stepper's world_size must be 1)")
 
     # ---- construction ----
     def _build(self, scene, ckpt, tracer):
@@ -540,21 +556,10 @@ class Trainer:
         while self.global_step < n_iter:
             g = self.global_step
             view = self.batch_index(g)
-            batch = self.train_batches[view]
             if (g > 0 or c["validate_first"]) and g % val_freq == 0:
                 self.validate()
-            refiner = self.refiner
-            if refiner is not None:
-                batch = refiner.begin(view, batch)          # the view's refined pose (its pending increment applied first)
-                switch = getattr(self.stepper, "enable_pose_gradient", None)
-                if switch is not None:                      # outside [start_iteration, end_iteration) the backward reduces nothing
-                    switch(refiner.active(g))
-            comp = self.exposure
-            if comp is not None:
-                batch = comp.begin(view, batch)             # batch.exposure: the view's row of the device state
-                switch = getattr(self.stepper, "enable_exposure_gradient", None)
-                if switch is not None:                      # outside [start_iteration, end_iteration) the loss reduces nothing
-                    switch(comp.active(g))
+            refiner, comp = self.refiner, self.exposure
+            batch = self._train_batch(view, g)
             self._last_loss, _ = self.stepper.step(batch)   # scheduler + SH ramp run at the end of step()
             if comp is not None and comp.active(g):
                 comp.end(view, self.stepper.exposure_gradient)   # twelve-float Adam on the device: nothing waits
@@ -577,9 +582,71 @@ class Trainer:
             self.stats.update(exposure_mean_gain=sm["mean_gain"], exposure_mean_offset=sm["mean_offset"])
         return self.stats
 
+    def _train_batch(self, view, g):
+        """Training batch `view` as step g trains on it: the view's refined pose and exposure row, the gradients' switches set."""
+        batch = self.train_batches[view]
+        refiner = self.refiner
+        if refiner is not None:
+            batch = refiner.begin(view, batch)          # the view's refined pose (its pending increment applied first)
+            switch = getattr(self.stepper, "enable_pose_gradient", None)
+            if switch is not None:                      # outside [start_iteration, end_iteration) the backward reduces nothing
+                switch(refiner.active(g))
+        comp = self.exposure
+        if comp is not None:
+            batch = comp.begin(view, batch)             # batch.exposure: the view's row of the device state
+            switch = getattr(self.stepper, "enable_exposure_gradient", None)
+            if switch is not None:                      # outside [start_iteration, end_iteration) the loss reduces nothing
+                switch(comp.active(g))
+        return batch
+
+    def _compaction_mask(self, result):
+        """The rows the compaction keeps, from the accumulated scores (contribution.keep_mask with the block's settings)."""
+        cp = self.conf["compaction"]
+        return contribution_mod.keep_mask(result, score=cp["score"], keep_fraction=float(cp["keep_fraction"]), min_pixels=int(cp["min_pixels"]))
+
+    def compact(self):
+        """The `compaction` block, after train(): the test split scored before the pruning, the contribution scores of the training
+        views (at their refined poses), the pruning, the fine-tuning steps with the strategy detached.  Fills and returns the
+        compaction_* statistics."""
+        cp = self.conf["compaction"]
+        before = None
+        if self.test_batches:
+            before = self.evaluator(self.model, self.tracer, self.test_batches, None, self.global_step, **self._evaluation_options())
+        scorer = contribution_mod.ContributionScores(self.model, self.tracer)
+        for view in range(len(self.train_batches)):
+            batch = self.train_batches[view]
+            if self.refiner is not None:
+                batch = self.refiner.begin(view, batch)
+            scorer.accumulate(batch)
+        n_before = int(self.model.num_gaussians)
+        mask = self._compaction_mask(scorer.result())
+        del scorer
+        detach = getattr(self.strategy, "detach", None)
+        if detach is not None:
+            detach()    # no densification statistics from here on
+        contribution_mod.compact(self.stepper, mask, self.strategy)
+        for _ in range(int(cp["finetune_iterations"])):
+            g = self.global_step
+            view = self.batch_index(g)
+            batch = self._train_batch(view, g)
+            self._last_loss, _ = self.stepper.step(batch)
+            if self.exposure is not None and self.exposure.active(g):
+                self.exposure.end(view, self.stepper.exposure_gradient)
+            if self.refiner is not None and self.refiner.active(g):
+                self.refiner.end(view, self.stepper.pose_gradient)
+            self.global_step = g + 1
+        self._sync()
+        out = dict(compaction_n_before=n_before, compaction_n_after=int(self.model.num_gaussians), compaction_score=str(cp["score"]),
+                   compaction_test_psnr_before=None if before is None else float(before["mean_psnr"]))
+        self.stats.update(out, n_gaussians=int(self.model.num_gaussians), n_steps=self.global_step)
+        return out
+
     def run(self):
-        """train(), print the statistics table, then (test_last) save ckpt_last.pt and evaluate the test split."""
+        """train(), (compaction.enabled) compact(), print the statistics table, then (test_last) save ckpt_last.pt and evaluate the
+        test split."""
         stats = self.train()
+        if self.conf["compaction"]["enabled"]:
+            self.compact()
         print("Training Statistics: " + json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in stats.items()}), flush=True)
         if self.conf["test_last"] and self.test_batches:
             self.save_checkpoint(last=True)
@@ -615,6 +682,11 @@ def build_parser():
                     help="also score held-out views pose-aligned: each test view's pose is optimised against its photo with the model "
                          "frozen before it is scored again (pose_alignment.enabled); the plain scores stay")
     ap.add_argument("--align-iterations", type=int, default=None, help="pose_alignment.iterations")
+    ap.add_argument("--compact-to", type=float, default=None, metavar="FRACTION",
+                    help="after training, keep this fraction of the Gaussians: the best by their contribution to the training views "
+                         "(compaction.enabled, compaction.keep_fraction)")
+    ap.add_argument("--compact-score", choices=contribution_mod.SCORES, default=None, help="compaction.score")
+    ap.add_argument("--compact-finetune", type=int, default=None, metavar="K", help="compaction.finetune_iterations")
     return ap
 
 
@@ -640,6 +712,13 @@ def config_from_args(a):
     conf["pose_alignment"]["enabled"] = bool(a.aligned_metrics)
     if a.align_iterations is not None:
         conf["pose_alignment"]["iterations"] = a.align_iterations
+    if a.compact_to is not None:
+        conf["compaction"]["enabled"] = True
+        conf["compaction"]["keep_fraction"] = a.compact_to
+    if a.compact_score is not None:
+        conf["compaction"]["score"] = a.compact_score
+    if a.compact_finetune is not None:
+        conf["compaction"]["finetune_iterations"] = a.compact_finetune
     return conf
 
 

@@ -46,7 +46,8 @@ extern "C" {
  * gut_photometric_exposure_workspace_bytes, gut_photometric_loss_exposure and gut_exposure_adam_step, new entry points next to the
  * other forms of the fused loss, which launch what they launched before; gut_image_metrics_cc_workspace_bytes and gut_image_metrics_cc,
  * new entry points next to gut_image_metrics, which launches what it launched before; GutPhotometricLoss and gut_photometric_loss_run,
- * the descriptor form of the fused loss: the four positional forms keep their signatures and call it). */
+ * the descriptor form of the fused loss: the four positional forms keep their signatures and call it; GutContribution and
+ * gut_trace_contribution, a new entry point: every other call queues what it queued before). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -650,6 +651,35 @@ int gut_trace_bwd_pose(gut_handle h, void* stream, uint32_t frame_number, int32_
                        const float* d_ray_direction, const GutCamera* camera, const float* d_ray_radiance_density,
                        const float* d_ray_radiance_density_grad, const float* d_ray_hit_distance,
                        const float* d_ray_hit_distance_grad /* may be NULL */);
+
+/* ---- Per-Gaussian contribution scores (new functionality, the reference has none) ----
+ * What each Gaussian contributed to the view of the cached forward, from the blending weights w = T * alpha the forward compositor
+ * formed (T: the ray's transmittance in front of the Gaussian): per Gaussian, over every pixel in which the forward composited it,
+ * the sum of w, the largest w and the number of such pixels (the pixels the hit-count plane counts).  One record of 16 bytes per
+ * Gaussian, ACCUMULATED INTO: the caller zeroes the array once and calls this after the forward of every view it wants scored. */
+typedef struct GutContribution {
+    uint64_t weight_sum_q32;   /* sum over (view, tile) of round(tile_sum * 2^32): integer adds, so the total is independent of arrival order */
+    uint32_t max_weight_bits;  /* float bits of the largest w seen; atomicMax on the bits (w >= 0, so the bits order like the values) */
+    uint32_t pixels;           /* pixels, over all views, in which the Gaussian was composited (w > 0) */
+} GutContribution;
+/* Follows any forward on the same handle and stream (arguments as gut_trace_bwd_pose's view; d_particle_density may be NULL after a
+ * *_fields forward: the rows that forward packed).  Two launches: the tile order by the forward's walked depth, then one walk of
+ * what the forward walked — the same ordered-id lists, bounded by the forward's per-tile depth as the backward compositor bounds
+ * them, the forward's tests by the forward's arithmetic, no colours read and no image written.  Per (tile, Gaussian) the 256 weights
+ * are reduced in a fixed order (inside each wave, then the four waves in wave order); a Gaussian no pixel of the tile composited
+ * issues nothing, the others one 64-bit integer add, one 32-bit integer max and one 32-bit integer add.  Identical inputs therefore
+ * give identical bytes, from run to run and whatever the order in which views are accumulated; a Gaussian without a tile, or behind
+ * every walked prefix, keeps its 16 bytes.  The forward context is NOT consumed: the gradient rows, the backward's traversal depths
+ * and every forward output are left alone, and any backward (or another gut_trace_contribution) may follow.
+ * Unsorted variant at the default kernel only.  Returns 1 on the host, before anything is queued and with the handle left as it was,
+ * for: a null handle, camera or ray pointer; d_scores NULL or not 8-byte aligned with num_particles > 0; no forward on this stream;
+ * arguments or a camera that differ from the cached forward; a handle created with k_buffer_size > 0 or particle_kernel_degree != 2;
+ * gut_optimize_rows_without_gradient called for this forward.  num_particles == 0 or a forward without intersections: nothing is
+ * queued, 0 is returned.  Not part of the kernel timers. */
+int gut_trace_contribution(gut_handle h, void* stream, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+                           const float* d_particle_density /* NULL: the rows the last *_fields forward packed */,
+                           int32_t width, int32_t height, const float* d_ray_origin, const float* d_ray_direction,
+                           const GutCamera* camera, GutContribution* d_scores /* [N], accumulated into */);
 
 /* ---- Per-view exposure in the fused loss (new functionality, the reference has none) ----
  * gut_photometric_loss_exposure is the fused loss of gut_photometric_loss[_masked | _background] on the AFFINE image of a view:
