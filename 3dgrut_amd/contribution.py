@@ -12,6 +12,15 @@ ONCE per pass, as pose_align.DeviceStep does) and SplatRaster.trace_contribution
 synchronisation in between.  The records are integers (the sum in units of 2^-32, the maximum as float bits, a count), updated by
 integer atomics: the result is the same bit for bit whatever the order of the views, from run to run.
 
+With a per-pixel plane e in [0, 1] (accumulate(batch, pixel_weight=plane)) the same walk also sums w * e:
+
+    weighted_sum the sum of w * e   ("how much of the per-pixel quantity e did this Gaussian draw")
+
+With e the rendering error of the view (accumulate_error) it is the error the Gaussian is responsible for, the score of error-based
+densification (strategy.select_by_error).  With e a 2-D segmentation mask (0 or 1) it lifts the mask to the Gaussians:
+weighted_sum / weight_sum is the share of the Gaussian's drawn weight that lies inside the mask, 1 for a Gaussian seen only inside
+it, 0 for one seen only outside, over as many views as were accumulated; threshold it for a 3-D selection.
+
 `keep_mask` turns a result into the rows to keep ("the best fraction"), deterministically; `compact` removes the others from a
 NativeTrainStep's model together with their optimiser state, the way the densification strategies prune.
 """
@@ -46,22 +55,45 @@ class ContributionScores:
             self.features = model.get_features().detach().to(torch.float32).contiguous()
         self.n_active_features = int(model.n_active_features)
         self.scores = torch.zeros((self.act.shape[0], 2), dtype=torch.int64, device=self.act.device)
+        self.weighted = None     # uint64 [N] in units of 2^-32, held as int64 (torch has no uint64 arithmetic); created by the first plane
         self.n_views = 0
 
-    def accumulate(self, batch):
-        """One forward at the batch's pose and its contribution walk; nothing is read back."""
+    def _accumulate(self, batch, plane_of):
         sensor, poses = self._create_camera(batch)
         rays_o, rays_d = batch.rays_ori.contiguous(), batch.rays_dir.contiguous()
         cam = (sensor, poses.timestamps_us[0], poses.timestamps_us[1], poses.T_world_sensors[0], poses.T_world_sensors[1])
-        self.raster.trace(0, self.n_active_features, self.act, self.features, rays_o, rays_d, None, *cam)
-        self.raster.trace_contribution(0, self.n_active_features, self.act, rays_o, rays_d, *cam, self.scores)
+        outs = self.raster.trace(0, self.n_active_features, self.act, self.features, rays_o, rays_d, None, *cam)
+        plane = plane_of(outs[0])
+        if plane is None:
+            self.raster.trace_contribution(0, self.n_active_features, self.act, rays_o, rays_d, *cam, self.scores)
+        else:
+            if self.weighted is None:
+                self.weighted = torch.zeros((self.act.shape[0],), dtype=torch.int64, device=self.act.device)
+            self.raster.trace_contribution(0, self.n_active_features, self.act, rays_o, rays_d, *cam, self.scores,
+                                           pixel_weight=plane, weighted=self.weighted)
         self.n_views += 1
         return self
 
+    def accumulate(self, batch, pixel_weight=None):
+        """One forward at the batch's pose and its contribution walk; nothing is read back.  pixel_weight: a contiguous float32
+        [H,W] plane on the device (clamped to [0, 1] by the kernel); the walk then also adds the sums of w * plane to weighted_sum."""
+        return self._accumulate(batch, lambda rgba: pixel_weight)
+
+    def accumulate_error(self, batch, background, mask=None, exposure=None):
+        """accumulate() with the view's rendering error as the plane (losses.fused_pixel_error of the forward's image against
+        batch.rgb_gt): the operands are fused_photometric_loss's — background "black", "white", a number or a tensor; mask None or
+        the view's mask; exposure None or the view's float32 [12] / [3,4] device tensor."""
+        from .losses import fused_pixel_error
+        return self._accumulate(batch, lambda rgba: fused_pixel_error(rgba, batch.rgb_gt.contiguous(), background, mask=mask, exposure=exposure))
+
     def result(self):
-        """dict(weight_sum float64 [N], max_weight float32 [N], pixels int64 [N], n_views), on the model's device."""
+        """dict(weight_sum float64 [N], max_weight float32 [N], pixels int64 [N], n_views), on the model's device; once a view was
+        accumulated with a plane also weighted_sum float64 [N]."""
         weight_sum, max_weight, pixels = unpack_scores(self.scores)
-        return dict(weight_sum=weight_sum, max_weight=max_weight, pixels=pixels, n_views=self.n_views)
+        out = dict(weight_sum=weight_sum, max_weight=max_weight, pixels=pixels, n_views=self.n_views)
+        if self.weighted is not None:
+            out["weighted_sum"] = self.weighted.to(torch.float64) * (2.0 ** -32)    # below 2^63: non-negative as int64
+        return out
 
 
 def keep_count_of(keep_fraction, n):

@@ -967,6 +967,47 @@ int trace_bwd_packed(gut_handle h, const char* name, const char* forwards, const
                                                d_particle_radiance_grad, f});
 }
 
+// The contribution scores of the cached forward's view (DESIGN.md §13, §14): the forward's walk once more, without colours, into the
+// caller's accumulating arrays.  Reads the forward's lists and depths, writes tile_order (every backward rebuilds it) and d_scores /
+// d_weighted_q32.  weighted: the form with a per-pixel plane (gut_trace_contribution_weighted), whose records are optional.
+int trace_contribution_impl(gut_handle h, const char* name, const TraceView& view, const float* d_particle_density,
+                            GutContribution* d_scores, bool weighted, const float* d_pixel_weight, uint64_t* d_weighted_q32) {
+    if (!h) return fail("%s: null handle", name);
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (h->cfg.k_buffer_size > 0 || h->cfg.particle_kernel_degree != 2)
+        return fail("%s: supported on the unsorted variant (k_buffer_size=0) at particle_kernel_degree=2 only; this handle has "
+                    "k_buffer_size=%d, particle_kernel_degree=%d", name, h->cfg.k_buffer_size, h->cfg.particle_kernel_degree);
+    if (check_follows_forward(h, view, name)) return 1;
+    if (!view.camera || !view.ray_origin || !view.ray_direction) return fail("%s: null pointer argument", name);
+    if (!d_particle_density) {
+        if (!h->packed_valid && view.n)
+            return fail("%s: d_particle_density is NULL and the last forward on this handle packed no rows (not a *_fields one)", name);
+        d_particle_density = h->packed12.as<float>();
+    }
+    if (view.n && !d_scores && !weighted) return fail("%s: d_scores is NULL with %u particles", name, view.n);
+    if (((uintptr_t)d_scores & 7u) != 0) return fail("%s: d_scores must be 8-byte aligned", name);
+    if (weighted) {
+        if (!d_pixel_weight) return fail("%s: d_pixel_weight is NULL", name);
+        if (view.n && !d_weighted_q32) return fail("%s: d_weighted_q32 is NULL with %u particles", name, view.n);
+        if (view.n && ((uintptr_t)d_weighted_q32 & 7u) != 0) return fail("%s: d_weighted_q32 must be 8-byte aligned", name);
+    }
+    if (h->early_ran)
+        return fail("%s: gut_optimize_rows_without_gradient was called for this forward: that optimiser step is half applied "
+                    "(gut_trace_bwd_ex(..., GUT_BWD_SKIP_EPILOGUE) and gut_optimize_after_bwd come first)", name);
+    DeviceGuard dev_guard;
+    HIP_TRY(dev_guard.set(h->device));
+    gut::ViewParams v;
+    if (check_same_camera(h, view, name, &v)) return 1;
+    if (h->n == 0 || h->m == 0) return 0;   // nothing was walked
+    const hipStream_t s = view.stream;
+    gut::launch_tile_order(s, (uint32_t)h->tiles, h->trav_fwd.as<uint32_t>(), h->tile_order.as<uint32_t>());
+    gut::launch_contribution(s, v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
+                             (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
+                             h->trav_fwd.as<uint32_t>(), h->n, d_scores, weighted ? d_pixel_weight : nullptr, d_weighted_q32);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1025,42 +1066,21 @@ int gut_trace_bwd_pose(gut_handle h, void* stream_, uint32_t frame_number, int32
                           BwdArgs{BwdMode::kPoseOnly, false, d_particle_density, nullptr, nullptr, gut::GradFields()});
 }
 
-// The contribution scores of the cached forward's view (DESIGN.md §13): the forward's walk once more, without colours, into the
-// caller's accumulating records.  Reads the forward's lists and depths, writes tile_order (every backward rebuilds it) and d_scores.
 int gut_trace_contribution(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
                            const float* d_particle_density, int32_t width, int32_t height, const float* d_ray_origin,
                            const float* d_ray_direction, const GutCamera* camera, GutContribution* d_scores) {
-    const char* const name = "gut_trace_contribution";
-    if (!h) return fail("%s: null handle", name);
-    const TraceView view = view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera);
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (h->cfg.k_buffer_size > 0 || h->cfg.particle_kernel_degree != 2)
-        return fail("%s: supported on the unsorted variant (k_buffer_size=0) at particle_kernel_degree=2 only; this handle has "
-                    "k_buffer_size=%d, particle_kernel_degree=%d", name, h->cfg.k_buffer_size, h->cfg.particle_kernel_degree);
-    if (check_follows_forward(h, view, name)) return 1;
-    if (!view.camera || !view.ray_origin || !view.ray_direction) return fail("%s: null pointer argument", name);
-    if (!d_particle_density) {
-        if (!h->packed_valid && view.n)
-            return fail("%s: d_particle_density is NULL and the last forward on this handle packed no rows (not a *_fields one)", name);
-        d_particle_density = h->packed12.as<float>();
-    }
-    if (view.n && !d_scores) return fail("%s: d_scores is NULL with %u particles", name, view.n);
-    if (((uintptr_t)d_scores & 7u) != 0) return fail("%s: d_scores must be 8-byte aligned", name);
-    if (h->early_ran)
-        return fail("%s: gut_optimize_rows_without_gradient was called for this forward: that optimiser step is half applied "
-                    "(gut_trace_bwd_ex(..., GUT_BWD_SKIP_EPILOGUE) and gut_optimize_after_bwd come first)", name);
-    DeviceGuard dev_guard;
-    HIP_TRY(dev_guard.set(h->device));
-    gut::ViewParams v;
-    if (check_same_camera(h, view, name, &v)) return 1;
-    if (h->n == 0 || h->m == 0) return 0;   // nothing was walked
-    const hipStream_t s = view.stream;
-    gut::launch_tile_order(s, (uint32_t)h->tiles, h->trav_fwd.as<uint32_t>(), h->tile_order.as<uint32_t>());
-    gut::launch_contribution(s, v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
-                             (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
-                             h->trav_fwd.as<uint32_t>(), h->n, d_scores);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return trace_contribution_impl(h, "gut_trace_contribution",
+                                   view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                                   d_particle_density, d_scores, false, nullptr, nullptr);
+}
+
+int gut_trace_contribution_weighted(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features,
+                                    uint32_t num_particles, const float* d_particle_density, int32_t width, int32_t height,
+                                    const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
+                                    const float* d_pixel_weight, GutContribution* d_scores, uint64_t* d_weighted_q32) {
+    return trace_contribution_impl(h, "gut_trace_contribution_weighted",
+                                   view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                                   d_particle_density, d_scores, true, d_pixel_weight, d_weighted_q32);
 }
 
 // SplatRaster::trace with the four activated tensors the reference's Tracer hands to _Autograd (tracer.py:317-327) instead of

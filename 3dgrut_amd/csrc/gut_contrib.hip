@@ -12,6 +12,10 @@
 // not fixed.  An entry no pixel composited issues nothing; the others add into the caller's 16-byte GutContribution record with
 // integer atomics only (the sum as round(sum * 2^32) in 64 bits), so the totals do not depend on the order in which tiles or views
 // arrive: identical inputs give identical bits.
+//
+// The weighted form (gut_trace_contribution_weighted) is the same walk with one more factor: each lane loads its pixel's
+// value e of a caller plane once, clamped to [0, 1], multiplies the weight `entry` returns by it AFTERWARDS (the evaluation itself is
+// untouched), and w * e goes through the same tree, its own LDS plane and the same wave order into a uint64 array of the caller's.
 #include "gut_internal.h"
 #include "gut_render_common.h"
 
@@ -66,12 +70,18 @@ __device__ __forceinline__ float wave_max_lane63(float v) {
 
 constexpr uint32_t kWaves = kBlock / 64;
 
+// kPlain: the GutContribution records (sum, maximum, count of w).  kWeighted: the sum of w * e into weighted_q32, e the pixel's value
+// of `plane` clamped to [0, 1].  <true, false> is the kernel of §13; the other two read `plane`, <false, true>
+// writes no record (scores is not read).
+template <bool kPlain, bool kWeighted>
 __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, RenderConsts c, const float4* __restrict__ density12,
                                                            const float* __restrict__ ray_ori, const float* __restrict__ ray_dir,
                                                            const uint2* __restrict__ ranges, const uint32_t* __restrict__ ordered_ids,
                                                            const uint32_t* __restrict__ tile_order,
                                                            const uint32_t* __restrict__ tile_walked, uint32_t num_particles,
-                                                           GutContribution* __restrict__ scores) {
+                                                           GutContribution* __restrict__ scores, const float* __restrict__ plane,
+                                                           unsigned long long* __restrict__ weighted_q32) {
+    static_assert(kPlain || kWeighted, "nothing to write");
     __shared__ ContribEntry stage[kBlock];
     __shared__ uint32_t s_id[kBlock];
     __shared__ uint32_t s_first_invalid;
@@ -79,8 +89,9 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
     __shared__ uint16_t s_list[kWaves][kBlock];      // see k_render
     __shared__ StripPlanes s_planes;
     // the waves' partials of the chunk: written by lane 63 of wave w for the entries some pixel of the wave composited; s_cnt is zeroed
-    // per chunk and says which of the other two are valid
-    __shared__ float s_sum[kWaves][kBlock], s_max[kWaves][kBlock];
+    // per chunk and says which of the others are valid (s_wsum: the weighted sums)
+    __shared__ float s_sum[kPlain ? kWaves : 1][kPlain ? kBlock : 1], s_max[kPlain ? kWaves : 1][kPlain ? kBlock : 1];
+    __shared__ float s_wsum[kWeighted ? kWaves : 1][kWeighted ? kBlock : 1];
     __shared__ uint32_t s_cnt[kWaves][kBlock];
 
     const uint32_t tile = tile_order[blockIdx.x];
@@ -90,6 +101,9 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
     const bool inside = (px < v.width) && (py < v.height);
     const size_t pix = (size_t)py * (size_t)v.width + (size_t)px;
     const RayState ray = make_ray(v, ray_ori, ray_dir, pix, inside);
+    // the pixel's weight, once: clamped on load, so a NaN counts as 0, every w * e lies in [0, w] and a tile's sum stays below 256
+    float e = 0.0f;
+    if constexpr (kWeighted) e = fminf(fmaxf(inside ? plane[pix] : 0.0f, 0.0f), 1.0f);
 
     if (tid == 0) s_first_invalid = kBlock;
     const bool centred = __syncthreads_and(ray.centred ? 1 : 0) != 0;  // block-uniform
@@ -193,12 +207,22 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
         auto reduce = [&](const float w, const uint32_t j) __attribute__((always_inline)) {
             const unsigned long long hit = __ballot(w > 0.0f);
             if (hit == 0ull) return;
-            const float sum = wave_sum_lane63(w), mx = wave_max_lane63(w);
-            if (lane == 63u) {
-                s_sum[wave][j] = sum;
-                s_max[wave][j] = mx;
-                s_cnt[wave][j] = (uint32_t)__popcll(hit);
+            if constexpr (kPlain) {
+                const float sum = wave_sum_lane63(w), mx = wave_max_lane63(w);
+                if (lane == 63u) {
+                    s_sum[wave][j] = sum;
+                    s_max[wave][j] = mx;
+                }
             }
+            if constexpr (kWeighted) {
+                // the product is rounded on its own in every instantiation: behind the empty asm the first add of the tree cannot
+                // be contracted with it into a fused multiply-add
+                float we = w * e;
+                asm volatile("" : "+v"(we));
+                const float wsum = wave_sum_lane63(we);
+                if (lane == 63u) s_wsum[wave][j] = wsum;
+            }
+            if (lane == 63u) s_cnt[wave][j] = (uint32_t)__popcll(hit);
         };
         // as in k_render: the wave compacts the chunk to the entries that can reach its 8x8 block, then walks that list with the
         // two-register-set software pipeline
@@ -245,22 +269,30 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
         __syncthreads();
         if (tid < cnt) {
             uint32_t pixels = 0;
-            float sum = 0.0f, mx = 0.0f;
+            float sum = 0.0f, mx = 0.0f, wsum = 0.0f;
 #pragma unroll
             for (uint32_t w = 0; w < kWaves; ++w) {
                 const uint32_t n = s_cnt[w][tid];
                 if (n != 0u) {
                     pixels += n;
-                    sum += s_sum[w][tid];
-                    mx = fmaxf(mx, s_max[w][tid]);
+                    if constexpr (kPlain) {
+                        sum += s_sum[w][tid];
+                        mx = fmaxf(mx, s_max[w][tid]);
+                    }
+                    if constexpr (kWeighted) wsum += s_wsum[w][tid];
                 }
             }
             if (pixels != 0u) {
-                GutContribution* const row = scores + s_id[tid];
                 // a tile's sum is at most 256: the product is below 2^41 and exact in fp32 (a power-of-two scale), the conversion rounds to nearest
-                atomicAdd(reinterpret_cast<unsigned long long*>(&row->weight_sum_q32), __float2ull_rn(sum * 4294967296.0f));
-                atomicMax(&row->max_weight_bits, __float_as_uint(mx));
-                atomicAdd(&row->pixels, pixels);
+                if constexpr (kPlain) {
+                    GutContribution* const row = scores + s_id[tid];
+                    atomicAdd(reinterpret_cast<unsigned long long*>(&row->weight_sum_q32), __float2ull_rn(sum * 4294967296.0f));
+                    atomicMax(&row->max_weight_bits, __float_as_uint(mx));
+                    atomicAdd(&row->pixels, pixels);
+                }
+                if constexpr (kWeighted) {
+                    if (wsum > 0.0f) atomicAdd(weighted_q32 + s_id[tid], __float2ull_rn(wsum * 4294967296.0f));
+                }
             }
         }
         // (the next chunk's staging starts behind the barrier at the head of the loop)
@@ -273,11 +305,15 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
 
 void launch_contribution(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
                          const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
-                         const uint32_t* tile_walked, uint32_t num_particles, GutContribution* scores) {
+                         const uint32_t* tile_walked, uint32_t num_particles, GutContribution* scores, const float* plane,
+                         uint64_t* weighted_q32) {
     const uint32_t tiles = (uint32_t)(v.grid_x * v.grid_y);
     if (tiles == 0) return;
-    hipLaunchKernelGGL(k_contribution, dim3(tiles), dim3(kBlock), 0, s, v, c, reinterpret_cast<const float4*>(density12), ray_ori,
-                       ray_dir, reinterpret_cast<const uint2*>(ranges), ordered_ids, tile_order, tile_walked, num_particles, scores);
+    // no plane: the records alone; a plane: its weighted sums, with the records in the same walk where the caller wants them
+    const auto kernel = !plane ? k_contribution<true, false> : scores ? k_contribution<true, true> : k_contribution<false, true>;
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(kBlock), 0, s, v, c, reinterpret_cast<const float4*>(density12), ray_ori, ray_dir,
+                       reinterpret_cast<const uint2*>(ranges), ordered_ids, tile_order, tile_walked, num_particles, scores, plane,
+                       reinterpret_cast<unsigned long long*>(weighted_q32));
 }
 
 }  // namespace gut

@@ -223,10 +223,13 @@ void launch_tile_order(hipStream_t s, uint32_t tiles, const uint32_t* traversed,
                        bool by_length = false, uint32_t* walk_sums = nullptr);
 // gut_contrib.hip: the forward's walk again (unsorted variant, kernel degree 2), without colours; adds every walked Gaussian's sum and
 // maximum of blending weights and its composited-pixel count to scores [N] (integer atomics).  ordered_ids: the list the backward
-// compositor reads; tile_order: a launch order of all the tiles (required); tile_walked: the forward's per-tile traversal depth
+// compositor reads; tile_order: a launch order of all the tiles (required); tile_walked: the forward's per-tile traversal depth.
+// plane [H,W] (null: the records alone): every weight is also multiplied by the pixel's value clamped to [0, 1] and summed into
+// weighted_q32 [N]; with a plane, scores may be null (the weighted sums alone)
 void launch_contribution(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
                          const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
-                         const uint32_t* tile_walked, uint32_t num_particles, GutContribution* scores);
+                         const uint32_t* tile_walked, uint32_t num_particles, GutContribution* scores, const float* plane = nullptr,
+                         uint64_t* weighted_q32 = nullptr);
 // sorted (k_buffer_size > 0) compositor variant, gut_render_sorted.hip
 void launch_render_sorted(hipStream_t s, const ViewParams& v, const RenderConsts& c, int K, const float* density12, const float* feat,
                           const float* ray_ori, const float* ray_dir, const uint32_t* ranges, const uint32_t* sorted_ids,

@@ -465,6 +465,34 @@ __global__ __launch_bounds__(256) void k_exposure_finish(uint32_t rows, const fl
     }
 }
 
+// The per-pixel rendering error of a view (gut_pixel_error), one lane per pixel: the mean absolute difference of the
+// three channels of the prediction — composite3 and the fma chain of load_pred, so the image is the fused loss's — and the ground
+// truth, clamped to [0, 1], times the mask.  A pixel whose mask is 0 gets 0.0f and reads nothing else.
+template <bool kBgImage, bool kExposure>
+__global__ __launch_bounds__(256) void k_pixel_error(size_t pixels, const float* __restrict__ rgba, const float* __restrict__ gt,
+                                                    const float* __restrict__ mask, const float* __restrict__ bg, float background,
+                                                    const float* __restrict__ exposure, float* __restrict__ error) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= pixels) return;
+    const float m = mask ? mask[i] : 1.0f;
+    if (m == 0.0f) {
+        error[i] = 0.0f;
+        return;
+    }
+    float comp[3];
+    composite3<kBgImage>(rgba + i * 4, 1, 3, background, kBgImage ? bg + i * 3 : nullptr, comp);
+    float sum = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float img = comp[c];
+        if constexpr (kExposure)
+            img = fmaf(exposure[4 * c + 0], comp[0], fmaf(exposure[4 * c + 1], comp[1], fmaf(exposure[4 * c + 2], comp[2], exposure[4 * c + 3])));
+        sum += fabsf(img - gt[i * 3 + c]);
+    }
+    const float e = fminf(fmaxf(sum / 3.0f, 0.0f), 1.0f);
+    error[i] = mask ? e * m : e;
+}
+
 // Adam on the 12 exposure values of ONE view (3dgrut_amd/exposure.py): the view's own moments and visit count, which is advanced
 // first and gives the bias correction; betas held in float32, 1 - beta^t formed in double from them and rounded once (the host form
 // of ExposureCompensation.end does the same).  One launch of one wave; no contraction, so that the host form can follow it.
@@ -794,6 +822,18 @@ int gut_exposure_adam_step(void* stream, const float* d_grad12, float* d_exposur
     if (!d_grad12 || !d_exposure12 || !d_m12 || !d_v12 || !d_count) return 1;
     hipLaunchKernelGGL(gut::k_exposure_adam, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), d_grad12, d_exposure12, d_m12,
                        d_v12, d_count, lr, beta1, beta2, eps);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// One elementwise launch, no workspace; the optional operands as in the fused loss.
+int gut_pixel_error(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb, const float* d_mask,
+                    const float* d_background, float background, const float* d_exposure12, float* d_error) {
+    if (!d_rgba || !d_gt_rgb || !d_error || height < 1 || width < 1) return 1;
+    const size_t pixels = (size_t)height * (size_t)width;
+    const auto kernel = d_background ? (d_exposure12 ? gut::k_pixel_error<true, true> : gut::k_pixel_error<true, false>)
+                                     : (d_exposure12 ? gut::k_pixel_error<false, true> : gut::k_pixel_error<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), pixels, d_rgba,
+                       d_gt_rgb, d_mask, d_background, background, d_exposure12, d_error);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -308,3 +308,51 @@ def _photometric_loss_call(lib, H, W, rgba, gt_rgb, bg, lambda_l1, lambda_ssim, 
         raise RuntimeError(f"[3dgut] photometric_loss failed ({rc}): " + ("a null pointer, or an image of 10x10 pixels or less"
                                                                          if rc == 1 else "the kernel launch failed"))
     return loss3, rgba_grad
+
+
+def pixel_error(rgba, gt_rgb, background=0.0, mask=None, exposure=None):
+    """The per-pixel rendering error of a view, in float64 torch on rgba's device: the definition that
+    fused_pixel_error (gut_pixel_error) computes in float32, for host tensors and tests.
+        comp = rgb + B (1 - alpha),  img = A comp + b with exposure E = [A | b] (comp without),
+        error = clamp(mean over the three channels of |img - gt|, 0, 1) * mask
+    rgba [H,W,4], gt_rgb [H,W,3]; background: "black", "white", a number, or a tensor that broadcasts to [H,W,3]; mask None or
+    [H,W] / [H,W,1]; exposure None or [3,4] / [12].  Returns [H,W] float64."""
+    f64 = lambda t: t.detach().to(device=rgba.device, dtype=torch.float64)
+    B = f64(background) if isinstance(background, torch.Tensor) else float(_constant_background(background, "pixel_error"))
+    x = f64(rgba)
+    img = x[..., :3] + B * (1.0 - x[..., 3:4])
+    if exposure is not None:
+        img = apply_exposure(img, f64(exposure))
+    e = (img - f64(gt_rgb)).abs().sum(-1).div(3.0).clamp(0.0, 1.0)
+    return e if mask is None else e * f64(mask).reshape(e.shape)
+
+
+def fused_pixel_error(rgba, gt_rgb, background, mask=None, exposure=None, out=None):
+    """pixel_error on the GPU in one elementwise launch (gut_pixel_error, csrc/gut_ssim.hip): a float32 [H,W] plane in [0, 1], the
+    weight plane of SplatRaster.trace_contribution for error-based densification.  The operands are fused_photometric_loss's: rgba
+    [H,W,4] (or [1,H,W,4]) and gt_rgb [H,W,3] (or [1,H,W,3]) contiguous float32 on one GPU; background "black", "white", a number
+    or a tensor ([H,W,3] / [1,H,W,3] / [3]); mask None or [H,W] / [H,W,1] / [1,H,W,1]; exposure None or a float32 [12] / [3,4]
+    tensor on the images' device, read there.  out: a contiguous float32 [H,W] tensor on the device to write into.  Nothing is read back."""
+    plane = isinstance(background, torch.Tensor)
+    bg = background if plane else _constant_background(background, "fused_pixel_error", "'black', 'white', a number or a tensor")
+    rgba, gt_rgb = _view_images(rgba, gt_rgb, "fused_pixel_error")
+    if not rgba.is_contiguous() or not gt_rgb.is_contiguous():
+        raise RuntimeError("[fused_pixel_error] expected contiguous tensors")
+    H, W = int(rgba.shape[0]), int(rgba.shape[1])
+    if mask is not None:
+        mask = _plane_mask(mask, H, W, rgba.device)
+    bg = _plane_background(bg, H, W, rgba.device) if plane else float(bg)
+    if exposure is not None:
+        exposure = _exposure12(exposure, rgba.device)
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.float32, device=rgba.device)
+    elif out.dtype != torch.float32 or out.device != rgba.device or tuple(out.shape) != (H, W) or not out.is_contiguous():
+        raise RuntimeError(f"[fused_pixel_error] out must be a contiguous float32 [{H},{W}] tensor on the images' device")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    stream = torch.cuda.current_stream(rgba.device).cuda_stream
+    with torch.cuda.device(rgba.device):
+        rc = _capi.load().gut_pixel_error(C.c_void_p(stream), H, W, rgba.data_ptr(), gt_rgb.data_ptr(), ptr(mask),
+                                          bg.data_ptr() if plane else None, 0.0 if plane else bg, ptr(exposure), out.data_ptr())
+    if rc:
+        raise RuntimeError(f"[3dgut] pixel_error failed ({rc}): " + ("a null pointer" if rc == 1 else "the kernel launch failed"))
+    return out

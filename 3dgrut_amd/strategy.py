@@ -14,6 +14,7 @@ generator seeded identically on every rank so replicas stay bit-identical.
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -90,6 +91,57 @@ class _StateOps:
         s.resize_workspace()
 
 
+CRITERIA = ("gradient", "error")
+ERROR_SCORES = ("error_sum", "error_mean")
+
+
+def error_score_of(result, score="error_sum"):
+    """The densification score of every row from a ContributionScores result with weighted_sum (the plane being the rendering
+    error, contribution.accumulate_error), as float64 numpy [N]:
+        error_sum   weighted_sum: the per-pixel error the Gaussian is responsible for, summed over pixels and views
+        error_mean  weighted_sum / weight_sum: the mean error of the pixels it draws, weighted as it draws them; 0 where it draws none"""
+    if score not in ERROR_SCORES:
+        raise ValueError(f"error score must be one of {ERROR_SCORES}, got {score!r}")
+    if "weighted_sum" not in result:
+        raise ValueError("select_by_error: the result has no weighted_sum (no view was accumulated with a plane)")
+    host = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    e = host(result["weighted_sum"]).astype(np.float64)
+    if score == "error_sum":
+        return e
+    w = host(result["weight_sum"]).astype(np.float64)
+    return np.divide(e, w, out=np.zeros_like(e), where=w > 0)
+
+
+def select_by_error(result, n, grow_fraction=0.05, score="error_sum", min_pixels=1, max_n_gaussians=None):
+    """The rows error-based densification grows, as a bool array [N] like result["weighted_sum"] (a torch tensor on
+    its device, or numpy).  Rows with pixels >= min_pixels and a score > 0 are eligible; of them the
+        min(ceil(grow_fraction * n), number eligible, max_n_gaussians - n)
+    best by `score` are selected (every selected row adds exactly one row: a clone, or a two-way split), equal scores ordered by
+    row index, the lower row first.  n: the model's number of rows, which the result must have.  Deterministic: a pure function."""
+    f = float(grow_fraction)
+    if isinstance(grow_fraction, (bool, str)) or not (0.0 <= f <= 1.0):
+        raise ValueError(f"grow_fraction must be in [0, 1], got {grow_fraction!r}")
+    if isinstance(min_pixels, bool) or int(min_pixels) != min_pixels or int(min_pixels) < 0:
+        raise ValueError(f"min_pixels must be an integer >= 0, got {min_pixels!r}")
+    if max_n_gaussians is not None and (isinstance(max_n_gaussians, bool) or int(max_n_gaussians) != max_n_gaussians or int(max_n_gaussians) < 0):
+        raise ValueError(f"max_n_gaussians must be None or an integer >= 0, got {max_n_gaussians!r}")
+    values = error_score_of(result, score)
+    px = result["pixels"]
+    px = px.detach().cpu().numpy() if isinstance(px, torch.Tensor) else np.asarray(px)
+    n = int(n)
+    if values.shape != (n,) or px.shape != (n,):
+        raise ValueError(f"select_by_error: the result's scores and pixels must be [{n}]")
+    budget = int(math.ceil(f * n - 1e-9))       # (a product within 1e-9 above an integer, 0.1 * 30 in binary, counts as it)
+    if max_n_gaussians is not None:
+        budget = min(budget, max(0, int(max_n_gaussians) - n))
+    eligible = np.nonzero((px >= int(min_pixels)) & (values > 0))[0]
+    order = np.argsort(-values[eligible], kind="stable")     # best first; ties: the lower row index first
+    mask = np.zeros(n, bool)
+    mask[eligible[order[:max(0, budget)]]] = True
+    like = result["weighted_sum"]
+    return torch.as_tensor(mask, device=like.device) if isinstance(like, torch.Tensor) else mask
+
+
 # configs/strategy/gs.yaml: (start_iteration, end_iteration, frequency) of each operation; -1 start = never
 GS_SCHEDULE = dict(densify=(500, 15000, 300), prune=(500, 15000, 100), reset_density=(0, 15000, 3000), density_decay=(-1, -1, 50))
 
@@ -101,11 +153,26 @@ class GSStrategy:
         gs = GSStrategy(stepper); gs.attach()          # per-view statistics hook + row bookkeeping
         for step ...: stepper.step(batch); gs.post_optimizer_step(step, scene_extent)
     attach() makes the stepper hand this view's position gradient to update_gradient_buffer after every backward
-    (post_backward, gs.py:60-73) and keeps the statistics rows aligned when the stepper re-sorts its rows."""
+    (post_backward, gs.py:60-73) and keeps the statistics rows aligned when the stepper re-sorts its rows.
+
+    criterion="error" (not the reference's) replaces the gradient statistics: at a densify step `error_scorer(step)`
+    — installed by the trainer, it returns a ContributionScores result over views scored with accumulate_error — is asked for the
+    rows' error scores, select_by_error picks the best grow_fraction of the rows under max_n_gaussians, and those are cloned or
+    split by the size rule and arithmetic of the gradient criterion.  attach() then installs no statistics hook."""
 
     def __init__(self, stepper, clone_grad_threshold=0.0002, split_grad_threshold=0.0002, relative_size_threshold=0.01,
                  split_n_gaussians=2, prune_density_threshold=0.005, new_max_density=0.01, density_decay_gamma=0.99, seed=0,
-                 schedule=None):
+                 schedule=None, criterion="gradient", grow_fraction=0.05, error_score="error_sum", min_pixels=1, max_n_gaussians=None):
+        if criterion not in CRITERIA:
+            raise ValueError(f"criterion must be one of {CRITERIA}, got {criterion!r}")
+        if error_score not in ERROR_SCORES:
+            raise ValueError(f"error_score must be one of {ERROR_SCORES}, got {error_score!r}")
+        if criterion == "error" and split_n_gaussians != 2:
+            raise ValueError("criterion='error' grows one row per selected row: split_n_gaussians must be 2")
+        self.criterion, self.grow_fraction, self.error_score = criterion, grow_fraction, error_score
+        self.min_pixels, self.max_n_gaussians = min_pixels, max_n_gaussians
+        self.error_scorer = None     # criterion "error": step -> ContributionScores result with weighted_sum, on the live model
+        self.error_passes = self.error_rows_added = 0
         self.ops = _StateOps(stepper)
         self.clone_thr, self.split_thr = clone_grad_threshold, split_grad_threshold
         self.rel_size, self.split_n = relative_size_threshold, split_n_gaussians
@@ -120,9 +187,10 @@ class GSStrategy:
     # ---- trainer callbacks (gs.py:60-104) ----
     def attach(self):
         s = self.ops.s
-        s.post_backward_hook = self._post_backward
-        if hasattr(s, "fused_statistics"):
-            s.fused_statistics = self._fused_statistics   # one view, fused optimiser: the optimiser kernel accumulates them itself
+        if self.criterion == "gradient":   # ("error" scores the model at the densify step itself: no per-step statistics)
+            s.post_backward_hook = self._post_backward
+            if hasattr(s, "fused_statistics"):
+                s.fused_statistics = self._fused_statistics   # one view, fused optimiser: the optimiser kernel accumulates them itself
         listeners = getattr(s, "row_listeners", None)
         if listeners is not None and self._rows_reordered not in listeners:
             listeners.append(self._rows_reordered)
@@ -160,7 +228,14 @@ class GSStrategy:
         from .schedule import check_step_condition
         sc, updated, appended = self.schedule, False, False
         if check_step_condition(step, *sc["densify"]):
-            self.densify(scene_extent, step, world)
+            if self.criterion == "error":
+                if world > 1:
+                    raise RuntimeError("[3dgut] error-based densification is single-GPU (world must be 1)")
+                if self.error_scorer is None:
+                    raise RuntimeError("[3dgut] criterion='error' needs error_scorer (step -> ContributionScores result); the trainer installs it")
+                self.densify_by_error(self.error_scorer(step), scene_extent, step)
+            else:
+                self.densify(scene_extent, step, world)
             updated = appended = True
         if check_step_condition(step, *sc["prune"]):
             self.prune_opacity()
@@ -213,22 +288,49 @@ class GSStrategy:
         self.split(g, scene_extent, step)
 
     @torch.no_grad()
+    def densify_by_error(self, result, scene_extent, step=0):
+        """Grows the rows select_by_error picks from `result`: the small ones (the size rule of clone / split) are cloned, the others
+        split in two; every selected row adds one row.  Returns the number selected."""
+        n = self.ops.n
+        selected = torch.as_tensor(select_by_error(result, n, self.grow_fraction, self.error_score, self.min_pixels, self.max_n_gaussians),
+                                   dtype=torch.bool, device=self.ops.m.raw.device)
+        small = self._small(scene_extent)
+        k = self.clone_rows(selected & small)
+        big = torch.zeros(self.ops.n, dtype=torch.bool, device=selected.device)
+        big[:n] = selected & ~small            # (the clones appended behind row n are not split)
+        k += self.split_rows(big, step)
+        self.error_passes += 1
+        self.error_rows_added += self.ops.n - n
+        return k
+
+    def _small(self, scene_extent):
+        """The size rule: rows whose largest scale is at most relative_size_threshold x the scene extent are cloned, the others split."""
+        return torch.exp(self.ops.m.raw[:, SCL]).max(dim=1).values <= self.rel_size * scene_extent
+
+    @torch.no_grad()
     def clone(self, grad_norm, scene_extent):
+        return self.clone_rows((grad_norm >= self.clone_thr) & self._small(scene_extent))
+
+    @torch.no_grad()
+    def clone_rows(self, mask):
+        """Appends a copy of the rows of `mask` [N] (moments of new rows are 0)."""
         m = self.ops.m
-        scale_max = torch.exp(m.raw[:, SCL]).max(dim=1).values
-        mask = (grad_norm >= self.clone_thr) & (scale_max <= self.rel_size * scene_extent)
         self.ops.append(m.raw[mask], m.features[mask])
         self.reset_buffers()
         return int(mask.sum())
 
     @torch.no_grad()
     def split(self, grad_norm, scene_extent, step=0):
-        m = self.ops.m
         n0 = self.ops.n
-        padded = torch.zeros(n0, device=m.raw.device)
+        padded = torch.zeros(n0, device=self.ops.m.raw.device)
         padded[: grad_norm.shape[0]] = grad_norm  # cloned rows appended after the statistics were taken get 0
+        return self.split_rows((padded >= self.split_thr) & ~self._small(scene_extent), step)
+
+    @torch.no_grad()
+    def split_rows(self, mask, step=0):
+        """Replaces every row of `mask` [N] by split_n children drawn inside it (gs.py:131-170)."""
+        m = self.ops.m
         scale = torch.exp(m.raw[:, SCL])
-        mask = (padded >= self.split_thr) & (scale.max(dim=1).values > self.rel_size * scene_extent)
         k = int(mask.sum())
         if k:
             stds = scale[mask].repeat(self.split_n, 1)

@@ -442,12 +442,15 @@ class SplatRaster:
                    ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(), rgba_g.data_ptr(), dist.data_ptr(), _ptr(dist_g))
 
     def trace_contribution(self, frame_number, num_active_features, particle_density, ray_ori, ray_dir, sensor_params, ts_start, ts_end,
-                           pose_start, pose_end, scores):
+                           pose_start, pose_end, scores, pixel_weight=None, weighted=None):
         """Adds the cached forward's per-Gaussian contribution to `scores` (gut_trace_contribution): an int64 [N,2] GPU tensor of
         GutContribution records the caller zeroed once (column 0: the weight sum in units of 2^-32; column 1: the float bits of the
         largest weight in the low word, the composited-pixel count in the high word; contribution.unpack_scores reads it).  Follows any
         forward on this handle, consumes nothing, and may be followed by any backward.  Unsorted variant at kernel degree 2 only.
-        particle_density: the [N,12] rows of the forward, or an int N after a *_fields forward (the rows that forward packed)."""
+        particle_density: the [N,12] rows of the forward, or an int N after a *_fields forward (the rows that forward packed).
+        pixel_weight with weighted (gut_trace_contribution_weighted): a contiguous float32 [H,W] plane on the rays'
+        GPU, clamped to [0, 1] by the kernel, and an int64 [N] tensor the caller zeroed once, which receives the sum of weight x
+        plane in units of 2^-32; `scores` may then be None (the weighted sums alone)."""
         ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
         rows = None
         if isinstance(particle_density, torch.Tensor):
@@ -456,12 +459,25 @@ class SplatRaster:
                 rows = _check_f32_cuda(particle_density, "particleDensity", (12,))
         else:
             n = int(particle_density)
-        if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.int64 and scores.is_contiguous()
+        with_plane = pixel_weight is not None or weighted is not None
+        if not (scores is None and with_plane) and not (
+                isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.int64 and scores.is_contiguous()
                 and tuple(scores.shape) == (n, 2) and scores.device == dev):
             raise RuntimeError(f"[3dgut] contribution scores: a contiguous int64 tensor [{n}, 2] on the rays' GPU")
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
-        self._call("trace_contribution", self._lib.gut_trace_contribution, dev, frame_number, int(num_active_features), n, _ptr(rows), W, H,
-                   ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), _ptr(scores, n))
+        if not with_plane:
+            self._call("trace_contribution", self._lib.gut_trace_contribution, dev, frame_number, int(num_active_features), n, _ptr(rows),
+                       W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), _ptr(scores, n))
+            return
+        if not (isinstance(pixel_weight, torch.Tensor) and pixel_weight.dtype == torch.float32 and pixel_weight.is_contiguous()
+                and tuple(pixel_weight.shape) == (H, W) and pixel_weight.device == dev):
+            raise RuntimeError(f"[3dgut] contribution pixel weight: a contiguous float32 tensor [{H}, {W}] on the rays' GPU")
+        if not (isinstance(weighted, torch.Tensor) and weighted.dtype == torch.int64 and weighted.is_contiguous()
+                and tuple(weighted.shape) == (n,) and weighted.device == dev):
+            raise RuntimeError(f"[3dgut] weighted contribution: a contiguous int64 tensor [{n}] on the rays' GPU")
+        self._call("trace_contribution_weighted", self._lib.gut_trace_contribution_weighted, dev, frame_number, int(num_active_features),
+                   n, _ptr(rows), W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), pixel_weight.data_ptr(),
+                   _ptr(scores, n) if scores is not None else None, _ptr(weighted, n))
 
     def set_regularisation(self, reg):
         """The NEXT optimiser step on the handle (optimize_rows_without_gradient + optimize_after_bwd, or

@@ -49,11 +49,20 @@ go first), the others leave with their optimiser state; `finetune_iterations` fu
 densification, the learning-rate schedule continuing); then the usual final checkpoint and test pass.  The test split is scored
 once more BEFORE the pruning, so that both sides of the trade are printed.  One GPU only.
 
+`strategy.densify.criterion: error` (default `gradient`; `--densify-by error`) densifies by rendering error: at every
+densify step `strategy.densify.error.views` training views (0: all; otherwise drawn from epoch_permutation(seed, step // frequency, V)) are
+rendered on the live model — at their refined poses, through their exposure rows, with their masks; a `random` background is scored
+over black — and every Gaussian is charged the per-pixel error it drew (ContributionScores.accumulate_error); the best
+`grow_fraction` of the rows by `score` are cloned or split by the reference's size rule, under `max_n_gaussians`.  The per-step
+gradient statistics are not collected.  The scores are recomputed at every densify step: the checkpoint holds nothing of them.
+GSStrategy, one GPU, the unsorted variant at kernel degree 2 only.  grow_fraction, views and min_pixels are untuned on real captures.
+
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
                                  [--refine-poses [--pose-lr-translation X] [--pose-lr-rotation R]]
                                  [--exposure [--exposure-lr X]] [--cc-metrics] [--aligned-metrics [--align-iterations K]]
                                  [--compact-to FRACTION [--compact-score weight_sum|max_weight] [--compact-finetune K]]
+                                 [--densify-by gradient|error [--densify-grow-fraction F] [--densify-views K]]
 """
 import argparse
 import copy
@@ -104,8 +113,14 @@ GS_CONFIG = {
     # training views go first), then finetune_iterations further steps without the strategy.
     "compaction": dict(contribution_mod.DEFAULTS),
     "strategy": {"method": "GSStrategy",
+                 # criterion and error are not reference keys: "error" grows, at every densify step, the grow_fraction of the rows
+                 # that are responsible for the most rendering error over `views` training views (0: all of them), instead of
+                 # thresholding the position-gradient statistics (strategy.select_by_error).  grow_fraction, views
+                 # and min_pixels are untuned on real captures.
                  "densify": {"frequency": 300, "start_iteration": 500, "end_iteration": 15000, "clone_grad_threshold": 0.0002,
-                             "split_grad_threshold": 0.0002, "relative_size_threshold": 0.01, "split": {"n_gaussians": 2}},
+                             "split_grad_threshold": 0.0002, "relative_size_threshold": 0.01, "split": {"n_gaussians": 2},
+                             "criterion": "gradient",
+                             "error": {"grow_fraction": 0.05, "score": "error_sum", "min_pixels": 1, "views": 0, "max_n_gaussians": None}},
                  "prune": {"frequency": 100, "start_iteration": 500, "end_iteration": 15000, "density_threshold": 0.005},
                  # end_iteration None: ${strategy.densify.end_iteration}, as the yaml interpolates it
                  "reset_density": {"frequency": 3000, "start_iteration": 0, "end_iteration": None, "new_max_density": 0.01},
@@ -157,10 +172,56 @@ def resolve_config(conf):
     check_evaluation_config(out["evaluation"])
     pose_align.check_config(out["pose_alignment"])
     contribution_mod.check_config(out["compaction"])
+    check_densify_config(out)
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
         out["optimizer"]["params"]["features_specular"] = {"lr": float(out["optimizer"]["params"]["features_albedo"]["lr"]) / 20}
     return out
+
+
+DENSIFY_ERROR_DEFAULTS = GS_CONFIG["strategy"]["densify"]["error"]
+
+
+def check_densify_config(conf):
+    """strategy.densify.criterion and strategy.densify.error of a resolved conf.  criterion "error" is refused where the weighted
+    contribution walk does not exist: MCMCStrategy, the sorted variant (render.splat.k_buffer_size > 0) and kernel degrees other
+    than 2; the data-parallel refusal needs the stepper and is the Trainer's."""
+    from .strategy import CRITERIA, ERROR_SCORES
+    densify = conf["strategy"].get("densify") or {}
+    criterion = densify.get("criterion", "gradient")
+    if criterion not in CRITERIA:
+        raise ValueError(f"strategy.densify.criterion must be one of {CRITERIA}, got {criterion!r}")
+    if conf["strategy"]["method"] != "GSStrategy":
+        if criterion != "gradient":
+            raise ValueError(f"strategy.densify.criterion: {criterion!r} is for GSStrategy only (MCMC sampling by error is out of scope)")
+        return conf
+    block = densify["error"]
+    unknown = set(block) - set(DENSIFY_ERROR_DEFAULTS)
+    if unknown:
+        raise ValueError(f"strategy.densify.error: unknown keys {sorted(unknown)}")
+    f = block["grow_fraction"]
+    if isinstance(f, (bool, str)) or not (0.0 < float(f) <= 1.0):
+        raise ValueError(f"strategy.densify.error.grow_fraction must be in (0, 1], got {f!r}")
+    if block["score"] not in ERROR_SCORES:
+        raise ValueError(f"strategy.densify.error.score must be one of {ERROR_SCORES}, got {block['score']!r}")
+    for k in ("min_pixels", "views"):
+        v = block[k]
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"strategy.densify.error.{k} must be an integer >= 0, got {v!r}")
+    cap = block["max_n_gaussians"]
+    if cap is not None and (isinstance(cap, bool) or not isinstance(cap, int) or cap < 1):
+        raise ValueError(f"strategy.densify.error.max_n_gaussians must be null or an integer >= 1, got {cap!r}")
+    if criterion == "error":
+        render = conf.get("render") or {}
+        k_buffer = int((render.get("splat") or {}).get("k_buffer_size", 0))
+        degree = int(render.get("particle_kernel_degree", 2))
+        if k_buffer > 0:
+            raise ValueError(f"strategy.densify.criterion: 'error' needs the unsorted variant (render.splat.k_buffer_size is {k_buffer})")
+        if degree != 2:
+            raise ValueError(f"strategy.densify.criterion: 'error' needs render.particle_kernel_degree 2 (it is {degree})")
+        if int(densify["split"]["n_gaussians"]) != 2:
+            raise ValueError("strategy.densify.criterion: 'error' grows one row per selected row (strategy.densify.split.n_gaussians must be 2)")
+    return conf
 
 
 def check_evaluation_config(block):
@@ -345,6 +406,13 @@ class Trainer:
             self.global_step = int(ckpt["global_step"])
         if c["compaction"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
             raise ValueError("compaction: data-parallel compaction is out of scope (the stepper's world_size must be 1)")
+        self.densify_criterion = (c["strategy"].get("densify") or {}).get("criterion", "gradient")
+        if self.densify_criterion == "error":
+            if int(getattr(stepper, "world_size", 1)) > 1:
+                raise ValueError("strategy.densify.criterion: data-parallel error-based densification is out of scope (the stepper's "
+                                 "world_size must be 1)")
+            if getattr(self.strategy, "error_scorer", None) is None:
+                self.strategy.error_scorer = self._score_error
 
     # ---- construction ----
     def _build(self, scene, ckpt, tracer):
@@ -459,7 +527,9 @@ class Trainer:
                             relative_size_threshold=float(d["relative_size_threshold"]), split_n_gaussians=int(d["split"]["n_gaussians"]),
                             prune_density_threshold=float(s["prune"]["density_threshold"]),
                             new_max_density=float(s["reset_density"]["new_max_density"]), density_decay_gamma=float(s["density_decay"]["gamma"]),
-                            seed=seed, schedule=gs_schedule(self.conf))
+                            seed=seed, schedule=gs_schedule(self.conf), criterion=d["criterion"],
+                            grow_fraction=float(d["error"]["grow_fraction"]), error_score=d["error"]["score"],
+                            min_pixels=int(d["error"]["min_pixels"]), max_n_gaussians=d["error"]["max_n_gaussians"])
             if ckpt is not None and "densify_grad_norm_accum" in ckpt:
                 dev = self.model.raw.device
                 gs.grad_norm_accum = ckpt["densify_grad_norm_accum"][0].to(dev).contiguous()
@@ -530,6 +600,32 @@ class Trainer:
             return self.strategy.post_optimizer_step(step, float(self.stepper.lr12[0]))
         return self.strategy.post_optimizer_step(step, self.scene_extent)
 
+    def _error_views(self, step):
+        """The training views densify step `step` scores: all of them with strategy.densify.error.views 0, otherwise that many from
+        epoch_permutation(seed, step // frequency, V) — a function of the step alone, so a resumed run scores the same ones."""
+        d = self.conf["strategy"]["densify"]
+        n, k = len(self.train_batches), int(d["error"]["views"])
+        if k == 0 or k >= n:
+            return list(range(n))
+        index = int(step) // max(1, int(d["frequency"]))     # (densify steps are multiples of the frequency)
+        return epoch_permutation(self.conf["seed"], index, n)[:k]
+
+    def _score_error(self, step):
+        """The strategy's error_scorer (criterion "error"): the contribution scores of the live model over _error_views(step), every
+        view weighted by its rendering error — at its refined pose, through its exposure row, with its mask, over the run's constant
+        background (`random` is scored over black, as the held-out views are).  Nothing is kept: the next pass starts from zero."""
+        color = self.conf["model"]["background"]["color"]
+        scorer = contribution_mod.ContributionScores(self.model, self.tracer)
+        for view in self._error_views(step):
+            batch = self.train_batches[view]
+            if self.refiner is not None:
+                batch = self.refiner.begin(view, batch)
+            if self.exposure is not None:
+                batch = self.exposure.begin(view, batch)
+            scorer.accumulate_error(batch, "black" if color == "random" else color, mask=getattr(batch, "mask", None),
+                                    exposure=getattr(batch, "exposure", None))
+        return scorer.result()
+
     def checkpoint(self):
         return make_checkpoint(self.stepper, self.conf, self.global_step, self.epoch, self.scene_extent,
                                self.strategy if self.method == "GSStrategy" else None, self.refiner, self.exposure)
@@ -574,6 +670,9 @@ class Trainer:
         self.stats = dict(n_steps=self.global_step, n_epochs=-(-self.global_step // len(self.train_batches)), steps_run=self.global_step - start,
                           training_time=elapsed, iteration_speed=self.global_step / elapsed if elapsed > 0 else float("inf"),
                           n_gaussians=int(self.model.num_gaussians))
+        if self.densify_criterion == "error":
+            self.stats.update(densify_criterion="error", densify_error_passes=int(getattr(self.strategy, "error_passes", 0)),
+                              densify_rows_added=int(getattr(self.strategy, "error_rows_added", 0)))
         if self.refiner is not None:
             ch = self.refiner.pose_change()
             self.stats.update(pose_mean_translation=ch["mean_translation"], pose_mean_rotation_deg=ch["mean_rotation_deg"])
@@ -687,6 +786,11 @@ def build_parser():
                          "(compaction.enabled, compaction.keep_fraction)")
     ap.add_argument("--compact-score", choices=contribution_mod.SCORES, default=None, help="compaction.score")
     ap.add_argument("--compact-finetune", type=int, default=None, metavar="K", help="compaction.finetune_iterations")
+    ap.add_argument("--densify-by", choices=("gradient", "error"), default=None,
+                    help="strategy.densify.criterion: error = grow the rows responsible for the most rendering error (default: gradient)")
+    ap.add_argument("--densify-grow-fraction", type=float, default=None, metavar="F", help="strategy.densify.error.grow_fraction")
+    ap.add_argument("--densify-views", type=int, default=None, metavar="K",
+                    help="strategy.densify.error.views: training views scored per densify step (0: all)")
     return ap
 
 
@@ -719,6 +823,15 @@ def config_from_args(a):
         conf["compaction"]["score"] = a.compact_score
     if a.compact_finetune is not None:
         conf["compaction"]["finetune_iterations"] = a.compact_finetune
+    densify = {}
+    if a.densify_by is not None:
+        densify["criterion"] = a.densify_by
+    if a.densify_grow_fraction is not None:
+        densify.setdefault("error", {})["grow_fraction"] = a.densify_grow_fraction
+    if a.densify_views is not None:
+        densify.setdefault("error", {})["views"] = a.densify_views
+    if densify:
+        conf["strategy"]["densify"] = _merge(conf["strategy"].get("densify") or {}, densify)
     return conf
 
 

@@ -47,7 +47,8 @@ extern "C" {
  * other forms of the fused loss, which launch what they launched before; gut_image_metrics_cc_workspace_bytes and gut_image_metrics_cc,
  * new entry points next to gut_image_metrics, which launches what it launched before; GutPhotometricLoss and gut_photometric_loss_run,
  * the descriptor form of the fused loss: the four positional forms keep their signatures and call it; GutContribution and
- * gut_trace_contribution, a new entry point: every other call queues what it queued before). */
+ * gut_trace_contribution, a new entry point: every other call queues what it queued before; gut_trace_contribution_weighted and
+ * gut_pixel_error, new entry points: gut_trace_contribution and every other call queue what they queued before). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -680,6 +681,30 @@ int gut_trace_contribution(gut_handle h, void* stream, uint32_t frame_number, in
                            const float* d_particle_density /* NULL: the rows the last *_fields forward packed */,
                            int32_t width, int32_t height, const float* d_ray_origin, const float* d_ray_direction,
                            const GutCamera* camera, GutContribution* d_scores /* [N], accumulated into */);
+
+/* ---- Contribution scores weighted by a per-pixel plane (new functionality) ----
+ * gut_trace_contribution_weighted is gut_trace_contribution — its scope, its walk, its refusals, nothing consumed — with a float
+ * plane [H,W] of the view: every weight w is also multiplied by e = min(max(plane[pixel], 0), 1) (the clamp is part of the contract:
+ * a NaN counts as 0, a value above 1 as 1) and the products are summed per Gaussian, by the reduction of the plain sum, into
+ * d_weighted_q32 [N]: round(tile_sum * 2^32) per (tile, Gaussian), one 64-bit integer add, ACCUMULATED INTO like the records, so the
+ * totals are independent of the order of tiles and views.  A plane of ones gives weight_sum_q32 bit for bit.  With the error plane of
+ * gut_pixel_error it is the rendering error each Gaussian is responsible for; with a 0/1 mask, weighted / weight_sum is the share of
+ * the Gaussian that lies inside the mask.  d_scores NULL: the weighted sums alone; otherwise the records are written in the same walk
+ * and equal those of gut_trace_contribution.  Additionally refused: d_pixel_weight NULL; d_weighted_q32 NULL or not 8-byte aligned
+ * with num_particles > 0. */
+int gut_trace_contribution_weighted(gut_handle h, void* stream, uint32_t frame_number, int32_t num_active_features,
+                                    uint32_t num_particles, const float* d_particle_density /* NULL: the packed rows */,
+                                    int32_t width, int32_t height, const float* d_ray_origin, const float* d_ray_direction,
+                                    const GutCamera* camera, const float* d_pixel_weight /* [H,W] */,
+                                    GutContribution* d_scores /* [N] or NULL */, uint64_t* d_weighted_q32 /* [N], accumulated into */);
+/* The per-pixel rendering error of a view, a float plane [H,W] in [0, 1] (operands as gut_photometric_loss_exposure's; d_mask,
+ * d_background and d_exposure12 may each be NULL):
+ *     comp_k = rgb_k + B_k (1 - alpha),   img_c = A[c] . comp + b_c with E = [A | b] read from device memory (comp_c without E),
+ *     error  = min(max((|img_0 - gt_0| + |img_1 - gt_1| + |img_2 - gt_2|) / 3, 0), 1) * mask
+ * One elementwise launch, no workspace, no synchronisation; every element of d_error is written.  Returns 1 on the host, before
+ * anything is queued, for a null d_rgba, d_gt_rgb or d_error or a height or width below 1; 2 for a launch failure. */
+int gut_pixel_error(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
+                    const float* d_mask, const float* d_background, float background, const float* d_exposure12, float* d_error);
 
 /* ---- Per-view exposure in the fused loss (new functionality, the reference has none) ----
  * gut_photometric_loss_exposure is the fused loss of gut_photometric_loss[_masked | _background] on the AFFINE image of a view:
