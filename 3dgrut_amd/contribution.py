@@ -41,9 +41,10 @@ def unpack_scores(scores):
     return weight_sum, max_weight, pixels
 
 
-class ContributionScores:
-    """Scores of `model`'s rows over the views handed to accumulate().  The [N,12] activated rows and the [N,48] features are
-    prepared here, once; the model must not change while a pass runs."""
+class FrozenModel:
+    """`model`'s rows as the rasteriser reads them, prepared once: the [N,12] activated rows, the [N,48] features, the number of
+    active features, and the tracer's rasteriser.  forward(batch) renders a view from them and returns the forward's outputs with
+    what a following call on the handle needs.  The model must not change while the object is in use."""
 
     def __init__(self, model, tracer):
         from .tracer import Tracer
@@ -54,15 +55,28 @@ class ContributionScores:
             self.act = torch.cat([model.positions, model.get_density(), model.get_rotation(), model.get_scale(), z], dim=1).to(torch.float32).contiguous()
             self.features = model.get_features().detach().to(torch.float32).contiguous()
         self.n_active_features = int(model.n_active_features)
+
+    def forward(self, batch):
+        """(outs, rays_o, rays_d, cam): the forward's four outputs, the rays and the camera tail of the following call."""
+        sensor, poses = self._create_camera(batch)
+        rays_o, rays_d = batch.rays_ori.contiguous(), batch.rays_dir.contiguous()
+        cam = (sensor, poses.timestamps_us[0], poses.timestamps_us[1], poses.T_world_sensors[0], poses.T_world_sensors[1])
+        outs = self.raster.trace(0, self.n_active_features, self.act, self.features, rays_o, rays_d, None, *cam)
+        return outs, rays_o, rays_d, cam
+
+
+class ContributionScores(FrozenModel):
+    """Scores of `model`'s rows over the views handed to accumulate().  The [N,12] activated rows and the [N,48] features are
+    prepared here, once; the model must not change while a pass runs."""
+
+    def __init__(self, model, tracer):
+        super().__init__(model, tracer)
         self.scores = torch.zeros((self.act.shape[0], 2), dtype=torch.int64, device=self.act.device)
         self.weighted = None     # uint64 [N] in units of 2^-32, held as int64 (torch has no uint64 arithmetic); created by the first plane
         self.n_views = 0
 
     def _accumulate(self, batch, plane_of):
-        sensor, poses = self._create_camera(batch)
-        rays_o, rays_d = batch.rays_ori.contiguous(), batch.rays_dir.contiguous()
-        cam = (sensor, poses.timestamps_us[0], poses.timestamps_us[1], poses.T_world_sensors[0], poses.T_world_sensors[1])
-        outs = self.raster.trace(0, self.n_active_features, self.act, self.features, rays_o, rays_d, None, *cam)
+        outs, rays_o, rays_d, cam = self.forward(batch)
         plane = plane_of(outs[0])
         if plane is None:
             self.raster.trace_contribution(0, self.n_active_features, self.act, rays_o, rays_d, *cam, self.scores)

@@ -967,11 +967,21 @@ int trace_bwd_packed(gut_handle h, const char* name, const char* forwards, const
                                                d_particle_radiance_grad, f});
 }
 
+// what gut_trace_attributes adds to the contribution call
+struct AttributeArgs {
+    int32_t channels;
+    const float* rows;
+    float* out;
+};
+
 // The contribution scores of the cached forward's view: the forward's walk once more, without colours, into the
 // caller's accumulating arrays.  Reads the forward's lists and depths, writes tile_order (every backward rebuilds it) and d_scores /
 // d_weighted_q32.  weighted: the form with a per-pixel plane (gut_trace_contribution_weighted), whose records are optional.
+// attr (gut_trace_attributes): the walk renders attr->rows [N, channels] into attr->out [channels, H, W] instead and
+// the three accumulating arrays are unused.
 int trace_contribution_impl(gut_handle h, const char* name, const TraceView& view, const float* d_particle_density,
-                            GutContribution* d_scores, bool weighted, const float* d_pixel_weight, uint64_t* d_weighted_q32) {
+                            GutContribution* d_scores, bool weighted, const float* d_pixel_weight, uint64_t* d_weighted_q32,
+                            const AttributeArgs* attr = nullptr) {
     if (!h) return fail("%s: null handle", name);
     std::lock_guard<std::mutex> lock(h->mu);
     if (h->cfg.k_buffer_size > 0 || h->cfg.particle_kernel_degree != 2)
@@ -984,7 +994,13 @@ int trace_contribution_impl(gut_handle h, const char* name, const TraceView& vie
             return fail("%s: d_particle_density is NULL and the last forward on this handle packed no rows (not a *_fields one)", name);
         d_particle_density = h->packed12.as<float>();
     }
-    if (view.n && !d_scores && !weighted) return fail("%s: d_scores is NULL with %u particles", name, view.n);
+    if (attr) {
+        if (attr->channels < 1 || attr->channels > 64) return fail("%s: num_channels must be in 1..64, got %d", name, attr->channels);
+        if (view.n && !attr->rows) return fail("%s: d_attributes is NULL with %u particles", name, view.n);
+        if (!attr->out) return fail("%s: d_out is NULL", name);
+        if (((uintptr_t)attr->out & 3u) != 0) return fail("%s: d_out must be 4-byte aligned", name);
+    }
+    if (view.n && !d_scores && !weighted && !attr) return fail("%s: d_scores is NULL with %u particles", name, view.n);
     if (((uintptr_t)d_scores & 7u) != 0) return fail("%s: d_scores must be 8-byte aligned", name);
     if (weighted) {
         if (!d_pixel_weight) return fail("%s: d_pixel_weight is NULL", name);
@@ -998,9 +1014,19 @@ int trace_contribution_impl(gut_handle h, const char* name, const TraceView& vie
     HIP_TRY(dev_guard.set(h->device));
     gut::ViewParams v;
     if (check_same_camera(h, view, name, &v)) return 1;
-    if (h->n == 0 || h->m == 0) return 0;   // nothing was walked
     const hipStream_t s = view.stream;
+    if (h->n == 0 || h->m == 0) {   // nothing was walked
+        if (attr) HIP_TRY(hipMemsetAsync(attr->out, 0, sizeof(float) * (size_t)attr->channels * (size_t)view.width * (size_t)view.height, s));
+        return 0;
+    }
     gut::launch_tile_order(s, (uint32_t)h->tiles, h->trav_fwd.as<uint32_t>(), h->tile_order.as<uint32_t>());
+    if (attr) {
+        gut::launch_attributes(s, v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
+                               (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
+                               h->trav_fwd.as<uint32_t>(), h->n, (uint32_t)attr->channels, attr->rows, attr->out);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     gut::launch_contribution(s, v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
                              (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
                              h->trav_fwd.as<uint32_t>(), h->n, d_scores, weighted ? d_pixel_weight : nullptr, d_weighted_q32);
@@ -1081,6 +1107,16 @@ int gut_trace_contribution_weighted(gut_handle h, void* stream_, uint32_t frame_
     return trace_contribution_impl(h, "gut_trace_contribution_weighted",
                                    view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
                                    d_particle_density, d_scores, true, d_pixel_weight, d_weighted_q32);
+}
+
+int gut_trace_attributes(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+                         const float* d_particle_density, int32_t width, int32_t height, const float* d_ray_origin,
+                         const float* d_ray_direction, const GutCamera* camera, int32_t num_channels, const float* d_attributes,
+                         float* d_out) {
+    const AttributeArgs attr{num_channels, d_attributes, d_out};
+    return trace_contribution_impl(h, "gut_trace_attributes",
+                                   view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                                   d_particle_density, nullptr, false, nullptr, nullptr, &attr);
 }
 
 // SplatRaster::trace with the four activated tensors the reference's Tracer hands to _Autograd (tracer.py:317-327) instead of

@@ -16,6 +16,10 @@
 // The weighted form (gut_trace_contribution_weighted) is the same walk with one more factor: each lane loads its pixel's
 // value e of a caller plane once, clamped to [0, 1], multiplies the weight `entry` returns by it AFTERWARDS (the evaluation itself is
 // untouched), and w * e goes through the same tree, its own LDS plane and the same wave order into a uint64 array of the caller's.
+//
+// The attribute form (gut_trace_attributes) is the walk in the other direction: per-Gaussian values are staged with the
+// entries and every lane sums w * value over the entries its pixel composited, in list order, in its own registers, and writes the
+// sums to the caller's planes: no reduction across lanes, no partials, no atomics.
 #include "gut_internal.h"
 #include "gut_render_common.h"
 
@@ -70,18 +74,35 @@ __device__ __forceinline__ float wave_max_lane63(float v) {
 
 constexpr uint32_t kWaves = kBlock / 64;
 
+// the attribute walk's operands (gut_trace_attributes), of one channel group
+struct AttrArgs {
+    const float* rows;   // the group's first channel of row 0
+    float* out;          // the group's first plane
+    uint32_t stride;     // floats per row: the number of channels
+    uint32_t cols;       // channels of this group, 1..4
+    uint32_t vec16;      // every row of the group starts on a 16-byte boundary and has four channels: one 16-byte load
+};
+struct NoAttrArgs {};
+
 // kPlain: the GutContribution records (sum, maximum, count of w).  kWeighted: the sum of w * e into weighted_q32, e the pixel's value
 // of `plane` clamped to [0, 1].  <true, false> is the kernel of §13; the other two read `plane`, <false, true>
 // writes no record (scores is not read).
-template <bool kPlain, bool kWeighted>
+// kAttr (1 or 4, with neither of the others): the walk renders per-Gaussian attributes.  Thread j also stages entry
+// j's values of the channel group (of a group of four the first attr.cols; one 16-byte load where attr.vec16 says the rows allow
+// it); a lane that composited entry j with w > 0 adds w x those values to its pixel's sums, which go to the planes
+// attr.out[k][H][W], every pixel of the tile.  No partials and no flush.  The mode's operands travel in one trailing argument,
+// empty in the other modes: their kernels keep their argument layout and their code.
+template <bool kPlain, bool kWeighted, int kAttr = 0>
 __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, RenderConsts c, const float4* __restrict__ density12,
                                                            const float* __restrict__ ray_ori, const float* __restrict__ ray_dir,
                                                            const uint2* __restrict__ ranges, const uint32_t* __restrict__ ordered_ids,
                                                            const uint32_t* __restrict__ tile_order,
                                                            const uint32_t* __restrict__ tile_walked, uint32_t num_particles,
                                                            GutContribution* __restrict__ scores, const float* __restrict__ plane,
-                                                           unsigned long long* __restrict__ weighted_q32) {
-    static_assert(kPlain || kWeighted, "nothing to write");
+                                                           unsigned long long* __restrict__ weighted_q32,
+                                                           std::conditional_t<kAttr != 0, AttrArgs, NoAttrArgs> attr) {
+    static_assert(kAttr == 0 ? (kPlain || kWeighted) : ((kAttr == 1 || kAttr == 4) && !kPlain && !kWeighted), "nothing to write");
+    using AttrSlot = std::conditional_t<kAttr == 1, float, float4>;
     __shared__ ContribEntry stage[kBlock];
     __shared__ uint32_t s_id[kBlock];
     __shared__ uint32_t s_first_invalid;
@@ -92,7 +113,8 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
     // per chunk and says which of the others are valid (s_wsum: the weighted sums)
     __shared__ float s_sum[kPlain ? kWaves : 1][kPlain ? kBlock : 1], s_max[kPlain ? kWaves : 1][kPlain ? kBlock : 1];
     __shared__ float s_wsum[kWeighted ? kWaves : 1][kWeighted ? kBlock : 1];
-    __shared__ uint32_t s_cnt[kWaves][kBlock];
+    __shared__ uint32_t s_cnt[kAttr ? 1 : kWaves][kAttr ? 1 : kBlock];
+    __shared__ AttrSlot s_attr[kAttr ? kBlock : 1];   // entry j's values of the channel group
 
     const uint32_t tile = tile_order[blockIdx.x];
     const uint32_t tid = threadIdx.x;
@@ -117,6 +139,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
     range.y = range.x + min(range.y - range.x, tile_walked[tile]);
     const uint32_t total = range.y - range.x;
     float T = ray.valid ? 1.0f : -1.0f;   // alive <=> T > 0; a ray that ends keeps -T (k_render)
+    float acc[kAttr ? kAttr : 1] = {};    // kAttr: the pixel's sums of w x attribute
 
     auto walk = [&](auto centred_tag) __attribute__((always_inline)) {
     constexpr bool kCentred = decltype(centred_tag)::value;
@@ -149,8 +172,26 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
             stage[tid] = e;
             s_id[tid] = id;
             s_mask[tid] = strips;
+            if constexpr (kAttr == 0) {
 #pragma unroll
-            for (uint32_t w = 0; w < kWaves; ++w) s_cnt[w][tid] = 0u;
+                for (uint32_t w = 0; w < kWaves; ++w) s_cnt[w][tid] = 0u;
+            } else if constexpr (kAttr == 1) {
+                s_attr[tid] = id != kInvalid ? attr.rows[(size_t)id * attr.stride] : 0.0f;
+            } else {
+                float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (id != kInvalid) {
+                    const float* const row = attr.rows + (size_t)id * attr.stride;
+                    if (attr.vec16 != 0u) {
+                        a = *reinterpret_cast<const float4*>(row);
+                    } else {   // never past the row's end: the last group of a K that is no multiple of four
+                        a.x = row[0];
+                        if (attr.cols > 1u) a.y = row[1];
+                        if (attr.cols > 2u) a.z = row[2];
+                        if (attr.cols > 3u) a.w = row[3];
+                    }
+                }
+                s_attr[tid] = a;
+            }
             if (id == kInvalid && k < range.y) atomicMin(&s_first_invalid, tid);
         }
         __syncthreads();
@@ -205,6 +246,21 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
         };
         // the wave's reduction of one entry's weights into its own slots (wave-uniform branch: nothing where no pixel composited)
         auto reduce = [&](const float w, const uint32_t j) __attribute__((always_inline)) {
+            if constexpr (kAttr != 0) {
+                // the lanes that composited read one address, a broadcast; an entry nobody composited is never multiplied in
+                if (w > 0.0f) {
+                    if constexpr (kAttr == 1) {
+                        acc[0] = __builtin_fmaf(w, s_attr[j], acc[0]);
+                    } else {
+                        const float4 a = s_attr[j];
+                        acc[0] = __builtin_fmaf(w, a.x, acc[0]);
+                        acc[1] = __builtin_fmaf(w, a.y, acc[1]);
+                        acc[2] = __builtin_fmaf(w, a.z, acc[2]);
+                        acc[3] = __builtin_fmaf(w, a.w, acc[3]);
+                    }
+                }
+                return;
+            }
             const unsigned long long hit = __ballot(w > 0.0f);
             if (hit == 0ull) return;
             if constexpr (kPlain) {
@@ -266,6 +322,8 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
         if (cnt < cnt_all) T = -fabsf(T);  // list ended at a padding entry
 
         // ---- flush: thread j combines the four waves' partials of entry j in wave order and adds them to the Gaussian's record ----
+        // (kAttr: nothing to flush; the barrier at the head of the loop stands between this chunk's reads and the next staging)
+        if constexpr (kAttr == 0) {
         __syncthreads();
         if (tid < cnt) {
             uint32_t pixels = 0;
@@ -295,10 +353,24 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
                 }
             }
         }
+        }
         // (the next chunk's staging starts behind the barrier at the head of the loop)
     }
     };
     if (centred) walk(std::true_type{}); else walk(std::false_type{});
+    if constexpr (kAttr != 0) {
+        // every pixel of the image, 0 where nothing was composited: the planes need no initialisation
+        if (inside) {
+            const size_t plane_stride = (size_t)v.width * (size_t)v.height;
+            float* const out = attr.out;
+            out[pix] = acc[0];
+            if constexpr (kAttr == 4) {
+                if (attr.cols > 1u) out[plane_stride + pix] = acc[1];
+                if (attr.cols > 2u) out[2 * plane_stride + pix] = acc[2];
+                if (attr.cols > 3u) out[3 * plane_stride + pix] = acc[3];
+            }
+        }
+    }
 }
 
 }  // namespace
@@ -313,7 +385,26 @@ void launch_contribution(hipStream_t s, const ViewParams& v, const RenderConsts&
     const auto kernel = !plane ? k_contribution<true, false> : scores ? k_contribution<true, true> : k_contribution<false, true>;
     hipLaunchKernelGGL(kernel, dim3(tiles), dim3(kBlock), 0, s, v, c, reinterpret_cast<const float4*>(density12), ray_ori, ray_dir,
                        reinterpret_cast<const uint2*>(ranges), ordered_ids, tile_order, tile_walked, num_particles, scores, plane,
-                       reinterpret_cast<unsigned long long*>(weighted_q32));
+                       reinterpret_cast<unsigned long long*>(weighted_q32), NoAttrArgs{});
+}
+
+void launch_attributes(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
+                       const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
+                       const uint32_t* tile_walked, uint32_t num_particles, uint32_t num_channels, const float* attrs, float* out) {
+    const uint32_t tiles = (uint32_t)(v.grid_x * v.grid_y);
+    if (tiles == 0) return;
+    const size_t plane_stride = (size_t)v.width * (size_t)v.height;
+    // one walk per group of four channels; a last group of one channel takes the single-channel kernel.  The 16-byte gather where
+    // every row of the group starts on a 16-byte boundary, decided from the pointer here
+    const bool aligned = (num_channels % 4u) == 0u && ((uintptr_t)attrs & 15u) == 0u;
+    for (uint32_t first = 0; first < num_channels; first += 4u) {
+        const uint32_t cols = num_channels - first < 4u ? num_channels - first : 4u;
+        const AttrArgs a{attrs + first, out + (size_t)first * plane_stride, num_channels, cols, aligned && cols == 4u ? 1u : 0u};
+        const auto kernel = cols == 1u ? k_contribution<false, false, 1> : k_contribution<false, false, 4>;
+        hipLaunchKernelGGL(kernel, dim3(tiles), dim3(kBlock), 0, s, v, c, reinterpret_cast<const float4*>(density12), ray_ori, ray_dir,
+                           reinterpret_cast<const uint2*>(ranges), ordered_ids, tile_order, tile_walked, num_particles,
+                           (GutContribution*)nullptr, (const float*)nullptr, (unsigned long long*)nullptr, a);
+    }
 }
 
 }  // namespace gut

@@ -230,6 +230,11 @@ void launch_contribution(hipStream_t s, const ViewParams& v, const RenderConsts&
                          const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
                          const uint32_t* tile_walked, uint32_t num_particles, GutContribution* scores, const float* plane = nullptr,
                          uint64_t* weighted_q32 = nullptr);
+// the same walk rendering per-Gaussian attributes: attrs [N, num_channels] row-major -> out [num_channels, H, W], every
+// element written; one launch per group of four channels
+void launch_attributes(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
+                       const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
+                       const uint32_t* tile_walked, uint32_t num_particles, uint32_t num_channels, const float* attrs, float* out);
 // sorted (k_buffer_size > 0) compositor variant, gut_render_sorted.hip
 void launch_render_sorted(hipStream_t s, const ViewParams& v, const RenderConsts& c, int K, const float* density12, const float* feat,
                           const float* ray_ori, const float* ray_dir, const uint32_t* ranges, const uint32_t* sorted_ids,

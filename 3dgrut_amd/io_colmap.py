@@ -290,8 +290,16 @@ class ColmapScene:
         sampled) images folder, converted to 8-bit grey and thresholded at value / 255 > 0.5 (dataset_colmap.py:376-381, 408-411).
         Raises ValueError when its size is not the image's: `size` (width, height) if the caller has decoded the image already,
         else the image file's if it is there, else the camera's resolution."""
+        return self._load_mask_file(i, "_mask", size)
+
+    def load_label_mask(self, i, suffix, size=None):
+        """load_mask for another file: `<image stem><suffix>.png` next to the image (a 2-D label of the view, e.g. "_object" for
+        the trainer's `selection` block), read, thresholded and size-checked as the mask is; None without the file."""
+        return self._load_mask_file(i, suffix, size)
+
+    def _load_mask_file(self, i, suffix, size):
         path = os.path.join(self.root, self.images_folder(), self.images[i].name)
-        mask_path = os.path.splitext(path)[0] + "_mask.png"
+        mask_path = os.path.splitext(path)[0] + suffix + ".png"
         if not os.path.isfile(mask_path):
             return None
         from PIL import Image

@@ -87,9 +87,13 @@ def scene_from_ply(path):
                 density=(1.0 / (1.0 + np.exp(-d["density_logit"]))).astype(np.float32), features=d["features48"])
 
 
-def export_native_model(model, path):
-    raw = model.raw.detach().cpu().numpy()
-    write_ply(path, raw[:, 0:3], raw[:, 3:4], raw[:, 4:8], raw[:, 8:11], model.features.detach().cpu().numpy())
+def export_native_model(model, path, rows=None):
+    """rows: the row indices to write (an int64 tensor on the model's device, as selection.split_rows gives them); None: all."""
+    raw, features = model.raw.detach(), model.features.detach()
+    if rows is not None:
+        raw, features = raw.index_select(0, rows), features.index_select(0, rows)
+    raw = raw.cpu().numpy()
+    write_ply(path, raw[:, 0:3], raw[:, 3:4], raw[:, 4:8], raw[:, 8:11], features.cpu().numpy())
 
 
 def checkpoint_dict(model, extra=None):

@@ -479,6 +479,35 @@ class SplatRaster:
                    n, _ptr(rows), W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), pixel_weight.data_ptr(),
                    _ptr(scores, n) if scores is not None else None, _ptr(weighted, n))
 
+    def trace_attributes(self, frame_number, num_active_features, particle_density, attributes, ray_ori, ray_dir, sensor_params, ts_start,
+                         ts_end, pose_start, pose_end, out=None):
+        """Renders per-Gaussian attributes into the cached forward's view (gut_trace_attributes): attributes, a
+        contiguous float32 [N,K] tensor on the rays' GPU (K in 1..64), blended with the forward's weights into a float32 [K,H,W]
+        tensor, every element written (`out`: a contiguous one to write into; otherwise a fresh one).  Follows any forward on this
+        handle, consumes nothing, and may be followed by any backward, contribution or attribute call.  Unsorted variant at kernel
+        degree 2 only.  particle_density: the [N,12] rows of the forward, or an int N after a *_fields forward."""
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
+        rows = None
+        if isinstance(particle_density, torch.Tensor):
+            n = int(particle_density.shape[0])
+            if n:
+                rows = _check_f32_cuda(particle_density, "particleDensity", (12,))
+        else:
+            n = int(particle_density)
+        if not (isinstance(attributes, torch.Tensor) and attributes.dtype == torch.float32 and attributes.is_contiguous()
+                and attributes.dim() == 2 and attributes.shape[0] == n and attributes.device == dev):
+            raise RuntimeError(f"[3dgut] attributes: a contiguous float32 tensor [{n}, K] on the rays' GPU")
+        k = int(attributes.shape[1])
+        if out is None:
+            out = torch.empty((k, H, W), dtype=torch.float32, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.is_contiguous()
+                  and tuple(out.shape) == (k, H, W) and out.device == dev):
+            raise RuntimeError(f"[3dgut] attribute output: a contiguous float32 tensor [{k}, {H}, {W}] on the rays' GPU")
+        cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
+        self._call("trace_attributes", self._lib.gut_trace_attributes, dev, frame_number, int(num_active_features), n, _ptr(rows), W, H,
+                   ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), k, _ptr(attributes, n), out.data_ptr() if out.numel() else None)
+        return out
+
     def set_regularisation(self, reg):
         """The NEXT optimiser step on the handle (optimize_rows_without_gradient + optimize_after_bwd, or
         finish_optimizer_step_without_gradient) adds the MCMC regularisers' gradient to every row it updates and writes the loss

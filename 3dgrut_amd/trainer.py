@@ -57,12 +57,20 @@ over black — and every Gaussian is charged the per-pixel error it drew (Contri
 gradient statistics are not collected.  The scores are recomputed at every densify step: the checkpoint holds nothing of them.
 GSStrategy, one GPU, the unsorted variant at kernel degree 2 only.  grow_fraction, views and min_pixels are untuned on real captures.
 
+`selection.enabled` (default off; `--select-by-masks [SUFFIX]`) selects Gaussians from 2-D label masks (selection.py),
+after train() and after the compaction when that is on: the label masks `<image stem><mask_suffix>.png` of the training views that
+have one are lifted to the Gaussians (the share of each Gaussian's drawn weight inside the masks), the rows with a share above
+`threshold` and at least `min_pixels` composited pixels are selected, and the selection is rendered into every held-out view and
+scored by IoU against that view's own label mask where it has one.  With an output directory: selection.npy (bool [N]),
+selected.ply, rest.ply and renders_selection/.  The model is not changed.  One GPU only; threshold is untuned on real captures.
+
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
                                  [--refine-poses [--pose-lr-translation X] [--pose-lr-rotation R]]
                                  [--exposure [--exposure-lr X]] [--cc-metrics] [--aligned-metrics [--align-iterations K]]
                                  [--compact-to FRACTION [--compact-score weight_sum|max_weight] [--compact-finetune K]]
                                  [--densify-by gradient|error [--densify-grow-fraction F] [--densify-views K]]
+                                 [--select-by-masks [SUFFIX] [--select-threshold T]]
 """
 import argparse
 import copy
@@ -77,6 +85,7 @@ import torch
 from . import contribution as contribution_mod
 from . import exposure as exposure_mod
 from . import losses, pose_align, pose_refine
+from . import selection as selection_mod
 from .evaluate import _check_batch, evaluate
 
 # configs/base_gs.yaml + configs/strategy/gs.yaml: the keys this trainer reads
@@ -112,6 +121,10 @@ GS_CONFIG = {
     # training iteration.  keep_fraction of the rows stay (the best by `score`; rows composited in fewer than min_pixels pixels of the
     # training views go first), then finetune_iterations further steps without the strategy.
     "compaction": dict(contribution_mod.DEFAULTS),
+    # not a reference key: a 3-D selection lifted from the training views' 2-D label masks `<image stem><mask_suffix>.png`
+    # (selection.py), after training and compaction; rendered into the held-out views and scored by IoU.  threshold is untuned on
+    # real captures.
+    "selection": dict(selection_mod.DEFAULTS),
     "strategy": {"method": "GSStrategy",
                  # criterion and error are not reference keys: "error" grows, at every densify step, the grow_fraction of the rows
                  # that are responsible for the most rendering error over `views` training views (0: all of them), instead of
@@ -172,6 +185,7 @@ def resolve_config(conf):
     check_evaluation_config(out["evaluation"])
     pose_align.check_config(out["pose_alignment"])
     contribution_mod.check_config(out["compaction"])
+    selection_mod.check_config(out["selection"])
     check_densify_config(out)
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
@@ -406,6 +420,8 @@ class Trainer:
             self.global_step = int(ckpt["global_step"])
         if c["compaction"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
             raise ValueError("compaction: data-parallel compaction is out of scope (the stepper's world_size must be 1)")
+        if c["selection"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
+            raise ValueError("selection: data-parallel selection is out of scope (the stepper's world_size must be 1)")
         self.densify_criterion = (c["strategy"].get("densify") or {}).get("criterion", "gradient")
         if self.densify_criterion == "error":
             if int(getattr(stepper, "world_size", 1)) > 1:
@@ -740,12 +756,53 @@ class Trainer:
         self.stats.update(out, n_gaussians=int(self.model.num_gaussians), n_steps=self.global_step)
         return out
 
+    def select_by_masks(self):
+        """The `selection` block, after train() and compact(): lifts the label masks of the training views that carry one (at their
+        refined poses) to the Gaussians, selects, renders the selection into every held-out view and scores the IoU against the
+        label masks those carry.  Writes selection.npy, selected.ply, rest.ply and renders_selection/ into the output directory
+        when there is one.  Fills and returns the selection_* statistics; the model is left as it is."""
+        from .attributes import AttributeRenderer
+        sel = self.conf["selection"]
+        labelled = [v for v in range(len(self.train_batches)) if getattr(self.train_batches[v], "label_mask", None) is not None]
+        if not labelled:
+            raise ValueError(f"selection: no training view has a label mask (<image stem>{sel['mask_suffix']}.png next to its image)")
+        batches = [self.train_batches[v] if self.refiner is None else self.refiner.begin(v, self.train_batches[v]) for v in labelled]
+        lifted = selection_mod.lift_masks(self.model, self.tracer, batches, [self.train_batches[v].label_mask for v in labelled])
+        selected = selection_mod.select(lifted, threshold=float(sel["threshold"]), min_pixels=int(sel["min_pixels"]))
+        out_dir = self._out_dir()
+        renders = None
+        if out_dir is not None:
+            from .io_ply import export_native_model
+            renders = os.path.join(out_dir, "renders_selection")
+            os.makedirs(renders, exist_ok=True)
+            np.save(os.path.join(out_dir, "selection.npy"), selected.detach().cpu().numpy().astype(bool))
+            rows_in, rows_out = selection_mod.split_rows(self.model, selected)
+            export_native_model(self.model, os.path.join(out_dir, "selected.ply"), rows=rows_in)
+            export_native_model(self.model, os.path.join(out_dir, "rest.ply"), rows=rows_out)
+        renderer = AttributeRenderer(self.model, self.tracer) if self.test_batches else None
+        ious = []
+        for i, batch in enumerate(self.test_batches):
+            s = selection_mod.render_selection(renderer, batch, selected)
+            label = getattr(batch, "label_mask", None)
+            if label is not None:
+                ious.append(selection_mod.mask_iou(s > 0.5, torch.as_tensor(label).reshape(s.shape) > 0.5))
+            if renders is not None:
+                from PIL import Image
+                grey = torch.round(255.0 * s.clamp(0.0, 1.0)).to(torch.uint8).cpu().numpy()
+                Image.fromarray(grey, mode="L").save(os.path.join(renders, f"{i:05d}.png"))
+        out = dict(selection_n_selected=int(selected.sum()), selection_n_views_lifted=len(labelled),
+                   selection_mean_iou=float(np.mean(ious)) if ious else None, selection_threshold=float(sel["threshold"]))
+        self.stats.update(out)
+        return out
+
     def run(self):
-        """train(), (compaction.enabled) compact(), print the statistics table, then (test_last) save ckpt_last.pt and evaluate the
-        test split."""
+        """train(), (compaction.enabled) compact(), (selection.enabled) select_by_masks(), print the statistics table, then
+        (test_last) save ckpt_last.pt and evaluate the test split."""
         stats = self.train()
         if self.conf["compaction"]["enabled"]:
             self.compact()
+        if self.conf["selection"]["enabled"]:
+            self.select_by_masks()
         print("Training Statistics: " + json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in stats.items()}), flush=True)
         if self.conf["test_last"] and self.test_batches:
             self.save_checkpoint(last=True)
@@ -786,6 +843,11 @@ def build_parser():
                          "(compaction.enabled, compaction.keep_fraction)")
     ap.add_argument("--compact-score", choices=contribution_mod.SCORES, default=None, help="compaction.score")
     ap.add_argument("--compact-finetune", type=int, default=None, metavar="K", help="compaction.finetune_iterations")
+    ap.add_argument("--select-by-masks", nargs="?", const=selection_mod.DEFAULTS["mask_suffix"], default=None, metavar="SUFFIX",
+                    help="after training, select the Gaussians inside the views' label masks <image stem>SUFFIX.png (default "
+                         "_object), render the selection into the held-out views and score its IoU (selection.enabled, "
+                         "selection.mask_suffix)")
+    ap.add_argument("--select-threshold", type=float, default=None, metavar="T", help="selection.threshold")
     ap.add_argument("--densify-by", choices=("gradient", "error"), default=None,
                     help="strategy.densify.criterion: error = grow the rows responsible for the most rendering error (default: gradient)")
     ap.add_argument("--densify-grow-fraction", type=float, default=None, metavar="F", help="strategy.densify.error.grow_fraction")
@@ -823,6 +885,11 @@ def config_from_args(a):
         conf["compaction"]["score"] = a.compact_score
     if a.compact_finetune is not None:
         conf["compaction"]["finetune_iterations"] = a.compact_finetune
+    if a.select_by_masks is not None:
+        conf["selection"]["enabled"] = True
+        conf["selection"]["mask_suffix"] = a.select_by_masks
+    if a.select_threshold is not None:
+        conf["selection"]["threshold"] = a.select_threshold
     densify = {}
     if a.densify_by is not None:
         densify["criterion"] = a.densify_by
@@ -846,6 +913,11 @@ def main(argv=None):
                                                          default_scale_factor=conf["model"]["default_scale_factor"], seed=a.seed)
     tb = [train.batch(i) for i in range(len(train))]
     vb = [test.batch(i) for i in range(len(test))]
+    if conf["selection"]["enabled"]:      # the views' label masks, where the files are there
+        for scene, batches in ((train, tb), (test, vb)):
+            for i, b in enumerate(batches):
+                label = scene.load_label_mask(i, conf["selection"]["mask_suffix"])
+                b.label_mask = None if label is None else torch.as_tensor(label[0, :, :, 0], device=b.rays_ori.device)
     trainer = Trainer(conf, init, tb, val_batches=vb, test_batches=vb, scene_extent=train.cameras_extent)
     res = trainer.run()
     test_res = res["test"]

@@ -48,7 +48,8 @@ extern "C" {
  * new entry points next to gut_image_metrics, which launches what it launched before; GutPhotometricLoss and gut_photometric_loss_run,
  * the descriptor form of the fused loss: the four positional forms keep their signatures and call it; GutContribution and
  * gut_trace_contribution, a new entry point: every other call queues what it queued before; gut_trace_contribution_weighted and
- * gut_pixel_error, new entry points: gut_trace_contribution and every other call queue what they queued before). */
+ * gut_pixel_error, new entry points: gut_trace_contribution and every other call queue what they queued before; added under 6
+ * without a bump: gut_trace_attributes, a new entry point: every other call queues what it queued before). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -705,6 +706,28 @@ int gut_trace_contribution_weighted(gut_handle h, void* stream, uint32_t frame_n
  * anything is queued, for a null d_rgba, d_gt_rgb or d_error or a height or width below 1; 2 for a launch failure. */
 int gut_pixel_error(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_gt_rgb,
                     const float* d_mask, const float* d_background, float background, const float* d_exposure12, float* d_error);
+
+/* ---- Rendering per-Gaussian attributes (new functionality, the reference has none) ----
+ * gut_trace_attributes is the other direction of gut_trace_contribution_weighted: where that sums a per-pixel plane onto the
+ * Gaussians, this blends per-Gaussian values into the pixels, out[k][pixel] = sum over the Gaussians the forward composited in the
+ * pixel of w * d_attributes[i][k], with the forward's blending weights w = T * alpha.  Scope, walk and refusals are
+ * gut_trace_contribution's: it follows any forward on the same handle and stream, walks what that forward walked by the forward's
+ * arithmetic, consumes nothing (gradient rows, traversal depths and forward outputs are left alone) and may be followed by any
+ * backward, contribution call or further attribute call.  The channels are rendered four at a time, one walk per group (1 + ceil(K/4)
+ * launches with the tile order); a pixel's sum is formed in the order of its tile's list by one fused multiply-add per composited
+ * Gaussian and channel, in the lane's registers: no atomics, identical inputs give identical bytes, a channel's plane does not depend
+ * on the other channels, and negated attributes give the negated image.  A Gaussian's values are multiplied in only where it was
+ * composited: a non-finite value reaches those pixels alone.  d_out is planar [K,H,W] (each plane is a plane for
+ * gut_trace_contribution_weighted) and written in full, 0 where nothing was composited, so it needs no initialisation; with
+ * num_particles == 0 or a forward without intersections it is zero-filled by one memset on the stream.  Rows of d_attributes are read
+ * by 16-byte loads where num_channels is a multiple of four and the pointer is 16-byte aligned, by 4-byte loads otherwise: no
+ * alignment beyond a float's is required.  Additionally refused, on the host before anything is queued: num_channels outside 1..64;
+ * d_attributes NULL with num_particles > 0; d_out NULL or not 4-byte aligned.  Not part of the kernel timers. */
+int gut_trace_attributes(gut_handle h, void* stream, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+                         const float* d_particle_density /* NULL: the packed rows */, int32_t width, int32_t height,
+                         const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
+                         int32_t num_channels /* 1..64 */, const float* d_attributes /* [N, num_channels] row-major */,
+                         float* d_out /* [num_channels, H, W], fully written */);
 
 /* ---- Per-view exposure in the fused loss (new functionality, the reference has none) ----
  * gut_photometric_loss_exposure is the fused loss of gut_photometric_loss[_masked | _background] on the AFFINE image of a view:
