@@ -640,7 +640,10 @@ __global__ __launch_bounds__(kBlock, kDistGrad ? 3 : 4) void k_render_backward(V
             const float w = am * T;
             const float Tn = (1.0f - am) * T;
             const float t = (u0 * o0 + u1 * o1 + u2 * o2) * il2;  // (u.o)/|u|^2
-            const float q0 = o0 - t * u0, q1 = o1 - t * u1, q2 = o2 - t * u2;  // o_perp
+            // o_perp = o - t u, taken as ((u x o) x u) / |u|^2 from the cross product d2 is built on: along a thin axis of a needle or
+            // disc (1/s ~ 5e3) o and t u are both ~1e4 and o - t u keeps eps 1e4 of error in a component of size ~1e-2, which
+            // M^T scales back up: rows of such Gaussians were 5 - 20 % off.  The cross products cancel 300 : 1 instead of 1e6 : 1.
+            const float q0 = c1 * u2 - c2 * u1, q1 = c2 * u0 - c0 * u2, q2 = c0 * u1 - c1 * u0;  // |u|^2 o_perp
             float ga_hit = 0.f;
             float k0 = 0.f, k1 = 0.f, k2 = 0.f, d0 = 0.f, d1 = 0.f, d2n = 0.f, il = 0.f;
             if (kDistGrad) {
@@ -674,7 +677,8 @@ __global__ __launch_bounds__(kBlock, kDistGrad ? 3 : 4) void k_render_backward(V
             g[12] = rm * G;                            // d density
             const float g_d2x2 = kGeneral ? 2.0f * kernel_response_grad(kernel_degree, d2, rm, ms.w * G)
                                           : -(rm * ms.w) * G;     // 2 * dL/d(d2) = 2 * (-1/2 resp sigma G)
-            float h0 = g_d2x2 * q0, h1 = g_d2x2 * q1, h2 = g_d2x2 * q2;  // dL/do
+            const float g_q = g_d2x2 * il2;
+            float h0 = g_q * q0, h1 = g_q * q1, h2 = g_q * q2;  // dL/do = 2 dL/d(d2) o_perp
             if (!kDistGrad) {
                 // m = (ray_o - mu) - t d = (e - t d) + (sensor_pos - mu); the second, per-entry constant part is
                 // added in the epilogue as H (x) (sensor_pos - mu)

@@ -218,8 +218,11 @@ __device__ void backward_hit(const ViewParams& v, const RenderConsts& c, int ker
     const float il2 = 1.0f / l2, il = fast_rsq(l2);
     const float uo = u[0] * o[0] + u[1] * o[1] + u[2] * o[2];
     const float t = uo * il2;
-    const float op[3] = {o[0] - t * u[0], o[1] - t * u[1], o[2] - t * u[2]};  // o_perp
-    const float d2 = op[0] * op[0] + op[1] * op[1] + op[2] * op[2];          // == |u x o|^2 / |u|^2
+    // o_perp = o - t u as ((u x o) x u) / |u|^2 and d2 = |u x o|^2 / |u|^2, the forward's form: o - t u loses a thin axis' component
+    // of o_perp to cancellation (see the unsorted backward, gut_render.hip)
+    const float x[3] = {u[1] * o[2] - u[2] * o[1], u[2] * o[0] - u[0] * o[2], u[0] * o[1] - u[1] * o[0]};
+    const float op[3] = {(x[1] * u[2] - x[2] * u[1]) * il2, (x[2] * u[0] - x[0] * u[2]) * il2, (x[0] * u[1] - x[1] * u[0]) * il2};
+    const float d2 = (x[0] * x[0] + x[1] * x[1] + x[2] * x[2]) * il2;
     const float resp = kernel_response(kernel_degree, d2);
     const float a0 = resp * mu.w;
 

@@ -1063,18 +1063,72 @@ void oracle_render_margins(const OracleParams* prm, const OracleCamera* cam, int
     render_impl(prm, cam, W, H, density12, feat, ray_ori, ray_dir, ranges, sorted_ids, rgba, dist, hits, NULL, margins);
 }
 
+/* fp32 noise of a pair's hit distance, in units of eps = 2^-24 and of length (tests only: the ORDER margins of the sorted variant).
+ * hit_t = |s o grd| |proj|, proj = -(grd . gro), and s o grdu = R d, so |s o grd| = |d| / |grdu| = 1 / lu for unit directions:
+ *   - proj is a dot product of grd (delta <= eps is_max / lu, as in hit_noise_d2) with gro (delta <= eps |o - mu| is_max):
+ *     delta(proj) <= eps (|gro| is_max / lu + |o - mu| is_max) — the same two anisotropy terms, with the same factor 1/2 and the
+ *     same floor |gro| as the `spread` of hit_noise_d2 (for an isotropic Gaussian both terms are |gro|);
+ *   - |s o grd| inherits delta(grd) scaled by s_max: |proj| s_max is_max / lu, again halved;
+ *   - the products, the sum of three squares and the square root (1 ulp on the device) round the result itself: 4 hit_t.
+ * For an isotropic Gaussian this is about 5.5 hit_t.  KB_HIT_T_NOISE scales the estimate to what two fp32 evaluations of the
+ * k-buffer oracle were MEASURED to swap at (tests/test_cpu_oracle.py::test_two_fp32_evaluations_measure_the_kbuffer_model and
+ * tests/test_cpu_sorted_cases.py; derivation at the end of tests/common.py): with factor 1 the farthest swapped pair sat at 0.50 of
+ * the summed estimates of its two hits (fisheye_144x96, K = 8 and 16, variant 2), 0.385 on fisheye_distorted, 0.32 on the
+ * order-heavy scene (24 - 50 swapped pixels per frame), 0.13 elsewhere: the derivation overestimates, as a sum of worst cases does.
+ * 0.25 puts the farthest swap at 2.01 widths, below the FLIP_MARGIN_BOUND / K_BAND = 2.4 the CPU tests assert, so that the
+ * GPU's bound of FLIP_MARGIN_BOUND = 6 widths keeps K_BAND over the measurement. */
+#define KB_HIT_T_NOISE 0.25f
+static float hit_t_noise(const Hit* h, const float* s, float hit_t) {
+    const float gn = sqrtf(h->gro[0] * h->gro[0] + h->gro[1] * h->gro[1] + h->gro[2] * h->gro[2]);
+    float is_max = 1.0f / s[0], s_max = s[0];
+    if (1.0f / s[1] > is_max) is_max = 1.0f / s[1];
+    if (1.0f / s[2] > is_max) is_max = 1.0f / s[2];
+    if (s[1] > s_max) s_max = s[1];
+    if (s[2] > s_max) s_max = s[2];
+    const float lu = sqrtf(h->grdu[0] * h->grdu[0] + h->grdu[1] * h->grdu[1] + h->grdu[2] * h->grdu[2]);
+    const float lp = sqrtf(h->gposc[0] * h->gposc[0] + h->gposc[1] * h->gposc[1] + h->gposc[2] * h->gposc[2]);
+    if (!(lu > 0.0f)) return 4.0f * hit_t + 1.0f;
+    float spread = 0.5f * (gn * is_max / lu + lp * is_max);
+    if (!(spread >= gn)) spread = gn;
+    const float proj = fabsf(h->grd[0] * h->gro[0] + h->grd[1] * h->gro[1] + h->grd[2] * h->gro[2]);
+    return KB_HIT_T_NOISE * ((spread + 0.5f * proj * s_max * is_max) / lu + 4.0f * hit_t);
+}
+
 /* K6, sorted variant (k_buffer_size = K > 0): render with a per-ray K-entry hit buffer kept sorted by hit distance —
  * gutKBufferRenderer.cuh:28-76 (HitParticleKBuffer::insert), :217-292 (evalKBuffer), :108-170 (processHitParticle).
  * Optionally records, per pixel, the particle ids in the order they were composited (for the autograd check of
- * the backward: oracle/per_ray_torch.py: composite_ordered). order_ids is [P, max_order], -1 padded. */
-void oracle_render_kbuffer(const OracleParams* prm, const OracleCamera* cam, int W, int H, int K,
-                           const float* density12, const float* feat, const float* ray_ori, const float* ray_dir,
-                           const uint32_t* ranges, const uint32_t* sorted_ids, float* rgba, float* dist, float* hits,
-                           int32_t* order_ids, int32_t* order_count, int max_order) {
+ * the backward: oracle/per_ray_torch.py: composite_ordered). order_ids is [P, max_order], -1 padded.
+ *
+ * Tests only (each pointer may be NULL):
+ *   margins [P,3]: how close the ray's decisions came to flipping, in estimated fp32 noise widths of the compared quantity (the unit
+ *     of oracle_render_margins).  [0] hit / no-hit: the response against min_kernel_density, alpha against alpha_threshold, and, for
+ *     entries that pass both, hit_t against the ray's tmin and tmax (hit_t_noise; an exactly zero distance has no margin against tmin); [1] the running transmittance against
+ *     min_transmittance at every composited hit; [2] ORDER: for every comparison `t > stored` of an insertion with a pending hit,
+ *     |t - stored| / (eps (noise(t) + noise(stored))).  Two hits of bit-equal position, rotation and scale have bit-equal hit
+ *     distances in every evaluation: their comparison is decided by the insertion rule and the list order, and has no margin.
+ *   pixel_budget [P,2], bound: the semantics of oracle_set_pixel_budget_out.  [0] += 2 alpha T for every hit / no-hit decision within
+ *     `bound` widths (T at the time the entry is met: an upper bound of T when it would be composited), 2 T once where the
+ *     termination is that close, 2 alpha_i alpha_j T for every such order comparison (swapping two adjacent hits moves the colour by
+ *     alpha_i alpha_j T |c_i - c_j|, colours of magnitude <= 2 ... and the hit distance by the same weight times |t_i - t_j|, which
+ *     is the noise itself); [1] = one count per hit / no-hit decision, 64 for the termination, none for a swap.
+ *   order_nu [P,max_order]: the response's noise estimate nu (hit_noise) of every recorded entry.
+ *   ghost_mode != 0: the ALTERNATIVE walk for the backward's flip budget, not a render: an entry each of whose failed tests is within
+ *     `bound` widths is taken as a hit, an order comparison within `bound` widths is decided the other way, and a ray whose termination
+ *     is that close walks on until T < min_transmittance / 4: a composite another evaluation may arrive at.
+ *   walk [P,2]: the number of list entries the ray evaluated, and the number of accepted hits still pending in its buffer when it
+ *     ended (never composited: the ray fell below min_transmittance first). */
+static void render_kbuffer_impl(const OracleParams* prm, const OracleCamera* cam, int W, int H, int K,
+                                const float* density12, const float* feat, const float* ray_ori, const float* ray_dir,
+                                const uint32_t* ranges, const uint32_t* sorted_ids, float* rgba, float* dist, float* hits,
+                                int32_t* order_ids, int32_t* order_count, int max_order,
+                                float* margins, float* pixel_budget, float bound, float* order_nu, int ghost_mode, int32_t* walk) {
     const PoseSet ps = make_pose_set(cam);
     const int gx = (W + GUT_TILE - 1) / GUT_TILE, gy = (H + GUT_TILE - 1) / GUT_TILE;
+    const float eps = 5.9604645e-08f, fmax_ = 3.4028235e+38f;
+    const int track = margins || pixel_budget || order_nu || ghost_mode;
     if (K < 1) K = 1;
     if (K > 64) K = 64;
+#pragma omp parallel for schedule(dynamic, 1)
     for (int tile = 0; tile < gx * gy; ++tile) {
         const int tx = tile % gx, ty = tile / gx;
         const uint32_t beg = ranges[2 * tile], end = ranges[2 * tile + 1];
@@ -1086,9 +1140,12 @@ void oracle_render_kbuffer(const OracleParams* prm, const OracleCamera* cam, int
                 if (!ray.alive) continue;
                 float T = 1.0f, rgb[3] = {0, 0, 0}, dsum = 0.0f;
                 uint32_t nh = 0;
-                float kb_t[64], kb_a[64]; uint32_t kb_i[64]; int num = 0;
-                for (int i = 0; i < K; ++i) { kb_t[i] = -1.0f; kb_a[i] = 0.0f; kb_i[i] = INVALID_IDX; }
-#define ORACLE_PROCESS(IDX, ALPHA, HITT)                                                    \
+                float kb_t[64], kb_a[64], kb_nt[64], kb_nu[64]; uint32_t kb_i[64]; int num = 0;
+                for (int i = 0; i < K; ++i) { kb_t[i] = -1.0f; kb_a[i] = 0.0f; kb_i[i] = INVALID_IDX; kb_nt[i] = 0.0f; kb_nu[i] = 0.0f; }
+                float m_thr = fmax_, m_trm = fmax_, m_ord = fmax_, t_noise = 1.0f, pb = 0.0f, pb_hits = 0.0f;
+                int pb_term = 0, term_prone = 0, ghost_walk = 0, n_acc = 0;
+                uint32_t k = beg;
+#define ORACLE_PROCESS(IDX, ALPHA, HITT, NU)                                                \
     do {                                                                                     \
         const float w_ = (ALPHA) * T;                                                        \
         dsum += (HITT) * w_;                                                                 \
@@ -1100,11 +1157,26 @@ void oracle_render_kbuffer(const OracleParams* prm, const OracleCamera* cam, int
             }                                                                                \
             nh++;                                                                            \
         }                                                                                    \
-        if (order_ids && order_count[pix] < max_order) order_ids[pix * (size_t)max_order + order_count[pix]] = (int32_t)(IDX); \
+        if (order_ids && order_count[pix] < max_order) {                                     \
+            order_ids[pix * (size_t)max_order + order_count[pix]] = (int32_t)(IDX);          \
+            if (order_nu) order_nu[pix * (size_t)max_order + order_count[pix]] = (NU);       \
+        }                                                                                    \
         if (order_count) order_count[pix]++;                                                 \
-        if (T < prm->min_transmittance) ray.alive = 0;                                       \
+        if (track) {                                                                         \
+            t_noise += (ALPHA) * (NU) / (1.0f - (ALPHA)) + 1.0f;                             \
+            const float mt_ = fabsf(T - prm->min_transmittance) / (prm->min_transmittance * eps * t_noise); \
+            if (mt_ < m_trm) m_trm = mt_;                                                    \
+            if (mt_ < bound) {                                                               \
+                term_prone = 1;                                                              \
+                if (!pb_term) { pb_term = 1; pb += 2.0f * T; pb_hits += 64.0f; }             \
+            }                                                                                \
+        }                                                                                    \
+        if (T < prm->min_transmittance) {                                                    \
+            if (ghost_mode && term_prone && !(T < 0.25f * prm->min_transmittance)) ghost_walk = 1; \
+            else { ray.alive = 0; ghost_walk = 0; }                                          \
+        }                                                                                    \
     } while (0)
-                for (uint32_t k = beg; k < end && ray.alive; ++k) {
+                for (; k < end && ray.alive; ++k) {
                     const uint32_t id = sorted_ids[k];
                     if (id == INVALID_IDX) break;
                     const float* g = density12 + (size_t)id * 12;
@@ -1112,38 +1184,104 @@ void oracle_render_kbuffer(const OracleParams* prm, const OracleCamera* cam, int
                     quat_to_rows(g + 4, rows);
                     Hit h;
                     eval_hit(prm, g, rows, &ray, &h);
-                    if (!((h.resp > prm->min_kernel_density) && (h.alpha > prm->alpha_threshold))) continue;
                     const float* s = g + 8;
                     const float proj = h.grd[0] * -h.gro[0] + h.grd[1] * -h.gro[1] + h.grd[2] * -h.gro[2];
                     const float v0 = s[0] * h.grd[0] * proj, v1 = s[1] * h.grd[1] * proj, v2 = s[2] * h.grd[2] * proj;
                     float hit_t = sqrtf(v0 * v0 + v1 * v1 + v2 * v2);
-                    if (!((hit_t > ray.tmin) && (hit_t < ray.tmax))) continue;
+                    const int ok_resp = h.resp > prm->min_kernel_density, ok_alpha = h.alpha > prm->alpha_threshold;
+                    const int ok_range = (hit_t > ray.tmin) && (hit_t < ray.tmax);
+                    int accept = ok_resp && ok_alpha && ok_range;
+                    float nu = 0.0f, nt = 0.0f;
+                    if (track) {
+                        nu = hit_noise(prm, &h, s);
+                        nt = hit_t_noise(&h, s, hit_t);
+                        /* the forward's three tests, each only when the ones before it pass (or, for the ghost walk, nearly pass) */
+                        const float mr = fabsf(h.resp - prm->min_kernel_density) / (prm->min_kernel_density * eps * nu);
+                        float me = mr;
+                        int near_all = ok_resp || mr < bound;
+                        if (ok_resp) {
+                            const float ma = fabsf(h.resp * g[3] - prm->alpha_threshold) / (prm->alpha_threshold * eps * nu);
+                            if (ma < me) me = ma;
+                            near_all = near_all && (ok_alpha || ma < bound);
+                            if (ok_alpha) {
+                                /* a hit distance that is zero because every product of grd . gro is exactly zero (a ray that starts in the
+                                 * Gaussian's centre plane, along one of its axes) is zero in every evaluation: no margin against tmin */
+                                const int exact_zero = hit_t == 0.0f && h.grd[0] * h.gro[0] == 0.0f && h.grd[1] * h.gro[1] == 0.0f && h.grd[2] * h.gro[2] == 0.0f;
+                                const float m0 = exact_zero ? fmax_ : fabsf(hit_t - ray.tmin) / (eps * nt), m1 = fabsf(ray.tmax - hit_t) / (eps * nt);
+                                const float mg = m0 < m1 ? m0 : m1;
+                                if (mg < me) me = mg;
+                                near_all = near_all && (ok_range || mg < bound);
+                            }
+                        } else {
+                            near_all = near_all && ok_alpha && ok_range;
+                        }
+                        if (me < m_thr) m_thr = me;
+                        if (me < bound) { pb += 2.0f * h.alpha * T; pb_hits += 1.0f; }
+                        if (ghost_mode && !accept && near_all) accept = 1;
+                    }
+                    if (!accept) continue;
+                    n_acc++;
                     if (num == K) {  /* full: composite the closest stored hit, then free its slot */
-                        ORACLE_PROCESS(kb_i[0], kb_a[0], kb_t[0]);
+                        ORACLE_PROCESS(kb_i[0], kb_a[0], kb_t[0], kb_nu[0]);
                         kb_t[0] = -1.0f;
                     } else {
                         num++;
                     }
                     /* insert (bubble towards the back while farther than the stored entries) */
-                    float ct = hit_t, ca = h.alpha; uint32_t ci = id;
-                    for (int i = K - 1; i >= 0; --i)
-                        if (ct > kb_t[i]) {
-                            const float tt = kb_t[i], ta = kb_a[i]; const uint32_t ti = kb_i[i];
-                            kb_t[i] = ct; kb_a[i] = ca; kb_i[i] = ci;
-                            ct = tt; ca = ta; ci = ti;
+                    float ct = hit_t, ca = h.alpha, cnt_ = nt, cnu = nu; uint32_t ci = id;
+                    for (int i = K - 1; i >= 0; --i) {
+                        int other_way = 0;   /* ghost walk: a comparison within `bound` widths is decided the other way */
+                        if (track && kb_t[i] >= 0.0f && ci != INVALID_IDX) {
+                            const float* ga = density12 + (size_t)ci * 12; const float* gb = density12 + (size_t)kb_i[i] * 12;
+                            const int same_geometry = ct == kb_t[i] && memcmp(ga, gb, 3 * sizeof(float)) == 0 && memcmp(ga + 4, gb + 4, 7 * sizeof(float)) == 0;
+                            if (!same_geometry) {
+                                const float mo = fabsf(ct - kb_t[i]) / (eps * (cnt_ + kb_nt[i]));
+                                if (mo < m_ord) m_ord = mo;
+                                if (mo < bound) { pb += 2.0f * ca * kb_a[i] * T; other_way = ghost_mode; }
+                            }
                         }
+                        if ((ct > kb_t[i]) != (other_way != 0)) {
+                            const float tt = kb_t[i], ta = kb_a[i], tn_ = kb_nt[i], tu = kb_nu[i]; const uint32_t ti = kb_i[i];
+                            kb_t[i] = ct; kb_a[i] = ca; kb_i[i] = ci; kb_nt[i] = cnt_; kb_nu[i] = cnu;
+                            ct = tt; ca = ta; ci = ti; cnt_ = tn_; cnu = tu;
+                        }
+                    }
                 }
-                for (int i = 0; ray.alive && i < num; ++i) {
+                for (int i = 0; (ray.alive || ghost_walk) && i < num; ++i) {
                     const int sl = K - num + i;
-                    ORACLE_PROCESS(kb_i[sl], kb_a[sl], kb_t[sl]);
+                    ORACLE_PROCESS(kb_i[sl], kb_a[sl], kb_t[sl], kb_nu[sl]);
                 }
 #undef ORACLE_PROCESS
-                rgba[4 * pix] = rgb[0]; rgba[4 * pix + 1] = rgb[1]; rgba[4 * pix + 2] = rgb[2];
-                rgba[4 * pix + 3] = 1.0f - T;
-                dist[pix] = dsum;
-                hits[pix] = prm->enable_hitcounts ? (float)nh : 0.0f;   /* rayPayload.cuh:126-128: written only when compiled in; the tensor is created zeroed (splatRaster.cpp:198) */
+                if (rgba) {
+                    rgba[4 * pix] = rgb[0]; rgba[4 * pix + 1] = rgb[1]; rgba[4 * pix + 2] = rgb[2];
+                    rgba[4 * pix + 3] = 1.0f - T;
+                    dist[pix] = dsum;
+                    hits[pix] = prm->enable_hitcounts ? (float)nh : 0.0f;   /* rayPayload.cuh:126-128: written only when compiled in; the tensor is created zeroed (splatRaster.cpp:198) */
+                }
+                if (walk) { walk[2 * pix] = (int32_t)(k - beg); walk[2 * pix + 1] = n_acc - order_count[pix]; }
+                if (margins) { margins[3 * pix] = m_thr; margins[3 * pix + 1] = m_trm; margins[3 * pix + 2] = m_ord; }
+                if (pixel_budget) { pixel_budget[2 * pix] = pb; pixel_budget[2 * pix + 1] = pb_hits; }
             }
     }
+}
+
+void oracle_render_kbuffer(const OracleParams* prm, const OracleCamera* cam, int W, int H, int K,
+                           const float* density12, const float* feat, const float* ray_ori, const float* ray_dir,
+                           const uint32_t* ranges, const uint32_t* sorted_ids, float* rgba, float* dist, float* hits,
+                           int32_t* order_ids, int32_t* order_count, int max_order) {
+    render_kbuffer_impl(prm, cam, W, H, K, density12, feat, ray_ori, ray_dir, ranges, sorted_ids, rgba, dist, hits,
+                        order_ids, order_count, max_order, NULL, NULL, 0.0f, NULL, 0, NULL);
+}
+
+/* the same render with the tests' extra outputs (render_kbuffer_impl); ghost_mode != 0 fills order_ids / order_count with the
+ * alternative walk and leaves the image outputs alone (pass NULL) */
+void oracle_render_kbuffer_margins(const OracleParams* prm, const OracleCamera* cam, int W, int H, int K,
+                                   const float* density12, const float* feat, const float* ray_ori, const float* ray_dir,
+                                   const uint32_t* ranges, const uint32_t* sorted_ids, float* rgba, float* dist, float* hits,
+                                   int32_t* order_ids, int32_t* order_count, int max_order,
+                                   float* margins, float* pixel_budget, float bound, float* order_nu, int ghost_mode, int32_t* walk) {
+    render_kbuffer_impl(prm, cam, W, H, K, density12, feat, ray_ori, ray_dir, ranges, sorted_ids, rgba, dist, hits,
+                        order_ids, order_count, max_order, margins, pixel_budget, bound, order_nu, ghost_mode, walk);
 }
 
 /* matmul_bw_quat — common/mathUtils.cuh:468-533 */

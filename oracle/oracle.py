@@ -208,9 +208,24 @@ def render_margins(cam: dict, fwd: dict, params=None, budget_bound=None):
     return margins if budget is None else (margins, budget)
 
 
-def render_kbuffer(cam: dict, fwd: dict, K=16, params=None, max_order=0):
+def render_kbuffer(cam: dict, fwd: dict, K=16, params=None, max_order=0, margins=False, budget_bound=None, ghosts=False):
     """Sorted-variant compositing (k_buffer_size=K) on top of a forward() result's tile lists.  Returns rgba, dist, hits and,
-    if max_order > 0, the per-pixel composited particle order (order_ids [P,max_order] int32 -1 padded, order_count [P])."""
+    if max_order > 0, the per-pixel composited particle order (order_ids [P,max_order] int32 -1 padded, order_count [P]).
+
+    margins=True (tests only; gut_oracle.c: render_kbuffer_impl) adds
+      margins [H,W,3] float32: how close the ray's decisions came to flipping, in estimated fp32 noise widths of the compared
+        quantity, the unit of render_margins: channel 0 hit / no-hit (response against min_kernel_density, alpha against
+        alpha_threshold, hit_t against the ray's tmin / tmax), channel 1 early termination (T against min_transmittance),
+        channel 2 ORDER (the gap between a hit's distance and each pending hit it is compared with on insertion, against the
+        noise of the two distances; bit-equal geometry has no margin: the insertion rule decides);
+      order_nu [P,max_order] float32: the response's noise estimate of every recorded entry;
+      walk [P,2] int32: list entries the ray evaluated; accepted hits still pending in its buffer when it terminated (never composited).
+    budget_bound (e.g. ROW_FLIP_BOUND) adds pixel_budget [H,W,2] float32 with the semantics of render_margins(budget_bound=):
+      how far the decisions within that many widths may move the pixel (2 alpha T per hit / no-hit decision, 2 T for the
+      termination, 2 alpha_i alpha_j T per order comparison) and by how many hits its count may differ.
+    ghosts=True (needs budget_bound and max_order) adds ghost_ids [P,max_order] / ghost_count [P]: the order of the ALTERNATIVE walk
+      that takes every nearly accepted entry as a hit, decides every near order comparison the other way and walks a nearly
+      terminated ray on: a composite another fp32 evaluation may arrive at on that pixel (kbuffer_backward budgets its rows)."""
     L = lib()
     prm = params or default_params()
     c = make_camera(cam)
@@ -218,11 +233,93 @@ def render_kbuffer(cam: dict, fwd: dict, K=16, params=None, max_order=0):
     rgba = np.zeros((H, W, 4), np.float32); dist = np.full((H, W, 1), 1e6, np.float32); hits = np.zeros((H, W, 1), np.float32)
     oc = np.zeros(W * H, np.int32)
     oi = np.full((W * H, max(1, max_order)), -1, np.int32)
-    if fwd["M"]:
+    out = dict(rgba=rgba, dist=dist, hits=hits, order_ids=oi, order_count=oc)
+    extras = margins or budget_bound is not None or ghosts
+    if extras:
+        out["margins"] = np.full((H, W, 3), np.finfo(np.float32).max, np.float32)
+        out["order_nu"] = np.zeros(oi.shape, np.float32)
+        out["walk"] = np.zeros((W * H, 2), np.int32)
+        if budget_bound is not None:
+            out["pixel_budget"] = np.zeros((H, W, 2), np.float32)
+        if ghosts:
+            assert budget_bound is not None and max_order > 0
+            out["ghost_ids"] = np.full(oi.shape, -1, np.int32)
+            out["ghost_count"] = np.zeros(W * H, np.int32)
+    if fwd["M"] and not extras:
         L.oracle_render_kbuffer(C.byref(prm), C.byref(c), C.c_int(W), C.c_int(H), C.c_int(K), _p(d12), _p(fwd["feat"]), _p(ro), _p(rd),
                                 _p(fwd["tile_ranges"]), _p(fwd["sorted_ids"]), _p(rgba), _p(dist), _p(hits),
                                 _p(oi) if max_order else None, _p(oc), C.c_int(max_order))
-    return dict(rgba=rgba, dist=dist, hits=hits, order_ids=oi, order_count=oc)
+    elif fwd["M"]:
+        bound = C.c_float(float(budget_bound) if budget_bound is not None else 0.0)
+        head = (C.byref(prm), C.byref(c), C.c_int(W), C.c_int(H), C.c_int(K), _p(d12), _p(fwd["feat"]), _p(ro), _p(rd),
+                _p(fwd["tile_ranges"]), _p(fwd["sorted_ids"]))
+        L.oracle_render_kbuffer_margins(*head, _p(rgba), _p(dist), _p(hits), _p(oi) if max_order else None, _p(oc), C.c_int(max_order),
+                                        _p(out["margins"]), _p(out["pixel_budget"]) if budget_bound is not None else None, bound,
+                                        _p(out["order_nu"]) if max_order else None, C.c_int(0), _p(out["walk"]))
+        if ghosts:
+            L.oracle_render_kbuffer_margins(*head, None, None, None, _p(out["ghost_ids"]), _p(out["ghost_count"]), C.c_int(max_order),
+                                            None, None, bound, None, C.c_int(1), None)
+    return out
+
+
+def kbuffer_backward(cam: dict, fwd: dict, K, rgba_grad, dist_grad=None, params=None, flip_bound=None, reference_undo_colour=False,
+                     max_order=None):
+    """Backward of the sorted variant: float64 autograd of per_ray_torch's ordered composite on the order render_kbuffer recorded
+    (the exact reference: true derivatives incl. min(max_alpha, .) and the hit distance).  Returns dict(ref = the render_kbuffer
+    result with margins, dens_g [N,12] f64, sph_g [N,48] f64, feat_g [N,3] f64) and, with flip_bound, budget [N,10] f64 in the
+    layout of backward(flip_bound=): columns 0..4 (positions, density, rotation, scale, colour) what another equally valid fp32
+    evaluation may move the row by —
+      * on a ray with ANY decision (hit / no-hit, range, termination, order) within flip_bound widths, every composited entry's row is
+        budgeted with its whole |contribution| from that pixel (a swap or a flipped hit changes T and what lies behind for all);
+      * where the alternative walk (render_kbuffer(ghosts=True): near hits taken, near comparisons decided the other way, a near
+        termination walked on) differs from the real one, every entry of THAT composite adds its |contribution| there as well: two
+        composites differ by at most the sum of their magnitudes, whatever the alphas (an entry that moves in front of an
+        alpha = 0.99 neighbour gains 100 x its weight);
+    columns 5..9 the fp32 conditioning: sum over hits of (relative fp32 noise of the hit) x |contribution|
+    (per_ray_torch.ordered_backward)."""
+    import importlib
+    import torch
+    prt = importlib.import_module("oracle.per_ray_torch")
+    prm = params or default_params()
+    d12, sph, ro, rd, sh_degree, W, H = fwd["_inputs"]
+    N = d12.shape[0]
+    if max_order is None:
+        max_order = int(render_kbuffer(cam, fwd, K=K, params=prm)["order_count"].max(initial=0)) + 64    # room for the alternative walk's extra entries
+    ref = render_kbuffer(cam, fwd, K=K, params=prm, max_order=max_order, margins=True, budget_bound=flip_bound, ghosts=flip_bound is not None)
+    assert int(ref["order_count"].max(initial=0)) <= max_order
+    Lmax = max(1, int(ref["order_count"].max(initial=0)))
+    rg = _f32(rgba_grad).reshape(H * W, 4)
+    dg = None if dist_grad is None else _f32(dist_grad).reshape(H * W)
+    p64 = dict(positions=d12[:, 0:3], density=d12[:, 3:4], rotation=d12[:, 4:8], scale=d12[:, 8:11], features=sph)
+    kw = dict(sh_degree=sh_degree, kernel_degree=int(prm.kernel_degree), max_alpha=float(prm.max_alpha), reference_undo_colour=reference_undo_colour)
+    res = prt.ordered_backward(p64, cam["pose_start"], ro, rd, ref["order_ids"][:, :Lmax], ref["order_count"], rg, dg,
+                               nu=ref["order_nu"][:, :Lmax], **kw)
+    out = dict(ref=ref, dens_g=res["dens_g"], sph_g=res["sph_g"], feat_g=res["feat_g"], rgba=res["rgba"], dist=res["dist"])
+    if flip_bound is None:
+        return out
+    budget = np.zeros((N, 10), np.float64)
+    budget[:, 5:] = res["noise"]
+    prone = np.nonzero(ref["margins"].reshape(H * W, 3).min(-1) < float(flip_bound))[0]
+    gprone = np.nonzero((ref["ghost_ids"] != ref["order_ids"]).any(1))[0]      # the alternative walk differs from the real one
+    out["prone_pixels"], out["ghost_pixels"] = prone, gprone
+    if prone.size:
+        ids = ref["order_ids"][prone, :Lmax]
+        ok = (np.arange(Lmax)[None, :] < ref["order_count"][prone, None]).reshape(-1)
+        con = res["contrib"][prone].reshape(-1, 5)[ok]
+        for j in range(5):
+            np.add.at(budget[:, j], ids.reshape(-1)[ok], con[:, j])
+    if gprone.size:
+        assert int(ref["ghost_count"].max()) <= max_order
+        Lg = max(1, int(ref["ghost_count"][gprone].max()))
+        gids, gcnt = ref["ghost_ids"][gprone, :Lg], ref["ghost_count"][gprone]
+        g = prt.ordered_backward(p64, cam["pose_start"], ro.reshape(-1, 3)[gprone], rd.reshape(-1, 3)[gprone], gids, gcnt, rg[gprone],
+                                 None if dg is None else dg[gprone], **kw)
+        sel = (np.arange(Lg)[None, :] < gcnt[:, None]).reshape(-1)
+        con = g["contrib"].reshape(-1, 5)[sel]
+        for j in range(5):
+            np.add.at(budget[:, j], gids.reshape(-1)[sel], con[:, j])
+    out["budget"] = budget
+    return out
 
 
 def backward(cam: dict, fwd: dict, rgba_grad, dist_grad, params=None, flip_bound=None):

@@ -419,41 +419,144 @@ class _ReferenceUndoColour(torch.autograd.Function):
         return d_alpha, d_col
 
 
-def composite_ordered(params, tq, W, H, ray_ori, ray_dir, order_ids, order_count, sh_degree=3, dtype=torch.float64,
-                      reference_undo_colour=False, kernel_degree=2):
-    """Exact (autograd) compositing of each pixel's particles in a GIVEN order — the sorted variant's semantics
-    (k_buffer_size > 0): the reference differentiates it with slang autodiff (gaussianParticles.slang:394-451,
-    shRadiativeParticles.slang:179-207), i.e. true derivatives incl. min(0.99, .) and the hit distance.
-    order_ids [P,L] (-1 padded) comes from the C oracle.  Returns rgba [P,4], dist [P].
-    reference_undo_colour=True: same forward, but the colour's backward is the reference's own un-do recurrence with the
-    unclamped colour (_ReferenceUndoColour) instead of the true derivative."""
-    R, t, Rinv, cam_pos = pose_matrices(tq, dtype)
-    pos, rot, scl, dns, sph = (params[k].to(dtype) for k in ("positions", "rotation", "scale", "density", "features"))
-    feat_unclamped = precompute_features(pos, sph, cam_pos, sh_degree)
-    feat_all = feat_unclamped.clamp(min=0)
-    rows_all = quat_rows(rot)
-    o, d = world_rays(torch.as_tensor(ray_ori, dtype=dtype), torch.as_tensor(ray_dir, dtype=dtype), Rinv, cam_pos)
-    ids = torch.as_tensor(order_ids.astype("int64"))
-    P, L = ids.shape
-    valid = torch.arange(L)[None, :] < torch.as_tensor(order_count.astype("int64"))[:, None]
-    idc = ids.clamp(min=0)
-    mu, rws, s, sg, ft = pos[idc], rows_all[idc], scl[idc], dns[idc, 0], feat_all[idc]      # [P,L,...]
+def _ordered_composite(o, d, mu, q, s, sg, ft_u, valid, kernel_degree, max_alpha, reference_undo_colour):
+    """The sorted variant's composite of [P,L] GATHERED per-(pixel, entry) parameters (centre, wxyz quaternion, scale, density,
+    unclamped colour) in the given order.  Returns rgba [P,4], dist [P] and the intermediates the noise model reads."""
+    P, L = valid.shape
+    rws = quat_rows(q)
     gposc = o[:, None, :] - mu
     gro = torch.einsum("plij,plj->pli", rws, gposc) / s
     grdu = torch.einsum("plij,pj->pli", rws, d) / s
     grd = grdu / grdu.norm(dim=-1, keepdim=True)
     c = torch.cross(grd, gro, dim=-1)
     resp = kernel_response((c * c).sum(-1), kernel_degree)
-    alpha = (resp * sg).clamp(max=ALPHA_MAX)
+    alpha = (resp * sg).clamp(max=max_alpha)
     alpha = torch.where(valid, alpha, torch.zeros_like(alpha))
     hit_t = (s * grd * (-(grd * gro).sum(-1))[..., None]).norm(dim=-1)
+    hit_t = torch.where(valid, hit_t, torch.zeros_like(hit_t))
     one_m = 1 - alpha
-    T_before = torch.cat([torch.ones(P, 1, dtype=dtype), torch.cumprod(one_m, dim=1)[:, :-1]], dim=1)
+    T_before = torch.cat([torch.ones(P, 1, dtype=alpha.dtype), torch.cumprod(one_m, dim=1)[:, :-1]], dim=1)
     w = alpha * T_before
     if reference_undo_colour:
-        rgb = _ReferenceUndoColour.apply(alpha, feat_unclamped[idc])
+        rgb = _ReferenceUndoColour.apply(alpha, ft_u)
     else:
-        rgb = (w[..., None] * ft).sum(1)
-    dist = (w * torch.where(valid, hit_t, torch.zeros_like(hit_t))).sum(1)
+        rgb = (w[..., None] * ft_u.clamp(min=0)).sum(1)
+    dist = (w * hit_t).sum(1)
     T = one_m.prod(dim=1)
-    return torch.cat([rgb, (1 - T)[:, None]], dim=1), dist
+    return torch.cat([rgb, (1 - T)[:, None]], dim=1), dist, dict(alpha=alpha, T_before=T_before, hit_t=hit_t, gro=gro)
+
+
+def composite_ordered(params, tq, W, H, ray_ori, ray_dir, order_ids, order_count, sh_degree=3, dtype=torch.float64,
+                      reference_undo_colour=False, kernel_degree=2, max_alpha=ALPHA_MAX):
+    """Exact (autograd) compositing of each pixel's particles in a GIVEN order — the sorted variant's semantics
+    (k_buffer_size > 0): the reference differentiates it with slang autodiff (gaussianParticles.slang:394-451,
+    shRadiativeParticles.slang:179-207), i.e. true derivatives incl. min(max_alpha, .) and the hit distance.
+    order_ids [P,L] (-1 padded) comes from the C oracle, which has applied the hit / no-hit, range and termination tests: no
+    threshold but max_alpha (render.particle_kernel_max_alpha, which the sorted backward honours) enters here.
+    Returns rgba [P,4], dist [P].
+    reference_undo_colour=True: same forward, but the colour's backward is the reference's own un-do recurrence with the
+    unclamped colour (_ReferenceUndoColour) instead of the true derivative."""
+    R, t, Rinv, cam_pos = pose_matrices(tq, dtype)
+    pos, rot, scl, dns, sph = (params[k].to(dtype) for k in ("positions", "rotation", "scale", "density", "features"))
+    feat_unclamped = precompute_features(pos, sph, cam_pos, sh_degree)
+    o, d = world_rays(torch.as_tensor(ray_ori, dtype=dtype), torch.as_tensor(ray_dir, dtype=dtype), Rinv, cam_pos)
+    ids = torch.as_tensor(order_ids.astype("int64"))
+    P, L = ids.shape
+    valid = torch.arange(L)[None, :] < torch.as_tensor(order_count.astype("int64"))[:, None]
+    idc = ids.clamp(min=0)
+    rgba, dist, _ = _ordered_composite(o, d, pos[idc], rot[idc], scl[idc], dns[idc, 0], feat_unclamped[idc], valid, kernel_degree,
+                                       max_alpha, reference_undo_colour)
+    return rgba, dist
+
+
+_EPS32 = 2.0 ** -24
+
+
+def ordered_backward(params, tq, ray_ori, ray_dir, order_ids, order_count, rgba_grad, dist_grad=None, nu=None, sh_degree=3,
+                     kernel_degree=2, max_alpha=ALPHA_MAX, reference_undo_colour=False, pix_chunk=4096):
+    """composite_ordered differentiated with the GATHERED [P,L,...] tensors as the leaves, so that every (pixel, entry) pair's own
+    gradient contribution is at hand: params (numpy: positions, density [N,1], rotation, scale, features [N,48]), rays [P,3] in
+    sensor space, rgba_grad [P,4], dist_grad [P] or None.  Returns numpy float64
+      rgba [P,4], dist [P], dens_g [N,12], feat_g [N,3], sph_g [N,48]: the exact gradients (index_add of the leaves' gradients);
+      contrib [P,L,5]: the norm of the pair's contribution to the positions / density / rotation / scale / colour row;
+      noise [N,5] (if nu [P,L], the C oracle's response noise of every recorded entry, is given): the fp32 conditioning of each row,
+        sum over its hits of (relative fp32 noise of the hit's contribution) x |contribution|, the terms of gut_oracle.c:
+        render_bwd_impl restated for this composite.  Every geometric and the density contribution is G = dL/dalpha times the
+        response's derivatives (plus the direct hit-distance term), so it inherits
+          eps (nu + 8 cond)                    the response's own noise; G is a sum of terms of either sign, cond = sum |terms| / |G|
+          eps 8 |gro|                          positions / rotation / scale: the cancellation that leaves the perpendicular offset
+          eps 2 R / |G|                        the residual form the kernel evaluates: (final - running) / T' of O(1) numbers,
+                                               R = (|dL/dopacity| + sum_c (|final_c| + |running_c|) |dL/dc|) / (1 - alpha)
+          eps tn_final sum |terms| / |G|       the transmittance chain: every alpha in front of, and behind, the hit (tn as t_noise
+                                               of the margins: 1 + sum (alpha nu / (1 - alpha) + 1))
+        with |G| floored at 1e-3 sum |terms| (cond <= 1e3), and the colour row w dL/drgb eps (nu + tn + 2)."""
+    dtype = torch.float64
+    R, t, Rinv, cam_pos = pose_matrices(tq, dtype)
+    P_all = {k: torch.as_tensor(params[k], dtype=dtype) for k in ("positions", "rotation", "scale", "density", "features")}
+    N = P_all["positions"].shape[0]
+    sph = P_all["features"].clone().requires_grad_(True)
+    feat_unclamped = precompute_features(P_all["positions"], sph, cam_pos, sh_degree)
+    o_all, d_all = world_rays(torch.as_tensor(ray_ori, dtype=dtype).reshape(-1, 3), torch.as_tensor(ray_dir, dtype=dtype).reshape(-1, 3), Rinv, cam_pos)
+    ids_all = torch.as_tensor(order_ids.astype("int64"))
+    cnt_all = torch.as_tensor(order_count.astype("int64"))
+    P, L = ids_all.shape
+    rg_all = torch.as_tensor(rgba_grad, dtype=dtype).reshape(P, 4)
+    dg_all = torch.zeros(P, dtype=dtype) if dist_grad is None else torch.as_tensor(dist_grad, dtype=dtype).reshape(P)
+    dens_g = torch.zeros(N, 12, dtype=dtype); feat_g = torch.zeros(N, 3, dtype=dtype); noise = torch.zeros(N, 5, dtype=dtype)
+    contrib = torch.zeros(P, L, 5, dtype=dtype)
+    rgba_o = torch.zeros(P, 4, dtype=dtype); dist_o = torch.zeros(P, dtype=dtype)
+    for p0 in range(0, P, pix_chunk):
+        sl = slice(p0, min(P, p0 + pix_chunk))
+        ids, rg, dg = ids_all[sl], rg_all[sl], dg_all[sl]
+        valid = torch.arange(L)[None, :] < cnt_all[sl, None]
+        idc = ids.clamp(min=0)
+        flat = idc.reshape(-1)
+        leaves = [P_all["positions"][idc], P_all["rotation"][idc], P_all["scale"][idc], P_all["density"][idc, 0], feat_unclamped.detach()[idc]]
+        leaves = [x.clone().requires_grad_(True) for x in leaves]
+        rgba, dist, aux = _ordered_composite(o_all[sl], d_all[sl], *leaves, valid, kernel_degree, max_alpha, reference_undo_colour)
+        aux["alpha"].retain_grad()
+        ((rgba * rg).sum() + (dist * dg).sum()).backward()
+        g_mu, g_q, g_s, g_sg, g_ft = (x.grad if x.grad is not None else torch.zeros_like(x) for x in leaves)
+        vm = valid.reshape(-1)
+        dens_g[:, 0:3].index_add_(0, flat[vm], g_mu.reshape(-1, 3)[vm])
+        dens_g[:, 3].index_add_(0, flat[vm], g_sg.reshape(-1)[vm])
+        dens_g[:, 4:8].index_add_(0, flat[vm], g_q.reshape(-1, 4)[vm])
+        dens_g[:, 8:11].index_add_(0, flat[vm], g_s.reshape(-1, 3)[vm])
+        feat_g.index_add_(0, flat[vm], g_ft.reshape(-1, 3)[vm])
+        con = torch.stack([g_mu.norm(dim=-1), g_sg.abs(), g_q.norm(dim=-1), g_s.norm(dim=-1), g_ft.norm(dim=-1)], -1) * valid[..., None]
+        contrib[sl] = con
+        rgba_o[sl], dist_o[sl] = rgba.detach(), dist.detach()
+        if nu is not None:
+            with torch.no_grad():
+                nuv = torch.as_tensor(nu[sl.start:sl.stop], dtype=dtype) * valid
+                a, Tb, ht = aux["alpha"].detach(), aux["T_before"].detach(), aux["hit_t"].detach()
+                G = aux["alpha"].grad if aux["alpha"].grad is not None else torch.zeros_like(a)
+                f = leaves[4].detach().clamp(min=0)
+                w = a * Tb
+                Tn = (Tb * (1 - a)).clamp(min=1e-20)
+                run = torch.cumsum(w[..., None] * f, dim=1)
+                drun = torch.cumsum(w * ht, dim=1)
+                fin, dfin, Tf = rgba.detach()[:, None, :3], dist.detach()[:, None], (1 - rgba.detach()[:, 3])[:, None]
+                behind = (fin - run).abs() / Tn[..., None]
+                dbehind = (dfin - drun).abs() / Tn
+                ag, aop, adg = rg[:, None, :3].abs(), rg[:, None, 3].abs(), dg[:, None].abs()
+                G_abs = aop * Tf / (1 - a) + adg * Tb * (ht + dbehind) + Tb * (ag * (f + behind)).sum(-1)
+                Gf = torch.maximum(G.abs(), 1e-30 + 1e-3 * G_abs)
+                cond = (G_abs / Gf).clamp(min=1.0)
+                R_abs = (aop + ((fin.abs() + run.abs()) * ag).sum(-1) + (dfin.abs() + drun.abs()) * adg) / (1 - a)
+                step = (a * nuv / (1 - a) + 1.0) * valid
+                tn_after = 1.0 + torch.cumsum(step, dim=1)
+                tn_before, tn_final = tn_after - step, tn_after[:, -1:]
+                rel = _EPS32 * (nuv + 8.0 * cond + (2.0 * R_abs + tn_final * G_abs) / Gf)
+                gn = aux["gro"].detach().norm(dim=-1)
+                rel_geo = rel + _EPS32 * 8.0 * gn
+                rels = torch.stack([rel_geo, rel, rel_geo, rel_geo, _EPS32 * (nuv + tn_before + 2.0)], -1)
+                noise.index_add_(0, flat[vm], (rels * con).reshape(-1, 5)[vm])
+    # K8: the colour gradient through the SH basis, with the (colour > 0) mask of the SH backward
+    mask = (feat_unclamped.detach() > 0).to(dtype)
+    (sph_g,) = torch.autograd.grad(feat_unclamped, sph, feat_g * mask)
+    out = dict(rgba=rgba_o.numpy(), dist=dist_o.numpy(), dens_g=dens_g.numpy(), feat_g=(feat_g * mask).numpy(), sph_g=sph_g.numpy(),
+               contrib=contrib.numpy())
+    if nu is not None:
+        out["noise"] = noise.numpy()
+    return out

@@ -311,6 +311,36 @@ def densified_like_scene(n=20000, seed=5):
 K_BAND = 2.5
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# The sorted variant (k-buffer compositing; oracle.render_kbuffer(margins=True, budget_bound=), oracle.kbuffer_backward) uses the same
+# constants.  What it adds to the model, and what was measured (tests/test_cpu_oracle.py::
+# test_two_fp32_evaluations_measure_the_kbuffer_model: c1_pinhole_128, fisheye_distorted, dense_big_splats, inside_cloud and the
+# order-heavy pairs scene at K = 1, 4, 16; tests/test_cpu_sorted_cases.py: every case of the GPU test at K = 1, 8, 16; variant 0 against
+# variants 1 and 2, every constant divided by K_BAND, no exceptions):
+#   * one new number, the noise factor of the hit distance (gut_oracle.c: hit_t_noise, KB_HIT_T_NOISE = 0.25).  The derived estimate
+#     (the anisotropy terms of hit_noise_d2 on proj = -(grd . gro), the roundings of the result: about 5.5 hit_t for an isotropic
+#     Gaussian) overestimates: with factor 1 two evaluations swapped pairs up to 0.50 of the summed estimates of the two hits apart
+#     (fisheye_144x96, K = 8 and 16), 0.385 (fisheye_distorted), 0.32 (order pairs, 24 - 50 swapped pixels a frame).  With 0.25 the
+#     farthest swap sits at 2.01 widths <= FLIP_MARGIN_BOUND / K_BAND = 2.4; every other differing pixel at <= 1.54.
+#   * margins: hit / no-hit now includes hit_t against tmin / tmax; ORDER is new (every `t > stored` comparison of an insertion with a
+#     pending hit).  Comparisons between bit-equal geometry (clones) and a hit distance that is a sum of exact zeros have NO margin:
+#     they come out the same in every evaluation, so they earn no allowance.
+#   * pixel budget: 2 alpha T per hit / no-hit decision, 2 T for the termination, 2 alpha_i alpha_j T per near order comparison.
+#     Measured worst |pixel difference| / (COLOUR_TOL + PIX_FLIP x budget): 0.081 (order pairs), calm pixels 4.6e-6 of COLOUR_TOL / 2 = 1e-4.
+#   * row budget: on a ray with any near decision every composited entry's whole |contribution|, plus every entry's |contribution| in
+#     the ALTERNATIVE composite (near hits taken, near comparisons decided the other way, a near termination walked on).  The first
+#     term alone does not bound a swap next to an opaque hit (an entry that moves in front of an alpha = 0.99 neighbour gains 100 x
+#     its weight: the SH rows of c1_pinhole_128 stood at 0.58 of the bound with it alone); with both the worst row is 0.17 (sh), 0.13
+#     (scale), 0.12 (rotation), 0.10 (positions), 0.09 (density) of the full bound, against the 1 / K_BAND = 0.4 asserted.  Rows needing
+#     their budget: at most 0.24 % of the non-zero rows on the GPU test's cases, 1.96 % on the order pairs scene (cap 2 %).
+#   * the exact reference of either evaluation is float64 autograd on the order THAT evaluation recorded, so the CPU band of the rows
+#     measures the flip budget only; the noise columns (per_ray_torch.ordered_backward) restate render_bwd_impl's terms for the true
+#     derivative and are exercised by the GPU (worst row at 0.24 of its bound, tests/test_gpu_sorted_variant.py).
+# The generalised kernels (particle_kernel_degree 0, 1, 3, 4, 5, 8; gut_oracle.c: hit_noise) went through the same band test on
+# c1_pinhole_128 and dense_big_splats (test_two_fp32_evaluations_measure_the_generalised_kernels): rows without a budget at <= 0.25 of
+# their noise estimate against ROW_NOISE / K_BAND = 2.4, every row at <= 0.10 of the full bound, pixels at <= 0.045 of theirs, one
+# differing pixel at a margin of 0.06: the constants of hit_noise bound the band and stay as they were.
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # The element-wise optimiser / activation tests (tests/reference_step.py, tests/test_gpu_step_elements.py): every element obeys
 #       |gpu - float64| <= K x 2^-23 x S + (half an ulp of the result, the format's underflow steps, the inputs' own uncertainty)
 # with S the sum of the ABSOLUTE terms the element is formed from (reference_step.Cond).  The one constant per family is measured on

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import sorted_cases
 from tests.common import (COLOUR_TOL, FISHEYE_DIST, FLIP_MARGIN_BOUND, GRAD_BLOCKS, K_BAND, PIX_FLIP, ROW_ABS, ROW_FLIP, ROW_FLIP_BOUND, ROW_NOISE, ROW_REL, cams,
                           densified_like_scene, fisheye_max_angle_edge_case, make_view, pose, scenes)
 
@@ -434,7 +435,133 @@ def test_two_fp32_evaluations_measure_the_tolerance_model(name):
     print(f"[band {name}] {report}")
 
 
+def _band_rows(report, tag, gA, gB, sA, sB, budget, sh_degree=3):
+    """|variant 0 - variant v| of every gradient row against the row model with every constant divided by K_BAND; fills
+    report[block] = worst row / its bound, returns the share of the non-zero rows that need their flip budget."""
+    blocks = [(name, gA[:, sl], gB[:, sl], budget[:, 5 + j], budget[:, j]) for j, (name, sl) in enumerate(GRAD_BLOCKS)]
+    y = math.sqrt((sh_degree + 1) ** 2 / (4 * math.pi))
+    blocks.append(("sh", sA, sB, budget[:, 9] * y, budget[:, 4] * y))
+    need_share = 0.0
+    for name, a, b, noise, flip in blocks:
+        nr, err = np.linalg.norm(a, axis=1), np.linalg.norm(a - b, axis=1)
+        scale = float(np.quantile(nr[nr > 0], 0.99))
+        tight = ROW_REL * nr + ROW_ABS * scale + ROW_NOISE * noise
+        r_full = float((err / np.maximum(tight + ROW_FLIP * flip, 1e-300)).max())
+        report[name] = round(r_full, 3)
+        assert r_full <= 1.0 / K_BAND, (tag, name, r_full)
+        need_share = max(need_share, float((err > tight).sum()) / max(1, int((nr > 0).sum())))
+    return need_share
+
+
+def _band_pixels(tag, A, B, margins, pixel_budget):
+    """|variant 0 - variant v| of every pixel against the pixel model (the statements of the unsorted band test)."""
+    diff = np.abs(A["rgba"] - B["rgba"]).max(-1)
+    out = (diff > COLOUR_TOL) | (A["hits"] != B["hits"])[..., 0]
+    worst_margin = float(margins[out].max()) if out.any() else 0.0
+    assert worst_margin <= FLIP_MARGIN_BOUND / K_BAND, (tag, worst_margin)
+    calm = margins >= FLIP_MARGIN_BOUND / K_BAND
+    worst_calm_pixel = float(diff[calm].max()) if calm.any() else 0.0
+    assert worst_calm_pixel <= COLOUR_TOL / 2.0, (tag, worst_calm_pixel)
+    ddist = np.abs(A["dist"] - B["dist"])[..., 0] / max(1.0, float(np.abs(A["dist"]).max()))
+    worst_budget = float((np.maximum(diff, ddist) / (COLOUR_TOL + PIX_FLIP * pixel_budget[..., 0])).max())
+    assert worst_budget <= 0.5, (tag, worst_budget)
+    assert bool((np.abs(A["hits"] - B["hits"])[..., 0] <= pixel_budget[..., 1]).all()), tag
+    assert out.mean() <= 5e-3, (tag, int(out.sum()))          # the helpers' cap on outliers, on the oracle alone
+    return dict(pixel_outliers=int(out.sum()), worst_flip_margin=round(worst_margin, 2), worst_calm_pixel=worst_calm_pixel,
+                worst_pixel_vs_budget=round(worst_budget, 3))
+
+
+KBUFFER_BAND_CASES = {
+    "c1_pinhole_128": lambda: sorted_cases.existing("c1_pinhole_128"),
+    "fisheye_distorted": lambda: sorted_cases._from_scene("fisheye_distorted", scenes.scene_c1(900, 12), "fisheye", 144, 96, (0.1, 0.0, -1.5),
+                                                          (0, 0, 0.5), dict(distortion=FISHEYE_DIST)),
+    "dense_big_splats": lambda: sorted_cases.existing("dense_big_splats"),
+    "inside_cloud": lambda: sorted_cases.existing("inside_cloud"),
+    "order_pairs": sorted_cases.order_pairs,
+}
+
+
+@pytest.mark.parametrize("K", [1, 4, 16])
+@pytest.mark.parametrize("name", list(KBUFFER_BAND_CASES))
+def test_two_fp32_evaluations_measure_the_kbuffer_model(name, K):
+    """The band test above for the SORTED variant: oracle.render_kbuffer's margins (hit / no-hit, range, termination and ORDER),
+    its per-pixel budget and kbuffer_backward's per-row budget must bound |variant 0 - variant v| (v = 1, 2) of the k-buffer oracle on
+    every pixel and every row with every constant divided by K_BAND.  The backward of either side is the float64 autograd of the
+    ordered composite on the order THAT evaluation recorded, so the rows differ exactly where a decision went the other way.  The
+    one constant measured here is the noise factor of the hit distance (gut_oracle.c: KB_HIT_T_NOISE): the order margin at which
+    two evaluations swap a pair is printed (`worst_order_margin`) and bounded like every other margin.  No escape clause."""
+    case = KBUFFER_BAND_CASES[name]()
+    cam, W, H, view = case["view"]["oracle_cam"], case["W"], case["H"], case["view"]
+    rng = np.random.default_rng(11)
+    rg = rng.normal(size=(H, W, 4)).astype(np.float32)
+    dg = (0.1 * rng.normal(size=(H, W, 1))).astype(np.float32)
+    A = case["ref"]
+    RA = oracle.kbuffer_backward(cam, A, K, rg, dg, flip_bound=ROW_FLIP_BOUND)
+    margins = RA["ref"]["margins"].min(-1)
+    report = {}
+    for v in (1, 2):
+        with oracle.variant(v):
+            B = oracle.forward(cam, W, H, case["d12"], case["sph"], view["ro"], view["rd"])
+            RB = oracle.kbuffer_backward(cam, B, K, rg, dg)
+        assert np.array_equal(A["sorted_ids"], B["sorted_ids"])
+        tag = (name, K, v)
+        rep = _band_pixels(tag, RA["ref"], RB["ref"], margins, RA["ref"]["pixel_budget"])
+        # pixels whose composite ORDER differs although their composited sets agree: a swap; the order margin it happened at
+        oa, ob = RA["ref"]["order_ids"], RB["ref"]["order_ids"]
+        L = min(oa.shape[1], ob.shape[1])
+        swapped = (oa[:, :L] != ob[:, :L]).any(1) & (np.sort(oa[:, :L], 1) == np.sort(ob[:, :L], 1)).all(1) & \
+                  (RA["ref"]["order_count"] == RB["ref"]["order_count"])
+        om = RA["ref"]["margins"].reshape(-1, 3)[:, 2]
+        rep.update(swapped_pixels=int(swapped.sum()), worst_order_margin=round(float(om[swapped].max()), 3) if swapped.any() else 0.0)
+        assert rep["worst_order_margin"] <= FLIP_MARGIN_BOUND / K_BAND, tag
+        need = _band_rows(rep, tag, RA["dens_g"], RB["dens_g"], RA["sph_g"], RB["sph_g"], RA["budget"])
+        assert need <= 0.02, (tag, need)                       # the helpers' cap on rows needing their budget, on the oracle alone
+        rep["rows_needing_budget_share"] = round(need, 4)
+        report[v] = rep
+    print(f"[kbuffer band {name} K={K}] {report}")
+
+
 KERNEL_DEGREES = [0, 1, 3, 4, 5, 8]
+
+
+@pytest.mark.parametrize("degree", KERNEL_DEGREES)
+@pytest.mark.parametrize("name", ["c1_pinhole_128", "dense_big_splats"])
+def test_two_fp32_evaluations_measure_the_generalised_kernels(name, degree):
+    """The band test for render.particle_kernel_degree != 2 (gut_render_general.hip): the noise estimate of the generalised responses
+    (gut_oracle.c: hit_noise) enters every margin and every row's conditioning, and the degree-2 constants of tests/common.py are
+    only valid for it if it bounds the band of ITS formulas.  Same statements as the degree-2 test, through
+    oracle.render_margins(params=) and oracle.backward(params=, flip_bound=)."""
+    mk, kind, W, H, c2w, kw = BAND_SCENES[name]
+    sc = mk()
+    view = make_view(kind, W, H, c2w(), **kw)
+    cam = view["oracle_cam"]
+    d12, sph = scenes.pack_density(sc), sc["features"]
+    prm = oracle.default_params()
+    prm.kernel_degree = degree
+    rng = np.random.default_rng(11)
+    rg = rng.normal(size=(H, W, 4)).astype(np.float32)
+    dg = (0.1 * rng.normal(size=(H, W, 1))).astype(np.float32)
+    A = oracle.forward(cam, W, H, d12, sph, view["ro"], view["rd"], params=prm)
+    margins2, pixel_budget = oracle.render_margins(cam, A, params=prm, budget_bound=ROW_FLIP_BOUND)
+    gA, sA, _, budget = oracle.backward(cam, A, rg, dg, params=prm, flip_bound=ROW_FLIP_BOUND)
+    report = {}
+    for v in (1, 2):
+        with oracle.variant(v):
+            B = oracle.forward(cam, W, H, d12, sph, view["ro"], view["rd"], params=prm)
+            gB, sB, _ = oracle.backward(cam, B, rg, dg, params=prm)
+        assert np.array_equal(A["sorted_ids"], B["sorted_ids"])
+        tag = (name, degree, v)
+        rep = _band_pixels(tag, A, B, margins2.min(-1), pixel_budget)
+        for j, (block, sl) in enumerate(GRAD_BLOCKS):      # rows no flip-prone decision touches: the noise estimate alone
+            nr, err = np.linalg.norm(gA[:, sl], axis=1), np.linalg.norm(gA[:, sl] - gB[:, sl], axis=1)
+            calm = (budget[:, j] == 0) & (nr > 0)
+            r_noise = float((err[calm] / np.maximum(budget[calm, 5 + j], 1e-300)).max()) if calm.any() else 0.0
+            assert r_noise <= ROW_NOISE / K_BAND, (tag, block, r_noise)
+            rep[block + "_noise"] = round(r_noise, 3)
+        need = _band_rows(rep, tag, gA, gB, sA, sB, budget)
+        assert need <= 0.02, (tag, need)
+        report[v] = rep
+    print(f"[band {name} degree {degree}] {report}")
 
 
 def test_generalised_kernel_known_answers():

@@ -3,8 +3,10 @@ Same bars as tests/test_gpu_parity.py: integer buffers and projection floats bit
 allowed on <= 0.1 % of the pixels, never above 1e-2), gradients within 3e-3 relative L2 per parameter block — except the
 geometry blocks (position / rotation / scale) of the deliberately ill-conditioned draws (scales down to 2e-4 scene units,
 20:1 needles): there the ray origin in the particle's canonical space is ~1e4 while the response depends on differences of
-order 1, fp32 loses three to four digits in ANY formulation (the fp32 oracle itself sits 2e-4 from a float64 autograd there,
-the kernel 3e-3 .. 7e-3), and the bar is 1.5e-2."""
+order 1, fp32 loses three to four digits (the fp32 oracle itself sits 2e-4 from a float64 autograd there), and the bar is 1.5e-2.
+Next to the block-wide bars every row of every block is held to its own fp32-noise and flip budget (check_rows_in_activated_space):
+that is what showed the position rows of those draws 5 - 20 % off (up to 3.5 x their bound, block-wide 3e-3 .. 8e-3) while
+K7 formed o_perp as the difference o - t u; built on the cross product they sit at <= 0.12 of their bound (block-wide 2e-4)."""
 import importlib
 
 import numpy as np
@@ -12,7 +14,7 @@ import pytest
 import torch
 
 from tests.common import FISHEYE_DIST, ROW_FLIP_BOUND, cams, check_colour_outliers, make_view, rel_l2, scenes
-from tests.test_gpu_parity import DIST, _activated_grads, _oracle_inputs, _run_gpu
+from tests.test_gpu_parity import DIST, _activated_grads, _oracle_inputs, _run_gpu, check_rows_in_activated_space
 
 pytestmark = pytest.mark.gpu
 oracle = importlib.import_module("oracle.oracle")
@@ -113,3 +115,5 @@ def test_random_configuration_matches_the_oracle(seed):
         tol = 1.5e-2 if k in ("positions", "rotation", "scale") else 3e-3
         assert rel_l2(g, e) <= tol, f"seed {seed} {k}: rel L2 {rel_l2(g, e)}"
     assert raster.stats()["traversed_bwd"] == ref["traversed_bwd"]
+    # ... and every row of every block inside its own fp32-noise and flip budget (the block-wide bars above hide single rows)
+    check_rows_in_activated_space(f"fuzz {seed}", view, d12, sph, sh, ref, rgba_grad, dist_grad, conf=conf, params=prm)

@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.common import FISHEYE_DIST, ROW_FLIP_BOUND, cams, check_colour_outliers, fisheye_max_angle_edge_case, make_view, rel_l2, scenes, to_batch
+from tests.common import (FISHEYE_DIST, ROW_FLIP_BOUND, cams, check_colour_outliers, check_gradients_per_row, fisheye_max_angle_edge_case, make_view,
+                          rel_l2, scenes, to_batch)
 
 pytestmark = pytest.mark.gpu
 
@@ -103,6 +104,28 @@ def _activated_grads(model, dens_g, sph_g):
     return {k: v.grad.numpy() for k, v in raw.items()}
 
 
+def check_rows_in_activated_space(label, view, d12, sph, sh, ref, rgba_grad, dist_grad=None, conf=None, params=None):
+    """The per-row statement for the UNSORTED compositors, next to the block-wide relative L2 the tests below keep: the activated
+    [N,12] / [N,3 (d+1)^2] rows the oracle got go through SplatRaster.trace / trace_bwd of a handle with `conf`, and every row of
+    every block must sit inside its own bound — fp32 noise and flip budget from oracle.backward(params=, flip_bound=ROW_FLIP_BOUND)
+    on the forward result `ref` (tests/common.check_gradients_per_row; the model's constants are measured per kernel degree by
+    tests/test_cpu_oracle.py)."""
+    W, H = view["W"], view["H"]
+    tr = gut.Tracer({"render": dict(conf or {})})
+    raster = tr.tracer_wrapper
+    sensor, poses = gut.Tracer.create_camera_parameters(to_batch(view, DEV))
+    ro, rd = torch.as_tensor(view["ro"], device=DEV).contiguous(), torch.as_tensor(view["rd"], device=DEV).contiguous()
+    width = raster._radiance_width
+    d12_t, sph_t = torch.as_tensor(d12, device=DEV).contiguous(), torch.as_tensor(np.ascontiguousarray(sph[:, :width]), device=DEV)
+    cam = (ro, rd, None, sensor, poses.timestamps_us[0], poses.timestamps_us[1], poses.T_world_sensors[0], poses.T_world_sensors[1])
+    rgba, dist, hits, _ = raster.trace(0, sh, d12_t, sph_t, *cam)
+    g12, g48 = raster.trace_bwd(0, sh, d12_t, sph_t, *cam, rgba, torch.as_tensor(rgba_grad, device=DEV), dist,
+                                None if dist_grad is None else torch.as_tensor(dist_grad, device=DEV))
+    dens_g, sph_g, _, budget = oracle.backward(view["oracle_cam"], ref, rgba_grad, dist_grad if dist_grad is not None else np.zeros((H, W, 1), np.float32),
+                                               params=params, flip_bound=ROW_FLIP_BOUND)
+    check_gradients_per_row(g12.cpu().numpy(), g48.cpu().numpy(), dens_g, sph_g[:, :width], label, budget, sh_degree=sh)
+
+
 def _check_ordered_ids(raster, ref):
     """What the compositors actually walked (the product path orders every tile lazily, chunk by chunk) must be the prefix
     of the reference's fully sorted list: identical ids on every position the forward staged, padding ids elsewhere, and
@@ -185,6 +208,7 @@ def test_backward_gradients(name, with_dist_grad):
         assert err <= 2e-3, f"{name}/{k}: rel L2 {err}"
     st = res["tracer"].tracer_wrapper.stats()
     assert st["traversed_bwd"] == ref["traversed_bwd"]
+    check_rows_in_activated_space(f"{name}/dist={int(with_dist_grad)}", view, d12, sph, 3, ref, rgba_grad, dist_grad)
 
 
 @pytest.mark.parametrize("sh", [0, 1, 2])
@@ -206,6 +230,7 @@ def test_lower_sh_degrees(sh):
     assert rel_l2(res["model"].features_albedo.grad.cpu().numpy(), exp["features_albedo"]) <= 2e-3
     if sh:
         assert rel_l2(g, exp["features_specular"]) <= 2e-3
+    check_rows_in_activated_space(f"sh{sh}", view, d12, sph, sh, ref, rgba_grad)
 
 
 def test_empty_and_culled_scenes():
@@ -350,6 +375,7 @@ def test_config_toggles_against_the_oracle(name, toggle):
         err = rel_l2(getattr(model, k).grad.cpu().numpy(), e)
         assert err <= 2e-3, f"{name}/{toggle}/{k}: rel L2 {err}"
     assert raster.stats()["traversed_bwd"] == ref["traversed_bwd"]
+    check_rows_in_activated_space(f"{name}/{toggle}", view, d12, sph, 3, ref, rgba_grad, dist_grad, conf=conf, params=prm)
 
 
 @pytest.mark.parametrize("degree", [0, 1, 2])
@@ -397,6 +423,7 @@ def test_radiance_sph_degree_below_three(name, degree):
             continue
         err = rel_l2(getattr(model, k).grad.cpu().numpy(), e)
         assert err <= 2e-3, f"{name}/sph{degree}/{k}: rel L2 {err}"
+    check_rows_in_activated_space(f"{name}/sph{degree}", view, d12, sph, degree, ref, rgba_grad, conf={"particle_radiance_sph_degree": degree})
     # one more active degree than the handle has coefficients for is refused (the reference would read past its coefficient array)
     model.n_active_features = degree + 1
     with pytest.raises(RuntimeError, match="active SH degrees"):
@@ -550,6 +577,16 @@ def test_timings_surface():
 # ---------------------------------------------------------------------------------------------------
 # sorted variant (render.splat.k_buffer_size > 0), SURVEY §8a row a14
 # ---------------------------------------------------------------------------------------------------
+def _check_sorted_rows(label, view, d12, sph, W, H, K, rgba_grad, dist_grad=None, reference_backward=False, kernel_degree=2):
+    """The per-row statement of tests/test_gpu_sorted_variant.py on the activated rows of the tests below, next to their block-wide bars."""
+    from tests import sorted_cases
+    from tests.test_gpu_sorted_variant import check_sorted_backward, check_sorted_forward, run_sorted
+    case = sorted_cases.from_rows(label, d12, sph, view, W, H, **({"kernel_degree": kernel_degree} if kernel_degree != 2 else {}))
+    got = run_sorted(case, K, rgba_grad, dist_grad, conf={"particle_kernel_degree": kernel_degree}, reference_backward=reference_backward)
+    check_sorted_forward(case, K, got, label)
+    check_sorted_backward(case, K, got, rgba_grad, dist_grad, label, reference_undo_colour=reference_backward)
+
+
 def _run_sorted(view, model, K, rgba_grad=None, dist_grad=None, reference_backward=None, kernel_degree=2):
     splat = {"k_buffer_size": K}
     if reference_backward is not None:          # None: the library's default (the reference's form since ABI 5)
@@ -586,6 +623,10 @@ def test_sorted_variant_forward(name, K):
           (np.abs(d - ref["dist"]).max(-1) > 2e-4 * max(1.0, float(np.abs(ref["dist"]).max())))
     assert bad.mean() <= 1e-3, f"{bad.sum()} of {bad.size} pixels differ"
     assert (hits != ref["hits"]).mean() <= 2e-3
+    # ... and per pixel: whatever differs is explained by the k-buffer oracle's own margins (hit / no-hit, range, termination, order)
+    # and stays within the pixel's own budget (tests/test_gpu_sorted_variant.py holds the edge cases to the same)
+    kb = oracle.render_kbuffer(view["oracle_cam"], fwd, K=K, margins=True, budget_bound=ROW_FLIP_BOUND)
+    check_colour_outliers(np.concatenate([rgb, op], -1), hits, kb, kb["margins"], label=f"sorted {name}/K={K}", dist_gpu=d, budget=kb["pixel_budget"])
     if K == 1 and name == "c1_pinhole_128":
         # K=1 composites in list order: must agree with the unsorted compositor
         ref0 = _run_gpu(sc, view, 3, model=model)["out"]
@@ -629,6 +670,7 @@ def test_sorted_variant_with_generalised_kernels(degree):
     for k, e in exp.items():
         err = rel_l2(getattr(model, k).grad.cpu().numpy(), e)
         assert err <= (2e-3 if degree else 5e-3), f"degree {degree}/{k}: rel L2 {err}"
+    _check_sorted_rows(f"sorted K={K}/degree {degree}", view, d12, sph, W, H, K, rgba_grad, kernel_degree=degree)
 
 
 @pytest.mark.parametrize("name", ["c1_pinhole_128", "fisheye_144x96", "dense_big_splats"])
@@ -671,6 +713,7 @@ def test_sorted_variant_backward(name, with_dist_grad):
         g = getattr(model, k).grad.cpu().numpy()
         err = rel_l2(g, e)
         assert err <= 2e-3, f"{name}/{k}: rel L2 {err}"
+    _check_sorted_rows(f"sorted {name}/K={K}/dist={int(with_dist_grad)}", view, d12, sph, W, H, K, rgba_grad, dist_grad)
 
 
 @pytest.mark.parametrize("name", ["c1_pinhole_128", "dense_big_splats"])
@@ -717,6 +760,8 @@ def test_sorted_variant_reference_backward(name):
         for k, e in grads[True if mode is None else mode].items():
             g = getattr(model, k).grad.cpu().numpy()
             assert rel_l2(g, e) <= 2e-3, f"{name}/{k} reference_backward={mode}: rel L2 {rel_l2(g, e)}"
+    for mode in (False, True):
+        _check_sorted_rows(f"sorted {name}/K={K}/reference_backward={mode}", view, d12, sph, W, H, K, rgba_grad, reference_backward=mode)
 
 
 def test_unusable_rays_do_not_poison_gradients():
@@ -746,6 +791,7 @@ def test_unusable_rays_do_not_poison_gradients():
         g = getattr(res["model"], k).grad.cpu().numpy()
         assert np.isfinite(g).all(), k
         assert rel_l2(g, e) <= 2e-3, f"{k}: rel L2 {rel_l2(g, e)}"
+    check_rows_in_activated_space("unusable rays", view, d12, sph, 3, ref, rgba_grad)
 
 
 @pytest.mark.parametrize("name", ["c1_pinhole_128", "fisheye_144x96", "dense_big_splats", "inside_cloud"])
