@@ -103,7 +103,8 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_photometric_loss_background", "gut_set_pose_gradient", "gut_pose_adam_step",
            "gut_photometric_exposure_workspace_bytes", "gut_photometric_loss_exposure", "gut_exposure_adam_step",
            "gut_image_metrics_cc_workspace_bytes", "gut_image_metrics_cc", "gut_photometric_loss_run", "gut_trace_bwd_pose",
-           "gut_trace_contribution", "gut_trace_contribution_weighted", "gut_pixel_error", "gut_trace_attributes")
+           "gut_trace_contribution", "gut_trace_contribution_weighted", "gut_pixel_error", "gut_trace_attributes",
+           "gut_trace_attributes_bwd")
 
 _lib = None
 
@@ -147,6 +148,7 @@ def load():
     lib.gut_trace_contribution.argtypes = [vp, vp, u32, i32, u32, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera), vp]
     lib.gut_trace_contribution_weighted.argtypes = [vp, vp, u32, i32, u32, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera), f_p, vp, vp]
     lib.gut_trace_attributes.argtypes = [vp, vp, u32, i32, u32, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera), i32, f_p, f_p]
+    lib.gut_trace_attributes_bwd.argtypes = lib.gut_trace_attributes.argtypes
     lib.gut_pixel_error.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, vp, vp]
     lib.gut_mcmc_perturb.argtypes = [vp, u32, f_p, f_p, C.c_float, C.c_uint64, C.c_uint64, f_p]
     lib.gut_collect_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]

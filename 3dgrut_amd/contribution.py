@@ -55,9 +55,11 @@ class FrozenModel:
             self.act = torch.cat([model.positions, model.get_density(), model.get_rotation(), model.get_scale(), z], dim=1).to(torch.float32).contiguous()
             self.features = model.get_features().detach().to(torch.float32).contiguous()
         self.n_active_features = int(model.n_active_features)
+        self.n_forwards = 0      # forwards rendered so far: what a later call that must follow ITS forward compares (attributes.py)
 
     def forward(self, batch):
         """(outs, rays_o, rays_d, cam): the forward's four outputs, the rays and the camera tail of the following call."""
+        self.n_forwards += 1
         sensor, poses = self._create_camera(batch)
         rays_o, rays_d = batch.rays_ori.contiguous(), batch.rays_dir.contiguous()
         cam = (sensor, poses.timestamps_us[0], poses.timestamps_us[1], poses.T_world_sensors[0], poses.T_world_sensors[1])

@@ -196,6 +196,7 @@ struct gut_context {
     uint32_t m_capacity = 0, m_peak = 0, sort_n = 0;
     uint64_t overflows = 0;
     DevBuf zero_word, tile_ordered, walk_sums;
+    DevBuf attr_grad_rows, attr_grad_max;   // gut_trace_attributes_bwd: [N,4] fixed-point sums of a channel group, its planes' maxima
     bool fwd_longest_first = false;   // forward compositor launched longest-lists-first (decided from the last frames' walked share)
     int fwd_order_mode = -1;          // GUT_OPT_FORWARD_TILE_ORDER: -1 auto, 0 image order, 1 longest first
     bool dbg_ordered_valid = false;
@@ -432,7 +433,7 @@ void gut_destroy(gut_handle h) {
                       &h->sort_temp, &h->ranges, &h->trav_fwd, &h->trav_bwd, &h->tile_order, &h->counters, &h->ids_ordered,
                       &h->dbg_keys_sorted, &h->dbg_ids_sorted, &h->zero_word, &h->tile_ordered, &h->wave_walked, &h->packed12, &h->walk_sums,
                       &h->wave_sums, &h->block_prefix, &h->scan_total, &h->sph_widened, &h->sph_grad_wide, &h->cam_pos,
-                      &h->tile_entries, &h->tile_start, &h->tile_cursor, &h->pose_partials};
+                      &h->tile_entries, &h->tile_start, &h->tile_cursor, &h->pose_partials, &h->attr_grad_rows, &h->attr_grad_max};
     for (DevBuf* b : bufs) b->release();
     if (h->host_count) (void)hipHostFree(h->host_count);
     if (h->count_event) (void)hipEventDestroy(h->count_event);
@@ -973,15 +974,23 @@ struct AttributeArgs {
     const float* rows;
     float* out;
 };
+// what gut_trace_attributes_bwd adds to it
+struct AttributeGradArgs {
+    int32_t channels;
+    const float* out_grad;
+    float* rows_grad;
+};
 
 // The contribution scores of the cached forward's view: the forward's walk once more, without colours, into the
 // caller's accumulating arrays.  Reads the forward's lists and depths, writes tile_order (every backward rebuilds it) and d_scores /
 // d_weighted_q32.  weighted: the form with a per-pixel plane (gut_trace_contribution_weighted), whose records are optional.
 // attr (gut_trace_attributes): the walk renders attr->rows [N, channels] into attr->out [channels, H, W] instead and
 // the three accumulating arrays are unused.
+// attr_grad (gut_trace_attributes_bwd): the adjoint of that, attr_grad->out_grad [channels, H, W] summed onto the rows
+// attr_grad->rows_grad [N, channels], every element written; the accumulating arrays are unused as well.
 int trace_contribution_impl(gut_handle h, const char* name, const TraceView& view, const float* d_particle_density,
                             GutContribution* d_scores, bool weighted, const float* d_pixel_weight, uint64_t* d_weighted_q32,
-                            const AttributeArgs* attr = nullptr) {
+                            const AttributeArgs* attr = nullptr, const AttributeGradArgs* attr_grad = nullptr) {
     if (!h) return fail("%s: null handle", name);
     std::lock_guard<std::mutex> lock(h->mu);
     if (h->cfg.k_buffer_size > 0 || h->cfg.particle_kernel_degree != 2)
@@ -1000,7 +1009,15 @@ int trace_contribution_impl(gut_handle h, const char* name, const TraceView& vie
         if (!attr->out) return fail("%s: d_out is NULL", name);
         if (((uintptr_t)attr->out & 3u) != 0) return fail("%s: d_out must be 4-byte aligned", name);
     }
-    if (view.n && !d_scores && !weighted && !attr) return fail("%s: d_scores is NULL with %u particles", name, view.n);
+    if (attr_grad) {
+        if (attr_grad->channels < 1 || attr_grad->channels > 64)
+            return fail("%s: num_channels must be in 1..64, got %d", name, attr_grad->channels);
+        if (view.n && !attr_grad->out_grad) return fail("%s: d_out_grad is NULL with %u particles", name, view.n);
+        if (view.n && !attr_grad->rows_grad) return fail("%s: d_attributes_grad is NULL with %u particles", name, view.n);
+        if (((uintptr_t)attr_grad->out_grad & 3u) != 0) return fail("%s: d_out_grad must be 4-byte aligned", name);
+        if (((uintptr_t)attr_grad->rows_grad & 3u) != 0) return fail("%s: d_attributes_grad must be 4-byte aligned", name);
+    }
+    if (view.n && !d_scores && !weighted && !attr && !attr_grad) return fail("%s: d_scores is NULL with %u particles", name, view.n);
     if (((uintptr_t)d_scores & 7u) != 0) return fail("%s: d_scores must be 8-byte aligned", name);
     if (weighted) {
         if (!d_pixel_weight) return fail("%s: d_pixel_weight is NULL", name);
@@ -1017,13 +1034,26 @@ int trace_contribution_impl(gut_handle h, const char* name, const TraceView& vie
     const hipStream_t s = view.stream;
     if (h->n == 0 || h->m == 0) {   // nothing was walked
         if (attr) HIP_TRY(hipMemsetAsync(attr->out, 0, sizeof(float) * (size_t)attr->channels * (size_t)view.width * (size_t)view.height, s));
+        if (attr_grad && h->n) HIP_TRY(hipMemsetAsync(attr_grad->rows_grad, 0, sizeof(float) * (size_t)attr_grad->channels * (size_t)h->n, s));
         return 0;
+    }
+    if (attr_grad) {
+        HIP_TRY(h->attr_grad_rows.ensure(4 * sizeof(int64_t) * (size_t)h->n));
+        HIP_TRY(h->attr_grad_max.ensure(4 * sizeof(uint32_t)));
     }
     gut::launch_tile_order(s, (uint32_t)h->tiles, h->trav_fwd.as<uint32_t>(), h->tile_order.as<uint32_t>());
     if (attr) {
         gut::launch_attributes(s, v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
                                (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
                                h->trav_fwd.as<uint32_t>(), h->n, (uint32_t)attr->channels, attr->rows, attr->out);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    if (attr_grad) {
+        gut::launch_attributes_bwd(s, v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
+                                   (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
+                                   h->trav_fwd.as<uint32_t>(), h->n, (uint32_t)attr_grad->channels, attr_grad->out_grad,
+                                   attr_grad->rows_grad, h->attr_grad_rows.p, h->attr_grad_max.as<uint32_t>());
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -1117,6 +1147,16 @@ int gut_trace_attributes(gut_handle h, void* stream_, uint32_t frame_number, int
     return trace_contribution_impl(h, "gut_trace_attributes",
                                    view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
                                    d_particle_density, nullptr, false, nullptr, nullptr, &attr);
+}
+
+int gut_trace_attributes_bwd(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+                             const float* d_particle_density, int32_t width, int32_t height, const float* d_ray_origin,
+                             const float* d_ray_direction, const GutCamera* camera, int32_t num_channels, const float* d_out_grad,
+                             float* d_attributes_grad) {
+    const AttributeGradArgs grad{num_channels, d_out_grad, d_attributes_grad};
+    return trace_contribution_impl(h, "gut_trace_attributes_bwd",
+                                   view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                                   d_particle_density, nullptr, false, nullptr, nullptr, nullptr, &grad);
 }
 
 // SplatRaster::trace with the four activated tensors the reference's Tracer hands to _Autograd (tracer.py:317-327) instead of

@@ -20,9 +20,16 @@
 // The attribute form (gut_trace_attributes) is the walk in the other direction: per-Gaussian values are staged with the
 // entries and every lane sums w * value over the entries its pixel composited, in list order, in its own registers, and writes the
 // sums to the caller's planes: no reduction across lanes, no partials, no atomics.
+//
+// The attribute gradient (gut_trace_attributes_bwd) is the adjoint of that form and the weighted form without its
+// clamp, four signed channels per walk: each lane loads its pixel's cotangent of the channel group once, every w * g[k] is rounded on
+// its own and goes through the tree, per-wave LDS slots and the wave order, and the flush adds round(sum * 2^s_k) with a 64-bit integer
+// atomic into a scratch row of the handle's, s_k a power of two from the largest |g[k]| of the plane (k_plane_max_abs).  k_grad_rows
+// turns the integers into the caller's float rows.
 #include "gut_internal.h"
 #include "gut_render_common.h"
 
+#include <algorithm>
 #include <type_traits>
 
 namespace gut {
@@ -84,6 +91,27 @@ struct AttrArgs {
 };
 struct NoAttrArgs {};
 
+// the attribute gradient's operands (gut_trace_attributes_bwd), of one channel group
+struct GradArgs {
+    const float* planes;        // the group's first cotangent plane [H,W]
+    long long* rows_q;          // [N,4] fixed-point sums, zeroed by the caller per group
+    const uint32_t* max_bits;   // [4]: the float bits of the largest finite |g| of each of the group's planes (k_plane_max_abs)
+    uint32_t cols;              // channels of this group, 1..4
+};
+
+// The exponent s of the fixed-point unit 2^-s of a plane whose largest finite |g| has the bits max_bits: |g| < 2^e with e read from
+// the exponent field, and s = 40 - e less the bits by which the view has more than 2^14 tiles.  A tile's sum of 256 products w g
+// (w <= 1) is then below 2^48 (+ its rounding) and a row's total over all the tiles below 2^62.  Clamped so that 2^s and 2^-s are
+// normal floats; a plane of zeros takes s = 0 (every product is 0).
+__device__ __forceinline__ int grad_scale_exponent(uint32_t max_bits, uint32_t tiles) {
+    if (max_bits == 0u) return 0;
+    const int e = max((int)(max_bits >> 23), 1) - 126;
+    const int extra = max(32 - (int)__clz((int)(tiles - 1u)) - 14, 0);   // ceil(log2(tiles)) - 14
+    return min(max(40 - e - (tiles > 1u ? extra : 0), -126), 126);
+}
+__device__ __forceinline__ float pow2f(int s) { return __uint_as_float((uint32_t)(s + 127) << 23); }   // s in -126..126
+__device__ __forceinline__ float finite_or_zero(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u ? 0.0f : x; }
+
 // kPlain: the GutContribution records (sum, maximum, count of w).  kWeighted: the sum of w * e into weighted_q32, e the pixel's value
 // of `plane` clamped to [0, 1].  <true, false> is the kernel of §13; the other two read `plane`, <false, true>
 // writes no record (scores is not read).
@@ -92,7 +120,11 @@ struct NoAttrArgs {};
 // it); a lane that composited entry j with w > 0 adds w x those values to its pixel's sums, which go to the planes
 // attr.out[k][H][W], every pixel of the tile.  No partials and no flush.  The mode's operands travel in one trailing argument,
 // empty in the other modes: their kernels keep their argument layout and their code.
-template <bool kPlain, bool kWeighted, int kAttr = 0>
+// kGrad (1 or 4, with none of the others): the adjoint of kAttr.  Each lane holds its pixel's cotangent g[k] of the
+// channel group (a non-finite value and a pixel outside the image count as 0, no clamp); per (wave, entry) some lane composited,
+// w * g[k] is rounded on its own, reduced by the tree into the wave's LDS slot, and thread j's flush combines the waves' slots of
+// entry j in wave order and adds round(sum * 2^s_k) to the Gaussian's row of grad.rows_q with a 64-bit integer atomic.
+template <bool kPlain, bool kWeighted, int kAttr = 0, int kGrad = 0>
 __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, RenderConsts c, const float4* __restrict__ density12,
                                                            const float* __restrict__ ray_ori, const float* __restrict__ ray_dir,
                                                            const uint2* __restrict__ ranges, const uint32_t* __restrict__ ordered_ids,
@@ -100,9 +132,11 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
                                                            const uint32_t* __restrict__ tile_walked, uint32_t num_particles,
                                                            GutContribution* __restrict__ scores, const float* __restrict__ plane,
                                                            unsigned long long* __restrict__ weighted_q32,
-                                                           std::conditional_t<kAttr != 0, AttrArgs, NoAttrArgs> attr) {
-    static_assert(kAttr == 0 ? (kPlain || kWeighted) : ((kAttr == 1 || kAttr == 4) && !kPlain && !kWeighted), "nothing to write");
+                                                           std::conditional_t<kAttr != 0, AttrArgs, std::conditional_t<kGrad != 0, GradArgs, NoAttrArgs>> attr) {
+    static_assert(kGrad != 0 ? ((kGrad == 1 || kGrad == 4) && kAttr == 0 && !kPlain && !kWeighted)
+                  : kAttr == 0 ? (kPlain || kWeighted) : ((kAttr == 1 || kAttr == 4) && !kPlain && !kWeighted), "nothing to write");
     using AttrSlot = std::conditional_t<kAttr == 1, float, float4>;
+    using GradSlot = std::conditional_t<kGrad == 1, float, float4>;
     __shared__ ContribEntry stage[kBlock];
     __shared__ uint32_t s_id[kBlock];
     __shared__ uint32_t s_first_invalid;
@@ -113,7 +147,10 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
     // per chunk and says which of the others are valid (s_wsum: the weighted sums)
     __shared__ float s_sum[kPlain ? kWaves : 1][kPlain ? kBlock : 1], s_max[kPlain ? kWaves : 1][kPlain ? kBlock : 1];
     __shared__ float s_wsum[kWeighted ? kWaves : 1][kWeighted ? kBlock : 1];
-    __shared__ uint32_t s_cnt[kAttr ? 1 : kWaves][kAttr ? 1 : kBlock];
+    __shared__ uint32_t s_cnt[(kAttr || kGrad) ? 1 : kWaves][(kAttr || kGrad) ? 1 : kBlock];
+    // kGrad: the waves' sums of w * g[k] of the chunk; s_hit (zeroed per chunk) says which slots are valid
+    __shared__ GradSlot s_gsum[kGrad ? kWaves : 1][kGrad ? kBlock : 1];
+    __shared__ uint8_t s_hit[kGrad ? kWaves : 1][kGrad ? kBlock : 4];
     __shared__ AttrSlot s_attr[kAttr ? kBlock : 1];   // entry j's values of the channel group
 
     const uint32_t tile = tile_order[blockIdx.x];
@@ -126,6 +163,20 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
     // the pixel's weight, once: clamped on load, so a NaN counts as 0, every w * e lies in [0, w] and a tile's sum stays below 256
     float e = 0.0f;
     if constexpr (kWeighted) e = fminf(fmaxf(inside ? plane[pix] : 0.0f, 0.0f), 1.0f);
+    // kGrad: the pixel's cotangent of the channel group, once, and the planes' fixed-point scales 2^s_k (block-uniform)
+    float g[kGrad ? kGrad : 1] = {};
+    float q_scale[kGrad ? kGrad : 1] = {};
+    if constexpr (kGrad != 0) {
+        const size_t plane_stride = (size_t)v.width * (size_t)v.height;
+        const uint32_t tiles = (uint32_t)(v.grid_x * v.grid_y);
+#pragma unroll
+        for (uint32_t k = 0; k < (uint32_t)kGrad; ++k) {
+            if (k < attr.cols) {
+                if (inside) g[k] = finite_or_zero(attr.planes[k * plane_stride + pix]);
+                q_scale[k] = pow2f(grad_scale_exponent(attr.max_bits[k], tiles));
+            }
+        }
+    }
 
     if (tid == 0) s_first_invalid = kBlock;
     const bool centred = __syncthreads_and(ray.centred ? 1 : 0) != 0;  // block-uniform
@@ -172,7 +223,10 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
             stage[tid] = e;
             s_id[tid] = id;
             s_mask[tid] = strips;
-            if constexpr (kAttr == 0) {
+            if constexpr (kGrad != 0) {
+#pragma unroll
+                for (uint32_t w = 0; w < kWaves; ++w) s_hit[w][tid] = 0u;
+            } else if constexpr (kAttr == 0) {
 #pragma unroll
                 for (uint32_t w = 0; w < kWaves; ++w) s_cnt[w][tid] = 0u;
             } else if constexpr (kAttr == 1) {
@@ -263,6 +317,22 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
             }
             const unsigned long long hit = __ballot(w > 0.0f);
             if (hit == 0ull) return;
+            if constexpr (kGrad != 0) {
+                // every product rounded on its own (see kWeighted below), every channel through its own tree
+                float sums[kGrad];
+#pragma unroll
+                for (int k = 0; k < kGrad; ++k) {
+                    float wg = w * g[k];
+                    asm volatile("" : "+v"(wg));
+                    sums[k] = wave_sum_lane63(wg);
+                }
+                if (lane == 63u) {
+                    if constexpr (kGrad == 1) s_gsum[wave][j] = sums[0];
+                    else s_gsum[wave][j] = make_float4(sums[0], sums[1], sums[2], sums[3]);
+                    s_hit[wave][j] = 1u;
+                }
+                return;
+            }
             if constexpr (kPlain) {
                 const float sum = wave_sum_lane63(w), mx = wave_max_lane63(w);
                 if (lane == 63u) {
@@ -323,7 +393,35 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
 
         // ---- flush: thread j combines the four waves' partials of entry j in wave order and adds them to the Gaussian's record ----
         // (kAttr: nothing to flush; the barrier at the head of the loop stands between this chunk's reads and the next staging)
-        if constexpr (kAttr == 0) {
+        if constexpr (kGrad != 0) {
+        __syncthreads();
+        if (tid < cnt) {
+            bool any = false;
+            float sum[kGrad] = {};
+#pragma unroll
+            for (uint32_t w = 0; w < kWaves; ++w) {
+                if (s_hit[w][tid] != 0u) {
+                    any = true;
+                    const GradSlot p = s_gsum[w][tid];
+                    if constexpr (kGrad == 1) {
+                        sum[0] += p;
+                    } else {
+                        sum[0] += p.x; sum[1] += p.y; sum[2] += p.z; sum[3] += p.w;
+                    }
+                }
+            }
+            if (any) {
+                // |sum| < 2^-s 2^48 (grad_scale_exponent): the product is exact in fp32 (a power-of-two scale), the conversion rounds
+                // to nearest, ties to even; the signed value is added in two's complement
+                long long* const row = attr.rows_q + 4 * (size_t)s_id[tid];
+#pragma unroll
+                for (int k = 0; k < kGrad; ++k) {
+                    const long long q = __float2ll_rn(sum[k] * q_scale[k]);
+                    if (q != 0ll) atomicAdd(reinterpret_cast<unsigned long long*>(row + k), (unsigned long long)q);
+                }
+            }
+        }
+        } else if constexpr (kAttr == 0) {
         __syncthreads();
         if (tid < cnt) {
             uint32_t pixels = 0;
@@ -373,6 +471,26 @@ __global__ __launch_bounds__(kBlock, 4) void k_contribution(ViewParams v, Render
     }
 }
 
+// the largest finite |g| of each of a group's planes, as float bits (non-negative floats order as their bits): blockIdx.y is the plane
+__global__ __launch_bounds__(kBlock) void k_plane_max_abs(const float* __restrict__ planes, size_t plane_stride, uint32_t* __restrict__ max_bits) {
+    const float* const plane = planes + (size_t)blockIdx.y * plane_stride;
+    float m = 0.0f;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < plane_stride; i += (size_t)gridDim.x * kBlock)
+        m = fmaxf(m, fabsf(finite_or_zero(plane[i])));
+    m = wave_max_lane63(m);
+    if ((threadIdx.x & 63u) == 63u && m > 0.0f) atomicMax(max_bits + blockIdx.y, __float_as_uint(m));
+}
+
+// row i of the caller's gradient [N, stride], channels first .. first + cols: float(q) * 2^-s_k; every element of the group is written
+__global__ __launch_bounds__(kBlock) void k_grad_rows(const long long* __restrict__ rows_q, const uint32_t* __restrict__ max_bits,
+                                                      uint32_t tiles, uint32_t n, uint32_t cols, uint32_t stride, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const long long* const q = rows_q + 4 * (size_t)i;
+    float* const row = out + (size_t)i * stride;
+    for (uint32_t k = 0; k < cols; ++k) row[k] = __ll2float_rn(q[k]) * pow2f(-grad_scale_exponent(max_bits[k], tiles));
+}
+
 }  // namespace
 
 void launch_contribution(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
@@ -404,6 +522,31 @@ void launch_attributes(hipStream_t s, const ViewParams& v, const RenderConsts& c
         hipLaunchKernelGGL(kernel, dim3(tiles), dim3(kBlock), 0, s, v, c, reinterpret_cast<const float4*>(density12), ray_ori, ray_dir,
                            reinterpret_cast<const uint2*>(ranges), ordered_ids, tile_order, tile_walked, num_particles,
                            (GutContribution*)nullptr, (const float*)nullptr, (unsigned long long*)nullptr, a);
+    }
+}
+
+void launch_attributes_bwd(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
+                           const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
+                           const uint32_t* tile_walked, uint32_t num_particles, uint32_t num_channels, const float* out_grad,
+                           float* attrs_grad, void* rows_q, uint32_t* max_bits) {
+    const uint32_t tiles = (uint32_t)(v.grid_x * v.grid_y);
+    if (tiles == 0 || num_particles == 0) return;
+    const size_t plane_stride = (size_t)v.width * (size_t)v.height;
+    const uint32_t max_blocks = (uint32_t)std::min<size_t>((plane_stride + kBlock - 1) / kBlock, 256);
+    const uint32_t row_blocks = (num_particles + kBlock - 1) / kBlock;
+    // per group of four channels: the planes' maxima, the walk into the zeroed fixed-point rows, the rows into the caller's floats
+    for (uint32_t first = 0; first < num_channels; first += 4u) {
+        const uint32_t cols = num_channels - first < 4u ? num_channels - first : 4u;
+        const GradArgs a{out_grad + (size_t)first * plane_stride, static_cast<long long*>(rows_q), max_bits, cols};
+        (void)hipMemsetAsync(max_bits, 0, 4 * sizeof(uint32_t), s);
+        (void)hipMemsetAsync(rows_q, 0, 4 * sizeof(long long) * (size_t)num_particles, s);
+        hipLaunchKernelGGL(k_plane_max_abs, dim3(max_blocks, cols), dim3(kBlock), 0, s, a.planes, plane_stride, max_bits);
+        const auto kernel = cols == 1u ? k_contribution<false, false, 0, 1> : k_contribution<false, false, 0, 4>;
+        hipLaunchKernelGGL(kernel, dim3(tiles), dim3(kBlock), 0, s, v, c, reinterpret_cast<const float4*>(density12), ray_ori, ray_dir,
+                           reinterpret_cast<const uint2*>(ranges), ordered_ids, tile_order, tile_walked, num_particles,
+                           (GutContribution*)nullptr, (const float*)nullptr, (unsigned long long*)nullptr, a);
+        hipLaunchKernelGGL(k_grad_rows, dim3(row_blocks), dim3(kBlock), 0, s, a.rows_q, max_bits, tiles, num_particles, cols, num_channels,
+                           attrs_grad + first);
     }
 }
 

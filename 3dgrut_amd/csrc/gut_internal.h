@@ -235,6 +235,13 @@ void launch_contribution(hipStream_t s, const ViewParams& v, const RenderConsts&
 void launch_attributes(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
                        const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
                        const uint32_t* tile_walked, uint32_t num_particles, uint32_t num_channels, const float* attrs, float* out);
+// the adjoint of launch_attributes: out_grad [num_channels, H, W] -> attrs_grad [N, num_channels] row-major, every
+// element written; per group of four channels the planes' maxima, one walk and one pass over the rows.  rows_q: scratch of
+// 32 bytes per particle; max_bits: scratch of four words
+void launch_attributes_bwd(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
+                           const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
+                           const uint32_t* tile_walked, uint32_t num_particles, uint32_t num_channels, const float* out_grad,
+                           float* attrs_grad, void* rows_q, uint32_t* max_bits);
 // sorted (k_buffer_size > 0) compositor variant, gut_render_sorted.hip
 void launch_render_sorted(hipStream_t s, const ViewParams& v, const RenderConsts& c, int K, const float* density12, const float* feat,
                           const float* ray_ori, const float* ray_dir, const uint32_t* ranges, const uint32_t* sorted_ids,

@@ -297,6 +297,36 @@ class ColmapScene:
         the trainer's `selection` block), read, thresholded and size-checked as the mask is; None without the file."""
         return self._load_mask_file(i, suffix, size)
 
+    def load_feature_map(self, i, suffix, size=None):
+        """The view's target map for the trainer's `features` block: `<image stem><suffix>.npy` next to the image, a float array
+        [K,H,W] or [H,W] (one channel) at the view's training resolution, returned as float32 [K,H,W]; None without the file.
+        Raises ValueError for any other shape or type, a non-finite value, or a size that is not the image's (`size` (width,
+        height) if the caller knows it, else the image file's if it is there, else the camera's resolution)."""
+        path = os.path.join(self.root, self.images_folder(), self.images[i].name)
+        map_path = os.path.splitext(path)[0] + suffix + ".npy"
+        if not os.path.isfile(map_path):
+            return None
+        if size is not None:
+            pass
+        elif os.path.isfile(path):
+            from PIL import Image
+            with Image.open(path) as img:
+                size = img.size
+        else:
+            size = self.resolution(self.cameras[self.images[i].camera_id])
+        m = np.load(map_path, allow_pickle=False)
+        if m.dtype.kind != "f" or m.ndim not in (2, 3):
+            raise ValueError(f"feature map {map_path}: a float array [K,H,W] or [H,W], got {m.dtype} {tuple(m.shape)}")
+        if m.ndim == 2:
+            m = m[None]
+        if not 1 <= m.shape[0] <= 64:
+            raise ValueError(f"feature map {map_path}: between 1 and 64 channels, got {m.shape[0]}")
+        if (m.shape[2], m.shape[1]) != tuple(size):
+            raise ValueError(f"feature map {map_path} is {m.shape[2]}x{m.shape[1]}, its image {size[0]}x{size[1]}")
+        if not np.isfinite(m).all():
+            raise ValueError(f"feature map {map_path} holds non-finite values")
+        return np.ascontiguousarray(m, dtype=np.float32)
+
     def _load_mask_file(self, i, suffix, size):
         path = os.path.join(self.root, self.images_folder(), self.images[i].name)
         mask_path = os.path.splitext(path)[0] + suffix + ".png"

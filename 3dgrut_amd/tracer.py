@@ -508,6 +508,37 @@ class SplatRaster:
                    ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), k, _ptr(attributes, n), out.data_ptr() if out.numel() else None)
         return out
 
+    def trace_attributes_bwd(self, frame_number, num_active_features, particle_density, out_grad, ray_ori, ray_dir, sensor_params,
+                             ts_start, ts_end, pose_start, pose_end, out=None):
+        """The gradient of trace_attributes' planes with respect to the attributes (gut_trace_attributes_bwd):
+        out_grad, a contiguous float32 [K,H,W] cotangent on the rays' GPU (K in 1..64, signed, a non-finite value counts as 0), summed
+        onto the Gaussians with the forward's weights into a float32 [N,K] tensor, every element written (`out`: a contiguous one to
+        write into; otherwise a fresh one).  The geometry gets no gradient.  Deterministic: identical inputs give identical bits.
+        Follows any forward on this handle, consumes nothing, and may be followed by any backward, contribution or attribute call.
+        Unsorted variant at kernel degree 2 only.  particle_density: the [N,12] rows of the forward, or an int N after a *_fields
+        forward."""
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
+        rows = None
+        if isinstance(particle_density, torch.Tensor):
+            n = int(particle_density.shape[0])
+            if n:
+                rows = _check_f32_cuda(particle_density, "particleDensity", (12,))
+        else:
+            n = int(particle_density)
+        if not (isinstance(out_grad, torch.Tensor) and out_grad.dtype == torch.float32 and out_grad.is_contiguous()
+                and out_grad.dim() == 3 and tuple(out_grad.shape[1:]) == (H, W) and out_grad.device == dev):
+            raise RuntimeError(f"[3dgut] attribute cotangent: a contiguous float32 tensor [K, {H}, {W}] on the rays' GPU")
+        k = int(out_grad.shape[0])
+        if out is None:
+            out = torch.empty((n, k), dtype=torch.float32, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.is_contiguous()
+                  and tuple(out.shape) == (n, k) and out.device == dev):
+            raise RuntimeError(f"[3dgut] attribute gradient: a contiguous float32 tensor [{n}, {k}] on the rays' GPU")
+        cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
+        self._call("trace_attributes_bwd", self._lib.gut_trace_attributes_bwd, dev, frame_number, int(num_active_features), n, _ptr(rows),
+                   W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), k, _ptr(out_grad, n), _ptr(out, n))
+        return out
+
     def set_regularisation(self, reg):
         """The NEXT optimiser step on the handle (optimize_rows_without_gradient + optimize_after_bwd, or
         finish_optimizer_step_without_gradient) adds the MCMC regularisers' gradient to every row it updates and writes the loss

@@ -64,6 +64,13 @@ have one are lifted to the Gaussians (the share of each Gaussian's drawn weight 
 scored by IoU against that view's own label mask where it has one.  With an output directory: selection.npy (bool [N]),
 selected.ply, rest.ply and renders_selection/.  The model is not changed.  One GPU only; threshold is untuned on real captures.
 
+`features.enabled` (default off; `--fit-features [SUFFIX]`) learns per-Gaussian features from 2-D maps with the model frozen
+(features.py), after train(), the compaction and the selection: the maps `<image stem><suffix>.npy` (float [K,H,W] or
+[H,W], at the view's training resolution) of the training views that have one are fitted by `iterations` Adam steps at rate `lr`,
+round-robin over those views, and every held-out view that has a map is scored by the same mean squared error.  With an output
+directory: features.npy (float32 [N,K]) and renders_features/<stem>.npy (the held-out views' rendered planes).  The model is not
+changed.  One GPU only; lr and iterations are UNTUNED on real captures.
+
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
                                  [--refine-poses [--pose-lr-translation X] [--pose-lr-rotation R]]
@@ -71,6 +78,7 @@ selected.ply, rest.ply and renders_selection/.  The model is not changed.  One G
                                  [--compact-to FRACTION [--compact-score weight_sum|max_weight] [--compact-finetune K]]
                                  [--densify-by gradient|error [--densify-grow-fraction F] [--densify-views K]]
                                  [--select-by-masks [SUFFIX] [--select-threshold T]]
+                                 [--fit-features [SUFFIX] [--feature-iterations K] [--feature-lr X]]
 """
 import argparse
 import copy
@@ -83,6 +91,7 @@ import numpy as np
 import torch
 
 from . import contribution as contribution_mod
+from . import features as features_mod
 from . import exposure as exposure_mod
 from . import losses, pose_align, pose_refine
 from . import selection as selection_mod
@@ -125,6 +134,10 @@ GS_CONFIG = {
     # (selection.py), after training and compaction; rendered into the held-out views and scored by IoU.  threshold is untuned on
     # real captures.
     "selection": dict(selection_mod.DEFAULTS),
+    # not a reference key: per-Gaussian features fitted to the training views' 2-D maps `<image stem><suffix>.npy` with the model
+    # frozen (features.py), after training, compaction and selection; scored on the held-out views' maps.  lr and iterations are
+    # untuned on real captures.
+    "features": dict(features_mod.DEFAULTS),
     "strategy": {"method": "GSStrategy",
                  # criterion and error are not reference keys: "error" grows, at every densify step, the grow_fraction of the rows
                  # that are responsible for the most rendering error over `views` training views (0: all of them), instead of
@@ -186,6 +199,7 @@ def resolve_config(conf):
     pose_align.check_config(out["pose_alignment"])
     contribution_mod.check_config(out["compaction"])
     selection_mod.check_config(out["selection"])
+    features_mod.check_config(out["features"])
     check_densify_config(out)
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
@@ -422,6 +436,8 @@ class Trainer:
             raise ValueError("compaction: data-parallel compaction is out of scope (the stepper's world_size must be 1)")
         if c["selection"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
             raise ValueError("selection: data-parallel selection is out of scope (the stepper's world_size must be 1)")
+        if c["features"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
+            raise ValueError("features: data-parallel feature fitting is out of scope (the stepper's world_size must be 1)")
         self.densify_criterion = (c["strategy"].get("densify") or {}).get("criterion", "gradient")
         if self.densify_criterion == "error":
             if int(getattr(stepper, "world_size", 1)) > 1:
@@ -795,14 +811,55 @@ class Trainer:
         self.stats.update(out)
         return out
 
+    def fit_features(self):
+        """The `features` block, after train(), compact() and select_by_masks(): fits per-Gaussian features to the maps of the
+        training views that carry one (batch.feature_map [K,H,W], at their refined poses) with the model frozen and scores them on
+        the held-out views that carry one.  Writes features.npy and renders_features/<stem>.npy into the output directory when
+        there is one.  Fills and returns the features_* statistics; the model is left as it is."""
+        from .attributes import AttributeRenderer
+        blk = self.conf["features"]
+        mapped = [v for v in range(len(self.train_batches)) if getattr(self.train_batches[v], "feature_map", None) is not None]
+        if not mapped:
+            raise ValueError(f"features: no training view has a target map (<image stem>{blk['suffix']}.npy next to its image)")
+        targets = [self.train_batches[v].feature_map for v in mapped]
+        channels = int(targets[0].shape[0])
+        for v, t in zip(mapped, targets):
+            if int(t.shape[0]) != channels:
+                raise ValueError(f"features: the map of training view {v} has {int(t.shape[0])} channels, the first one {channels}")
+        batches = [self.train_batches[v] if self.refiner is None else self.refiner.begin(v, self.train_batches[v]) for v in mapped]
+        renderer = AttributeRenderer(self.model, self.tracer)
+        feats = features_mod.fit_features(renderer, batches, targets, channels, int(blk["iterations"]), float(blk["lr"]))
+        train_mse = features_mod.score_features(renderer, batches, targets, feats)
+        held = [i for i, b in enumerate(self.test_batches) if getattr(b, "feature_map", None) is not None]
+        for i in held:
+            if int(self.test_batches[i].feature_map.shape[0]) != channels:
+                raise ValueError(f"features: the map of held-out view {i} has {int(self.test_batches[i].feature_map.shape[0])} "
+                                 f"channels, the training views' {channels}")
+        held_mse = features_mod.score_features(renderer, [self.test_batches[i] for i in held],
+                                               [self.test_batches[i].feature_map for i in held], feats) if held else None
+        out_dir = self._out_dir()
+        if out_dir is not None:
+            renders = os.path.join(out_dir, "renders_features")
+            os.makedirs(renders, exist_ok=True)
+            np.save(os.path.join(out_dir, "features.npy"), feats.cpu().numpy())
+            for i, batch in enumerate(self.test_batches):
+                stem = getattr(batch, "image_stem", None) or f"{i:05d}"
+                np.save(os.path.join(renders, stem + ".npy"), renderer.render(batch, feats).cpu().numpy())
+        out = dict(features_channels=channels, features_n_views_fitted=len(mapped), features_train_mse=float(train_mse.mean()),
+                   features_heldout_mse=None if held_mse is None else float(held_mse.mean()))
+        self.stats.update(out)
+        return out
+
     def run(self):
-        """train(), (compaction.enabled) compact(), (selection.enabled) select_by_masks(), print the statistics table, then
-        (test_last) save ckpt_last.pt and evaluate the test split."""
+        """train(), (compaction.enabled) compact(), (selection.enabled) select_by_masks(), (features.enabled) fit_features(), print
+        the statistics table, then (test_last) save ckpt_last.pt and evaluate the test split."""
         stats = self.train()
         if self.conf["compaction"]["enabled"]:
             self.compact()
         if self.conf["selection"]["enabled"]:
             self.select_by_masks()
+        if self.conf["features"]["enabled"]:
+            self.fit_features()
         print("Training Statistics: " + json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in stats.items()}), flush=True)
         if self.conf["test_last"] and self.test_batches:
             self.save_checkpoint(last=True)
@@ -848,6 +905,11 @@ def build_parser():
                          "_object), render the selection into the held-out views and score its IoU (selection.enabled, "
                          "selection.mask_suffix)")
     ap.add_argument("--select-threshold", type=float, default=None, metavar="T", help="selection.threshold")
+    ap.add_argument("--fit-features", nargs="?", const=features_mod.DEFAULTS["suffix"], default=None, metavar="SUFFIX",
+                    help="after training, fit per-Gaussian features to the views' maps <image stem>SUFFIX.npy (default _features) with "
+                         "the model frozen and score them on the held-out views' maps (features.enabled, features.suffix)")
+    ap.add_argument("--feature-iterations", type=int, default=None, metavar="K", help="features.iterations (untuned on real captures)")
+    ap.add_argument("--feature-lr", type=float, default=None, metavar="X", help="features.lr (untuned on real captures)")
     ap.add_argument("--densify-by", choices=("gradient", "error"), default=None,
                     help="strategy.densify.criterion: error = grow the rows responsible for the most rendering error (default: gradient)")
     ap.add_argument("--densify-grow-fraction", type=float, default=None, metavar="F", help="strategy.densify.error.grow_fraction")
@@ -890,6 +952,13 @@ def config_from_args(a):
         conf["selection"]["mask_suffix"] = a.select_by_masks
     if a.select_threshold is not None:
         conf["selection"]["threshold"] = a.select_threshold
+    if a.fit_features is not None:
+        conf["features"]["enabled"] = True
+        conf["features"]["suffix"] = a.fit_features
+    if a.feature_iterations is not None:
+        conf["features"]["iterations"] = a.feature_iterations
+    if a.feature_lr is not None:
+        conf["features"]["lr"] = a.feature_lr
     densify = {}
     if a.densify_by is not None:
         densify["criterion"] = a.densify_by
@@ -918,6 +987,12 @@ def main(argv=None):
             for i, b in enumerate(batches):
                 label = scene.load_label_mask(i, conf["selection"]["mask_suffix"])
                 b.label_mask = None if label is None else torch.as_tensor(label[0, :, :, 0], device=b.rays_ori.device)
+    if conf["features"]["enabled"]:       # the views' target maps, where the files are there
+        for scene, batches in ((train, tb), (test, vb)):
+            for i, b in enumerate(batches):
+                fmap = scene.load_feature_map(i, conf["features"]["suffix"], size=(int(b.rays_ori.shape[2]), int(b.rays_ori.shape[1])))
+                b.feature_map = None if fmap is None else torch.as_tensor(fmap, device=b.rays_ori.device)
+                b.image_stem = os.path.splitext(os.path.basename(scene.images[i].name))[0]
     trainer = Trainer(conf, init, tb, val_batches=vb, test_batches=vb, scene_extent=train.cameras_extent)
     res = trainer.run()
     test_res = res["test"]

@@ -49,7 +49,8 @@ extern "C" {
  * the descriptor form of the fused loss: the four positional forms keep their signatures and call it; GutContribution and
  * gut_trace_contribution, a new entry point: every other call queues what it queued before; gut_trace_contribution_weighted and
  * gut_pixel_error, new entry points: gut_trace_contribution and every other call queue what they queued before; added under 6
- * without a bump: gut_trace_attributes, a new entry point: every other call queues what it queued before). */
+ * without a bump: gut_trace_attributes, a new entry point: every other call queues what it queued before; gut_trace_attributes_bwd,
+ * likewise). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -728,6 +729,26 @@ int gut_trace_attributes(gut_handle h, void* stream, uint32_t frame_number, int3
                          const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
                          int32_t num_channels /* 1..64 */, const float* d_attributes /* [N, num_channels] row-major */,
                          float* d_out /* [num_channels, H, W], fully written */);
+
+/* ---- The gradient of rendered attributes with respect to the attributes (new functionality) ----
+ * gut_trace_attributes_bwd is the adjoint of gut_trace_attributes: for a cotangent d_out_grad [K,H,W] of the planes,
+ *     d_attributes_grad[i][k] = sum over the pixels in which the forward composited Gaussian i of w * d_out_grad[k][pixel],
+ * with the forward's blending weights w, signed and without a clamp (the exact adjoint, where gut_trace_contribution_weighted is the
+ * adjoint for planes in [0, 1] only).  The geometry gets no gradient.  Scope, walk and refusals are gut_trace_contribution's; it
+ * consumes nothing and may be followed by any backward, contribution or attribute call.  Four channels per walk.  A non-finite
+ * cotangent value counts as 0.  The sums are formed in a fixed order per tile and added across tiles as 64-bit integers in units of
+ * 2^-s_k, s_k a power-of-two exponent taken per channel from the plane's largest |value| (unit: at most 2^-39 of it): identical
+ * inputs give identical bytes whatever the order in which tiles run, a channel does not depend on the other channels of the call,
+ * a negated cotangent gives the negated gradient and a cotangent scaled by a power of two the scaled gradient.  Every element of
+ * d_attributes_grad is written, 0 for rows nobody composited; with num_particles == 0 or a forward without intersections it is
+ * zero-filled by one memset and nothing is walked.  Per group of four channels: two memsets (32 bytes per Gaussian of handle
+ * scratch), a reduction of the planes, the walk and one pass over the rows.  Additionally refused, on the host before anything is
+ * queued: num_channels outside 1..64; d_out_grad or d_attributes_grad NULL with num_particles > 0, or not 4-byte aligned. */
+int gut_trace_attributes_bwd(gut_handle h, void* stream, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+                             const float* d_particle_density /* NULL: the packed rows */, int32_t width, int32_t height,
+                             const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
+                             int32_t num_channels /* 1..64 */, const float* d_out_grad /* [num_channels, H, W] */,
+                             float* d_attributes_grad /* [N, num_channels] row-major, fully written */);
 
 /* ---- Per-view exposure in the fused loss (new functionality, the reference has none) ----
  * gut_photometric_loss_exposure is the fused loss of gut_photometric_loss[_masked | _background] on the AFFINE image of a view:
