@@ -968,29 +968,75 @@ int trace_bwd_packed(gut_handle h, const char* name, const char* forwards, const
                                                d_particle_radiance_grad, f});
 }
 
-// what gut_trace_attributes adds to the contribution call
-struct AttributeArgs {
+// The forms of the contribution walk (trace_walk_impl below): what each adds to the call.  check: the form's own refusals, `name` the
+// entry point; nothing_walked: what the form owes its caller when the forward walked nothing; scratch: the handle's scratch the
+// form needs; launch: the form on the walk's operands.
+struct ScoreForm {   // gut_trace_contribution and, with weighted, gut_trace_contribution_weighted (§14: scores optional)
+    GutContribution* scores;
+    bool weighted;
+    const float* pixel_weight;
+    uint64_t* weighted_q32;
+    int check(const char* name, const TraceView& view) const {
+        if (view.n && !scores && !weighted) return fail("%s: d_scores is NULL with %u particles", name, view.n);
+        if (((uintptr_t)scores & 7u) != 0) return fail("%s: d_scores must be 8-byte aligned", name);
+        if (weighted) {
+            if (!pixel_weight) return fail("%s: d_pixel_weight is NULL", name);
+            if (view.n && !weighted_q32) return fail("%s: d_weighted_q32 is NULL with %u particles", name, view.n);
+            if (view.n && ((uintptr_t)weighted_q32 & 7u) != 0) return fail("%s: d_weighted_q32 must be 8-byte aligned", name);
+        }
+        return 0;
+    }
+    hipError_t nothing_walked(gut_handle, const TraceView&) const { return hipSuccess; }   // (the arrays accumulate)
+    hipError_t scratch(gut_handle) const { return hipSuccess; }
+    void launch(gut_handle, hipStream_t s, const gut::WalkOperands& o) const {
+        gut::launch_contribution(s, o, scores, weighted ? pixel_weight : nullptr, weighted_q32);
+    }
+};
+struct AttributeForm {   // gut_trace_attributes: rows [N, channels] -> out [channels, H, W], every element written
     int32_t channels;
     const float* rows;
     float* out;
+    int check(const char* name, const TraceView& view) const {
+        if (channels < 1 || channels > 64) return fail("%s: num_channels must be in 1..64, got %d", name, channels);
+        if (view.n && !rows) return fail("%s: d_attributes is NULL with %u particles", name, view.n);
+        if (!out) return fail("%s: d_out is NULL", name);
+        if (((uintptr_t)out & 3u) != 0) return fail("%s: d_out must be 4-byte aligned", name);
+        return 0;
+    }
+    hipError_t nothing_walked(gut_handle, const TraceView& view) const {
+        return hipMemsetAsync(out, 0, sizeof(float) * (size_t)channels * (size_t)view.width * (size_t)view.height, view.stream);
+    }
+    hipError_t scratch(gut_handle) const { return hipSuccess; }
+    void launch(gut_handle, hipStream_t s, const gut::WalkOperands& o) const { gut::launch_attributes(s, o, (uint32_t)channels, rows, out); }
 };
-// what gut_trace_attributes_bwd adds to it
-struct AttributeGradArgs {
+struct AttributeGradForm {   // gut_trace_attributes_bwd: out_grad [channels, H, W] -> rows_grad [N, channels], every element written
     int32_t channels;
     const float* out_grad;
     float* rows_grad;
+    int check(const char* name, const TraceView& view) const {
+        if (channels < 1 || channels > 64) return fail("%s: num_channels must be in 1..64, got %d", name, channels);
+        if (view.n && !out_grad) return fail("%s: d_out_grad is NULL with %u particles", name, view.n);
+        if (view.n && !rows_grad) return fail("%s: d_attributes_grad is NULL with %u particles", name, view.n);
+        if (((uintptr_t)out_grad & 3u) != 0) return fail("%s: d_out_grad must be 4-byte aligned", name);
+        if (((uintptr_t)rows_grad & 3u) != 0) return fail("%s: d_attributes_grad must be 4-byte aligned", name);
+        return 0;
+    }
+    hipError_t nothing_walked(gut_handle h, const TraceView& view) const {
+        return h->n ? hipMemsetAsync(rows_grad, 0, sizeof(float) * (size_t)channels * (size_t)h->n, view.stream) : hipSuccess;
+    }
+    hipError_t scratch(gut_handle h) const {
+        const hipError_t e = h->attr_grad_rows.ensure(4 * sizeof(int64_t) * (size_t)h->n);
+        return e != hipSuccess ? e : h->attr_grad_max.ensure(4 * sizeof(uint32_t));
+    }
+    void launch(gut_handle h, hipStream_t s, const gut::WalkOperands& o) const {
+        gut::launch_attributes_bwd(s, o, (uint32_t)channels, out_grad, rows_grad, h->attr_grad_rows.p, h->attr_grad_max.as<uint32_t>());
+    }
 };
 
-// The contribution scores of the cached forward's view: the forward's walk once more, without colours, into the
-// caller's accumulating arrays.  Reads the forward's lists and depths, writes tile_order (every backward rebuilds it) and d_scores /
-// d_weighted_q32.  weighted: the form with a per-pixel plane (gut_trace_contribution_weighted), whose records are optional.
-// attr (gut_trace_attributes): the walk renders attr->rows [N, channels] into attr->out [channels, H, W] instead and
-// the three accumulating arrays are unused.
-// attr_grad (gut_trace_attributes_bwd): the adjoint of that, attr_grad->out_grad [channels, H, W] summed onto the rows
-// attr_grad->rows_grad [N, channels], every element written; the accumulating arrays are unused as well.
-int trace_contribution_impl(gut_handle h, const char* name, const TraceView& view, const float* d_particle_density,
-                            GutContribution* d_scores, bool weighted, const float* d_pixel_weight, uint64_t* d_weighted_q32,
-                            const AttributeArgs* attr = nullptr, const AttributeGradArgs* attr_grad = nullptr) {
+// The forward's walk once more over the cached forward's view, without colours, in the form `form`.  Reads the
+// forward's lists and depths, writes tile_order (every backward rebuilds it) and what the form writes.
+template <class Form>
+int trace_walk_impl(gut_handle h, const char* name, const TraceView& view, const float* d_particle_density, const Form& form) {
     if (!h) return fail("%s: null handle", name);
     std::lock_guard<std::mutex> lock(h->mu);
     if (h->cfg.k_buffer_size > 0 || h->cfg.particle_kernel_degree != 2)
@@ -1003,27 +1049,7 @@ int trace_contribution_impl(gut_handle h, const char* name, const TraceView& vie
             return fail("%s: d_particle_density is NULL and the last forward on this handle packed no rows (not a *_fields one)", name);
         d_particle_density = h->packed12.as<float>();
     }
-    if (attr) {
-        if (attr->channels < 1 || attr->channels > 64) return fail("%s: num_channels must be in 1..64, got %d", name, attr->channels);
-        if (view.n && !attr->rows) return fail("%s: d_attributes is NULL with %u particles", name, view.n);
-        if (!attr->out) return fail("%s: d_out is NULL", name);
-        if (((uintptr_t)attr->out & 3u) != 0) return fail("%s: d_out must be 4-byte aligned", name);
-    }
-    if (attr_grad) {
-        if (attr_grad->channels < 1 || attr_grad->channels > 64)
-            return fail("%s: num_channels must be in 1..64, got %d", name, attr_grad->channels);
-        if (view.n && !attr_grad->out_grad) return fail("%s: d_out_grad is NULL with %u particles", name, view.n);
-        if (view.n && !attr_grad->rows_grad) return fail("%s: d_attributes_grad is NULL with %u particles", name, view.n);
-        if (((uintptr_t)attr_grad->out_grad & 3u) != 0) return fail("%s: d_out_grad must be 4-byte aligned", name);
-        if (((uintptr_t)attr_grad->rows_grad & 3u) != 0) return fail("%s: d_attributes_grad must be 4-byte aligned", name);
-    }
-    if (view.n && !d_scores && !weighted && !attr && !attr_grad) return fail("%s: d_scores is NULL with %u particles", name, view.n);
-    if (((uintptr_t)d_scores & 7u) != 0) return fail("%s: d_scores must be 8-byte aligned", name);
-    if (weighted) {
-        if (!d_pixel_weight) return fail("%s: d_pixel_weight is NULL", name);
-        if (view.n && !d_weighted_q32) return fail("%s: d_weighted_q32 is NULL with %u particles", name, view.n);
-        if (view.n && ((uintptr_t)d_weighted_q32 & 7u) != 0) return fail("%s: d_weighted_q32 must be 8-byte aligned", name);
-    }
+    if (form.check(name, view)) return 1;
     if (h->early_ran)
         return fail("%s: gut_optimize_rows_without_gradient was called for this forward: that optimiser step is half applied "
                     "(gut_trace_bwd_ex(..., GUT_BWD_SKIP_EPILOGUE) and gut_optimize_after_bwd come first)", name);
@@ -1033,33 +1059,15 @@ int trace_contribution_impl(gut_handle h, const char* name, const TraceView& vie
     if (check_same_camera(h, view, name, &v)) return 1;
     const hipStream_t s = view.stream;
     if (h->n == 0 || h->m == 0) {   // nothing was walked
-        if (attr) HIP_TRY(hipMemsetAsync(attr->out, 0, sizeof(float) * (size_t)attr->channels * (size_t)view.width * (size_t)view.height, s));
-        if (attr_grad && h->n) HIP_TRY(hipMemsetAsync(attr_grad->rows_grad, 0, sizeof(float) * (size_t)attr_grad->channels * (size_t)h->n, s));
+        HIP_TRY(form.nothing_walked(h, view));
         return 0;
     }
-    if (attr_grad) {
-        HIP_TRY(h->attr_grad_rows.ensure(4 * sizeof(int64_t) * (size_t)h->n));
-        HIP_TRY(h->attr_grad_max.ensure(4 * sizeof(uint32_t)));
-    }
+    HIP_TRY(form.scratch(h));
     gut::launch_tile_order(s, (uint32_t)h->tiles, h->trav_fwd.as<uint32_t>(), h->tile_order.as<uint32_t>());
-    if (attr) {
-        gut::launch_attributes(s, v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
-                               (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
-                               h->trav_fwd.as<uint32_t>(), h->n, (uint32_t)attr->channels, attr->rows, attr->out);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    if (attr_grad) {
-        gut::launch_attributes_bwd(s, v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
-                                   (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
-                                   h->trav_fwd.as<uint32_t>(), h->n, (uint32_t)attr_grad->channels, attr_grad->out_grad,
-                                   attr_grad->rows_grad, h->attr_grad_rows.p, h->attr_grad_max.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    gut::launch_contribution(s, v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
-                             (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
-                             h->trav_fwd.as<uint32_t>(), h->n, d_scores, weighted ? d_pixel_weight : nullptr, d_weighted_q32);
+    const gut::WalkOperands o{v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
+                              (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
+                              h->trav_fwd.as<uint32_t>(), h->n, (uint32_t)(v.grid_x * v.grid_y)};
+    form.launch(h, s, o);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1125,38 +1133,36 @@ int gut_trace_bwd_pose(gut_handle h, void* stream_, uint32_t frame_number, int32
 int gut_trace_contribution(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
                            const float* d_particle_density, int32_t width, int32_t height, const float* d_ray_origin,
                            const float* d_ray_direction, const GutCamera* camera, GutContribution* d_scores) {
-    return trace_contribution_impl(h, "gut_trace_contribution",
-                                   view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
-                                   d_particle_density, d_scores, false, nullptr, nullptr);
+    return trace_walk_impl(h, "gut_trace_contribution",
+                           view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                           d_particle_density, ScoreForm{d_scores, false, nullptr, nullptr});
 }
 
 int gut_trace_contribution_weighted(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features,
                                     uint32_t num_particles, const float* d_particle_density, int32_t width, int32_t height,
                                     const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
                                     const float* d_pixel_weight, GutContribution* d_scores, uint64_t* d_weighted_q32) {
-    return trace_contribution_impl(h, "gut_trace_contribution_weighted",
-                                   view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
-                                   d_particle_density, d_scores, true, d_pixel_weight, d_weighted_q32);
+    return trace_walk_impl(h, "gut_trace_contribution_weighted",
+                           view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                           d_particle_density, ScoreForm{d_scores, true, d_pixel_weight, d_weighted_q32});
 }
 
 int gut_trace_attributes(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
                          const float* d_particle_density, int32_t width, int32_t height, const float* d_ray_origin,
                          const float* d_ray_direction, const GutCamera* camera, int32_t num_channels, const float* d_attributes,
                          float* d_out) {
-    const AttributeArgs attr{num_channels, d_attributes, d_out};
-    return trace_contribution_impl(h, "gut_trace_attributes",
-                                   view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
-                                   d_particle_density, nullptr, false, nullptr, nullptr, &attr);
+    return trace_walk_impl(h, "gut_trace_attributes",
+                           view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                           d_particle_density, AttributeForm{num_channels, d_attributes, d_out});
 }
 
 int gut_trace_attributes_bwd(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
                              const float* d_particle_density, int32_t width, int32_t height, const float* d_ray_origin,
                              const float* d_ray_direction, const GutCamera* camera, int32_t num_channels, const float* d_out_grad,
                              float* d_attributes_grad) {
-    const AttributeGradArgs grad{num_channels, d_out_grad, d_attributes_grad};
-    return trace_contribution_impl(h, "gut_trace_attributes_bwd",
-                                   view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
-                                   d_particle_density, nullptr, false, nullptr, nullptr, nullptr, &grad);
+    return trace_walk_impl(h, "gut_trace_attributes_bwd",
+                           view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                           d_particle_density, AttributeGradForm{num_channels, d_out_grad, d_attributes_grad});
 }
 
 // SplatRaster::trace with the four activated tensors the reference's Tracer hands to _Autograd (tracer.py:317-327) instead of

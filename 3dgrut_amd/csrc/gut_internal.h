@@ -221,27 +221,34 @@ void launch_render_bwd_general(hipStream_t s, const ViewParams& v, const RenderC
                                uint32_t* tile_traversed, const uint32_t* tile_order, const uint32_t* tile_walked, int kernel_degree);
 void launch_tile_order(hipStream_t s, uint32_t tiles, const uint32_t* traversed, uint32_t* order, const uint32_t* ranges = nullptr,
                        bool by_length = false, uint32_t* walk_sums = nullptr);
-// gut_contrib.hip: the forward's walk again (unsorted variant, kernel degree 2), without colours; adds every walked Gaussian's sum and
-// maximum of blending weights and its composited-pixel count to scores [N] (integer atomics).  ordered_ids: the list the backward
-// compositor reads; tile_order: a launch order of all the tiles (required); tile_walked: the forward's per-tile traversal depth.
+// gut_contrib.hip: the forward's walk again (unsorted variant, kernel degree 2), without colours.  What every form of
+// the walk reads, built once per call (gut_api.cpp) and passed to the kernel by value
+struct WalkOperands {
+    ViewParams v;
+    RenderConsts c;
+    const float* density12;
+    const float* ray_ori;
+    const float* ray_dir;
+    const uint32_t* ranges;
+    const uint32_t* ordered_ids;   // the list the backward compositor reads
+    const uint32_t* tile_order;    // a launch order of all the tiles (required)
+    const uint32_t* tile_walked;   // the forward's per-tile traversal depth
+    uint32_t num_particles;
+    uint32_t tiles;                // v.grid_x * v.grid_y: one workgroup each
+};
+// adds every walked Gaussian's sum and maximum of blending weights and its composited-pixel count to scores [N] (integer atomics).
 // plane [H,W] (null: the records alone): every weight is also multiplied by the pixel's value clamped to [0, 1] and summed into
 // weighted_q32 [N]; with a plane, scores may be null (the weighted sums alone)
-void launch_contribution(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
-                         const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
-                         const uint32_t* tile_walked, uint32_t num_particles, GutContribution* scores, const float* plane = nullptr,
+void launch_contribution(hipStream_t s, const WalkOperands& o, GutContribution* scores, const float* plane = nullptr,
                          uint64_t* weighted_q32 = nullptr);
 // the same walk rendering per-Gaussian attributes: attrs [N, num_channels] row-major -> out [num_channels, H, W], every
 // element written; one launch per group of four channels
-void launch_attributes(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
-                       const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
-                       const uint32_t* tile_walked, uint32_t num_particles, uint32_t num_channels, const float* attrs, float* out);
+void launch_attributes(hipStream_t s, const WalkOperands& o, uint32_t num_channels, const float* attrs, float* out);
 // the adjoint of launch_attributes: out_grad [num_channels, H, W] -> attrs_grad [N, num_channels] row-major, every
 // element written; per group of four channels the planes' maxima, one walk and one pass over the rows.  rows_q: scratch of
 // 32 bytes per particle; max_bits: scratch of four words
-void launch_attributes_bwd(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* ray_ori,
-                           const float* ray_dir, const uint32_t* ranges, const uint32_t* ordered_ids, const uint32_t* tile_order,
-                           const uint32_t* tile_walked, uint32_t num_particles, uint32_t num_channels, const float* out_grad,
-                           float* attrs_grad, void* rows_q, uint32_t* max_bits);
+void launch_attributes_bwd(hipStream_t s, const WalkOperands& o, uint32_t num_channels, const float* out_grad, float* attrs_grad,
+                           void* rows_q, uint32_t* max_bits);
 // sorted (k_buffer_size > 0) compositor variant, gut_render_sorted.hip
 void launch_render_sorted(hipStream_t s, const ViewParams& v, const RenderConsts& c, int K, const float* density12, const float* feat,
                           const float* ray_ori, const float* ray_dir, const uint32_t* ranges, const uint32_t* sorted_ids,

@@ -92,25 +92,13 @@ __device__ __forceinline__ const PackEntry& stage_at(const PackEntry* stage, uin
     return *reinterpret_cast<const PackEntry*>(reinterpret_cast<const char*>(stage) + __umul24(j, (uint32_t)sizeof(PackEntry)));
 }
 
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int moved = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), kCtrl, kRowMask, 0xF, true);
-    return v + __builtin_bit_cast(float, moved);
-}
-
 // sum over the 64 lanes of the wave; the total ends up in lane 63
 __device__ __forceinline__ float wave_sum_lane63(float v) {
 #ifdef GUT_REDUCE_SHFL
     for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
     return v;
 #else
-    v = dpp_add<0x111, 0xF>(v);  // row_shr:1
-    v = dpp_add<0x112, 0xF>(v);  // row_shr:2
-    v = dpp_add<0x114, 0xF>(v);  // row_shr:4
-    v = dpp_add<0x118, 0xF>(v);  // row_shr:8   -> lane 15 of every row holds the row total
-    v = dpp_add<0x142, 0xA>(v);  // row_bcast:15 into rows 1 and 3
-    v = dpp_add<0x143, 0xC>(v);  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave total
-    return v;
+    return dpp_wave_sum_lane63(v);
 #endif
 }
 

@@ -40,6 +40,38 @@ __device__ __forceinline__ float kernel_response_grad(int degree, float d2, floa
     default: return -0.5f * resp * g_resp;
     }
 }
+// Sum / maximum over the 64 lanes of the wave in a FIXED tree (the lane pairing of every step is fixed); the result ends up in lane 63.
+// The contribution walk (gut_contrib.hip) calls these forms directly and must never take a shuffle form: the summation order is part
+// of its contract.
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ float dpp_add(float v) {
+    const int moved = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), kCtrl, kRowMask, 0xF, true);
+    return v + __builtin_bit_cast(float, moved);
+}
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ float dpp_max(float v) {   // v >= 0: the 0 a lane without a source reads is neutral
+    const int moved = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), kCtrl, kRowMask, 0xF, true);
+    return fmaxf(v, __builtin_bit_cast(float, moved));
+}
+__device__ __forceinline__ float dpp_wave_sum_lane63(float v) {
+    v = dpp_add<0x111, 0xF>(v);  // row_shr:1
+    v = dpp_add<0x112, 0xF>(v);  // row_shr:2
+    v = dpp_add<0x114, 0xF>(v);  // row_shr:4
+    v = dpp_add<0x118, 0xF>(v);  // row_shr:8   -> lane 15 of every row holds the row total
+    v = dpp_add<0x142, 0xA>(v);  // row_bcast:15 into rows 1 and 3
+    v = dpp_add<0x143, 0xC>(v);  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave total
+    return v;
+}
+__device__ __forceinline__ float dpp_wave_max_lane63(float v) {
+    v = dpp_max<0x111, 0xF>(v);
+    v = dpp_max<0x112, 0xF>(v);
+    v = dpp_max<0x114, 0xF>(v);
+    v = dpp_max<0x118, 0xF>(v);
+    v = dpp_max<0x142, 0xA>(v);
+    v = dpp_max<0x143, 0xC>(v);
+    return v;
+}
+
 struct RayState {
     float ox, oy, oz, dx, dy, dz, tmin, tmax;
     float ex, ey, ez;  // ray origin minus the sensor position (all zero for pinhole / fisheye rays)

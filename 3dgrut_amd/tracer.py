@@ -180,6 +180,23 @@ def _ptr(t, n=1):
     return t.data_ptr() if (n and t is not None) else None
 
 
+def _density_rows(particle_density):
+    """(rows, n) of a call that follows a forward: particle_density is the [N,12] rows of that forward (rows: checked, None for
+    N == 0), or an int N after a *_fields forward (rows: None, the library reads the rows that forward packed)."""
+    if not isinstance(particle_density, torch.Tensor):
+        return None, int(particle_density)
+    n = int(particle_density.shape[0])
+    return (_check_f32_cuda(particle_density, "particleDensity", (12,)) if n else None), n
+
+
+def _require_tensor(t, dtype, shape, dev, text):
+    """t, if it is a contiguous `dtype` tensor of `shape` (None: any extent) on the device `dev`; RuntimeError(text) otherwise."""
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.dim() == len(shape)
+            and all(want is None or have == want for have, want in zip(t.shape, shape)) and t.device == dev):
+        raise RuntimeError(text)
+    return t
+
+
 _F32P = C.POINTER(C.c_float)
 
 
@@ -430,13 +447,7 @@ class SplatRaster:
         particle_density: the [N,12] rows of the forward, or an int N after a *_fields forward (the rows that forward packed)."""
         ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
         rgba, rgba_g, dist, dist_g = self._upstream(ray_radiance_density, ray_radiance_density_grd, ray_hit_distance, ray_hit_distance_grd)
-        rows = None
-        if isinstance(particle_density, torch.Tensor):
-            n = int(particle_density.shape[0])
-            if n:
-                rows = _check_f32_cuda(particle_density, "particleDensity", (12,))
-        else:
-            n = int(particle_density)
+        rows, n = _density_rows(particle_density)
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
         self._call("trace_bwd_pose", self._lib.gut_trace_bwd_pose, dev, frame_number, int(num_active_features), n, _ptr(rows), W, H,
                    ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), rgba.data_ptr(), rgba_g.data_ptr(), dist.data_ptr(), _ptr(dist_g))
@@ -452,29 +463,18 @@ class SplatRaster:
         GPU, clamped to [0, 1] by the kernel, and an int64 [N] tensor the caller zeroed once, which receives the sum of weight x
         plane in units of 2^-32; `scores` may then be None (the weighted sums alone)."""
         ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
-        rows = None
-        if isinstance(particle_density, torch.Tensor):
-            n = int(particle_density.shape[0])
-            if n:
-                rows = _check_f32_cuda(particle_density, "particleDensity", (12,))
-        else:
-            n = int(particle_density)
+        rows, n = _density_rows(particle_density)
         with_plane = pixel_weight is not None or weighted is not None
-        if not (scores is None and with_plane) and not (
-                isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.int64 and scores.is_contiguous()
-                and tuple(scores.shape) == (n, 2) and scores.device == dev):
-            raise RuntimeError(f"[3dgut] contribution scores: a contiguous int64 tensor [{n}, 2] on the rays' GPU")
+        if not (scores is None and with_plane):
+            _require_tensor(scores, torch.int64, (n, 2), dev, f"[3dgut] contribution scores: a contiguous int64 tensor [{n}, 2] on the rays' GPU")
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
         if not with_plane:
             self._call("trace_contribution", self._lib.gut_trace_contribution, dev, frame_number, int(num_active_features), n, _ptr(rows),
                        W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), _ptr(scores, n))
             return
-        if not (isinstance(pixel_weight, torch.Tensor) and pixel_weight.dtype == torch.float32 and pixel_weight.is_contiguous()
-                and tuple(pixel_weight.shape) == (H, W) and pixel_weight.device == dev):
-            raise RuntimeError(f"[3dgut] contribution pixel weight: a contiguous float32 tensor [{H}, {W}] on the rays' GPU")
-        if not (isinstance(weighted, torch.Tensor) and weighted.dtype == torch.int64 and weighted.is_contiguous()
-                and tuple(weighted.shape) == (n,) and weighted.device == dev):
-            raise RuntimeError(f"[3dgut] weighted contribution: a contiguous int64 tensor [{n}] on the rays' GPU")
+        _require_tensor(pixel_weight, torch.float32, (H, W), dev,
+                        f"[3dgut] contribution pixel weight: a contiguous float32 tensor [{H}, {W}] on the rays' GPU")
+        _require_tensor(weighted, torch.int64, (n,), dev, f"[3dgut] weighted contribution: a contiguous int64 tensor [{n}] on the rays' GPU")
         self._call("trace_contribution_weighted", self._lib.gut_trace_contribution_weighted, dev, frame_number, int(num_active_features),
                    n, _ptr(rows), W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), pixel_weight.data_ptr(),
                    _ptr(scores, n) if scores is not None else None, _ptr(weighted, n))
@@ -487,22 +487,14 @@ class SplatRaster:
         handle, consumes nothing, and may be followed by any backward, contribution or attribute call.  Unsorted variant at kernel
         degree 2 only.  particle_density: the [N,12] rows of the forward, or an int N after a *_fields forward."""
         ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
-        rows = None
-        if isinstance(particle_density, torch.Tensor):
-            n = int(particle_density.shape[0])
-            if n:
-                rows = _check_f32_cuda(particle_density, "particleDensity", (12,))
-        else:
-            n = int(particle_density)
-        if not (isinstance(attributes, torch.Tensor) and attributes.dtype == torch.float32 and attributes.is_contiguous()
-                and attributes.dim() == 2 and attributes.shape[0] == n and attributes.device == dev):
-            raise RuntimeError(f"[3dgut] attributes: a contiguous float32 tensor [{n}, K] on the rays' GPU")
+        rows, n = _density_rows(particle_density)
+        _require_tensor(attributes, torch.float32, (n, None), dev, f"[3dgut] attributes: a contiguous float32 tensor [{n}, K] on the rays' GPU")
         k = int(attributes.shape[1])
         if out is None:
             out = torch.empty((k, H, W), dtype=torch.float32, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.is_contiguous()
-                  and tuple(out.shape) == (k, H, W) and out.device == dev):
-            raise RuntimeError(f"[3dgut] attribute output: a contiguous float32 tensor [{k}, {H}, {W}] on the rays' GPU")
+        else:
+            _require_tensor(out, torch.float32, (k, H, W), dev,
+                            f"[3dgut] attribute output: a contiguous float32 tensor [{k}, {H}, {W}] on the rays' GPU")
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
         self._call("trace_attributes", self._lib.gut_trace_attributes, dev, frame_number, int(num_active_features), n, _ptr(rows), W, H,
                    ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), k, _ptr(attributes, n), out.data_ptr() if out.numel() else None)
@@ -518,22 +510,14 @@ class SplatRaster:
         Unsorted variant at kernel degree 2 only.  particle_density: the [N,12] rows of the forward, or an int N after a *_fields
         forward."""
         ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
-        rows = None
-        if isinstance(particle_density, torch.Tensor):
-            n = int(particle_density.shape[0])
-            if n:
-                rows = _check_f32_cuda(particle_density, "particleDensity", (12,))
-        else:
-            n = int(particle_density)
-        if not (isinstance(out_grad, torch.Tensor) and out_grad.dtype == torch.float32 and out_grad.is_contiguous()
-                and out_grad.dim() == 3 and tuple(out_grad.shape[1:]) == (H, W) and out_grad.device == dev):
-            raise RuntimeError(f"[3dgut] attribute cotangent: a contiguous float32 tensor [K, {H}, {W}] on the rays' GPU")
+        rows, n = _density_rows(particle_density)
+        _require_tensor(out_grad, torch.float32, (None, H, W), dev,
+                        f"[3dgut] attribute cotangent: a contiguous float32 tensor [K, {H}, {W}] on the rays' GPU")
         k = int(out_grad.shape[0])
         if out is None:
             out = torch.empty((n, k), dtype=torch.float32, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.is_contiguous()
-                  and tuple(out.shape) == (n, k) and out.device == dev):
-            raise RuntimeError(f"[3dgut] attribute gradient: a contiguous float32 tensor [{n}, {k}] on the rays' GPU")
+        else:
+            _require_tensor(out, torch.float32, (n, k), dev, f"[3dgut] attribute gradient: a contiguous float32 tensor [{n}, {k}] on the rays' GPU")
         cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
         self._call("trace_attributes_bwd", self._lib.gut_trace_attributes_bwd, dev, frame_number, int(num_active_features), n, _ptr(rows),
                    W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), k, _ptr(out_grad, n), _ptr(out, n))
