@@ -467,7 +467,7 @@ TraceView view_of(void* stream_, int32_t num_active_features, uint32_t num_parti
     return TraceView{static_cast<hipStream_t>(stream_), num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera};
 }
 struct FwdOutputs { float *rgba, *hit_distance, *hit_count, *visibility; };
-struct BwdUpstream { const float *rgba, *rgba_grad, *hit_distance, *hit_distance_grad /* may be NULL (= all zeros) */; };
+using gut::BwdUpstream;
 // what follows the backward compositor: the per-Gaussian epilogue in one of its two forms, nothing, or the consuming pose reduction alone
 enum class BwdMode { kDense, kCompact, kSkipEpilogue, kPoseOnly };
 struct BwdArgs {
@@ -645,6 +645,15 @@ bool want_lazy(gut_handle h, int tiles, uint64_t count) {
 }
 
 // One binning + compositing pass over `sort_n` list slots (>= the real count, the tail is padding); the rare overflow runs it twice.
+// what every compositor launch of the view reads (the handle's lists and colours, the caller's rows and rays), over the id list `ids`
+gut::CompositorOperands compositor_operands(gut_handle h, const TraceView& view, const gut::ViewParams& v, const float* d_particle_density,
+                                            const uint32_t* ids) {
+    return gut::CompositorOperands{v, h->consts, d_particle_density, h->feat.as<float>(), view.ray_origin, view.ray_direction,
+                                   h->ranges.as<uint32_t>(), ids, h->cfg.particle_kernel_degree};
+}
+// the id list the cached forward left in the order it walked it: what the backward compositor and the contribution walk read
+const uint32_t* walked_ids(gut_handle h) { return (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(); }
+
 int bin_and_render(gut_handle h, const TraceView& view, const FwdFrame& f, const float* d_particle_density, const FwdOutputs& out,
                    uint32_t sort_n) {
     const hipStream_t s = view.stream;
@@ -687,11 +696,11 @@ int bin_and_render(gut_handle h, const TraceView& view, const FwdFrame& f, const
     }
     // with zero intersections the reference returns its freshly initialised outputs (gutRenderer.cu:323-325);
     // running the compositor over empty ranges writes exactly those values
+    const gut::CompositorOperands o = compositor_operands(h, view, f.v, d_particle_density, h->ids_sorted.as<uint32_t>());
+    const gut::RenderImages images{out.rgba, out.hit_distance, out.hit_count};
     if (h->cfg.k_buffer_size > 0) {
         HIP_TRY(hipMemsetAsync(h->trav_fwd.p, 0, sizeof(uint32_t) * (size_t)tiles, s));
-        gut::launch_render_sorted(s, f.v, h->consts, h->cfg.k_buffer_size, d_particle_density, h->feat.as<float>(), view.ray_origin,
-                                  view.ray_direction, h->ranges.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), f.d_count,
-                                  out.rgba, out.hit_distance, out.hit_count, h->cfg.particle_kernel_degree);
+        gut::launch_render_sorted(s, o, h->cfg.k_buffer_size, f.d_count, images);
     } else {
         // Longest lists first (as the backward launches its deepest tiles first), when the frames before this one walked a good part
         // of their lists: then a tile's list length says how long it will run, and the few long ones must not form the tail of the
@@ -700,11 +709,10 @@ int bin_and_render(gut_handle h, const TraceView& view, const FwdFrame& f, const
         const bool fwd_order = h->fwd_order_mode >= 0 ? h->fwd_order_mode != 0 : h->fwd_longest_first;   // GUT_OPT_FORWARD_TILE_ORDER
         if (fwd_order && sort_n)
             gut::launch_tile_order(s, (uint32_t)tiles, nullptr, h->tile_order.as<uint32_t>(), h->ranges.as<uint32_t>(), true);
-        gut::launch_render(s, f.v, h->consts, d_particle_density, h->feat.as<float>(), view.ray_origin, view.ray_direction,
-                           h->ranges.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), f.d_count, out.rgba, out.hit_distance, out.hit_count,
-                           h->trav_fwd.as<uint32_t>(), lazy ? h->keys_sorted.as<uint64_t>() : nullptr,
-                           lazy ? h->ids_ordered.as<uint32_t>() : nullptr, lazy ? h->tile_ordered.as<uint32_t>() : nullptr,
-                           (fwd_order && sort_n) ? h->tile_order.as<uint32_t>() : nullptr, h->cfg.particle_kernel_degree);
+        gut::LazyOrderLists lists;
+        if (lazy) lists = {h->keys_sorted.as<uint64_t>(), h->ids_ordered.as<uint32_t>(), h->tile_ordered.as<uint32_t>()};
+        gut::launch_render(s, o, f.d_count, images, h->trav_fwd.as<uint32_t>(), lists,
+                           (fwd_order && sort_n) ? h->tile_order.as<uint32_t>() : nullptr);
     }
     // render.enable_hitcounts = false: the reference compiles the counter out (rayPayload.cuh:44-46,69-73,126-128) and its
     // output tensor keeps the zeros it was created with (splatRaster.cpp:198).  Not a configuration worth a kernel variant.
@@ -870,17 +878,14 @@ int queue_bwd_compositor(gut_handle h, const TraceView& view, const gut::ViewPar
     if (h->m && h->cfg.k_buffer_size > 0) {
         if (!up.hit_distance) return fail("gut_trace_bwd: the sorted variant needs d_ray_hit_distance");
         HIP_TRY(hipMemsetAsync(h->trav_bwd.p, 0, sizeof(uint32_t) * (size_t)h->tiles, s));
-        gut::launch_render_sorted_bwd(s, v, h->consts, h->cfg.k_buffer_size, d_particle_density, h->feat.as<float>(), view.ray_origin,
-                                      view.ray_direction, h->ranges.as<uint32_t>(), h->ids_sorted.as<uint32_t>(), up.rgba, up.hit_distance,
-                                      up.rgba_grad, up.hit_distance_grad, h->grad16.as<float>(), h->sorted_reference_bwd, h->cfg.particle_kernel_degree);
+        gut::launch_render_sorted_bwd(s, compositor_operands(h, view, v, d_particle_density, h->ids_sorted.as<uint32_t>()), h->cfg.k_buffer_size,
+                                      up, h->grad16.as<float>(), h->sorted_reference_bwd);
     } else if (h->m) {
         HIP_TRY(h->walk_sums.ensure(2 * sizeof(uint32_t)));
         gut::launch_tile_order(s, (uint32_t)h->tiles, h->trav_fwd.as<uint32_t>(), h->tile_order.as<uint32_t>(), h->ranges.as<uint32_t>(), false,
                                h->walk_sums.as<uint32_t>());
-        gut::launch_render_bwd(s, v, h->consts, d_particle_density, h->feat.as<float>(), view.ray_origin, view.ray_direction,
-                               h->ranges.as<uint32_t>(), (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(),
-                               up.rgba, up.rgba_grad, up.hit_distance_grad, h->grad16.as<float>(),
-                               h->trav_bwd.as<uint32_t>(), h->tile_order.as<uint32_t>(), h->trav_fwd.as<uint32_t>(), h->cfg.particle_kernel_degree);
+        gut::launch_render_bwd(s, compositor_operands(h, view, v, d_particle_density, walked_ids(h)), up, h->grad16.as<float>(),
+                               h->trav_bwd.as<uint32_t>(), h->tile_order.as<uint32_t>(), h->trav_fwd.as<uint32_t>());
     }
     return 0;
 }
@@ -1064,9 +1069,8 @@ int trace_walk_impl(gut_handle h, const char* name, const TraceView& view, const
     }
     HIP_TRY(form.scratch(h));
     gut::launch_tile_order(s, (uint32_t)h->tiles, h->trav_fwd.as<uint32_t>(), h->tile_order.as<uint32_t>());
-    const gut::WalkOperands o{v, h->consts, d_particle_density, view.ray_origin, view.ray_direction, h->ranges.as<uint32_t>(),
-                              (h->lazy_order ? h->ids_ordered : h->ids_sorted).as<uint32_t>(), h->tile_order.as<uint32_t>(),
-                              h->trav_fwd.as<uint32_t>(), h->n, (uint32_t)(v.grid_x * v.grid_y)};
+    const gut::WalkOperands o = gut::walk_operands(compositor_operands(h, view, v, d_particle_density, walked_ids(h)),
+                                                   h->tile_order.as<uint32_t>(), h->trav_fwd.as<uint32_t>(), h->n);
     form.launch(h, s, o);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -5,7 +5,10 @@
 // one lane per pixel, the tile's ordered-id list in chunks of 256 entries staged in LDS, bounded by the forward's per-tile walked
 // depth as the backward compositor bounds it — and takes the forward's decisions by the forward's arithmetic: the per-(pixel, entry)
 // evaluation below is a copy of k_render's without the colours, and this unit is built with the flags of gut_render.hip, so the
-// compiler contracts the same expressions (the one place where it does not is pinned with explicit FMAs, see `entry`).  It reads no
+// compiler contracts the same expressions (the one place where it does not is pinned with explicit FMAs, see `entry`).  The pixel
+// layout (tile_pixel), the staged entry (TestEntry: k_render's PackEntry without the colour and id), stage_at, the strip culling and
+// the per-wave compaction (compact_wave_list) are the compositors' own, from gut_render_common.h; the walk loop and `entry` are this
+// kernel's, and so is the conversion of a list entry in its staging (see there for why not make_entry).  It reads no
 // colours and writes no image.  Where the forward composited, w = T_before * alpha; 0 elsewhere.  The walk names no form: every
 // evaluated (pixel, entry) weight goes to a SINK, a struct with its operands (Args, by value), its LDS (Shared, declared once by
 // the kernel), its per-lane state and one hook per place where the forms differ:
@@ -47,19 +50,6 @@
 namespace gut {
 
 namespace {
-
-// the staged entry of k_render (gut_render.hip) without its colour: the thirteen floats of every (pixel, entry) test, the scales (read
-// by hits only) and the particle id
-struct ContribEntry {  // 64 bytes
-    float4 q0;         // oc = M (sensor_pos - mean), density
-    float4 q1;         // m00 m01 m02 m10
-    float4 q2;         // m11 m12 m20 m21
-    float4 q3;         // s.x s.y s.z m22
-};
-
-__device__ __forceinline__ const ContribEntry& stage_at(const ContribEntry* stage, uint32_t j) {
-    return *reinterpret_cast<const ContribEntry*>(reinterpret_cast<const char*>(stage) + __umul24(j, (uint32_t)sizeof(ContribEntry)));
-}
 
 constexpr uint32_t kWaves = kBlock / 64;
 
@@ -343,7 +333,7 @@ __global__ __launch_bounds__(kBlock) void k_grad_rows(const long long* __restric
 // ---- the walk --------------------------------------------------------------------------------------------------------------------
 template <class Sink>
 __global__ __launch_bounds__(kBlock, 4) void k_walk(const WalkOperands o, const typename Sink::Args args) {
-    __shared__ ContribEntry stage[kBlock];
+    __shared__ TestEntry stage[kBlock];   // k_render's staged entry without its colour (gut_render_common.h); the id goes to s_id
     __shared__ uint32_t s_id[kBlock];
     __shared__ uint32_t s_first_invalid;
     __shared__ uint32_t s_mask[kBlock];              // see k_render
@@ -356,16 +346,13 @@ __global__ __launch_bounds__(kBlock, 4) void k_walk(const WalkOperands o, const 
     const float4* const density12 = reinterpret_cast<const float4*>(o.density12);
     const uint32_t tile = o.tile_order[blockIdx.x];
     const uint32_t tid = threadIdx.x;
-    const int px = (int)(tile % (uint32_t)v.grid_x) * kTile + tile_px(tid);   // wave = 8x8 block (gut_render_common.h)
-    const int py = (int)(tile / (uint32_t)v.grid_x) * kTile + tile_py(tid);
-    const bool inside = (px < v.width) && (py < v.height);
-    const size_t pix = (size_t)py * (size_t)v.width + (size_t)px;
-    const RayState ray = make_ray(v, o.ray_ori, o.ray_dir, pix, inside);
-    Sink sink(args, s_sink, v, pix, inside);
+    const TilePixel at = tile_pixel(v, tile, tid);   // wave = 8x8 block
+    const RayState ray = make_ray(v, o.ray_ori, o.ray_dir, at.pix, at.inside);
+    Sink sink(args, s_sink, v, at.pix, at.inside);
 
     if (tid == 0) s_first_invalid = kBlock;
     const bool centred = __syncthreads_and(ray.centred ? 1 : 0) != 0;  // block-uniform
-    build_strip_planes(s_planes, ray, inside, centred, tid);
+    build_strip_planes(s_planes, ray, at.inside, centred, tid);
     const uint32_t wave_bit = 1u << (tid >> 6);
     const uint32_t wave = tid >> 6, lane = tid & 63u;
 
@@ -385,7 +372,10 @@ __global__ __launch_bounds__(kBlock, 4) void k_walk(const WalkOperands o, const 
             uint32_t id = kInvalid;
             if (k < range.y) id = o.ordered_ids[k];
             if (id != kInvalid && id >= o.num_particles) id = kInvalid;   // (never in a list the forward built: keeps every access in bounds)
-            ContribEntry e;
+            // (make_entry's conversion once more, straight into the packed form and without the colour: through make_entry the compiler
+            // orders this kernel's values differently and rounds other products of `entry` on their own in the walk of rays that do not
+            // start at the sensor position — the contractions `entry` is pinned against, see there)
+            TestEntry e;
             uint32_t strips = 0xFu;
             if (id != kInvalid) {
                 const float4 a = density12[3 * (size_t)id + 0];
@@ -464,18 +454,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_walk(const WalkOperands o, const 
         // two-register-set software pipeline
         {
             uint16_t* list = s_list[wave];
-            uint32_t nw = 0;
-#pragma unroll
-            for (uint32_t r = 0; r < kWaves; ++r) {
-                const uint32_t e = r * 64u + lane;
-                const bool keep = (e < cnt) && ((s_mask[e] & wave_bit) != 0u);
-                const unsigned long long bal = __ballot(keep);
-                if (keep) list[nw + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)e;
-                nw += (uint32_t)__popcll(bal);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const uint32_t nw = compact_wave_list(list, s_mask, cnt, wave_bit, lane);
             uint32_t ja = list[0], jb = list[1];  // list positions i and i+1 (garbage beyond nw is never evaluated)
             ja = min(ja, (uint32_t)kBlock - 1u);
             jb = min(jb, (uint32_t)kBlock - 1u);
@@ -509,7 +488,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_walk(const WalkOperands o, const 
     }
     };
     if (centred) walk(std::true_type{}); else walk(std::false_type{});
-    sink.finish(v, pix, inside);
+    sink.finish(v, at.pix, at.inside);
 }
 
 template <class Sink>

@@ -196,33 +196,43 @@ void launch_resize_sph_rows(hipStream_t s, uint32_t n, uint32_t in_width, uint32
 void launch_pack_activate_fields(hipStream_t s, uint32_t n, const float* pos, const float* dns_logit, const float* rot_raw,
                                  const float* log_scl, float* act12);   // gut_train.hip (activate_row)
 
-void launch_render(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12,
-                   const float* feat, const float* ray_ori, const float* ray_dir, const uint32_t* ranges,
-                   const uint32_t* sorted_ids, const uint32_t* d_num_intersections, float* rgba, float* dist, float* hits,
-                   uint32_t* tile_traversed, const uint64_t* tile_keys /* lazy order only */, uint32_t* ordered_ids /* NULL = list is fully sorted */,
-                   uint32_t* tile_ordered /* lazy order: entries of each tile's list written to ordered_ids */,
-                   const uint32_t* tile_order = nullptr /* launch order of the tiles (longest lists first) or NULL */,
-                   int kernel_degree = 2 /* render.particle_kernel_degree; != 2 runs the kGeneral instantiation */);
-void launch_render_bwd(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12,
-                       const float* feat, const float* ray_ori, const float* ray_dir, const uint32_t* ranges,
-                       const uint32_t* sorted_ids, const float* rgba, const float* rgba_grad, const float* dist_grad,
-                       float* grad16, uint32_t* tile_traversed, const uint32_t* tile_order,
-                       const uint32_t* tile_walked /* forward's per-tile traversal depth: the backward stops there */,
-                       int kernel_degree = 2);
+// ---- the compositors (gut_render.hip, gut_render_general.hip, gut_render_sorted.hip) and the walk (gut_contrib.hip) ----
+// What every compositor launch reads, built once per call (gut_api.cpp); host side only, the kernels take its fields as arguments
+struct CompositorOperands {
+    const ViewParams& v;
+    const RenderConsts& c;
+    const float* density12;    // [N,12] rows
+    const float* feat;         // [N,3] per-Gaussian colours of the cached forward
+    const float* ray_ori;
+    const float* ray_dir;
+    const uint32_t* ranges;    // [tiles] uint2: each tile's slice of the id list
+    const uint32_t* ids;       // the depth-ordered id list (forward with the lazy order: unused, see LazyOrderLists)
+    int kernel_degree;         // render.particle_kernel_degree; != 2 runs the kGeneral instantiations
+};
+struct RenderImages { float *rgba, *dist, *hits; };   // the forward's three planes
+// lazy order only (all null: the id list is fully sorted): the tiles' {depth bits, particle id} words, grouped by tile, in; the ids
+// in the order the forward consumed them and the number of each tile's entries it ordered, out
+struct LazyOrderLists {
+    const uint64_t* tile_keys = nullptr;
+    uint32_t* ordered_ids = nullptr;
+    uint32_t* tile_ordered = nullptr;
+};
+// the forward's planes and the loss's gradients with respect to them; hit_distance: read by the sorted variant only
+struct BwdUpstream { const float *rgba, *rgba_grad, *hit_distance, *hit_distance_grad /* may be NULL (= all zeros) */; };
+
+// tile_order: launch order of the tiles (longest lists first) or null
+void launch_render(hipStream_t s, const CompositorOperands& o, const uint32_t* d_num_intersections, const RenderImages& out,
+                   uint32_t* tile_traversed, const LazyOrderLists& lazy, const uint32_t* tile_order);
+// tile_walked: the forward's per-tile traversal depth, the backward stops there
+void launch_render_bwd(hipStream_t s, const CompositorOperands& o, const BwdUpstream& up, float* grad16, uint32_t* tile_traversed,
+                       const uint32_t* tile_order, const uint32_t* tile_walked);
 // the same two launches for render.particle_kernel_degree != 2 (gut_render_general.hip; reached through launch_render / launch_render_bwd)
-void launch_render_general(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* feat,
-                           const float* ray_ori, const float* ray_dir, const uint32_t* ranges, const uint32_t* sorted_ids,
-                           const uint32_t* d_num_intersections, float* rgba, float* dist, float* hits, uint32_t* tile_traversed,
-                           const uint64_t* tile_keys, uint32_t* ordered_ids, uint32_t* tile_ordered, const uint32_t* tile_order,
-                           int kernel_degree);
-void launch_render_bwd_general(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* feat,
-                               const float* ray_ori, const float* ray_dir, const uint32_t* ranges, const uint32_t* sorted_ids,
-                               const float* rgba, const float* rgba_grad, const float* dist_grad, float* grad16,
-                               uint32_t* tile_traversed, const uint32_t* tile_order, const uint32_t* tile_walked, int kernel_degree);
+decltype(launch_render) launch_render_general;
+decltype(launch_render_bwd) launch_render_bwd_general;
 void launch_tile_order(hipStream_t s, uint32_t tiles, const uint32_t* traversed, uint32_t* order, const uint32_t* ranges = nullptr,
                        bool by_length = false, uint32_t* walk_sums = nullptr);
 // gut_contrib.hip: the forward's walk again (unsorted variant, kernel degree 2), without colours.  What every form of
-// the walk reads, built once per call (gut_api.cpp) and passed to the kernel by value
+// the walk reads, built once per call from the compositors' record (walk_operands) and passed to the kernel by value
 struct WalkOperands {
     ViewParams v;
     RenderConsts c;
@@ -236,6 +246,10 @@ struct WalkOperands {
     uint32_t num_particles;
     uint32_t tiles;                // v.grid_x * v.grid_y: one workgroup each
 };
+inline WalkOperands walk_operands(const CompositorOperands& o, const uint32_t* tile_order, const uint32_t* tile_walked, uint32_t num_particles) {
+    return WalkOperands{o.v, o.c, o.density12, o.ray_ori, o.ray_dir, o.ranges, o.ids, tile_order, tile_walked, num_particles,
+                        (uint32_t)(o.v.grid_x * o.v.grid_y)};
+}
 // adds every walked Gaussian's sum and maximum of blending weights and its composited-pixel count to scores [N] (integer atomics).
 // plane [H,W] (null: the records alone): every weight is also multiplied by the pixel's value clamped to [0, 1] and summed into
 // weighted_q32 [N]; with a plane, scores may be null (the weighted sums alone)
@@ -249,14 +263,9 @@ void launch_attributes(hipStream_t s, const WalkOperands& o, uint32_t num_channe
 // 32 bytes per particle; max_bits: scratch of four words
 void launch_attributes_bwd(hipStream_t s, const WalkOperands& o, uint32_t num_channels, const float* out_grad, float* attrs_grad,
                            void* rows_q, uint32_t* max_bits);
-// sorted (k_buffer_size > 0) compositor variant, gut_render_sorted.hip
-void launch_render_sorted(hipStream_t s, const ViewParams& v, const RenderConsts& c, int K, const float* density12, const float* feat,
-                          const float* ray_ori, const float* ray_dir, const uint32_t* ranges, const uint32_t* sorted_ids,
-                          const uint32_t* d_num_intersections, float* rgba, float* dist, float* hits, int kernel_degree = 2);
-void launch_render_sorted_bwd(hipStream_t s, const ViewParams& v, const RenderConsts& c, int K, const float* density12,
-                              const float* feat, const float* ray_ori, const float* ray_dir, const uint32_t* ranges,
-                              const uint32_t* sorted_ids, const float* rgba, const float* dist, const float* rgba_grad,
-                              const float* dist_grad, float* grad16, bool reference_undo, int kernel_degree = 2);
+// sorted (k_buffer_size = K > 0) compositor variant, gut_render_sorted.hip
+void launch_render_sorted(hipStream_t s, const CompositorOperands& o, int K, const uint32_t* d_num_intersections, const RenderImages& out);
+void launch_render_sorted_bwd(hipStream_t s, const CompositorOperands& o, int K, const BwdUpstream& up, float* grad16, bool reference_undo);
 void launch_project_bwd_compact(hipStream_t s, uint32_t n, const float* density12, const uint32_t* tiles_count,
                                 const float* feat, float* grad16 /* rows read are left zero */, float* raw_grad12, float* mrgb);
 // fused per-Gaussian backward epilogue + SH-gradient + Adam (gut_train.hip), single view, reads the handle's gradient rows

@@ -18,16 +18,21 @@
 // scheme, and each wave-instruction of the flush covers 4 rows x 16 contiguous floats.  Waves in
 // which no lane hit the entry skip the reduction altogether (wave-uniform branch on __ballot).
 //
-// Three further pieces live in gut_render_common.h: the per-wave strip culling (double-wedge test of each staged entry's
-// cut-off ellipsoid against the elevation and azimuth wedges of each wave's 8x8 block; every wave walks its own compacted entry list), the lazy per-tile depth order (the global sort only
-// groups by tile; K6 orders 512 entries at a time as far as the tile is walked and hands the ordered ids to K7), and the
-// staging form of an entry.  The backward launches its tiles deepest-first (k_tile_order).
+// What the two kernels share with each other, with the contribution walk (gut_contrib.hip) and with the sorted variant lives in
+// gut_render_common.h: the tile's pixel layout (tile_pixel), the staged entry and its one conversion from the parameter rows
+// (PackEntry, make_entry), the per-wave strip culling (double-wedge test of each staged entry's cut-off ellipsoid against the elevation
+// and azimuth wedges of each wave's 8x8 block) and the compaction of a chunk to the entries a wave has to walk (compact_wave_list),
+// and the lazy per-tile depth order (the global sort only groups by tile; K6 orders 512 entries at a time as far as the tile is walked
+// and hands the ordered ids to K7).  Each kernel keeps its own walk loop and its own evaluation of an entry.  The backward launches
+// its tiles deepest-first (k_tile_order).  The diagnostic builds' stamps and LDS ballast are in gut_render_diag.h; here they show as
+// the GUT_STAMP / GUT_K*_BALLAST lines, which are empty in the product.
 //
 // Colour/gradient buffers are compared with the oracle by tolerance, so this file is compiled with FMA
 // contraction on and uses the hardware exp/rcp/rsq approximations.  Build flags that matter: -fno-slp-vectorize (the
 // SLP vectoriser's v_pk_* packing is a net loss here) and the launch bounds of k_render (5 waves per SIMD).
 #include "gut_internal.h"
 #include "gut_render_common.h"
+#include "gut_render_diag.h"
 
 #include <type_traits>
 
@@ -47,60 +52,6 @@ constexpr bool kTuGeneral = false;
 #define GUT_LAUNCH_RENDER launch_render
 #define GUT_LAUNCH_RENDER_BWD launch_render_bwd
 #endif
-
-#ifdef GUT_CLOCK_STAMPS
-// DIAGNOSTIC BUILD ONLY (tools/clock_probe.py builds tools/bin/libgut_hip_stamps.so with -DGUT_CLOCK_STAMPS; the product library
-// has none of this): every workgroup of the backward compositor stamps the shader clock (s_memtime, cycles) and the constant
-// 100 MHz counter (s_memrealtime) at its start and end into a buffer no other code reads — delta cycles / delta real time is the
-// clock the chip actually held during the launch (MI355X_MICROARCH.md, "DVFS give-back" item 6).
-__device__ unsigned long long g_clock_stamps[8192][4];
-// ... and thread 0 of every workgroup of the FORWARD compositor adds up the cycles it spent in the phases of its chunk loop:
-// [0] whole workgroup, [1] lazy selection, [2] staging (id + parameter gather, conversion, up to the barrier), [3] walking the
-// chunk (incl. the wait for the slowest wave at the next loop head)
-__device__ unsigned long long g_k6_phases[8192][4];
-__device__ unsigned long long g_k7_phases[8192][4];   // backward: [0] staging, [1] walk, [2] epilogue + flush, [3] whole workgroup
-#define GUT_K6_STAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define GUT_K6_ADD(slot, a, b) do { if (threadIdx.x == 0) k6_acc[slot] += (b) - (a); } while (0)
-#else
-#define GUT_K6_STAMP(var) do { } while (0)
-#define GUT_K6_ADD(slot, a, b) do { } while (0)
-#endif
-
-// Staged entry of the two unsorted compositors: the thirteen floats every (pixel, entry) test needs sit in the first 13 dwords read
-// per entry (three ds_read_b128 + one ds_read_b32); the scales — needed by a HIT only (hit distance) — follow as one aligned
-// ds_read_b96, the colour and the id as before.  Against FwdEntry's rows [m_i.xyz | s_i] this frees three VGPRs in each of the two
-// register sets of the software pipeline (round 4: k_render no longer spills inside its loop).
-struct PackEntry {     // 80 bytes
-    float4 q0;         // oc = M (sensor_pos - mean), density
-    float4 q1;         // m00 m01 m02 m10
-    float4 q2;         // m11 m12 m20 m21
-    float4 q3;         // s.x s.y s.z m22
-    float4 feat_id;    // max(rgb, 0), particle id (bit pattern)
-};
-__device__ __forceinline__ PackEntry pack_entry(const FwdEntry& e) {
-    PackEntry p;
-    p.q0 = e.mu_sigma;
-    p.q1 = make_float4(e.m0.x, e.m0.y, e.m0.z, e.m1.x);
-    p.q2 = make_float4(e.m1.y, e.m1.z, e.m2.x, e.m2.y);
-    p.q3 = make_float4(e.m0.w, e.m1.w, e.m2.w, e.m2.z);
-    p.feat_id = e.feat_id;
-    return p;
-}
-
-// stage[j] for a list index held in a VGPR: 24-bit multiply (full rate) instead of the quarter-rate 32-bit one
-__device__ __forceinline__ const PackEntry& stage_at(const PackEntry* stage, uint32_t j) {
-    return *reinterpret_cast<const PackEntry*>(reinterpret_cast<const char*>(stage) + __umul24(j, (uint32_t)sizeof(PackEntry)));
-}
-
-// sum over the 64 lanes of the wave; the total ends up in lane 63
-__device__ __forceinline__ float wave_sum_lane63(float v) {
-#ifdef GUT_REDUCE_SHFL
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-#else
-    return dpp_wave_sum_lane63(v);
-#endif
-}
 
 // ---------------------------------------------------------------------------------------------------
 // K6 forward
@@ -126,35 +77,24 @@ __global__ __launch_bounds__(kBlock, 5) void k_render(ViewParams v, RenderConsts
     __shared__ uint16_t s_list[kBlock / 64][kBlock];  // per wave: the staged entries it has to evaluate (index), in list order
     __shared__ StripPlanes s_planes;
     __shared__ LazyOrder s_lazy;
-#ifdef GUT_K6_EXTRA_LDS
-    // DIAGNOSTIC BUILD ONLY: ballast that lowers the number of resident workgroups per CU (what a second staging area would cost)
-    __shared__ float s_ballast6[GUT_K6_EXTRA_LDS / 4];
-    if (threadIdx.x == 0 && v.width < 0) s_ballast6[0] = 1.0f;
-    if (v.width < -1) dist[0] = s_ballast6[threadIdx.x];
-#endif
+    GUT_K6_BALLAST(v, dist);
 
     const uint32_t tile = tile_order ? tile_order[blockIdx.x] : blockIdx.x;  // (optional) longest lists first
     const uint32_t tid = threadIdx.x;
-#ifdef GUT_CLOCK_STAMPS
-    unsigned long long k6_acc[4] = {0, 0, 0, 0}, k6_prev = 0;
-#endif
-    GUT_K6_STAMP(k6_t_begin);
-    const int px = (int)(tile % (uint32_t)v.grid_x) * kTile + tile_px(tid);   // wave = 8x8 block (gut_render_common.h)
-    const int py = (int)(tile / (uint32_t)v.grid_x) * kTile + tile_py(tid);
-    const bool inside = (px < v.width) && (py < v.height);
-    const size_t pix = (size_t)py * (size_t)v.width + (size_t)px;
+    GUT_STAMPS(K6Stamps, stamps);
+    const TilePixel at = tile_pixel(v, tile, tid);   // wave = 8x8 block
     // zero intersections: the reference returns before rendering and the outputs keep their initial values
     // (gutRenderer.cu:323-325); treating every ray as invalid writes exactly those.  The count is read on the device: the
     // host queues this launch before it knows it.
     const uint32_t num_intersections = *d_num_intersections;
-    const RayState ray = make_ray(v, ray_ori, ray_dir, pix, inside && (num_intersections != 0));
+    const RayState ray = make_ray(v, ray_ori, ray_dir, at.pix, at.inside && (num_intersections != 0));
 
     if (tid == 0) {
         s_deepest = 0;
         s_first_invalid = kBlock;
     }
     const bool centred = __syncthreads_and(ray.centred ? 1 : 0) != 0;  // block-uniform
-    build_strip_planes(s_planes, ray, inside, centred, tid);
+    build_strip_planes(s_planes, ray, at.inside, centred, tid);
     const uint32_t wave_bit = 1u << (tid >> 6);
 
     const uint2 range = ranges[tile];
@@ -179,21 +119,14 @@ __global__ __launch_bounds__(kBlock, 5) void k_render(ViewParams v, RenderConsts
         {
             const uint32_t k = range.x + base + tid;
             uint32_t id = kInvalid;
-#ifdef GUT_CLOCK_STAMPS
-            const unsigned long long k6_tA = __builtin_amdgcn_s_memtime();
-            if (k6_prev) GUT_K6_ADD(3, k6_prev, k6_tA);    // walking the previous chunk + the wait for its slowest wave
-            unsigned long long k6_tB = k6_tA;
-#endif
+            GUT_STAMP(stamps.chunk_begin());
             if (kLazy) {
                 if (batch_used == batch_n) {  // block-uniform: order the next kLazyBatch entries of the tile
                     batch_n = min(kLazyBatch, total - base);
                     // (the staging area is free here: every wave has left the previous chunk at the barrier above)
                     static_assert(sizeof(stage) >= kLazyCache * sizeof(uint32_t), "depth cache aliases the staging area");
                     lazy_select(s_lazy, reinterpret_cast<uint32_t*>(stage), tile_keys + range.x, total, batch_n, have_lo, lo, tid);
-#ifdef GUT_CLOCK_STAMPS
-                    k6_tB = __builtin_amdgcn_s_memtime();
-                    GUT_K6_ADD(1, k6_tA, k6_tB);
-#endif
+                    GUT_STAMP(stamps.selected());
                     have_lo = true;
                     lo = s_lazy.sel[batch_n - 1];
                     batch_used = 0;
@@ -208,34 +141,11 @@ __global__ __launch_bounds__(kBlock, 5) void k_render(ViewParams v, RenderConsts
                 id = sorted_ids[k];
             }
             FwdEntry e;
-            uint32_t strips = 0xFu;
-            e.feat_id.w = __uint_as_float(id);
-            if (id != kInvalid) {
-                const float4 a = density12[3 * (size_t)id + 0];
-                const float4 q = density12[3 * (size_t)id + 1];
-                const float4 s = density12[3 * (size_t)id + 2];
-                float r[3][3];
-                quat_rows(q.x, q.y, q.z, q.w, r);
-                const float i0 = 1.0f / s.x, i1 = 1.0f / s.y, i2 = 1.0f / s.z;
-                e.m0 = make_float4(r[0][0] * i0, r[0][1] * i0, r[0][2] * i0, s.x);
-                e.m1 = make_float4(r[1][0] * i1, r[1][1] * i1, r[1][2] * i1, s.y);
-                e.m2 = make_float4(r[2][0] * i2, r[2][1] * i2, r[2][2] * i2, s.z);
-                const float c0 = v.s2w.t[0] - a.x, c1 = v.s2w.t[1] - a.y, c2 = v.s2w.t[2] - a.z;
-                e.mu_sigma = make_float4(e.m0.x * c0 + e.m0.y * c1 + e.m0.z * c2, e.m1.x * c0 + e.m1.y * c1 + e.m1.z * c2,
-                                         e.m2.x * c0 + e.m2.y * c1 + e.m2.z * c2, a.w);
-                e.feat_id.x = fmaxf(feat[3 * (size_t)id + 0], 0.0f);
-                e.feat_id.y = fmaxf(feat[3 * (size_t)id + 1], 0.0f);
-                e.feat_id.z = fmaxf(feat[3 * (size_t)id + 2], 0.0f);
-                strips = strip_mask<kGeneral>(s_planes, v, c, a, r, s, kernel_degree);
-            }
+            const uint32_t strips = make_entry<true, kGeneral>(e, v, density12, feat, id, &s_planes, &c, kernel_degree);
             stage[tid] = pack_entry(e);
             s_mask[tid] = strips;
             if (id == kInvalid && k < range.y) atomicMin(&s_first_invalid, tid);
-#ifdef GUT_CLOCK_STAMPS
-            __syncthreads();
-            k6_prev = __builtin_amdgcn_s_memtime();
-            GUT_K6_ADD(2, k6_tB, k6_prev);
-#endif
+            GUT_STAMP(stamps.staged());
         }
         __syncthreads();
 
@@ -287,25 +197,16 @@ __global__ __launch_bounds__(kBlock, 5) void k_render(ViewParams v, RenderConsts
                 }
             }
         };
-        // The wave first compacts the chunk to the entries whose cut-off ellipsoid can reach its 8x8 block (ballot prefix,
-        // indices into a wave-private LDS list), then walks that list.  Software pipeline, unrolled by two (two alternating
-        // register sets, no per-iteration moves): the parameters of the next listed entry are fetched from LDS while the
-        // current one is evaluated.
+        // The wave first compacts the chunk to the entries whose cut-off ellipsoid can reach its 8x8 block, then walks that list.
+        // Software pipeline, unrolled by two (two alternating register sets, no per-iteration moves): the parameters of the next
+        // listed entry are fetched from LDS while the current one is evaluated.
         {
             uint16_t* list = s_list[tid >> 6];
             const uint32_t lane = tid & 63u;
+            // (assigned, not initialised: from `const uint32_t nw = ...` the compiler builds this loop's header with a dozen more
+            // scalar instructions per chunk; this form compiles to the instruction stream of the compaction written out here)
             uint32_t nw = 0;
-#pragma unroll
-            for (uint32_t r = 0; r < kBlock / 64; ++r) {
-                const uint32_t e = r * 64u + lane;
-                const bool keep = (e < cnt) && ((s_mask[e] & wave_bit) != 0u);
-                const unsigned long long bal = __ballot(keep);
-                if (keep) list[nw + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)e;
-                nw += (uint32_t)__popcll(bal);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            nw = compact_wave_list(list, s_mask, cnt, wave_bit, lane);
             uint32_t ja = list[0], jb = list[1];  // list positions i and i+1 (garbage beyond nw is never evaluated)
             float4 a0 = stage_at(stage, ja).q0, a1 = stage_at(stage, ja).q1, a2 = stage_at(stage, ja).q2;
             float a3 = stage_at(stage, ja).q3.w;
@@ -334,27 +235,20 @@ __global__ __launch_bounds__(kBlock, 5) void k_render(ViewParams v, RenderConsts
     };
     if (centred) walk(std::true_type{}); else walk(std::false_type{});
 
-    if (inside) {
+    if (at.inside) {
         if (ray.valid) {
-            rgba[pix] = make_float4(cr, cg, cb, 1.0f - fabsf(T));
-            dist[pix] = dsum;
-            hits[pix] = (float)nhits;
+            rgba[at.pix] = make_float4(cr, cg, cb, 1.0f - fabsf(T));
+            dist[at.pix] = dsum;
+            hits[at.pix] = (float)nhits;
         } else {  // initial values of the reference's output tensors (splatRaster.cpp:196-198)
-            rgba[pix] = make_float4(0.f, 0.f, 0.f, 0.f);
-            dist[pix] = 1e06f;
-            hits[pix] = 0.0f;
+            rgba[at.pix] = make_float4(0.f, 0.f, 0.f, 0.f);
+            dist[at.pix] = 1e06f;
+            hits[at.pix] = 0.0f;
         }
     }
     // traversal statistics (E_f of the roofline model): deepest list position any pixel of the tile consumed (s_deepest)
     __syncthreads();
-#ifdef GUT_CLOCK_STAMPS
-    if (tid == 0 && blockIdx.x < 8192) {
-        const unsigned long long k6_t_end = __builtin_amdgcn_s_memtime();
-        if (k6_prev) k6_acc[3] += k6_t_end - k6_prev;
-        g_k6_phases[blockIdx.x][0] = k6_t_end - k6_t_begin;
-        g_k6_phases[blockIdx.x][1] = k6_acc[1]; g_k6_phases[blockIdx.x][2] = k6_acc[2]; g_k6_phases[blockIdx.x][3] = k6_acc[3];
-    }
-#endif
+    GUT_STAMP(stamps.finish());
     if (tid == 0) {
         tile_traversed[tile] = s_deepest;
         if (kLazy) tile_ordered[tile] = min(base, total);  // the backward reads ordered_ids[range.x .. range.x + that) only
@@ -482,35 +376,21 @@ __global__ __launch_bounds__(kBlock, kDistGrad ? 3 : 4) void k_render_backward(V
     __shared__ uint32_t s_mask[kBlock];              // see k_render
     __shared__ uint16_t s_list[kBlock / 64][kBlock];  // see k_render
     __shared__ StripPlanes s_planes;
-#ifdef GUT_K7_EXTRA_LDS
-    // DIAGNOSTIC BUILD ONLY: ballast that lowers the number of resident workgroups per CU (occupancy experiment, tools/clock_probe.py)
-    __shared__ float s_ballast[GUT_K7_EXTRA_LDS / 4];
-    if (threadIdx.x == 0 && v.width < 0) s_ballast[0] = 1.0f;
-    if (v.width < -1) grad16[0] = s_ballast[threadIdx.x];
-#endif
+    GUT_K7_BALLAST(v, grad16);
 
     const uint32_t tile = tile_order ? tile_order[blockIdx.x] : blockIdx.x;  // deepest tiles are dispatched first
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63;
-#ifdef GUT_CLOCK_STAMPS
-    unsigned long long k7_acc[3] = {0, 0, 0};
-    if (tid == 0 && blockIdx.x < 8192) {
-        g_clock_stamps[blockIdx.x][0] = __builtin_amdgcn_s_memtime();
-        g_clock_stamps[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
-    const int px = (int)(tile % (uint32_t)v.grid_x) * kTile + tile_px(tid);   // wave = 8x8 block (gut_render_common.h)
-    const int py = (int)(tile / (uint32_t)v.grid_x) * kTile + tile_py(tid);
-    const bool inside = (px < v.width) && (py < v.height);
-    const size_t pix = (size_t)py * (size_t)v.width + (size_t)px;
-    const RayState ray = make_ray(v, ray_ori, ray_dir, pix, inside);
+    GUT_STAMPS(K7Stamps, stamps);
+    const TilePixel at = tile_pixel(v, tile, tid);   // wave = 8x8 block
+    const RayState ray = make_ray(v, ray_ori, ray_dir, at.pix, at.inside);
 
     if (tid == 0) {
         s_deepest = 0;
         s_first_invalid = kBlock;
     }
     const bool centred = __syncthreads_and(ray.centred ? 1 : 0) != 0;  // block-uniform
-    build_strip_planes(s_planes, ray, inside, centred, tid);
+    build_strip_planes(s_planes, ray, at.inside, centred, tid);
     const uint32_t wave_bit = 1u << (tid >> 6);
 #pragma unroll
     for (int k = 0; k < W; ++k) acc[k * kBlock + tid] = 0.0f;
@@ -518,20 +398,20 @@ __global__ __launch_bounds__(kBlock, kDistGrad ? 3 : 4) void k_render_backward(V
     // forward results and upstream gradients of this pixel (rayPayloadBackward.cuh:30-58)
     float T_final = 1.f, Tg = 0.f, fr = 0.f, fg = 0.f, fb = 0.f, gr = 0.f, gg = 0.f, gb = 0.f, gd = 0.f;
     if (ray.valid) {
-        const float4 o = rgba[pix];
-        const float4 g = rgba_grad[pix];
+        const float4 o = rgba[at.pix];
+        const float4 g = rgba_grad[at.pix];
         T_final = 1.0f - o.w;
         Tg = -g.w;  // transmittanceGradient = -dL/d(opacity)
         fr = o.x; fg = o.y; fb = o.z;
         gr = g.x; gg = g.y; gb = g.z;
-        if (kDistGrad) gd = dist_grad[pix];
+        if (kDistGrad) gd = dist_grad[at.pix];
     }
 
     // out-of-image lanes (ragged right/bottom tiles) never hit, but they run the gradient arithmetic with zero weights
     // once any lane of their wave hits: give them a unit direction so that arithmetic stays finite
     const float dir2 = ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz;
     const float ori1 = fabsf(ray.ex) + fabsf(ray.ey) + fabsf(ray.ez);
-    const bool usable = inside && (dir2 > 0.0f) && (dir2 < 3.0e38f) && (ori1 < 3.0e38f);  // false for NaN / inf / zero rays
+    const bool usable = at.inside && (dir2 > 0.0f) && (dir2 < 3.0e38f) && (ori1 < 3.0e38f);  // false for NaN / inf / zero rays
     const float rdx = usable ? ray.dx : 0.0f, rdy = usable ? ray.dy : 0.0f, rdz = usable ? ray.dz : 1.0f;
     const float rex = usable ? ray.ex : 0.0f, rey = usable ? ray.ey : 0.0f, rez = usable ? ray.ez : 0.0f;
 
@@ -552,42 +432,19 @@ __global__ __launch_bounds__(kBlock, kDistGrad ? 3 : 4) void k_render_backward(V
     constexpr bool kCentred = decltype(centred_tag)::value;
     for (uint32_t base = 0; base < total; base += kBlock) {
         if (!__syncthreads_or(alive ? 1 : 0)) break;
-#ifdef GUT_CLOCK_STAMPS
-        const unsigned long long k7_tA = __builtin_amdgcn_s_memtime();
-#endif
+        GUT_STAMP(stamps.chunk_begin());
         {
             const uint32_t k = range.x + base + tid;
             uint32_t id = kInvalid;
             if (k < range.y) id = sorted_ids[k];
             FwdEntry e;
-            uint32_t strips = 0xFu;
-            e.feat_id.w = __uint_as_float(id);
-            if (id != kInvalid) {
-                const float4 a = density12[3 * (size_t)id + 0];
-                const float4 q = density12[3 * (size_t)id + 1];
-                const float4 sc = density12[3 * (size_t)id + 2];
-                float r[3][3];
-                quat_rows(q.x, q.y, q.z, q.w, r);
-                const float i0 = 1.0f / sc.x, i1 = 1.0f / sc.y, i2 = 1.0f / sc.z;
-                e.m0 = make_float4(r[0][0] * i0, r[0][1] * i0, r[0][2] * i0, sc.x);
-                e.m1 = make_float4(r[1][0] * i1, r[1][1] * i1, r[1][2] * i1, sc.y);
-                e.m2 = make_float4(r[2][0] * i2, r[2][1] * i2, r[2][2] * i2, sc.z);
-                const float c0 = v.s2w.t[0] - a.x, c1 = v.s2w.t[1] - a.y, c2 = v.s2w.t[2] - a.z;
-                e.mu_sigma = make_float4(e.m0.x * c0 + e.m0.y * c1 + e.m0.z * c2, e.m1.x * c0 + e.m1.y * c1 + e.m1.z * c2,
-                                         e.m2.x * c0 + e.m2.y * c1 + e.m2.z * c2, a.w);
-                e.feat_id.x = fmaxf(feat[3 * (size_t)id + 0], 0.0f);
-                e.feat_id.y = fmaxf(feat[3 * (size_t)id + 1], 0.0f);
-                e.feat_id.z = fmaxf(feat[3 * (size_t)id + 2], 0.0f);
-                strips = strip_mask<kGeneral>(s_planes, v, c, a, r, sc, kernel_degree);
-            }
+            const uint32_t strips = make_entry<true, kGeneral>(e, v, density12, feat, id, &s_planes, &c, kernel_degree);
             stage[tid] = pack_entry(e);
             s_mask[tid] = strips;
             if (id == kInvalid && k < range.y) atomicMin(&s_first_invalid, tid);
         }
         __syncthreads();
-#ifdef GUT_CLOCK_STAMPS
-        const unsigned long long k7_tB = __builtin_amdgcn_s_memtime();
-#endif
+        GUT_STAMP(stamps.staged());
 
         const uint32_t cnt_all = min((uint32_t)kBlock, total - base);
         const uint32_t cnt = min(cnt_all, s_first_invalid);  // padding ids end the list for everyone
@@ -703,7 +560,7 @@ __global__ __launch_bounds__(kBlock, kDistGrad ? 3 : 4) void k_render_backward(V
             const float r = wave_transpose_reduce16(g, lane);
             if ((lane & 12u) == 0u) atomicAdd(&acc[j * W + my_slot], r);  // 16 lanes, 16 distinct addresses
             if (kDistGrad) {
-                const float t0 = wave_sum_lane63(gs0), t1 = wave_sum_lane63(gs1), t2 = wave_sum_lane63(gs2);
+                const float t0 = dpp_wave_sum_lane63(gs0), t1 = dpp_wave_sum_lane63(gs1), t2 = dpp_wave_sum_lane63(gs2);
                 if (lane == 63) {
                     atomicAdd(&acc[j * W + 16], t0);
                     atomicAdd(&acc[j * W + 17], t1);
@@ -715,18 +572,7 @@ __global__ __launch_bounds__(kBlock, kDistGrad ? 3 : 4) void k_render_backward(V
         // two-register-set software pipeline
         {
             uint16_t* list = s_list[tid >> 6];
-            uint32_t nw = 0;
-#pragma unroll
-            for (uint32_t r = 0; r < kBlock / 64; ++r) {
-                const uint32_t e = r * 64u + lane;
-                const bool keep = (e < cnt) && ((s_mask[e] & wave_bit) != 0u);
-                const unsigned long long bal = __ballot(keep);
-                if (keep) list[nw + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)e;
-                nw += (uint32_t)__popcll(bal);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const uint32_t nw = compact_wave_list(list, s_mask, cnt, wave_bit, lane);
             uint32_t ja = list[0], jb = list[1];
             // (without the hit-distance terms only q3.w = m22 is used: the compiler keeps one dword of the fourth read)
             float4 a0 = stage_at(stage, ja).q0, a1 = stage_at(stage, ja).q1, a2 = stage_at(stage, ja).q2, a3 = stage_at(stage, ja).q3;
@@ -752,9 +598,7 @@ __global__ __launch_bounds__(kBlock, kDistGrad ? 3 : 4) void k_render_backward(V
         if (cnt < cnt_all) alive = false;  // list ended at a padding entry
         // ---- chunk epilogue: (A, H) -> d(position), d(scale), d(quaternion), one entry per lane ----
         __syncthreads();
-#ifdef GUT_CLOCK_STAMPS
-        const unsigned long long k7_tC = __builtin_amdgcn_s_memtime();
-#endif
+        GUT_STAMP(stamps.walked());
         if (tid < cnt) {
             float* a = &acc[tid * W];
             const uint32_t id = __float_as_uint(stage[tid].feat_id.w);
@@ -817,12 +661,7 @@ __global__ __launch_bounds__(kBlock, kDistGrad ? 3 : 4) void k_render_backward(V
             acc[e * W + k] = 0.0f;
             if (kDistGrad && k < 4) acc[e * W + 16 + k] = 0.0f;
         }
-#ifdef GUT_CLOCK_STAMPS
-        if (tid == 0) {   // [0] staging, [1] walking + wait for the slowest wave, [2] epilogue + flush
-            const unsigned long long k7_tD = __builtin_amdgcn_s_memtime();
-            k7_acc[0] += k7_tB - k7_tA; k7_acc[1] += k7_tC - k7_tB; k7_acc[2] += k7_tD - k7_tC;
-        }
-#endif
+        GUT_STAMP(stamps.chunk_end());
     }
     };
     if (centred) walk(std::true_type{}); else walk(std::false_type{});
@@ -830,36 +669,22 @@ __global__ __launch_bounds__(kBlock, kDistGrad ? 3 : 4) void k_render_backward(V
     atomicMax(&s_deepest, consumed);
     __syncthreads();
     if (tid == 0) tile_traversed[tile] = s_deepest;
-#ifdef GUT_CLOCK_STAMPS
-    if (tid == 0 && blockIdx.x < 8192) {
-        g_clock_stamps[blockIdx.x][2] = __builtin_amdgcn_s_memtime();
-        g_clock_stamps[blockIdx.x][3] = __builtin_amdgcn_s_memrealtime();
-        g_k7_phases[blockIdx.x][0] = k7_acc[0]; g_k7_phases[blockIdx.x][1] = k7_acc[1]; g_k7_phases[blockIdx.x][2] = k7_acc[2];
-        g_k7_phases[blockIdx.x][3] = g_clock_stamps[blockIdx.x][2] - g_clock_stamps[blockIdx.x][0];
-    }
-#endif
+    GUT_STAMP(stamps.finish());
 }
 
 // ---------------------------------------------------------------------------------------------------
-void GUT_LAUNCH_RENDER(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12, const float* feat,
-                   const float* ray_ori, const float* ray_dir, const uint32_t* ranges, const uint32_t* sorted_ids,
-                   const uint32_t* d_num_intersections, float* rgba, float* dist, float* hits, uint32_t* tile_traversed,
-                   const uint64_t* tile_keys, uint32_t* ordered_ids, uint32_t* tile_ordered, const uint32_t* tile_order,
-                   int kernel_degree) {
-    const uint32_t tiles = (uint32_t)(v.grid_x * v.grid_y);
+void GUT_LAUNCH_RENDER(hipStream_t s, const CompositorOperands& o, const uint32_t* d_num_intersections, const RenderImages& out,
+                       uint32_t* tile_traversed, const LazyOrderLists& lazy, const uint32_t* tile_order) {
+    const uint32_t tiles = (uint32_t)(o.v.grid_x * o.v.grid_y);
     if (tiles == 0) return;
 #ifndef GUT_RENDER_GENERAL_TU
-    if (kernel_degree != 2) {
-        launch_render_general(s, v, c, density12, feat, ray_ori, ray_dir, ranges, sorted_ids, d_num_intersections, rgba, dist, hits,
-                              tile_traversed, tile_keys, ordered_ids, tile_ordered, tile_order, kernel_degree);
-        return;
-    }
+    if (o.kernel_degree != 2) return launch_render_general(s, o, d_num_intersections, out, tile_traversed, lazy, tile_order);
 #endif
-    auto kern = ordered_ids != nullptr ? k_render<true, kTuGeneral> : k_render<false, kTuGeneral>;
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(kBlock), 0, s, v, c, reinterpret_cast<const float4*>(density12), feat,
-                       ray_ori, ray_dir, reinterpret_cast<const uint2*>(ranges), sorted_ids, d_num_intersections,
-                       reinterpret_cast<float4*>(rgba), dist, hits, tile_traversed, reinterpret_cast<const uint2*>(tile_keys),
-                       ordered_ids, tile_ordered, tile_order, kernel_degree);
+    auto kern = lazy.ordered_ids != nullptr ? k_render<true, kTuGeneral> : k_render<false, kTuGeneral>;
+    hipLaunchKernelGGL(kern, dim3(tiles), dim3(kBlock), 0, s, o.v, o.c, reinterpret_cast<const float4*>(o.density12), o.feat, o.ray_ori,
+                       o.ray_dir, reinterpret_cast<const uint2*>(o.ranges), o.ids, d_num_intersections,
+                       reinterpret_cast<float4*>(out.rgba), out.dist, out.hits, tile_traversed,
+                       reinterpret_cast<const uint2*>(lazy.tile_keys), lazy.ordered_ids, lazy.tile_ordered, tile_order, o.kernel_degree);
 }
 
 #ifndef GUT_RENDER_GENERAL_TU
@@ -908,21 +733,6 @@ __global__ __launch_bounds__(1024) void k_tile_order(uint32_t tiles, const uint3
     for (uint32_t t = tid; t < tiles; t += 1024) order[atomicAdd(&s_base[255 - min(255u, key(t) / width)], 1u)] = t;
 }
 
-#ifdef GUT_CLOCK_STAMPS
-}  // namespace gut
-// diagnostic build only: copies the backward compositor's clock stamps [8192][4] u64 to the host
-extern "C" int gut_debug_clock_stamps(void* host_dst) {
-    return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(gut::g_clock_stamps), sizeof(unsigned long long) * 8192 * 4) == hipSuccess ? 0 : 1;
-}
-extern "C" int gut_debug_k7_phases(void* host_dst) {
-    return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(gut::g_k7_phases), sizeof(unsigned long long) * 8192 * 4) == hipSuccess ? 0 : 1;
-}
-extern "C" int gut_debug_k6_phases(void* host_dst) {
-    return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(gut::g_k6_phases), sizeof(unsigned long long) * 8192 * 4) == hipSuccess ? 0 : 1;
-}
-namespace gut {
-#endif
-
 void launch_tile_order(hipStream_t s, uint32_t tiles, const uint32_t* traversed, uint32_t* order, const uint32_t* ranges, bool by_length,
                        uint32_t* walk_sums) {
     if (tiles == 0) return;
@@ -931,25 +741,18 @@ void launch_tile_order(hipStream_t s, uint32_t tiles, const uint32_t* traversed,
 }
 #endif  // !GUT_RENDER_GENERAL_TU
 
-void GUT_LAUNCH_RENDER_BWD(hipStream_t s, const ViewParams& v, const RenderConsts& c, const float* density12,
-                       const float* feat, const float* ray_ori, const float* ray_dir, const uint32_t* ranges,
-                       const uint32_t* sorted_ids, const float* rgba, const float* rgba_grad, const float* dist_grad,
-                       float* grad16, uint32_t* tile_traversed, const uint32_t* tile_order, const uint32_t* tile_walked,
-                       int kernel_degree) {
-    const uint32_t tiles = (uint32_t)(v.grid_x * v.grid_y);
+void GUT_LAUNCH_RENDER_BWD(hipStream_t s, const CompositorOperands& o, const BwdUpstream& up, float* grad16, uint32_t* tile_traversed,
+                           const uint32_t* tile_order, const uint32_t* tile_walked) {
+    const uint32_t tiles = (uint32_t)(o.v.grid_x * o.v.grid_y);
     if (tiles == 0) return;
 #ifndef GUT_RENDER_GENERAL_TU
-    if (kernel_degree != 2) {
-        launch_render_bwd_general(s, v, c, density12, feat, ray_ori, ray_dir, ranges, sorted_ids, rgba, rgba_grad, dist_grad, grad16,
-                                  tile_traversed, tile_order, tile_walked, kernel_degree);
-        return;
-    }
+    if (o.kernel_degree != 2) return launch_render_bwd_general(s, o, up, grad16, tile_traversed, tile_order, tile_walked);
 #endif
-    auto kern = dist_grad != nullptr ? k_render_backward<true, kTuGeneral> : k_render_backward<false, kTuGeneral>;
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(kBlock), 0, s, v, c, reinterpret_cast<const float4*>(density12),
-                       feat, ray_ori, ray_dir, reinterpret_cast<const uint2*>(ranges), sorted_ids,
-                       reinterpret_cast<const float4*>(rgba), reinterpret_cast<const float4*>(rgba_grad), dist_grad, grad16,
-                       tile_traversed, tile_order, tile_walked, kernel_degree);
+    auto kern = up.hit_distance_grad != nullptr ? k_render_backward<true, kTuGeneral> : k_render_backward<false, kTuGeneral>;
+    hipLaunchKernelGGL(kern, dim3(tiles), dim3(kBlock), 0, s, o.v, o.c, reinterpret_cast<const float4*>(o.density12), o.feat, o.ray_ori,
+                       o.ray_dir, reinterpret_cast<const uint2*>(o.ranges), o.ids, reinterpret_cast<const float4*>(up.rgba),
+                       reinterpret_cast<const float4*>(up.rgba_grad), up.hit_distance_grad, grad16, tile_traversed, tile_order, tile_walked,
+                       o.kernel_degree);
 }
 
 }  // namespace gut

@@ -1,4 +1,6 @@
-// gut_render_common.h — device helpers shared by the compositing kernels (gut_render.hip, gut_render_sorted.hip)
+// gut_render_common.h — device helpers shared by the compositing kernels (gut_render.hip, gut_render_sorted.hip) and the contribution
+// walk (gut_contrib.hip): rays, the staged entry and its one conversion (make_entry), the tile's pixel layout, per-wave culling and
+// compaction, the lazy depth order
 #pragma once
 #include "gut_internal.h"
 
@@ -146,6 +148,35 @@ struct FwdEntry {      // 80 bytes, 16-byte aligned: five ds_read_b128 broadcast
     float4 feat_id;    // max(rgb, 0), particle id (bit pattern)
 };
 
+// Staged entry of the unsorted compositors and of the contribution walk: the thirteen floats every (pixel, entry) test needs sit in the
+// first 13 dwords read per entry (three ds_read_b128 + one ds_read_b32); the scales — needed by a HIT only (hit distance) — follow as
+// one aligned ds_read_b96.  Against FwdEntry's rows [m_i.xyz | s_i] this frees three VGPRs in each of the two register sets of the
+// software pipeline (round 4: k_render no longer spills inside its loop).  The walk stages TestEntry, the compositors add the colour.
+struct TestEntry {     // 64 bytes
+    float4 q0;         // oc = M (sensor_pos - mean), density
+    float4 q1;         // m00 m01 m02 m10
+    float4 q2;         // m11 m12 m20 m21
+    float4 q3;         // s.x s.y s.z m22
+};
+struct PackEntry : TestEntry {   // 80 bytes
+    float4 feat_id;    // max(rgb, 0), particle id (bit pattern)
+};
+__device__ __forceinline__ PackEntry pack_entry(const FwdEntry& e) {
+    PackEntry p;
+    p.q0 = e.mu_sigma;
+    p.q1 = make_float4(e.m0.x, e.m0.y, e.m0.z, e.m1.x);
+    p.q2 = make_float4(e.m1.y, e.m1.z, e.m2.x, e.m2.y);
+    p.q3 = make_float4(e.m0.w, e.m1.w, e.m2.w, e.m2.z);
+    p.feat_id = e.feat_id;
+    return p;
+}
+
+// stage[j] for a list index held in a VGPR: 24-bit multiply (full rate) instead of the quarter-rate 32-bit one
+template <class Entry>
+__device__ __forceinline__ const Entry& stage_at(const Entry* stage, uint32_t j) {
+    return *reinterpret_cast<const Entry*>(reinterpret_cast<const char*>(stage) + __umul24(j, (uint32_t)sizeof(Entry)));
+}
+
 
 // ---- pixel layout of a tile and per-wave culling -----------------------------------------------------
 // A wave owns an 8x8-pixel block of the 16x16 tile (wave w: block column w & 1, block row w >> 1; lane l: pixel (l & 7, l >> 3)
@@ -170,6 +201,21 @@ __device__ __forceinline__ int tile_px(uint32_t tid) { return (int)(((tid >> 6) 
 __device__ __forceinline__ int tile_py(uint32_t tid) { return (int)((tid >> 7) * 8u + ((tid >> 3) & 7u)); }
 __device__ __forceinline__ uint32_t tid_of_tile_pixel(int x, int y) {
     return (uint32_t)(((y >> 3) * 2 + (x >> 3)) * 64 + (y & 7) * 8 + (x & 7));
+}
+
+// thread tid's pixel of tile `tile` in that layout (k_render, k_render_backward, k_walk; the sorted kernels map row-major)
+struct TilePixel {
+    int px, py;
+    bool inside;   // ragged right / bottom tiles
+    size_t pix;    // py * width + px
+};
+__device__ __forceinline__ TilePixel tile_pixel(const ViewParams& v, uint32_t tile, uint32_t tid) {
+    TilePixel p;
+    p.px = (int)(tile % (uint32_t)v.grid_x) * kTile + tile_px(tid);
+    p.py = (int)(tile / (uint32_t)v.grid_x) * kTile + tile_py(tid);
+    p.inside = (p.px < v.width) && (p.py < v.height);
+    p.pix = (size_t)p.py * (size_t)v.width + (size_t)p.px;
+    return p;
 }
 
 struct StripPlanes {
@@ -280,6 +326,25 @@ __device__ __forceinline__ uint32_t strip_mask(const StripPlanes& sp, const View
         if (!outside) mask |= 1u << w;
     }
     return mask;
+}
+
+// The wave compacts a staged chunk to the entries whose cut-off ellipsoid can reach its 8x8 block: list[0 .. nw) := the indices e < cnt
+// with the wave's bit set in s_mask[e], in list order (ballot prefix into the wave-private LDS list); returns nw.  The fences make the
+// list readable by every lane of the wave on return.
+__device__ __forceinline__ uint32_t compact_wave_list(uint16_t* list, const uint32_t* s_mask, uint32_t cnt, uint32_t wave_bit, uint32_t lane) {
+    uint32_t nw = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kBlock / 64; ++r) {
+        const uint32_t e = r * 64u + lane;
+        const bool keep = (e < cnt) && ((s_mask[e] & wave_bit) != 0u);
+        const unsigned long long bal = __ballot(keep);
+        if (keep) list[nw + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)e;
+        nw += (uint32_t)__popcll(bal);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return nw;
 }
 
 // ---- lazy per-tile depth order ------------------------------------------------------------------------
@@ -516,10 +581,15 @@ __device__ __noinline__ void lazy_select(LazyOrder& S, uint32_t* __restrict__ kc
         }
 }
 
-// stage one list entry (lane-private id) into its LDS slot in the canonical-space form
-__device__ __forceinline__ FwdEntry make_entry(const ViewParams& v, const float4* __restrict__ density12,
-                                               const float* __restrict__ feat, uint32_t id) {
-    FwdEntry e;
+// The one conversion of a list entry (lane-private id) to the canonical-space form its LDS slot holds: rows -> M = diag(1/s) rotationT,
+// oc = M (sensor - mean), the clamped colour.  Returns the waves that have to evaluate the entry: strip_mask against `sp` in the forms
+// that cull (kCull), all four otherwise.  (e by reference and the mask by value: the form from which k_render and k_render_backward
+// compile to the instruction streams they had with this body written out in them.)
+template <bool kCull, bool kGeneral = false>
+__device__ __forceinline__ uint32_t make_entry(FwdEntry& e, const ViewParams& v, const float4* __restrict__ density12,
+                                               const float* __restrict__ feat, uint32_t id, const StripPlanes* sp = nullptr,
+                                               const RenderConsts* c = nullptr, int kernel_degree = 2) {
+    uint32_t strips = 0xFu;
     e.feat_id.w = __uint_as_float(id);
     if (id != kInvalid) {
         const float4 a = density12[3 * (size_t)id + 0];
@@ -537,7 +607,14 @@ __device__ __forceinline__ FwdEntry make_entry(const ViewParams& v, const float4
         e.feat_id.x = fmaxf(feat[3 * (size_t)id + 0], 0.0f);
         e.feat_id.y = fmaxf(feat[3 * (size_t)id + 1], 0.0f);
         e.feat_id.z = fmaxf(feat[3 * (size_t)id + 2], 0.0f);
+        if constexpr (kCull) strips = strip_mask<kGeneral>(*sp, v, *c, a, r, s, kernel_degree);
     }
+    return strips;
+}
+// the forms that do not cull (the sorted kernels)
+__device__ __forceinline__ FwdEntry make_entry(const ViewParams& v, const float4* density12, const float* feat, uint32_t id) {
+    FwdEntry e;
+    make_entry<false>(e, v, density12, feat, id);
     return e;
 }
 

@@ -3,7 +3,4 @@
 // (threedgut.cuh:35, particleResponse<> / particleResponseGrd<> in kernels/cuda/models/gaussianParticles.cuh:211-306).
 // Its own translation unit so that the default kernels are compiled exactly as without it (see the note at the top of gut_render.hip).
 #define GUT_RENDER_GENERAL_TU 1
-#undef GUT_CLOCK_STAMPS   // the diagnostic stamps exist in the default unit only
-#undef GUT_K7_EXTRA_LDS
-#undef GUT_K6_EXTRA_LDS
 #include "gut_render.hip"

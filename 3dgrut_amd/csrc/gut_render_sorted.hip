@@ -401,26 +401,21 @@ __global__ __launch_bounds__(kBlock) void k_render_sorted_backward(ViewParams v,
         }
 }
 
-void launch_render_sorted(hipStream_t s, const ViewParams& v, const RenderConsts& c, int K, const float* density12, const float* feat,
-                          const float* ray_ori, const float* ray_dir, const uint32_t* ranges, const uint32_t* sorted_ids,
-                          const uint32_t* d_num_intersections, float* rgba, float* dist, float* hits, int kernel_degree) {
-    const uint32_t tiles = (uint32_t)(v.grid_x * v.grid_y);
+void launch_render_sorted(hipStream_t s, const CompositorOperands& o, int K, const uint32_t* d_num_intersections, const RenderImages& out) {
+    const uint32_t tiles = (uint32_t)(o.v.grid_x * o.v.grid_y);
     if (tiles == 0) return;
-    hipLaunchKernelGGL(k_render_sorted, dim3(tiles), dim3(kBlock), 0, s, v, c, K, reinterpret_cast<const float4*>(density12), feat,
-                       ray_ori, ray_dir, reinterpret_cast<const uint2*>(ranges), sorted_ids, d_num_intersections,
-                       reinterpret_cast<float4*>(rgba), dist, hits, kernel_degree);
+    hipLaunchKernelGGL(k_render_sorted, dim3(tiles), dim3(kBlock), 0, s, o.v, o.c, K, reinterpret_cast<const float4*>(o.density12), o.feat,
+                       o.ray_ori, o.ray_dir, reinterpret_cast<const uint2*>(o.ranges), o.ids, d_num_intersections,
+                       reinterpret_cast<float4*>(out.rgba), out.dist, out.hits, o.kernel_degree);
 }
 
-void launch_render_sorted_bwd(hipStream_t s, const ViewParams& v, const RenderConsts& c, int K, const float* density12,
-                              const float* feat, const float* ray_ori, const float* ray_dir, const uint32_t* ranges,
-                              const uint32_t* sorted_ids, const float* rgba, const float* dist, const float* rgba_grad,
-                              const float* dist_grad, float* grad16, bool reference_undo, int kernel_degree) {
-    const uint32_t tiles = (uint32_t)(v.grid_x * v.grid_y);
+void launch_render_sorted_bwd(hipStream_t s, const CompositorOperands& o, int K, const BwdUpstream& up, float* grad16, bool reference_undo) {
+    const uint32_t tiles = (uint32_t)(o.v.grid_x * o.v.grid_y);
     if (tiles == 0) return;
-    hipLaunchKernelGGL(k_render_sorted_backward, dim3(tiles), dim3(kBlock), 0, s, v, c, K, reinterpret_cast<const float4*>(density12),
-                       feat, ray_ori, ray_dir, reinterpret_cast<const uint2*>(ranges), sorted_ids,
-                       reinterpret_cast<const float4*>(rgba), dist, reinterpret_cast<const float4*>(rgba_grad), dist_grad, grad16,
-                       reference_undo ? 1 : 0, kernel_degree);
+    hipLaunchKernelGGL(k_render_sorted_backward, dim3(tiles), dim3(kBlock), 0, s, o.v, o.c, K, reinterpret_cast<const float4*>(o.density12),
+                       o.feat, o.ray_ori, o.ray_dir, reinterpret_cast<const uint2*>(o.ranges), o.ids,
+                       reinterpret_cast<const float4*>(up.rgba), up.hit_distance, reinterpret_cast<const float4*>(up.rgba_grad), up.hit_distance_grad, grad16,
+                       reference_undo ? 1 : 0, o.kernel_degree);
 }
 
 }  // namespace gut
