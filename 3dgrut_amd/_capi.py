@@ -89,6 +89,8 @@ class GutContribution(C.Structure):
     _fields_ = [("weight_sum_q32", C.c_uint64), ("max_weight_bits", C.c_uint32), ("pixels", C.c_uint32)]
 
 
+SURFACE_LEVEL, SURFACE_MAX_WEIGHT = 0, 1   # gut_hip.h, GUT_SURFACE_*
+
 EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_trace_bwd", "gut_collect_times",
            "gut_get_stats", "gut_debug_buffer", "gut_debug_copy", "gut_kernel_times", "gut_kernel_times_mean", "gut_last_error", "gut_abi_version",
            "gut_ssim_workspace_bytes", "gut_ssim_forward", "gut_ssim_backward",
@@ -104,7 +106,7 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_photometric_exposure_workspace_bytes", "gut_photometric_loss_exposure", "gut_exposure_adam_step",
            "gut_image_metrics_cc_workspace_bytes", "gut_image_metrics_cc", "gut_photometric_loss_run", "gut_trace_bwd_pose",
            "gut_trace_contribution", "gut_trace_contribution_weighted", "gut_pixel_error", "gut_trace_attributes",
-           "gut_trace_attributes_bwd")
+           "gut_trace_attributes_bwd", "gut_trace_surface")
 
 _lib = None
 
@@ -149,6 +151,7 @@ def load():
     lib.gut_trace_contribution_weighted.argtypes = [vp, vp, u32, i32, u32, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera), f_p, vp, vp]
     lib.gut_trace_attributes.argtypes = [vp, vp, u32, i32, u32, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera), i32, f_p, f_p]
     lib.gut_trace_attributes_bwd.argtypes = lib.gut_trace_attributes.argtypes
+    lib.gut_trace_surface.argtypes = [vp, vp, u32, i32, u32, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera), i32, C.c_float, f_p, vp, f_p]
     lib.gut_pixel_error.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, vp, vp]
     lib.gut_mcmc_perturb.argtypes = [vp, u32, f_p, f_p, C.c_float, C.c_uint64, C.c_uint64, f_p]
     lib.gut_collect_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]

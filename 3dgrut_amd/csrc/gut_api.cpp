@@ -1037,6 +1037,36 @@ struct AttributeGradForm {   // gut_trace_attributes_bwd: out_g
         gut::launch_attributes_bwd(s, o, (uint32_t)channels, out_grad, rows_grad, h->attr_grad_rows.p, h->attr_grad_max.as<uint32_t>());
     }
 };
+struct SurfaceForm {   // gut_trace_surface: one composited entry per pixel -> distance, id, weight [H,W], every element written
+    int32_t mode;
+    float level;
+    float min_transmittance;   // the handle's: the walk ends a ray below it
+    float* distance;
+    uint32_t* id;
+    float* weight;
+    int check(const char* name, const TraceView&) const {
+        if (mode != GUT_SURFACE_LEVEL && mode != GUT_SURFACE_MAX_WEIGHT)
+            return fail("%s: mode must be GUT_SURFACE_LEVEL (%d) or GUT_SURFACE_MAX_WEIGHT (%d), got %d", name, (int)GUT_SURFACE_LEVEL,
+                        (int)GUT_SURFACE_MAX_WEIGHT, mode);
+        if (mode == GUT_SURFACE_LEVEL && !(std::isfinite(level) && level > min_transmittance && level < 1.0f))
+            return fail("%s: level must be finite and inside (min_transmittance, 1) = (%g, 1), got %g", name, (double)min_transmittance,
+                        (double)level);
+        if (!distance) return fail("%s: d_distance is NULL", name);
+        if (((uintptr_t)distance & 3u) != 0) return fail("%s: d_distance must be 4-byte aligned", name);
+        if (((uintptr_t)id & 3u) != 0) return fail("%s: d_id must be 4-byte aligned", name);
+        if (((uintptr_t)weight & 3u) != 0) return fail("%s: d_weight must be 4-byte aligned", name);
+        return 0;
+    }
+    hipError_t nothing_walked(gut_handle, const TraceView& view) const {   // the no-hit values: 0.0f, 0xFFFFFFFF, 0.0f
+        const size_t bytes = sizeof(float) * (size_t)view.width * (size_t)view.height;
+        hipError_t e = hipMemsetAsync(distance, 0, bytes, view.stream);
+        if (e == hipSuccess && id) e = hipMemsetAsync(id, 0xFF, bytes, view.stream);
+        if (e == hipSuccess && weight) e = hipMemsetAsync(weight, 0, bytes, view.stream);
+        return e;
+    }
+    hipError_t scratch(gut_handle) const { return hipSuccess; }
+    void launch(gut_handle, hipStream_t s, const gut::WalkOperands& o) const { gut::launch_surface(s, o, mode, level, distance, id, weight); }
+};
 
 // The forward's walk once more over the cached forward's view, without colours, in the form `form`.  Reads the
 // forward's lists and depths, writes tile_order (every backward rebuilds it) and what the form writes.
@@ -1167,6 +1197,16 @@ int gut_trace_attributes_bwd(gut_handle h, void* stream_, uint32_t frame_number,
     return trace_walk_impl(h, "gut_trace_attributes_bwd",
                            view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
                            d_particle_density, AttributeGradForm{num_channels, d_out_grad, d_attributes_grad});
+}
+
+int gut_trace_surface(gut_handle h, void* stream_, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+                      const float* d_particle_density, int32_t width, int32_t height, const float* d_ray_origin,
+                      const float* d_ray_direction, const GutCamera* camera, int32_t mode, float level, float* d_distance,
+                      uint32_t* d_id, float* d_weight) {
+    // (the handle's settings are fixed at creation: read without the lock; a null handle is refused by the walk)
+    return trace_walk_impl(h, "gut_trace_surface",
+                           view_of(stream_, num_active_features, num_particles, width, height, d_ray_origin, d_ray_direction, camera),
+                           d_particle_density, SurfaceForm{mode, level, h ? h->cfg.min_transmittance : 0.0f, d_distance, d_id, d_weight});
 }
 
 // SplatRaster::trace with the four activated tensors the reference's Tracer hands to _Autograd (tracer.py:317-327) instead of

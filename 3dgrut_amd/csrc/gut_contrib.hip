@@ -15,6 +15,8 @@
 //     Sink(args, shared, v, pix, inside)   per-lane set-up from the pixel
 //     stage(tid, id)                       per-thread staging of the chunk's entry tid (its own barrier-protected LDS)
 //     accept(w, j, wave, lane)             per evaluated entry j of the chunk, all 64 lanes of the wave, w = 0 where not composited
+//     kWantsHit, hit(w, hit_t, t_after, id)  at the place where the lane's pixel composites an entry: its weight, its hit distance
+//                                          as `entry` formed it and |T| behind it (compiled in for a sink that asks for it only)
 //     kFlush, flush(j, s_id)               after a chunk's walk, behind a barrier, thread j < the chunk's count
 //     finish(v, pix, inside)               after the tile's walk
 //
@@ -41,6 +43,11 @@
 // the image count as 0), every w * g[k] is rounded on its own and goes through the tree, per-wave LDS slots and the wave order, and
 // the flush adds round(sum * 2^s_k) with a 64-bit integer atomic into a scratch row of the handle's, s_k a power of two from the
 // largest |g[k]| of the plane (k_plane_max_abs).  k_grad_rows turns the integers into the caller's float rows.
+//
+// SurfaceSink<kMode> (gut_trace_surface, §18) answers "where": per pixel ONE composited entry's hit distance, id and weight, chosen
+// in the lane's own registers while the walk passes — the first entry behind which |T| is below a level (GUT_SURFACE_LEVEL; 0.5: the
+// median), or the entry of the largest weight (GUT_SURFACE_MAX_WEIGHT).  The only sink that takes the hit hook.  A choice per pixel
+// from that pixel's entries alone: no reduction across lanes, no LDS, no flush, no atomics; every pixel of the image is written.
 #include "gut_internal.h"
 #include "gut_render_common.h"
 
@@ -73,6 +80,7 @@ struct ScoreSink {
     using Args = ScoreArgs;
     struct Shared : PlainSlots<kPlain>, WeightedSlots<kWeighted> { uint32_t cnt[kWaves][kBlock]; };
     static constexpr bool kFlush = true;
+    static constexpr bool kWantsHit = false;
 
     const Args& a;
     Shared& sh;
@@ -155,6 +163,7 @@ struct AttributeSink {
     struct Shared { Slot attr[kBlock]; };   // entry j's values of the channel group
     // (nothing to flush; the barrier at the head of the chunk loop stands between this chunk's reads and the next staging)
     static constexpr bool kFlush = false;
+    static constexpr bool kWantsHit = false;
 
     const Args& a;
     Shared& sh;
@@ -242,6 +251,7 @@ struct GradientSink {
         uint8_t hit[kWaves][kBlock];
     };
     static constexpr bool kFlush = true;
+    static constexpr bool kWantsHit = false;
 
     const Args& a;
     Shared& sh;
@@ -329,6 +339,51 @@ __global__ __launch_bounds__(kBlock) void k_grad_rows(const long long* __restric
     float* const row = out + (size_t)i * stride;
     for (uint32_t k = 0; k < cols; ++k) row[k] = __ll2float_rn(q[k]) * pow2f(-grad_scale_exponent(max_bits[k], tiles));
 }
+
+// ---- SurfaceSink: one composited entry per pixel, chosen by a level of the transmittance or by the largest weight ---------------------
+struct SurfaceArgs {
+    float* distance;   // [H,W]
+    uint32_t* id;      // [H,W] or null
+    float* weight;     // [H,W] or null
+    float level;       // GUT_SURFACE_LEVEL: the transmittance below which the pixel's surface lies
+};
+
+template <int kMode>
+struct SurfaceSink {
+    static_assert(kMode == GUT_SURFACE_LEVEL || kMode == GUT_SURFACE_MAX_WEIGHT, "one of the two modes");
+    using Args = SurfaceArgs;
+    struct Shared {};   // (the state is the lane's own)
+    static constexpr bool kFlush = false;
+    static constexpr bool kWantsHit = true;
+
+    const Args& a;
+    // the pixel's choice so far, carried across the chunks; kInvalid: none yet (a list holds no such id)
+    float dist = 0.0f, wgt = 0.0f;
+    uint32_t gid = kInvalid;
+
+    __device__ __forceinline__ SurfaceSink(const Args& args, Shared&, const ViewParams&, size_t, bool) : a(args) {}
+    __device__ __forceinline__ void stage(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void accept(float, uint32_t, uint32_t, uint32_t) {}
+    // level: the first entry, in list order, behind which |T| < level, and nothing after it.  Largest weight: a strictly greater
+    // weight replaces the choice, so of equal weights the first in list order stays (every composited w is above 0)
+    __device__ __forceinline__ void hit(const float w, const float hit_t, const float t_after, const uint32_t id) {
+        const bool take = kMode == GUT_SURFACE_LEVEL ? (gid == kInvalid && t_after < a.level) : (w > wgt);
+        if (take) {
+            dist = hit_t;
+            wgt = w;
+            gid = id;
+        }
+    }
+    __device__ __forceinline__ void flush(uint32_t, const uint32_t*) {}
+    // every pixel of the image, the no-hit values where nothing was chosen: the planes need no initialisation
+    __device__ __forceinline__ void finish(const ViewParams&, size_t pix, bool inside) {
+        if (inside) {
+            a.distance[pix] = dist;
+            if (a.id) a.id[pix] = gid;
+            if (a.weight) a.weight[pix] = wgt;
+        }
+    }
+};
 
 // ---- the walk --------------------------------------------------------------------------------------------------------------------
 template <class Sink>
@@ -444,6 +499,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_walk(const WalkOperands o, const 
                             T *= (1.0f - alpha);
                             wout = w;
                             if (T < c.min_transmittance) T = -T;   // the ray ends here
+                            if constexpr (Sink::kWantsHit) sink.hit(w, hit_t, fabsf(T), s_id[j]);
                         }
                     }
                 }
@@ -516,6 +572,12 @@ void launch_attributes(hipStream_t s, const WalkOperands& o, uint32_t num_channe
         const auto launch = cols == 1u ? launch_walk<AttributeSink<1>> : launch_walk<AttributeSink<4>>;
         launch(s, o, {attrs + first, out + (size_t)first * plane_stride, num_channels, cols, aligned && cols == 4u ? 1u : 0u});
     }
+}
+
+void launch_surface(hipStream_t s, const WalkOperands& o, int mode, float level, float* distance, uint32_t* id, float* weight) {
+    if (o.tiles == 0) return;
+    const auto launch = mode == GUT_SURFACE_LEVEL ? launch_walk<SurfaceSink<GUT_SURFACE_LEVEL>> : launch_walk<SurfaceSink<GUT_SURFACE_MAX_WEIGHT>>;
+    launch(s, o, {distance, id, weight, level});
 }
 
 void launch_attributes_bwd(hipStream_t s, const WalkOperands& o, uint32_t num_channels, const float* out_grad, float* attrs_grad,

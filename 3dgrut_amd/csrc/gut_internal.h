@@ -263,6 +263,10 @@ void launch_attributes(hipStream_t s, const WalkOperands& o, uint32_t num_channe
 // 32 bytes per particle; max_bits: scratch of four words
 void launch_attributes_bwd(hipStream_t s, const WalkOperands& o, uint32_t num_channels, const float* out_grad, float* attrs_grad,
                            void* rows_q, uint32_t* max_bits);
+// the same walk choosing one composited entry per pixel: mode GUT_SURFACE_LEVEL (the first entry behind which the
+// transmittance is below `level`) or GUT_SURFACE_MAX_WEIGHT; its hit distance, id and weight to [H,W] planes, every element written
+// (0.0f, 0xFFFFFFFF, 0.0f where nothing was chosen); id and weight may be null
+void launch_surface(hipStream_t s, const WalkOperands& o, int mode, float level, float* distance, uint32_t* id, float* weight);
 // sorted (k_buffer_size = K > 0) compositor variant, gut_render_sorted.hip
 void launch_render_sorted(hipStream_t s, const CompositorOperands& o, int K, const uint32_t* d_num_intersections, const RenderImages& out);
 void launch_render_sorted_bwd(hipStream_t s, const CompositorOperands& o, int K, const BwdUpstream& up, float* grad16, bool reference_undo);

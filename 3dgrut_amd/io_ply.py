@@ -37,8 +37,27 @@ def write_ply(path, positions, density_logit, rotation_raw, log_scale, features4
         fh.write(np.ascontiguousarray(table).tobytes())
 
 
+def write_point_cloud(path, xyz, rgb):
+    """A plain point cloud, binary little-endian: per vertex float32 x y z and uchar red green blue.  xyz [P,3]; rgb [P,3] in
+    [0, 1] (clamped, rounded to the nearest of 255 steps).  read_ply reads it back as dict(positions, rgb uint8)."""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.asarray(rgb, np.float32).reshape(-1, 3)
+    if xyz.shape[0] != rgb.shape[0]:
+        raise ValueError(f"{xyz.shape[0]} points and {rgb.shape[0]} colours")
+    table = np.zeros(xyz.shape[0], dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    table["x"], table["y"], table["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    q = np.rint(np.clip(np.nan_to_num(rgb), 0.0, 1.0) * 255.0).astype(np.uint8)
+    table["red"], table["green"], table["blue"] = q[:, 0], q[:, 1], q[:, 2]
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % xyz.shape[0]
+    header += "".join(f"property float {a}\n" for a in "xyz") + "".join(f"property uchar {a}\n" for a in ("red", "green", "blue")) + "end_header\n"
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(table.tobytes())
+
+
 def read_ply(path):
-    """Returns dict(positions, density_logit[N,1], rotation_raw[N,4], log_scale[N,3], features48[N,48]) (pre-activation)."""
+    """Returns dict(positions, density_logit[N,1], rotation_raw[N,4], log_scale[N,3], features48[N,48]) (pre-activation); of a
+    plain point cloud (x y z red green blue and no Gaussian attributes, write_point_cloud) dict(positions, rgb uint8 [N,3])."""
     with open(path, "rb") as fh:
         if fh.readline().strip() != b"ply":
             raise ValueError("not a PLY file")
@@ -67,6 +86,10 @@ def read_ply(path):
             raise ValueError(f"unsupported PLY format {fmt!r} (binary_little_endian only)")
         data = np.frombuffer(fh.read(n * np.dtype(props).itemsize), dtype=np.dtype(props), count=n)
     col = lambda k: np.asarray(data[k], np.float32)
+    names = [p for p, _ in props]
+    if all(c in names for c in ("red", "green", "blue")) and not any(p.startswith(("f_rest_", "f_dc_", "scale_", "rot")) for p in names):
+        return dict(positions=np.stack([col("x"), col("y"), col("z")], 1),
+                    rgb=np.stack([np.asarray(data[c]).astype(np.uint8) for c in ("red", "green", "blue")], 1))
     rest = sorted((p for p, _ in props if p.startswith("f_rest_")), key=lambda s: int(s.split("_")[-1]))
     if len(rest) != 3 * _N_SPEC:
         raise ValueError(f"expected {3 * _N_SPEC} f_rest_* properties (SH degree 3), found {len(rest)}")

@@ -523,6 +523,42 @@ class SplatRaster:
                    W, H, ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), k, _ptr(out_grad, n), _ptr(out, n))
         return out
 
+    def trace_surface(self, frame_number, num_active_features, particle_density, ray_ori, ray_dir, sensor_params, ts_start, ts_end,
+                      pose_start, pose_end, mode="level", level=0.5, with_id=True, with_weight=False, out=None):
+        """The surface of the cached forward's view (gut_trace_surface): per pixel ONE of the Gaussians the forward
+        composited there.  mode "level": the first, in list order, behind which the transmittance is below `level` (0.5: the median
+        distance; level inside (min_transmittance, 1)); mode "max_weight": the one with the largest blending weight.  Returns
+        (distance, id, weight): distance float32 [H,W], the Gaussian's hit distance along the ray, 0 where nothing was chosen; id
+        int64 [H,W] with -1 for none (None without with_id); weight float32 [H,W], its blending weight (None without with_weight).
+        `out`: (distance, id, weight) to write into, contiguous [H,W] tensors on the rays' GPU, float32, int32 (the kernel's word;
+        the returned id is its int64 copy) and float32, None where not asked for.  Every element is written.  Follows any forward on
+        this handle, consumes nothing, and may be followed by any backward, contribution or attribute call.  Unsorted variant at
+        kernel degree 2 only.  particle_density: the [N,12] rows of the forward, or an int N after a *_fields forward."""
+        ray_ori, ray_dir, H, W, dev = self._rays(ray_ori, ray_dir)
+        rows, n = _density_rows(particle_density)
+        modes = {"level": _capi.SURFACE_LEVEL, "max_weight": _capi.SURFACE_MAX_WEIGHT}
+        if mode not in modes:
+            raise RuntimeError(f"[3dgut] surface mode: one of {sorted(modes)}, got {mode!r}")
+        if out is None:
+            dist = torch.empty((H, W), dtype=torch.float32, device=dev)
+            ids = torch.empty((H, W), dtype=torch.int32, device=dev) if with_id else None
+            wgt = torch.empty((H, W), dtype=torch.float32, device=dev) if with_weight else None
+        else:
+            if not (isinstance(out, (tuple, list)) and len(out) == 3):
+                raise RuntimeError("[3dgut] surface output: a (distance, id, weight) triple")
+            dist, ids, wgt = out
+            _require_tensor(dist, torch.float32, (H, W), dev, f"[3dgut] surface distance: a contiguous float32 tensor [{H}, {W}] on the rays' GPU")
+            if (ids is not None) != bool(with_id) or (wgt is not None) != bool(with_weight):
+                raise RuntimeError("[3dgut] surface output: id and weight tensors exactly where with_id / with_weight ask for them")
+            if with_id:
+                _require_tensor(ids, torch.int32, (H, W), dev, f"[3dgut] surface id: a contiguous int32 tensor [{H}, {W}] on the rays' GPU")
+            if with_weight:
+                _require_tensor(wgt, torch.float32, (H, W), dev, f"[3dgut] surface weight: a contiguous float32 tensor [{H}, {W}] on the rays' GPU")
+        cam = self._camera(sensor_params, ts_start, ts_end, pose_start, pose_end)
+        self._call("trace_surface", self._lib.gut_trace_surface, dev, frame_number, int(num_active_features), n, _ptr(rows), W, H,
+                   ray_ori.data_ptr(), ray_dir.data_ptr(), C.byref(cam), modes[mode], float(level), dist.data_ptr(), _ptr(ids), _ptr(wgt))
+        return dist, (ids.to(torch.int64) if with_id else None), wgt
+
     def set_regularisation(self, reg):
         """The NEXT optimiser step on the handle (optimize_rows_without_gradient + optimize_after_bwd, or
         finish_optimizer_step_without_gradient) adds the MCMC regularisers' gradient to every row it updates and writes the loss

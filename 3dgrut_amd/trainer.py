@@ -71,6 +71,13 @@ round-robin over those views, and every held-out view that has a map is scored b
 directory: features.npy (float32 [N,K]) and renders_features/<stem>.npy (the held-out views' rendered planes).  The model is not
 changed.  One GPU only; lr and iterations are UNTUNED on real captures.
 
+`points.enabled` (default off; `--export-points`) exports the scene as points (surface.py), after train(), the
+compaction, the selection and the feature fitting: the median surface point (the Gaussian at which the transmittance first drops
+below `level`, 0.5) of every `stride`-th pixel of every training view, at its refined pose, coloured with the rendered pixel, one
+point per cell of edge `voxel` (0: all).  With an output directory: points.ply (x y z red green blue) and renders_depth/<stem>.npy,
+the median distance of every held-out view (float32 [H,W], 0 where there is no surface).  The model is not changed.  One GPU only;
+stride and voxel are UNTUNED on real captures.
+
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
                                  [--refine-poses [--pose-lr-translation X] [--pose-lr-rotation R]]
@@ -79,6 +86,7 @@ changed.  One GPU only; lr and iterations are UNTUNED on real captures.
                                  [--densify-by gradient|error [--densify-grow-fraction F] [--densify-views K]]
                                  [--select-by-masks [SUFFIX] [--select-threshold T]]
                                  [--fit-features [SUFFIX] [--feature-iterations K] [--feature-lr X]]
+                                 [--export-points [--points-level T] [--points-stride S] [--points-voxel V]]
 """
 import argparse
 import copy
@@ -95,6 +103,7 @@ from . import features as features_mod
 from . import exposure as exposure_mod
 from . import losses, pose_align, pose_refine
 from . import selection as selection_mod
+from . import surface as surface_mod
 from .evaluate import _check_batch, evaluate
 
 # configs/base_gs.yaml + configs/strategy/gs.yaml: the keys this trainer reads
@@ -138,6 +147,9 @@ GS_CONFIG = {
     # frozen (features.py), after training, compaction and selection; scored on the held-out views' maps.  lr and iterations are
     # untuned on real captures.
     "features": dict(features_mod.DEFAULTS),
+    # not a reference key: the scene as points (surface.py), after everything above: the median surface points of the training views,
+    # fused; the held-out views' median distance planes.  stride and voxel are UNTUNED on real captures.
+    "points": dict(surface_mod.DEFAULTS),
     "strategy": {"method": "GSStrategy",
                  # criterion and error are not reference keys: "error" grows, at every densify step, the grow_fraction of the rows
                  # that are responsible for the most rendering error over `views` training views (0: all of them), instead of
@@ -200,6 +212,7 @@ def resolve_config(conf):
     contribution_mod.check_config(out["compaction"])
     selection_mod.check_config(out["selection"])
     features_mod.check_config(out["features"])
+    surface_mod.check_config(out["points"])
     check_densify_config(out)
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
@@ -438,6 +451,8 @@ class Trainer:
             raise ValueError("selection: data-parallel selection is out of scope (the stepper's world_size must be 1)")
         if c["features"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
             raise ValueError("features: data-parallel feature fitting is out of scope (the stepper's world_size must be 1)")
+        if c["points"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
+            raise ValueError("points: data-parallel point export is out of scope (the stepper's world_size must be 1)")
         self.densify_criterion = (c["strategy"].get("densify") or {}).get("criterion", "gradient")
         if self.densify_criterion == "error":
             if int(getattr(stepper, "world_size", 1)) > 1:
@@ -850,9 +865,32 @@ class Trainer:
         self.stats.update(out)
         return out
 
+    def export_points(self):
+        """The `points` block, after train(), compact(), select_by_masks() and fit_features(): fuses the median surface points of
+        the training views (at their refined poses) into one coloured cloud.  Writes points.ply and renders_depth/<stem>.npy (the
+        held-out views' median distance planes) into the output directory when there is one.  Fills and returns the points_*
+        statistics; the model is left as it is."""
+        blk = self.conf["points"]
+        level = float(blk["level"])
+        renderer = surface_mod.SurfaceRenderer(self.model, self.tracer)
+        batches = [b if self.refiner is None else self.refiner.begin(v, b) for v, b in enumerate(self.train_batches)]
+        xyz, rgb, _ = surface_mod.fuse_points(renderer, batches, level=level, stride=int(blk["stride"]), voxel=float(blk["voxel"]))
+        out_dir = self._out_dir()
+        if out_dir is not None:
+            from .io_ply import write_point_cloud
+            renders = os.path.join(out_dir, "renders_depth")
+            os.makedirs(renders, exist_ok=True)
+            write_point_cloud(os.path.join(out_dir, "points.ply"), xyz.cpu().numpy(), rgb.cpu().numpy())
+            for i, batch in enumerate(self.test_batches):
+                stem = getattr(batch, "image_stem", None) or f"{i:05d}"
+                np.save(os.path.join(renders, stem + ".npy"), renderer.render(batch, mode="level", level=level)["distance"].cpu().numpy())
+        out = dict(points_n=int(xyz.shape[0]), points_views=len(batches), points_level=level)
+        self.stats.update(out)
+        return out
+
     def run(self):
-        """train(), (compaction.enabled) compact(), (selection.enabled) select_by_masks(), (features.enabled) fit_features(), print
-        the statistics table, then (test_last) save ckpt_last.pt and evaluate the test split."""
+        """train(), (compaction.enabled) compact(), (selection.enabled) select_by_masks(), (features.enabled) fit_features(),
+        (points.enabled) export_points(), print the statistics table, then (test_last) save ckpt_last.pt and evaluate the test split."""
         stats = self.train()
         if self.conf["compaction"]["enabled"]:
             self.compact()
@@ -860,6 +898,8 @@ class Trainer:
             self.select_by_masks()
         if self.conf["features"]["enabled"]:
             self.fit_features()
+        if self.conf["points"]["enabled"]:
+            self.export_points()
         print("Training Statistics: " + json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in stats.items()}), flush=True)
         if self.conf["test_last"] and self.test_batches:
             self.save_checkpoint(last=True)
@@ -910,6 +950,13 @@ def build_parser():
                          "the model frozen and score them on the held-out views' maps (features.enabled, features.suffix)")
     ap.add_argument("--feature-iterations", type=int, default=None, metavar="K", help="features.iterations (untuned on real captures)")
     ap.add_argument("--feature-lr", type=float, default=None, metavar="X", help="features.lr (untuned on real captures)")
+    ap.add_argument("--export-points", action="store_true",
+                    help="after training, export the scene as points: the median surface points of the training views, fused into "
+                         "points.ply, and the held-out views' median distance planes (points.enabled)")
+    ap.add_argument("--points-level", type=float, default=None, metavar="T", help="points.level: the transmittance level, 0.5 = the median")
+    ap.add_argument("--points-stride", type=int, default=None, metavar="S", help="points.stride: every S-th pixel (untuned on real captures)")
+    ap.add_argument("--points-voxel", type=float, default=None, metavar="V",
+                    help="points.voxel: one point per cell of this edge length, 0 = all (untuned on real captures)")
     ap.add_argument("--densify-by", choices=("gradient", "error"), default=None,
                     help="strategy.densify.criterion: error = grow the rows responsible for the most rendering error (default: gradient)")
     ap.add_argument("--densify-grow-fraction", type=float, default=None, metavar="F", help="strategy.densify.error.grow_fraction")
@@ -959,6 +1006,13 @@ def config_from_args(a):
         conf["features"]["iterations"] = a.feature_iterations
     if a.feature_lr is not None:
         conf["features"]["lr"] = a.feature_lr
+    conf["points"]["enabled"] = bool(a.export_points)
+    if a.points_level is not None:
+        conf["points"]["level"] = a.points_level
+    if a.points_stride is not None:
+        conf["points"]["stride"] = a.points_stride
+    if a.points_voxel is not None:
+        conf["points"]["voxel"] = a.points_voxel
     densify = {}
     if a.densify_by is not None:
         densify["criterion"] = a.densify_by
@@ -993,6 +1047,9 @@ def main(argv=None):
                 fmap = scene.load_feature_map(i, conf["features"]["suffix"], size=(int(b.rays_ori.shape[2]), int(b.rays_ori.shape[1])))
                 b.feature_map = None if fmap is None else torch.as_tensor(fmap, device=b.rays_ori.device)
                 b.image_stem = os.path.splitext(os.path.basename(scene.images[i].name))[0]
+    if conf["points"]["enabled"]:         # the names of the held-out views' distance planes
+        for i, b in enumerate(vb):
+            b.image_stem = os.path.splitext(os.path.basename(test.images[i].name))[0]
     trainer = Trainer(conf, init, tb, val_batches=vb, test_batches=vb, scene_extent=train.cameras_extent)
     res = trainer.run()
     test_res = res["test"]

@@ -50,7 +50,7 @@ extern "C" {
  * gut_trace_contribution, a new entry point: every other call queues what it queued before; gut_trace_contribution_weighted and
  * gut_pixel_error, new entry points: gut_trace_contribution and every other call queue what they queued before; added under 6
  * without a bump: gut_trace_attributes, a new entry point: every other call queues what it queued before; gut_trace_attributes_bwd,
- * likewise). */
+ * likewise; gut_trace_surface, likewise). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -749,6 +749,32 @@ int gut_trace_attributes_bwd(gut_handle h, void* stream, uint32_t frame_number, 
                              const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
                              int32_t num_channels /* 1..64 */, const float* d_out_grad /* [num_channels, H, W] */,
                              float* d_attributes_grad /* [N, num_channels] row-major, fully written */);
+
+/* ---- The surface of a view: a distance and an id per pixel (new functionality, the reference has none) ----
+ * Every other form of the walk answers "how much"; gut_trace_surface answers "where".  Per pixel it chooses ONE of the Gaussians the
+ * forward composited there and writes that Gaussian's hit distance along the ray (the hitT of the forward's distance plane, which
+ * is the un-normalised mean sum w * hitT and lies between surfaces), its index and its blending weight w = T_before * alpha:
+ *     GUT_SURFACE_LEVEL       the first, in the order of the tile's list, behind which the transmittance T is below `level`
+ *                             (T counted after the Gaussian; level 0.5: the median distance).  Later Gaussians change nothing.
+ *     GUT_SURFACE_MAX_WEIGHT  the one with the largest w; of equal weights the first in the order of the list.
+ * A pixel in which nothing is chosen (nothing composited; in level mode, T never below the level) gets distance 0.0f, id
+ * 0xFFFFFFFF and weight 0.0f.  Every element of the given planes is written, so they need no initialisation; d_id and d_weight may
+ * be NULL and do not change d_distance.  The choice is made per pixel in the lane's registers while the walk passes: no reduction,
+ * no atomics, identical inputs give identical bytes; the weight is the very w gut_trace_contribution takes the maximum of.  Scope,
+ * walk and refusals are gut_trace_contribution's: it follows any forward on the same handle and stream, walks what that forward
+ * walked by the forward's arithmetic, consumes nothing and may be followed by any backward or walk; unsorted variant at kernel
+ * degree 2 only; refused after gut_optimize_rows_without_gradient.  One launch besides the tile order; with num_particles == 0 or a
+ * forward without intersections the planes are filled with the no-hit values by memsets on the stream (0xFF bytes for d_id) and
+ * nothing is walked.  Additionally refused, on the host before anything is queued: a mode that is neither of the two; in level mode
+ * a level that is not finite or not inside (min_transmittance, 1) (the walk ends a ray below min_transmittance: a level there is
+ * never crossed); d_distance NULL; a given plane not 4-byte aligned.  Render-only: nothing has a gradient.  Not part of the kernel
+ * timers. */
+enum { GUT_SURFACE_LEVEL = 0, GUT_SURFACE_MAX_WEIGHT = 1 };
+int gut_trace_surface(gut_handle h, void* stream, uint32_t frame_number, int32_t num_active_features, uint32_t num_particles,
+                      const float* d_particle_density /* NULL: the packed rows */, int32_t width, int32_t height,
+                      const float* d_ray_origin, const float* d_ray_direction, const GutCamera* camera,
+                      int32_t mode /* GUT_SURFACE_* */, float level /* GUT_SURFACE_LEVEL only */,
+                      float* d_distance /* [H,W], fully written */, uint32_t* d_id /* [H,W] or NULL */, float* d_weight /* [H,W] or NULL */);
 
 /* ---- Per-view exposure in the fused loss (new functionality, the reference has none) ----
  * gut_photometric_loss_exposure is the fused loss of gut_photometric_loss[_masked | _background] on the AFFINE image of a view:

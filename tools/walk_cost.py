@@ -1,4 +1,4 @@
-"""Dev probe (GPU): what the forms of the contribution walk (DESIGN.md §13–§15, §17) cost on a bench workload, next to the forward
+"""Dev probe (GPU): what the forms of the contribution walk (DESIGN.md §13–§15, §17, §18) cost on a bench workload, next to the forward
 compositor they re-walk.
 
 Per iteration: a forward of one of eight orbit views on frozen, packed rows (FrozenModel's), then every requested form, each timed
@@ -12,8 +12,9 @@ kernel timers (gut_kernel_times: `render`).  Prints one JSON line: the medians o
     attributes      gut_trace_attributes at every K of --channels (one walk per group of four channels)
     attributes_bwd  gut_trace_attributes_bwd at every K of --channels (per group two memsets, the planes' maxima, the walk and the
                     pass over the rows)
+    surface         gut_trace_surface in both modes (level 0.5 and the largest weight), all three planes written
 
-    python tools/walk_cost.py [--forms plain,weighted,attributes,attributes_bwd] [--channels 1,4,8]
+    python tools/walk_cost.py [--forms plain,weighted,attributes,attributes_bwd,surface] [--channels 1,4,8]
                               [--workload bicycle_like_6M_1237x822] [--num-gaussians N] [--iterations 48] [--warmup 8]
 """
 import argparse
@@ -26,7 +27,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-FORMS = ("plain", "weighted", "attributes", "attributes_bwd")
+FORMS = ("plain", "weighted", "attributes", "attributes_bwd", "surface")
 
 
 def spread(key, ms):
@@ -82,6 +83,8 @@ def main():
     planes = {k: torch.empty((k, H, W), dtype=torch.float32, device=dev) for k in channels}
     cots = {k: torch.rand((k, H, W), generator=gen, device=dev) * 2.0 - 1.0 for k in channels}
     grads = {k: torch.empty((n, k), dtype=torch.float32, device=dev) for k in channels}
+    surf = (torch.empty((H, W), dtype=torch.float32, device=dev), torch.empty((H, W), dtype=torch.int32, device=dev),
+            torch.empty((H, W), dtype=torch.float32, device=dev))
     times = {}   # key -> the timed iterations' milliseconds
 
     def timed(fn):
@@ -106,6 +109,10 @@ def main():
                 events[f"attributes_k{k}"] = timed(lambda: raster.trace_attributes(0, 3, act, rows[k], ro_t, rd_t, *cam, out=planes[k]))
             if "attributes_bwd" in forms:
                 events[f"attributes_bwd_k{k}"] = timed(lambda: raster.trace_attributes_bwd(0, 3, act, cots[k], ro_t, rd_t, *cam, out=grads[k]))
+        if "surface" in forms:
+            for mode in ("level", "max_weight"):
+                events[f"surface_{mode}"] = timed(lambda: raster.trace_surface(0, 3, act, ro_t, rd_t, *cam, mode=mode, level=0.5,
+                                                                               with_id=True, with_weight=True, out=surf))
         torch.cuda.synchronize(dev)
         if it >= a.warmup:
             times.setdefault("render", []).append(raster.kernel_times()["render"])
@@ -125,7 +132,7 @@ def main():
                    weighted_over_plain=statistics.median(times["weighted"]) / statistics.median(times["contribution"]),
                    weighted_over_render=statistics.median(times["weighted"]) / render, rows_with_error=int((weighted > 0).sum()))
     for key in times:
-        if key.startswith("attributes"):
+        if key.startswith(("attributes", "surface")):
             out.update(**spread(key, times[key]), **{f"{key}_over_render": statistics.median(times[key]) / render})
     print(json.dumps(out), flush=True)
 
