@@ -91,6 +91,21 @@ class GutContribution(C.Structure):
 
 SURFACE_LEVEL, SURFACE_MAX_WEIGHT = 0, 1   # gut_hip.h, GUT_SURFACE_*
 
+TSDF_MAX_VIEWS = 8   # gut_hip.h, GUT_TSDF_MAX_VIEWS
+
+
+class GutTsdfGrid(C.Structure):
+    """The TSDF volume (gut_hip.h): the box and the caller's state tensors, None = no colours."""
+    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float), ("dims", C.c_int32 * 3), ("truncation", C.c_float),
+                ("d_acc", C.c_void_p), ("d_cnt", C.c_void_p), ("d_rgb_sum", C.c_void_p), ("d_rgb_cnt", C.c_void_p)]
+
+
+class GutTsdfView(C.Structure):
+    """One view of gut_tsdf_integrate: the camera (host), the planes (device; rgba and ray origin may be None)."""
+    _fields_ = [("camera", C.POINTER(GutCamera)), ("width", C.c_int32), ("height", C.c_int32), ("d_distance", C.c_void_p),
+                ("d_rgba", C.c_void_p), ("d_ray_origin", C.c_void_p)]
+
+
 EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_trace_bwd", "gut_collect_times",
            "gut_get_stats", "gut_debug_buffer", "gut_debug_copy", "gut_kernel_times", "gut_kernel_times_mean", "gut_last_error", "gut_abi_version",
            "gut_ssim_workspace_bytes", "gut_ssim_forward", "gut_ssim_backward",
@@ -106,7 +121,7 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_photometric_exposure_workspace_bytes", "gut_photometric_loss_exposure", "gut_exposure_adam_step",
            "gut_image_metrics_cc_workspace_bytes", "gut_image_metrics_cc", "gut_photometric_loss_run", "gut_trace_bwd_pose",
            "gut_trace_contribution", "gut_trace_contribution_weighted", "gut_pixel_error", "gut_trace_attributes",
-           "gut_trace_attributes_bwd", "gut_trace_surface")
+           "gut_trace_attributes_bwd", "gut_trace_surface", "gut_tsdf_integrate", "gut_surface_nets_count", "gut_surface_nets_emit")
 
 _lib = None
 
@@ -152,6 +167,9 @@ def load():
     lib.gut_trace_attributes.argtypes = [vp, vp, u32, i32, u32, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera), i32, f_p, f_p]
     lib.gut_trace_attributes_bwd.argtypes = lib.gut_trace_attributes.argtypes
     lib.gut_trace_surface.argtypes = [vp, vp, u32, i32, u32, f_p, i32, i32, f_p, f_p, C.POINTER(GutCamera), i32, C.c_float, f_p, vp, f_p]
+    lib.gut_tsdf_integrate.argtypes = [vp, C.POINTER(GutTsdfGrid), i32, C.POINTER(GutTsdfView)]
+    lib.gut_surface_nets_count.argtypes = [vp, C.POINTER(GutTsdfGrid), u32, vp, vp]
+    lib.gut_surface_nets_emit.argtypes = [vp, C.POINTER(GutTsdfGrid), u32, vp, vp, vp, vp, vp, vp, vp]
     lib.gut_pixel_error.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, vp, vp]
     lib.gut_mcmc_perturb.argtypes = [vp, u32, f_p, f_p, C.c_float, C.c_uint64, C.c_uint64, f_p]
     lib.gut_collect_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]

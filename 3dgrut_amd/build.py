@@ -26,6 +26,7 @@ UNITS = [
     ("gut_ssim.hip", ["-ffp-contract=fast"]),
     ("gut_train.hip", ["-ffp-contract=fast"]),
     ("gut_pose.hip", ["-ffp-contract=off"]),
+    ("gut_fuse.hip", ["-ffp-contract=off"]),   # a voxel's pixel is an integer decision of K1's projection arithmetic
     ("gut_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 

@@ -1375,6 +1375,118 @@ int gut_pose_adam_step(void* stream_, const float* d_grad8, float* d_m6, float* 
     return 0;
 }
 
+// ---- the scene as a mesh (gut_fuse.hip): handle-free; everything is checked here, before anything is queued ----
+namespace {
+
+bool misaligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
+
+int build_fuse_grid(const char* who, const GutTsdfGrid* grid, gut::FuseGrid* g) {
+    if (!grid) return fail("%s: null grid", who);
+    if (!(std::isfinite(grid->voxel) && grid->voxel > 0.0f)) return fail("%s: the voxel edge must be finite and positive, got %g", who, (double)grid->voxel);
+    if (!(std::isfinite(grid->truncation) && grid->truncation > 0.0f))
+        return fail("%s: the truncation must be finite and positive, got %g", who, (double)grid->truncation);
+    uint64_t total = 1;
+    for (int i = 0; i < 3; ++i) {
+        if (!std::isfinite(grid->origin[i])) return fail("%s: the grid origin must be finite", who);
+        if (grid->dims[i] < 1) return fail("%s: dims must be >= 1, got (%d, %d, %d)", who, grid->dims[0], grid->dims[1], grid->dims[2]);
+        total *= (uint64_t)grid->dims[i];
+        if (total > (1ull << 30)) return fail("%s: dims (%d, %d, %d) exceed 2^30 voxels", who, grid->dims[0], grid->dims[1], grid->dims[2]);
+    }
+    if (!grid->d_acc || !grid->d_cnt) return fail("%s: null d_acc or d_cnt", who);
+    if ((grid->d_rgb_sum == nullptr) != (grid->d_rgb_cnt == nullptr)) return fail("%s: d_rgb_sum and d_rgb_cnt come together or not at all", who);
+    if (misaligned4(grid->d_acc) || misaligned4(grid->d_cnt) || misaligned4(grid->d_rgb_sum) || misaligned4(grid->d_rgb_cnt))
+        return fail("%s: a state pointer is not 4-byte aligned", who);
+    for (int i = 0; i < 3; ++i) g->origin[i] = grid->origin[i];
+    g->voxel = grid->voxel;
+    g->X = grid->dims[0];
+    g->Y = grid->dims[1];
+    g->Z = grid->dims[2];
+    g->truncation = grid->truncation;
+    g->acc = grid->d_acc;
+    g->cnt = grid->d_cnt;
+    g->rgb_sum = grid->d_rgb_sum;
+    g->rgb_cnt = grid->d_rgb_cnt;
+    return 0;
+}
+
+}  // namespace
+
+int gut_tsdf_integrate(void* stream_, const GutTsdfGrid* grid, int32_t n_views, const GutTsdfView* views) {
+    static_assert(sizeof(gut::FuseViews) + sizeof(gut::FuseGrid) + 16 <= 4096, "the view records travel as kernel arguments");
+    gut::FuseGrid g;
+    if (int rc = build_fuse_grid("gut_tsdf_integrate", grid, &g)) return rc;
+    if (n_views < 1 || n_views > GUT_TSDF_MAX_VIEWS) return fail("gut_tsdf_integrate: n_views must be 1 .. %d, got %d", GUT_TSDF_MAX_VIEWS, n_views);
+    if (!views) return fail("gut_tsdf_integrate: null views");
+    gut::FuseViews fv;
+    memset(&fv, 0, sizeof(fv));
+    for (int n = 0; n < n_views; ++n) {
+        const GutTsdfView& in = views[n];
+        const GutCamera* cam = in.camera;
+        if (!cam) return fail("gut_tsdf_integrate: view %d: null camera", n);
+        if (in.width < 1 || in.height < 1) return fail("gut_tsdf_integrate: view %d: width and height must be >= 1, got %d x %d", n, in.width, in.height);
+        if (!in.d_distance) return fail("gut_tsdf_integrate: view %d: null d_distance", n);
+        if (misaligned4(in.d_distance) || misaligned4(in.d_rgba) || misaligned4(in.d_ray_origin))
+            return fail("gut_tsdf_integrate: view %d: a plane is not 4-byte aligned", n);
+        if (cam->model != GUT_CAMERA_OPENCV_PINHOLE && cam->model != GUT_CAMERA_OPENCV_FISHEYE)
+            return fail("gut_tsdf_integrate: view %d: unsupported camera model %d", n, cam->model);
+        for (int k = 0; k < 7; ++k)
+            if (cam->pose_start[k] != cam->pose_end[k])
+                return fail("gut_tsdf_integrate: view %d: the start and end poses differ (a rolling shutter in motion): a voxel has one "
+                            "pixel for pose_start == pose_end only", n);
+        gut::FuseView& v = fv.v[n];
+        const float* s = cam->pose_start;
+        quat_to_rot(s[6], s[3], s[4], s[5], v.w2s.r);
+        for (int i = 0; i < 3; ++i) v.w2s.t[i] = s[i];
+        bool distorted = false;
+        for (float c : cam->radial_coeffs) distorted |= (c != 0.0f);
+        for (float c : cam->tangential_coeffs) distorted |= (c != 0.0f);
+        for (float c : cam->thin_prism_coeffs) distorted |= (c != 0.0f);
+        v.variant = cam->model == GUT_CAMERA_OPENCV_FISHEYE ? 2 : (distorted ? 1 : 0);
+        v.width = in.width;
+        v.height = in.height;
+        for (int i = 0; i < 2; ++i) {
+            v.principal_point[i] = cam->principal_point[i];
+            v.focal_length[i] = cam->focal_length[i];
+            v.tangential[i] = cam->tangential_coeffs[i];
+        }
+        for (int i = 0; i < 6; ++i) v.radial[i] = cam->radial_coeffs[i];
+        for (int i = 0; i < 4; ++i) v.thin_prism[i] = cam->thin_prism_coeffs[i];
+        v.max_angle = cam->max_angle;
+        v.distance = in.d_distance;
+        v.rgba = in.d_rgba;
+        v.origin = in.d_ray_origin;
+    }
+    gut::launch_tsdf_integrate(static_cast<hipStream_t>(stream_), g, n_views, fv);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int gut_surface_nets_count(void* stream_, const GutTsdfGrid* grid, uint32_t min_count, uint8_t* d_cell, uint8_t* d_quads) {
+    gut::FuseGrid g;
+    if (int rc = build_fuse_grid("gut_surface_nets_count", grid, &g)) return rc;
+    if (min_count < 1) return fail("gut_surface_nets_count: min_count must be >= 1");
+    if (!d_cell || !d_quads) return fail("gut_surface_nets_count: null d_cell or d_quads");
+    gut::launch_surface_nets_count(static_cast<hipStream_t>(stream_), g, min_count, d_cell, d_quads);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int gut_surface_nets_emit(void* stream_, const GutTsdfGrid* grid, uint32_t min_count, const uint8_t* d_cell, const uint8_t* d_quads,
+                          const int32_t* d_vertex_offset, const int32_t* d_quad_offset, float* d_vertices, float* d_colours,
+                          int32_t* d_faces) {
+    gut::FuseGrid g;
+    if (int rc = build_fuse_grid("gut_surface_nets_emit", grid, &g)) return rc;
+    if (min_count < 1) return fail("gut_surface_nets_emit: min_count must be >= 1");
+    if (!d_cell || !d_quads || !d_vertex_offset || !d_quad_offset || !d_vertices || !d_colours || !d_faces)
+        return fail("gut_surface_nets_emit: null pointer argument");
+    if (misaligned4(d_vertex_offset) || misaligned4(d_quad_offset) || misaligned4(d_vertices) || misaligned4(d_colours) || misaligned4(d_faces))
+        return fail("gut_surface_nets_emit: a pointer is not 4-byte aligned");
+    gut::launch_surface_nets_emit(static_cast<hipStream_t>(stream_), g, min_count, d_cell, d_quads, d_vertex_offset, d_quad_offset, d_vertices,
+                                  d_colours, d_faces);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int gut_set_regularisation(gut_handle h, const GutRegularisation* reg) {
     if (!h) return fail("gut_set_regularisation: null handle");
     if (reg && !(reg->density_coeff >= 0.0f && reg->scale_coeff >= 0.0f && reg->density_coeff < INFINITY && reg->scale_coeff < INFINITY))

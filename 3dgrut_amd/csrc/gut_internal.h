@@ -304,6 +304,40 @@ void launch_pose_gradient_consume(hipStream_t s, uint32_t n, const uint32_t* til
 void launch_pose_adam(hipStream_t s, const float* grad8, float* m6, float* v6, int32_t* count, float lr_translation, float lr_rotation,
                       float beta1, float beta2, float eps, float* delta6);
 
+// gut_fuse.hip: TSDF fusion of distance planes into the caller's integer volume, surface nets on it.  The records
+// are built and checked on the host (gut_api.cpp) and travel as kernel arguments.
+struct FuseGrid {
+    float origin[3];
+    float voxel;
+    int32_t X, Y, Z;
+    float truncation;
+    int32_t* acc;
+    uint32_t* cnt;
+    uint32_t* rgb_sum;   // [Z,Y,X,3] or null
+    uint32_t* rgb_cnt;   // null with rgb_sum
+};
+struct FuseView {
+    Affine w2s;          // world->sensor (pose_start == pose_end)
+    int32_t variant;     // K1's: 0 pinhole without distortion, 1 pinhole with, 2 fisheye
+    int32_t width, height;
+    float principal_point[2];
+    float focal_length[2];
+    float radial[6];
+    float tangential[2];
+    float thin_prism[4];
+    float max_angle;
+    const float* distance;   // [H,W]
+    const float* rgba;       // [H,W,4] or null
+    const float* origin;     // [H,W,3], sensor frame, or null
+};
+struct FuseViews {
+    FuseView v[GUT_TSDF_MAX_VIEWS];
+};
+void launch_tsdf_integrate(hipStream_t s, const FuseGrid& g, int n_views, const FuseViews& views);
+void launch_surface_nets_count(hipStream_t s, const FuseGrid& g, uint32_t min_count, uint8_t* cell, uint8_t* quads);
+void launch_surface_nets_emit(hipStream_t s, const FuseGrid& g, uint32_t min_count, const uint8_t* cell, const uint8_t* quads,
+                              const int32_t* vertex_offset, const int32_t* quad_offset, float* vertices, float* colours, int32_t* faces);
+
 // scan / sort (rocPRIM device-wide primitives; temp storage owned by the caller)
 size_t scan_temp_bytes(uint32_t n);
 hipError_t run_scan(hipStream_t s, void* temp, size_t temp_bytes, const uint32_t* in, uint32_t* out, uint32_t n);

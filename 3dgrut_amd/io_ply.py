@@ -55,13 +55,41 @@ def write_point_cloud(path, xyz, rgb):
         fh.write(table.tobytes())
 
 
+def write_mesh(path, vertices, colours, faces):
+    """A triangle mesh, binary little-endian: per vertex float32 x y z and uchar red green blue (colours [V,3] in [0, 1], clamped and
+    rounded as write_point_cloud does), per face `list uchar int vertex_indices` with three indices.  vertices [V,3], faces [F,3]
+    integers in [0, V).  read_ply reads it back as dict(positions, rgb uint8, faces int32 [F,3])."""
+    xyz = np.asarray(vertices, np.float32).reshape(-1, 3)
+    rgb = np.asarray(colours, np.float32).reshape(-1, 3)
+    tri = np.asarray(faces).reshape(-1, 3)
+    if xyz.shape[0] != rgb.shape[0]:
+        raise ValueError(f"{xyz.shape[0]} vertices and {rgb.shape[0]} colours")
+    if tri.size and (not np.issubdtype(tri.dtype, np.integer) or int(tri.min()) < 0 or int(tri.max()) >= xyz.shape[0]):
+        raise ValueError(f"faces must be integer indices in [0, {xyz.shape[0]})")
+    table = np.zeros(xyz.shape[0], dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    table["x"], table["y"], table["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    q = np.rint(np.clip(np.nan_to_num(rgb), 0.0, 1.0) * 255.0).astype(np.uint8)
+    table["red"], table["green"], table["blue"] = q[:, 0], q[:, 1], q[:, 2]
+    records = np.zeros(tri.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    records["n"], records["v"] = 3, tri
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % xyz.shape[0]
+    header += "".join(f"property float {a}\n" for a in "xyz") + "".join(f"property uchar {a}\n" for a in ("red", "green", "blue"))
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % tri.shape[0]
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(table.tobytes())
+        fh.write(records.tobytes())
+
+
 def read_ply(path):
     """Returns dict(positions, density_logit[N,1], rotation_raw[N,4], log_scale[N,3], features48[N,48]) (pre-activation); of a
-    plain point cloud (x y z red green blue and no Gaussian attributes, write_point_cloud) dict(positions, rgb uint8 [N,3])."""
+    plain point cloud (x y z red green blue and no Gaussian attributes, write_point_cloud) dict(positions, rgb uint8 [N,3]), of a
+    mesh (write_mesh: a face element of triangles after the vertices) with faces int32 [F,3] besides."""
     with open(path, "rb") as fh:
         if fh.readline().strip() != b"ply":
             raise ValueError("not a PLY file")
         fmt, n, props, in_vertex = None, None, [], False
+        n_faces, face_list = None, None
         while True:
             line = fh.readline()
             if not line:
@@ -75,6 +103,10 @@ def read_ply(path):
                 in_vertex = tok[1] == "vertex"
                 if in_vertex:
                     n = int(tok[2])
+                elif tok[1] == "face":
+                    n_faces = int(tok[2])
+            elif tok[0] == "property" and not in_vertex and n_faces is not None and tok[1] == "list":
+                face_list = tok[2:]
             elif tok[0] == "property" and in_vertex:
                 if tok[1] == "list":
                     raise ValueError("list properties are not supported on the vertex element")
@@ -85,11 +117,23 @@ def read_ply(path):
         if fmt != "binary_little_endian":
             raise ValueError(f"unsupported PLY format {fmt!r} (binary_little_endian only)")
         data = np.frombuffer(fh.read(n * np.dtype(props).itemsize), dtype=np.dtype(props), count=n)
+        faces = None
+        if n_faces is not None:
+            if face_list is None or face_list[:2] not in (["uchar", "int"], ["uint8", "int32"], ["uchar", "int32"], ["uint8", "int"]):
+                raise ValueError("unsupported face element (property list uchar int vertex_indices only)")
+            face_type = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+            records = np.frombuffer(fh.read(n_faces * face_type.itemsize), dtype=face_type, count=n_faces)
+            if n_faces and not (records["n"] == 3).all():
+                raise ValueError("unsupported face element (triangles only)")
+            faces = np.ascontiguousarray(records["v"], np.int32).reshape(n_faces, 3)
     col = lambda k: np.asarray(data[k], np.float32)
     names = [p for p, _ in props]
     if all(c in names for c in ("red", "green", "blue")) and not any(p.startswith(("f_rest_", "f_dc_", "scale_", "rot")) for p in names):
-        return dict(positions=np.stack([col("x"), col("y"), col("z")], 1),
-                    rgb=np.stack([np.asarray(data[c]).astype(np.uint8) for c in ("red", "green", "blue")], 1))
+        cloud = dict(positions=np.stack([col("x"), col("y"), col("z")], 1).reshape(n, 3),
+                     rgb=np.stack([np.asarray(data[c]).astype(np.uint8) for c in ("red", "green", "blue")], 1).reshape(n, 3))
+        if faces is not None:
+            cloud["faces"] = faces
+        return cloud
     rest = sorted((p for p, _ in props if p.startswith("f_rest_")), key=lambda s: int(s.split("_")[-1]))
     if len(rest) != 3 * _N_SPEC:
         raise ValueError(f"expected {3 * _N_SPEC} f_rest_* properties (SH degree 3), found {len(rest)}")

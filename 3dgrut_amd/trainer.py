@@ -78,6 +78,13 @@ point per cell of edge `voxel` (0: all).  With an output directory: points.ply (
 the median distance of every held-out view (float32 [H,W], 0 where there is no surface).  The model is not changed.  One GPU only;
 stride and voxel are UNTUNED on real captures.
 
+`mesh.enabled` (default off; `--export-mesh`) exports the scene as a triangle mesh (mesh.py), after the points: the
+level-`level` distance planes of the training views, at their refined poses, are fused into a TSDF volume (mesh.volume_for: `bounds`
+or the 1 % .. 99 % quantile box of the positions grown by the truncation, `voxel` or the longest edge / `resolution`, truncation =
+`truncation_voxels` voxels) and its zero level is extracted by surface nets among the voxels at least `min_count` views updated.  With
+an output directory: mesh.ply (x y z red green blue, vertex_indices).  The model is not changed.  One GPU, the unsorted variant at
+kernel degree 2 only; resolution, truncation_voxels and the quantile box are UNTUNED on real captures.
+
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
                                  [--refine-poses [--pose-lr-translation X] [--pose-lr-rotation R]]
@@ -87,6 +94,7 @@ stride and voxel are UNTUNED on real captures.
                                  [--select-by-masks [SUFFIX] [--select-threshold T]]
                                  [--fit-features [SUFFIX] [--feature-iterations K] [--feature-lr X]]
                                  [--export-points [--points-level T] [--points-stride S] [--points-voxel V]]
+                                 [--export-mesh [--mesh-resolution R] [--mesh-voxel V]]
 """
 import argparse
 import copy
@@ -102,6 +110,7 @@ from . import contribution as contribution_mod
 from . import features as features_mod
 from . import exposure as exposure_mod
 from . import losses, pose_align, pose_refine
+from . import mesh as mesh_mod
 from . import selection as selection_mod
 from . import surface as surface_mod
 from .evaluate import _check_batch, evaluate
@@ -150,6 +159,9 @@ GS_CONFIG = {
     # not a reference key: the scene as points (surface.py), after everything above: the median surface points of the training views,
     # fused; the held-out views' median distance planes.  stride and voxel are UNTUNED on real captures.
     "points": dict(surface_mod.DEFAULTS),
+    # not a reference key: the scene as a triangle mesh (mesh.py), after the points: the training views' median distance planes fused
+    # into a TSDF volume, its zero level by surface nets.  resolution, truncation_voxels and the quantile box are UNTUNED on real captures.
+    "mesh": dict(mesh_mod.DEFAULTS),
     "strategy": {"method": "GSStrategy",
                  # criterion and error are not reference keys: "error" grows, at every densify step, the grow_fraction of the rows
                  # that are responsible for the most rendering error over `views` training views (0: all of them), instead of
@@ -213,11 +225,28 @@ def resolve_config(conf):
     selection_mod.check_config(out["selection"])
     features_mod.check_config(out["features"])
     surface_mod.check_config(out["points"])
+    check_mesh_config(out)
     check_densify_config(out)
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
         out["optimizer"]["params"]["features_specular"] = {"lr": float(out["optimizer"]["params"]["features_albedo"]["lr"]) / 20}
     return out
+
+
+def check_mesh_config(conf):
+    """The `mesh` block of a resolved conf (mesh.check_config); enabled, it is refused where the surface walk does not exist: the
+    sorted variant (render.splat.k_buffer_size > 0) and kernel degrees other than 2.  The data-parallel refusal needs the stepper and
+    is the Trainer's."""
+    block = mesh_mod.check_config(conf["mesh"])
+    if block["enabled"]:
+        render = conf.get("render") or {}
+        k_buffer = int((render.get("splat") or {}).get("k_buffer_size", 0))
+        degree = int(render.get("particle_kernel_degree", 2))
+        if k_buffer > 0:
+            raise ValueError(f"mesh: the mesh export needs the unsorted variant (render.splat.k_buffer_size is {k_buffer})")
+        if degree != 2:
+            raise ValueError(f"mesh: the mesh export needs render.particle_kernel_degree 2 (it is {degree})")
+    return conf
 
 
 DENSIFY_ERROR_DEFAULTS = GS_CONFIG["strategy"]["densify"]["error"]
@@ -453,6 +482,8 @@ class Trainer:
             raise ValueError("features: data-parallel feature fitting is out of scope (the stepper's world_size must be 1)")
         if c["points"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
             raise ValueError("points: data-parallel point export is out of scope (the stepper's world_size must be 1)")
+        if c["mesh"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
+            raise ValueError("mesh: data-parallel mesh export is out of scope (the stepper's world_size must be 1)")
         self.densify_criterion = (c["strategy"].get("densify") or {}).get("criterion", "gradient")
         if self.densify_criterion == "error":
             if int(getattr(stepper, "world_size", 1)) > 1:
@@ -888,9 +919,31 @@ class Trainer:
         self.stats.update(out)
         return out
 
+    def export_mesh(self):
+        """The `mesh` block, after export_points(): fuses the level-mode distance planes of the training views (at their refined
+        poses) into a TSDF volume sized by mesh.volume_for and extracts its zero level.  Writes mesh.ply into the output directory
+        when there is one.  Fills and returns the mesh_* statistics; the model is left as it is."""
+        blk = self.conf["mesh"]
+        renderer = surface_mod.SurfaceRenderer(self.model, self.tracer)
+        batches = [b if self.refiner is None else self.refiner.begin(v, b) for v, b in enumerate(self.train_batches)]
+        with torch.no_grad():
+            volume = mesh_mod.volume_for(self.model, resolution=int(blk["resolution"]), voxel=blk["voxel"], bounds=blk["bounds"],
+                                         truncation_voxels=float(blk["truncation_voxels"]), device=renderer.act.device)
+            mesh_mod.fuse_mesh(renderer, batches, volume, level=float(blk["level"]))
+            vertices, colours, faces = volume.extract(min_count=int(blk["min_count"]))
+        out_dir = self._out_dir()
+        if out_dir is not None:
+            from .io_ply import write_mesh
+            os.makedirs(out_dir, exist_ok=True)
+            write_mesh(os.path.join(out_dir, "mesh.ply"), vertices.cpu().numpy(), colours.cpu().numpy(), faces.cpu().numpy())
+        out = dict(mesh_vertices=int(vertices.shape[0]), mesh_faces=int(faces.shape[0]), mesh_views=int(volume.n_views),
+                   mesh_voxel=float(volume.voxel), mesh_dims=[int(d) for d in volume.dims])
+        self.stats.update(out)
+        return out
+
     def run(self):
         """train(), (compaction.enabled) compact(), (selection.enabled) select_by_masks(), (features.enabled) fit_features(),
-        (points.enabled) export_points(), print the statistics table, then (test_last) save ckpt_last.pt and evaluate the test split."""
+        (points.enabled) export_points(), (mesh.enabled) export_mesh(), print the statistics table, then (test_last) save ckpt_last.pt and evaluate the test split."""
         stats = self.train()
         if self.conf["compaction"]["enabled"]:
             self.compact()
@@ -900,6 +953,8 @@ class Trainer:
             self.fit_features()
         if self.conf["points"]["enabled"]:
             self.export_points()
+        if self.conf["mesh"]["enabled"]:
+            self.export_mesh()
         print("Training Statistics: " + json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in stats.items()}), flush=True)
         if self.conf["test_last"] and self.test_batches:
             self.save_checkpoint(last=True)
@@ -957,6 +1012,12 @@ def build_parser():
     ap.add_argument("--points-stride", type=int, default=None, metavar="S", help="points.stride: every S-th pixel (untuned on real captures)")
     ap.add_argument("--points-voxel", type=float, default=None, metavar="V",
                     help="points.voxel: one point per cell of this edge length, 0 = all (untuned on real captures)")
+    ap.add_argument("--export-mesh", action="store_true",
+                    help="after training, export the scene as a triangle mesh: the training views' median distance planes fused into a "
+                         "TSDF volume, its zero level written to mesh.ply (mesh.enabled)")
+    ap.add_argument("--mesh-resolution", type=int, default=None, metavar="R",
+                    help="mesh.resolution: voxels along the longest edge of the box (untuned on real captures)")
+    ap.add_argument("--mesh-voxel", type=float, default=None, metavar="V", help="mesh.voxel: the voxel edge length, instead of a resolution")
     ap.add_argument("--densify-by", choices=("gradient", "error"), default=None,
                     help="strategy.densify.criterion: error = grow the rows responsible for the most rendering error (default: gradient)")
     ap.add_argument("--densify-grow-fraction", type=float, default=None, metavar="F", help="strategy.densify.error.grow_fraction")
@@ -1013,6 +1074,11 @@ def config_from_args(a):
         conf["points"]["stride"] = a.points_stride
     if a.points_voxel is not None:
         conf["points"]["voxel"] = a.points_voxel
+    conf["mesh"]["enabled"] = bool(a.export_mesh)
+    if a.mesh_resolution is not None:
+        conf["mesh"]["resolution"] = a.mesh_resolution
+    if a.mesh_voxel is not None:
+        conf["mesh"]["voxel"] = a.mesh_voxel
     densify = {}
     if a.densify_by is not None:
         densify["criterion"] = a.densify_by

@@ -50,7 +50,8 @@ extern "C" {
  * gut_trace_contribution, a new entry point: every other call queues what it queued before; gut_trace_contribution_weighted and
  * gut_pixel_error, new entry points: gut_trace_contribution and every other call queue what they queued before; added under 6
  * without a bump: gut_trace_attributes, a new entry point: every other call queues what it queued before; gut_trace_attributes_bwd,
- * likewise; gut_trace_surface, likewise). */
+ * likewise; gut_trace_surface, likewise; gut_tsdf_integrate, gut_surface_nets_count and gut_surface_nets_emit, handle-free new entry
+ * points). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -838,6 +839,66 @@ int gut_mcmc_relocation(void* stream, int32_t n, const float* d_opacities, const
  * row index as counter (the same draws on every rank).  One pass, 96 bytes per Gaussian, instead of four batched 3x3 matmuls. */
 int gut_mcmc_perturb(void* stream, uint32_t num_particles, float* d_raw12, float* d_act12, float noise_scale, uint64_t seed,
                      uint64_t step, const float* d_unit_normals);
+
+/* ---- The scene as a mesh: TSDF fusion of distance planes, surface nets (new functionality, the reference has none) ----
+ * The volume is a dense axis-aligned box of X x Y x Z voxels of edge `voxel`; voxel (i, j, k) has its centre at
+ * origin + voxel * (i + 1/2, j + 1/2, k + 1/2) and the linear index (k Y + j) X + i.  The state is the caller's: int32 d_acc and
+ * uint32 d_cnt [Z,Y,X], optionally uint32 d_rgb_sum [Z,Y,X,3] and d_rgb_cnt [Z,Y,X] (both or neither); all zero = empty.
+ *
+ * gut_tsdf_integrate adds n_views (1 .. GUT_TSDF_MAX_VIEWS) views in ONE launch, one thread per voxel, the state words of a voxel
+ * read once, held in registers over the views and stored once, only if a view updated the voxel.  Per view and voxel, in fp32
+ * without contraction: the centre p goes to the sensor frame by the camera's world-to-sensor pose and through the camera model by the
+ * projection kernel's arithmetic (pinhole without and with distortion, fisheye); an invalid projection or one outside the image skips
+ * the view; the pixel is (floor(u), floor(v)); D = d_distance there, 0 or not finite skips; s = D - |p - o| with o the pixel's ray
+ * origin in the sensor frame (d_ray_origin NULL: the sensor position); s < -truncation skips; else
+ *     acc += rint(min(1, s / truncation) * 65536),  cnt += 1,
+ * and, with colours on both sides and |s| <= truncation, rgb_sum += rint(255 * clamp(rgb, 0, 1)) per channel, rgb_cnt += 1.
+ * Sums of integers: the state does not depend on the order of the views or on how they are split into calls; no atomics, a voxel
+ * belongs to one thread.  The caller keeps the number of integrated views at or below 32767 (acc is an int32 of quanta).
+ * Refused on the host, nothing written: a NULL grid / views / camera / d_acc / d_cnt / d_distance, a pointer not 4-byte aligned,
+ * one of d_rgb_sum and d_rgb_cnt without the other, n_views outside 1 .. GUT_TSDF_MAX_VIEWS, voxel or truncation not finite and
+ * positive, a dimension < 1 or X Y Z > 2^30, width or height < 1, an unknown camera model, and a rolling shutter in motion
+ * (pose_start != pose_end).  Handle-free; everything is queued on `stream`. */
+#define GUT_TSDF_MAX_VIEWS 8
+typedef struct GutTsdfGrid {
+    float origin[3];
+    float voxel;
+    int32_t dims[3];            /* X, Y, Z */
+    float truncation;
+    int32_t* d_acc;             /* [Z,Y,X] sum of rint(f * 65536) */
+    uint32_t* d_cnt;            /* [Z,Y,X] views that updated the voxel */
+    uint32_t* d_rgb_sum;        /* [Z,Y,X,3] or NULL */
+    uint32_t* d_rgb_cnt;        /* [Z,Y,X] or NULL */
+} GutTsdfGrid;
+typedef struct GutTsdfView {
+    const GutCamera* camera;    /* host */
+    int32_t width, height;
+    const float* d_distance;    /* [H,W], gut_trace_surface's level-mode plane: 0 = no surface */
+    const float* d_rgba;        /* [H,W,4] of the forward, or NULL */
+    const float* d_ray_origin;  /* [H,W,3] in the sensor frame, or NULL: the sensor position */
+} GutTsdfView;
+int gut_tsdf_integrate(void* stream, const GutTsdfGrid* grid, int32_t n_views, const GutTsdfView* views);
+
+/* Surface nets on the integer state.  A lattice point is OBSERVED iff cnt >= min_count, INSIDE iff acc < 0; its value is
+ * float(acc) / (float(cnt) * 65536).  Cell (i, j, k), i < X-1, j < Y-1, k < Z-1, has the corners (i + dx, j + dy, k + dz), corner
+ * number dx + 2 dy + 4 dz; it is ACTIVE iff all eight are observed and not all on one side.  Its vertex is the mean of the crossings
+ * t = f0 / (f0 - f1) of those of its twelve edges whose ends differ in side, summed in this order of (corner, corner):
+ *     x: (0,1) (2,3) (4,5) (6,7)   y: (0,2) (1,3) (4,6) (5,7)   z: (0,4) (1,5) (2,6) (3,7)
+ * at origin + voxel * ((i, j, k) + 1/2 + mean); its colour the mean of rgb_sum / (255 rgb_cnt) over the corners with rgb_cnt > 0,
+ * grey 0.5 without any.  Vertices are ordered by the cell's linear index.  A lattice edge p -> p + e_a (a = x, y, z) whose ends are
+ * observed and differ in side emits one quad if its four surrounding cells lie in the grid and are fully observed: with (a, b, c) a
+ * cyclic permutation of (x, y, z), the cells p - e_b - e_c, p - e_c, p, p - e_b in this order if p is inside, in the reverse
+ * order starting from the same cell otherwise (the normal points from inside to outside), split into the triangles (0,1,2), (0,2,3).
+ * Quads are ordered by the linear index of p, then by axis.
+ *   gut_surface_nets_count: d_cell [Z,Y,X] bytes (bit 0: the cell exists and is fully observed, bit 1: active), d_quads [Z,Y,X]
+ *     bytes (the lattice point's number of quads, 0 .. 3).  Two launches.
+ *   gut_surface_nets_emit:  with the EXCLUSIVE prefix sums of (d_cell >> 1) and of d_quads as int32 [Z,Y,X] (the caller scans),
+ *     writes d_vertices / d_colours [V,3] and d_faces int32 [2 Q,3].  One launch.
+ * Refusals as above (grid, min_count < 1, NULL or misaligned pointers); the colour arrays of the grid may be NULL. */
+int gut_surface_nets_count(void* stream, const GutTsdfGrid* grid, uint32_t min_count, uint8_t* d_cell, uint8_t* d_quads);
+int gut_surface_nets_emit(void* stream, const GutTsdfGrid* grid, uint32_t min_count, const uint8_t* d_cell, const uint8_t* d_quads,
+                          const int32_t* d_vertex_offset, const int32_t* d_quad_offset, float* d_vertices, float* d_colours,
+                          int32_t* d_faces);
 
 const char* gut_last_error(void);
 int gut_abi_version(void);
