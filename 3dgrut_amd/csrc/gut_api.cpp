@@ -15,7 +15,7 @@
 #include <new>
 #include <string>
 
-#include "gut_internal.h"
+#include "gut_camera.h"
 
 namespace {
 
@@ -116,6 +116,27 @@ void interpolate_pose(const float* a, const float* b, float t, float* out) {
     }
     for (int i = 0; i < 3; ++i) out[i] = a[i] * (1.0f - t) + b[i] * t;
     out[3] = q[1]; out[4] = q[2]; out[5] = q[3]; out[6] = q[0];
+}
+
+// pose = t(3), q(x,y,z,w)  ->  y = R x + t
+void pose_affine(const float pose[7], gut::Affine* a) {
+    quat_to_rot(pose[6], pose[3], pose[4], pose[5], a->r);
+    for (int i = 0; i < 3; ++i) a->t[i] = pose[i];
+}
+
+// the fields of a `View` (gut_camera.h) from the caller's camera and the image size
+template <class View>
+void fill_intrinsics(const GutCamera& cam, int W, int H, View* v) {
+    v->width = W;
+    v->height = H;
+    for (int i = 0; i < 2; ++i) {
+        v->principal_point[i] = cam.principal_point[i];
+        v->focal_length[i] = cam.focal_length[i];
+        v->tangential[i] = cam.tangential_coeffs[i];
+    }
+    for (int i = 0; i < 6; ++i) v->radial[i] = cam.radial_coeffs[i];
+    for (int i = 0; i < 4; ++i) v->thin_prism[i] = cam.thin_prism_coeffs[i];
+    v->max_angle = cam.max_angle;
 }
 
 uint32_t bit_width_u32(uint32_t n) {  // == higherMsb of gutRenderer.cu:79-94 for n >= 1
@@ -238,18 +259,11 @@ int build_view(const GutCamera* cam, int W, int H, int shutter_iterations, gut::
         v->pose_start[i] = cam->pose_start[i];
         v->pose_end[i] = cam->pose_end[i];
     }
-    {
-        const float* e = cam->pose_end;
-        quat_to_rot(e[6], e[3], e[4], e[5], v->w2s_end.r);
-        for (int i = 0; i < 3; ++i) v->w2s_end.t[i] = e[i];
-    }
-    const float* s = cam->pose_start;
-    quat_to_rot(s[6], s[3], s[4], s[5], v->w2s_start.r);
-    for (int i = 0; i < 3; ++i) v->w2s_start.t[i] = s[i];
+    pose_affine(cam->pose_end, &v->w2s_end);
+    pose_affine(cam->pose_start, &v->w2s_start);
     float mid[7];
     interpolate_pose(cam->pose_start, cam->pose_end, 0.5f, mid);
-    quat_to_rot(mid[6], mid[3], mid[4], mid[5], v->w2s_mid.r);
-    for (int i = 0; i < 3; ++i) v->w2s_mid.t[i] = mid[i];
+    pose_affine(mid, &v->w2s_mid);
     // sensor->world = (R^T, -R^T t).  The reference round-trips R^T through a quaternion
     // (sensors.h:44-53); skipping that removes rounding noise and changes no integer buffer.
     for (int r = 0; r < 3; ++r)
@@ -257,18 +271,9 @@ int build_view(const GutCamera* cam, int W, int H, int shutter_iterations, gut::
     for (int r = 0; r < 3; ++r)
         v->s2w.t[r] = -1.0f * (v->s2w.r[r][0] * mid[0] + v->s2w.r[r][1] * mid[1] + v->s2w.r[r][2] * mid[2]);
     v->model = cam->model;
-    v->width = W;
-    v->height = H;
+    fill_intrinsics(*cam, W, H, v);
     v->grid_x = (W + gut::kTile - 1) / gut::kTile;
     v->grid_y = (H + gut::kTile - 1) / gut::kTile;
-    for (int i = 0; i < 2; ++i) {
-        v->principal_point[i] = cam->principal_point[i];
-        v->focal_length[i] = cam->focal_length[i];
-        v->tangential[i] = cam->tangential_coeffs[i];
-    }
-    for (int i = 0; i < 6; ++i) v->radial[i] = cam->radial_coeffs[i];
-    for (int i = 0; i < 4; ++i) v->thin_prism[i] = cam->thin_prism_coeffs[i];
-    v->max_angle = cam->max_angle;
     v->shutter_iterations = shutter_iterations;
     return 0;
 }
@@ -1434,24 +1439,9 @@ int gut_tsdf_integrate(void* stream_, const GutTsdfGrid* grid, int32_t n_views, 
                 return fail("gut_tsdf_integrate: view %d: the start and end poses differ (a rolling shutter in motion): a voxel has one "
                             "pixel for pose_start == pose_end only", n);
         gut::FuseView& v = fv.v[n];
-        const float* s = cam->pose_start;
-        quat_to_rot(s[6], s[3], s[4], s[5], v.w2s.r);
-        for (int i = 0; i < 3; ++i) v.w2s.t[i] = s[i];
-        bool distorted = false;
-        for (float c : cam->radial_coeffs) distorted |= (c != 0.0f);
-        for (float c : cam->tangential_coeffs) distorted |= (c != 0.0f);
-        for (float c : cam->thin_prism_coeffs) distorted |= (c != 0.0f);
-        v.variant = cam->model == GUT_CAMERA_OPENCV_FISHEYE ? 2 : (distorted ? 1 : 0);
-        v.width = in.width;
-        v.height = in.height;
-        for (int i = 0; i < 2; ++i) {
-            v.principal_point[i] = cam->principal_point[i];
-            v.focal_length[i] = cam->focal_length[i];
-            v.tangential[i] = cam->tangential_coeffs[i];
-        }
-        for (int i = 0; i < 6; ++i) v.radial[i] = cam->radial_coeffs[i];
-        for (int i = 0; i < 4; ++i) v.thin_prism[i] = cam->thin_prism_coeffs[i];
-        v.max_angle = cam->max_angle;
+        pose_affine(cam->pose_start, &v.w2s);
+        fill_intrinsics(*cam, in.width, in.height, &v);
+        v.variant = gut::camera_variant(cam->model, v);
         v.distance = in.d_distance;
         v.rgba = in.d_rgba;
         v.origin = in.d_ray_origin;

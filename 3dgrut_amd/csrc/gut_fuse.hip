@@ -5,108 +5,13 @@
 //   k_nets_emit        surface nets: the vertices and the triangles, behind the caller's exclusive scans
 //
 // THIS FILE IS COMPILED WITH -ffp-contract=off, as gut_project.hip is: a voxel's pixel and its side of the truncation are integer
-// decisions of fp32 arithmetic, evaluated in one documented order with IEEE-exact +,-,*,/,sqrt.  The projection functions are
-// gut_project.hip's, copied with their bodies unchanged (the view record's type is the one difference): K1's translation unit is left
-// byte for byte alone ("the projection").
-#include "gut_internal.h"
+// decisions of fp32 arithmetic, evaluated in one documented order with IEEE-exact +,-,*,/,sqrt.  The projection IS K1's: both
+// units include gut_camera.h, whose functions are generic over the view record ("the projection").
+#include "gut_camera.h"
 
 namespace gut {
 
 namespace {
-
-// ---- gut_project.hip's projection, copied: det_atan2f_pos, within_resolution, project_pinhole, project_fisheye, project_camera ----
-// atan2(y, x), y > 0: Cephes atanf reduction + polynomial
-__device__ float det_atan2f_pos(float y, float x) {
-    const float ax = fabsf(x);
-    const float lo = y < ax ? y : ax;
-    const float hi = y < ax ? ax : y;
-    float t = lo / hi;
-    float base = 0.0f;
-    if (t > 0.4142135679721832f) {
-        base = 0.7853981852531433f;
-        t = (t - 1.0f) / (t + 1.0f);
-    }
-    const float z = t * t;
-    float a = (((8.05374449538e-2f * z - 1.38776856032e-1f) * z + 1.99777106478e-1f) * z - 3.33329491539e-1f) * z * t + t;
-    a = base + a;
-    if (y > ax) a = 1.5707963705062866f - a;
-    if (x < 0.0f) a = 3.1415927410125732f - a;
-    return a;
-}
-
-__device__ __forceinline__ bool within_resolution(float rx, float ry, float tol, float px, float py) {
-    const float mx = rx * tol, my = ry * tol;
-    return (px > -mx) && (py > -my) && (px < rx + mx) && (py < ry + my);
-}
-
-// OpenCV pinhole with rational radial / tangential / thin-prism distortion
-template <bool kDistorted>
-__device__ __forceinline__ bool project_pinhole(const FuseView& v, float px, float py, float pz, float tol, float& ox,
-                                                float& oy) {
-    if (pz <= 0.0f) {
-        ox = 0.0f;
-        oy = 0.0f;
-        return false;
-    }
-    // xy / z as multiplication by one IEEE reciprocal (numerics contract, mirrored by the oracle)
-    const float rz = 1.0f / pz;
-    const float un = px * rz, vn = py * rz;
-    if (!kDistorted) {  // all distortion coefficients are zero: icd == 1, delta == 0 exactly
-        ox = un * v.focal_length[0] + v.principal_point[0];
-        oy = vn * v.focal_length[1] + v.principal_point[1];
-        return within_resolution((float)v.width, (float)v.height, tol, ox, oy);
-    }
-    const float u2 = un * un, v2 = vn * vn;
-    const float r2 = u2 + v2;
-    const float a1 = 2.0f * un * vn;
-    const float a2 = r2 + 2.0f * u2;
-    const float a3 = r2 + 2.0f * v2;
-    const float num = 1.0f + r2 * (v.radial[0] + r2 * (v.radial[1] + r2 * v.radial[2]));
-    const float den = 1.0f + r2 * (v.radial[3] + r2 * (v.radial[4] + r2 * v.radial[5]));
-    const float icd = num / den;
-    const float dx = v.tangential[0] * a1 + v.tangential[1] * a2 + r2 * (v.thin_prism[0] + r2 * v.thin_prism[1]);
-    const float dy = v.tangential[0] * a3 + v.tangential[1] * a1 + r2 * (v.thin_prism[2] + r2 * v.thin_prism[3]);
-    const float xd = icd * un + dx, yd = icd * vn + dy;
-    const bool radial_ok = (icd > 0.8f) && (icd < 1.2f);
-    if (radial_ok) {
-        ox = xd * v.focal_length[0] + v.principal_point[0];
-        oy = yd * v.focal_length[1] + v.principal_point[1];
-    } else {
-        const float fw = (float)v.width, fh = (float)v.height;
-        const float clip = sqrtf(fw * fw + fh * fh);
-        const float k = clip / sqrtf(r2);
-        ox = k * un + v.principal_point[0];
-        oy = k * vn + v.principal_point[1];
-    }
-    return radial_ok && within_resolution((float)v.width, (float)v.height, tol, ox, oy);
-}
-
-// OpenCV fisheye, theta clamped to max_angle
-__device__ __forceinline__ bool project_fisheye(const FuseView& v, float px, float py, float pz, float tol, float& ox, float& oy) {
-    const float eps = 1.1920929e-07f;
-    float rho = sqrtf(px * px + py * py);
-    rho = rho > eps ? rho : eps;
-    const float theta_full = det_atan2f_pos(rho, pz);
-    const float theta = theta_full < v.max_angle ? theta_full : v.max_angle;
-    const float t2 = theta * theta;
-    float poly = v.radial[3];
-    poly = t2 * poly + v.radial[2];
-    poly = t2 * poly + v.radial[1];
-    poly = t2 * poly + v.radial[0];
-    const float delta = (theta * (poly * t2 + 1.0f)) / rho;
-    ox = v.focal_length[0] * px * delta + v.principal_point[0];
-    oy = v.focal_length[1] * py * delta + v.principal_point[1];
-    return (theta < v.max_angle) && within_resolution((float)v.width, (float)v.height, tol, ox, oy);
-}
-
-// kVariant: 0 = pinhole without distortion, 1 = pinhole with distortion, 2 = fisheye
-template <int kVariant>
-__device__ __forceinline__ int project_camera(const FuseView& v, float cx, float cy, float cz, float tol, float& ox, float& oy) {
-    if (kVariant == 0) return project_pinhole<false>(v, cx, cy, cz, tol, ox, oy) ? 1 : 0;
-    if (kVariant == 1) return project_pinhole<true>(v, cx, cy, cz, tol, ox, oy) ? 1 : 0;
-    return project_fisheye(v, cx, cy, cz, tol, ox, oy) ? 1 : 0;
-}
-// ---- end of the copy ----
 
 __device__ __forceinline__ float voxel_centre(float origin, float voxel, int i) { return origin + voxel * ((float)i + 0.5f); }
 
@@ -114,11 +19,8 @@ __device__ __forceinline__ float voxel_centre(float origin, float voxel, int i) 
 template <bool kColour>
 __device__ __forceinline__ void integrate_view(const FuseView& v, float truncation, float wx, float wy, float wz, int32_t& acc,
                                                uint32_t& cnt, uint32_t (&rgb)[3], uint32_t& rgb_cnt) {
-    const Affine& a = v.w2s;
-    const float cx = a.r[0][0] * wx + a.r[0][1] * wy + a.r[0][2] * wz + a.t[0];
-    const float cy = a.r[1][0] * wx + a.r[1][1] * wy + a.r[1][2] * wz + a.t[1];
-    const float cz = a.r[2][0] * wx + a.r[2][1] * wy + a.r[2][2] * wz + a.t[2];
-    float u, w;
+    float cx, cy, cz, u, w;
+    affine_point(v.w2s, wx, wy, wz, cx, cy, cz);
     int valid;
     if (v.variant == 0) valid = project_camera<0>(v, cx, cy, cz, 0.0f, u, w);
     else if (v.variant == 1) valid = project_camera<1>(v, cx, cy, cz, 0.0f, u, w);

@@ -17,6 +17,22 @@ struct Affine {
     float r[3][3];
     float t[3];
 };
+__device__ __forceinline__ void affine_point(const Affine& a, float wx, float wy, float wz, float& cx, float& cy, float& cz) {
+    cx = a.r[0][0] * wx + a.r[0][1] * wy + a.r[0][2] * wz + a.t[0];
+    cy = a.r[1][0] * wx + a.r[1][1] * wy + a.r[1][2] * wz + a.t[1];
+    cz = a.r[2][0] * wx + a.r[2][1] * wy + a.r[2][2] * wz + a.t[2];
+}
+
+// rows of rotationT from a wxyz quaternion (slang/common/transforms.slang:22-39); forced inline, so every unit compiles it under
+// its own contraction flags
+__device__ __forceinline__ void quat_rows(float w, float x, float y, float z, float r[3][3]) {
+    const float xx = x * x, yy = y * y, zz = z * z;
+    const float xy = x * y, xz = x * z, yz = y * z;
+    const float rx = w * x, ry = w * y, rz = w * z;
+    r[0][0] = 1.0f - 2.0f * (yy + zz); r[0][1] = 2.0f * (xy + rz); r[0][2] = 2.0f * (xz - ry);
+    r[1][0] = 2.0f * (xy - rz); r[1][1] = 1.0f - 2.0f * (xx + zz); r[1][2] = 2.0f * (yz + rx);
+    r[2][0] = 2.0f * (xz + ry); r[2][1] = 2.0f * (yz - rx); r[2][2] = 1.0f - 2.0f * (xx + yy);
+}
 
 // Everything the device code needs to know about the view; built on the host (gut_api.cpp).
 struct ViewParams {

@@ -10,7 +10,9 @@
 // instead of the device math library, so that tile/key buffers are reproducible bit for bit
 // (numerics contract in DESIGN.md §4).  These kernels are HBM-streaming (one thread per Gaussian,
 // 48 B in / 56 B out, +192 B of SH for survivors), so the missing FMA contraction costs nothing.
-#include "gut_internal.h"
+// The camera projection itself (sensor-space point -> pixel) lives in gut_camera.h, shared with
+// gut_fuse.hip; the shutter, the sigma points and everything per Gaussian are here.
+#include "gut_camera.h"
 
 namespace gut {
 
@@ -45,90 +47,6 @@ __device__ float det_logf(float x) {
     return dk * 6.9313812256e-01f - ((hfsq - (s * (hfsq + R) + dk * 9.0580006145e-06f)) - f);
 }
 
-// atan2(y, x), y > 0: Cephes atanf reduction + polynomial
-__device__ float det_atan2f_pos(float y, float x) {
-    const float ax = fabsf(x);
-    const float lo = y < ax ? y : ax;
-    const float hi = y < ax ? ax : y;
-    float t = lo / hi;
-    float base = 0.0f;
-    if (t > 0.4142135679721832f) {
-        base = 0.7853981852531433f;
-        t = (t - 1.0f) / (t + 1.0f);
-    }
-    const float z = t * t;
-    float a = (((8.05374449538e-2f * z - 1.38776856032e-1f) * z + 1.99777106478e-1f) * z - 3.33329491539e-1f) * z * t + t;
-    a = base + a;
-    if (y > ax) a = 1.5707963705062866f - a;
-    if (x < 0.0f) a = 3.1415927410125732f - a;
-    return a;
-}
-
-__device__ __forceinline__ bool within_resolution(float rx, float ry, float tol, float px, float py) {
-    const float mx = rx * tol, my = ry * tol;
-    return (px > -mx) && (py > -my) && (px < rx + mx) && (py < ry + my);
-}
-
-// OpenCV pinhole with rational radial / tangential / thin-prism distortion (cameraProjections.cuh:57-103)
-template <bool kDistorted>
-__device__ __forceinline__ bool project_pinhole(const ViewParams& v, float px, float py, float pz, float tol, float& ox,
-                                                float& oy) {
-    if (pz <= 0.0f) {
-        ox = 0.0f;
-        oy = 0.0f;
-        return false;
-    }
-    // xy / z as multiplication by one IEEE reciprocal (numerics contract, mirrored by the oracle)
-    const float rz = 1.0f / pz;
-    const float un = px * rz, vn = py * rz;
-    if (!kDistorted) {  // all distortion coefficients are zero: icd == 1, delta == 0 exactly
-        ox = un * v.focal_length[0] + v.principal_point[0];
-        oy = vn * v.focal_length[1] + v.principal_point[1];
-        return within_resolution((float)v.width, (float)v.height, tol, ox, oy);
-    }
-    const float u2 = un * un, v2 = vn * vn;
-    const float r2 = u2 + v2;
-    const float a1 = 2.0f * un * vn;
-    const float a2 = r2 + 2.0f * u2;
-    const float a3 = r2 + 2.0f * v2;
-    const float num = 1.0f + r2 * (v.radial[0] + r2 * (v.radial[1] + r2 * v.radial[2]));
-    const float den = 1.0f + r2 * (v.radial[3] + r2 * (v.radial[4] + r2 * v.radial[5]));
-    const float icd = num / den;
-    const float dx = v.tangential[0] * a1 + v.tangential[1] * a2 + r2 * (v.thin_prism[0] + r2 * v.thin_prism[1]);
-    const float dy = v.tangential[0] * a3 + v.tangential[1] * a1 + r2 * (v.thin_prism[2] + r2 * v.thin_prism[3]);
-    const float xd = icd * un + dx, yd = icd * vn + dy;
-    const bool radial_ok = (icd > 0.8f) && (icd < 1.2f);
-    if (radial_ok) {
-        ox = xd * v.focal_length[0] + v.principal_point[0];
-        oy = yd * v.focal_length[1] + v.principal_point[1];
-    } else {
-        const float fw = (float)v.width, fh = (float)v.height;
-        const float clip = sqrtf(fw * fw + fh * fh);
-        const float k = clip / sqrtf(r2);
-        ox = k * un + v.principal_point[0];
-        oy = k * vn + v.principal_point[1];
-    }
-    return radial_ok && within_resolution((float)v.width, (float)v.height, tol, ox, oy);
-}
-
-// OpenCV fisheye, theta clamped to max_angle (cameraProjections.cuh:105-128)
-__device__ __forceinline__ bool project_fisheye(const ViewParams& v, float px, float py, float pz, float tol, float& ox, float& oy) {
-    const float eps = 1.1920929e-07f;
-    float rho = sqrtf(px * px + py * py);
-    rho = rho > eps ? rho : eps;
-    const float theta_full = det_atan2f_pos(rho, pz);
-    const float theta = theta_full < v.max_angle ? theta_full : v.max_angle;
-    const float t2 = theta * theta;
-    float poly = v.radial[3];
-    poly = t2 * poly + v.radial[2];
-    poly = t2 * poly + v.radial[1];
-    poly = t2 * poly + v.radial[0];
-    const float delta = (theta * (poly * t2 + 1.0f)) / rho;
-    ox = v.focal_length[0] * px * delta + v.principal_point[0];
-    oy = v.focal_length[1] * py * delta + v.principal_point[1];
-    return (theta < v.max_angle) && within_resolution((float)v.width, (float)v.height, tol, ox, oy);
-}
-
 // acos on [0,1] / sin on [0, pi/2] for the rolling-shutter slerp: fdlibm e_acosf / k_sinf / k_cosf in plain fp32
 __device__ float det_acosf01(float x) {
     const float pio2_hi = 1.5707962513e+00f, pio2_lo = 7.5497894159e-08f;
@@ -158,15 +76,6 @@ __device__ float det_sinf_0_pio2(float x) {
     const float z = y * y;
     const float r = z * (4.1666667908e-02f + z * (-1.3888889225e-03f + z * (2.4801587642e-05f + z * (-2.7557314297e-07f + z * (2.0875723372e-09f + z * -1.1359647598e-11f)))));
     return 1.0f - (0.5f * z - z * r);
-}
-
-// kVariant: 0 = pinhole without distortion, 1 = pinhole with distortion, 2 = fisheye (compile-time specialisation of
-// the reference's run-time camera-model switch, cameraProjections.cuh:130-144)
-template <int kVariant>
-__device__ __forceinline__ int project_camera(const ViewParams& v, float cx, float cy, float cz, float tol, float& ox, float& oy) {
-    if (kVariant == 0) return project_pinhole<false>(v, cx, cy, cz, tol, ox, oy) ? 1 : 0;
-    if (kVariant == 1) return project_pinhole<true>(v, cx, cy, cz, tol, ox, oy) ? 1 : 0;
-    return project_fisheye(v, cx, cy, cz, tol, ox, oy) ? 1 : 0;
 }
 
 __device__ __forceinline__ float relative_shutter_time(const ViewParams& v, float px, float py) {
@@ -213,17 +122,12 @@ __device__ void shutter_pose_transform(const ViewParams& v, float a, float wx, f
 template <int kVariant, bool kRolling>
 __device__ __forceinline__ int project_world(const ViewParams& v, float wx, float wy, float wz, float tol, float& ox,
                                              float& oy) {
-    const Affine& a = v.w2s_start;
-    float cx = a.r[0][0] * wx + a.r[0][1] * wy + a.r[0][2] * wz + a.t[0];
-    float cy = a.r[1][0] * wx + a.r[1][1] * wy + a.r[1][2] * wz + a.t[1];
-    float cz = a.r[2][0] * wx + a.r[2][1] * wy + a.r[2][2] * wz + a.t[2];
+    float cx, cy, cz;
+    affine_point(v.w2s_start, wx, wy, wz, cx, cy, cz);
     int valid = project_camera<kVariant>(v, cx, cy, cz, tol, ox, oy);
     if (!kRolling) return valid;
     if (!valid) {
-        const Affine& e = v.w2s_end;
-        cx = e.r[0][0] * wx + e.r[0][1] * wy + e.r[0][2] * wz + e.t[0];
-        cy = e.r[1][0] * wx + e.r[1][1] * wy + e.r[1][2] * wz + e.t[1];
-        cz = e.r[2][0] * wx + e.r[2][1] * wy + e.r[2][2] * wz + e.t[2];
+        affine_point(v.w2s_end, wx, wy, wz, cx, cy, cz);
         valid = project_camera<kVariant>(v, cx, cy, cz, tol, ox, oy);
         if (!valid) return 0;
     }
@@ -233,16 +137,6 @@ __device__ __forceinline__ int project_world(const ViewParams& v, float wx, floa
         valid = project_camera<kVariant>(v, cx, cy, cz, tol, ox, oy);
     }
     return valid;
-}
-
-// rows of rotationT from a wxyz quaternion (slang/common/transforms.slang:22-39)
-__device__ __forceinline__ void quat_rows(float w, float x, float y, float z, float r[3][3]) {
-    const float xx = x * x, yy = y * y, zz = z * z;
-    const float xy = x * y, xz = x * z, yz = y * z;
-    const float rx = w * x, ry = w * y, rz = w * z;
-    r[0][0] = 1.0f - 2.0f * (yy + zz); r[0][1] = 2.0f * (xy + rz); r[0][2] = 2.0f * (xz - ry);
-    r[1][0] = 2.0f * (xy - rz); r[1][1] = 1.0f - 2.0f * (xx + zz); r[1][2] = 2.0f * (yz + rx);
-    r[2][0] = 2.0f * (xz + ry); r[2][1] = 2.0f * (yz - rx); r[2][2] = 1.0f - 2.0f * (xx + yy);
 }
 
 // real SH basis up to degree 3 (gaussianParticles.cuh:57-96)
@@ -1291,11 +1185,7 @@ void launch_project(hipStream_t s, const ViewParams& v, const RenderConsts& c, u
                     float* conic_opacity, float* extent, float* depth, float* feat, float* visibility,
                     uint32_t* wave_sums, const float* sph_albedo, const FrameClears& clears) {
     if (n == 0) return;
-    bool distorted = false;
-    for (float k : v.radial) distorted |= (k != 0.0f);
-    for (float k : v.tangential) distorted |= (k != 0.0f);
-    for (float k : v.thin_prism) distorted |= (k != 0.0f);
-    const int variant = v.model == GUT_CAMERA_OPENCV_FISHEYE ? 2 : (distorted ? 1 : 0);
+    const int variant = camera_variant(v.model, v);
     const bool rolling = v.shutter != GUT_SHUTTER_GLOBAL;
     auto kern = rolling ? (variant == 0 ? k_project_on_tiles<0, true, false> : (variant == 1 ? k_project_on_tiles<1, true, false> : k_project_on_tiles<2, true, false>))
                         : (variant == 0 ? k_project_on_tiles<0, false, false> : (variant == 1 ? k_project_on_tiles<1, false, false> : k_project_on_tiles<2, false, false>));

@@ -127,15 +127,6 @@ __device__ __forceinline__ RayState make_ray(const ViewParams& v, const float* _
     return r;
 }
 
-__device__ __forceinline__ void quat_rows(float w, float x, float y, float z, float r[3][3]) {
-    const float xx = x * x, yy = y * y, zz = z * z;
-    const float xy = x * y, xz = x * z, yz = y * z;
-    const float rx = w * x, ry = w * y, rz = w * z;
-    r[0][0] = 1.0f - 2.0f * (yy + zz); r[0][1] = 2.0f * (xy + rz); r[0][2] = 2.0f * (xz - ry);
-    r[1][0] = 2.0f * (xy - rz); r[1][1] = 1.0f - 2.0f * (xx + zz); r[1][2] = 2.0f * (yz + rx);
-    r[2][0] = 2.0f * (xz + ry); r[2][1] = 2.0f * (yz - rx); r[2][2] = 1.0f - 2.0f * (xx + yy);
-}
-
 // Canonical-space ray origin:  o = M (ray_o - mu) = M (sensor_pos - mu) + M (ray_o - sensor_pos) = oc + M e.
 // oc is a per-entry constant computed once at staging; e is a per-pixel constant that is exactly zero for every
 // camera the reference has (rays start at the sensor position), in which case the whole tile skips the M e term
