@@ -5,12 +5,17 @@
  * region) may link, load or call this file.  Only tests/, __graft_entry__.smoke() and
  * bench.py's `cpu_baseline` leg use it, and only as the checker.
  *
- * PARITY STATUS: "parity unpinned" for the device kernels — the reference holds no tests, golden
- * images or known-answer vectors for this path, and its CUDA/Slang sources
- * cannot be compiled here (no nvcc, no slangc, tiny-cuda-nn un-vendored).  This file restates the
- * reference sources read as text; every function cites the reference file:line it follows.  The
- * host-side pose math is pinned by tests/golden/pose_golden.npz (generated from the reference's
- * own Python, see tests/golden/gen_pose_golden.py).
+ * PARITY STATUS: the reference holds no tests, golden images or known-answer vectors for this path
+ * (SURVEY.md §4, §8c), and most of its CUDA/Slang sources cannot be compiled here (no nvcc, no
+ * slangc, tiny-cuda-nn un-vendored).  This file restates the reference sources read as text; every
+ * function cites the reference file:line it follows.  PINNED, bit for bit at variant 0, by results
+ * recorded from the reference's own per-hit header compiled for the host (oracle/ref_host/,
+ * tests/golden/hit_golden.npz, tests/test_cpu_reference_hits.py): kernel_response,
+ * kernel_response_grad, eval_hit + hit_bwd_terms (one processHitBwd step), sh_radiance,
+ * sh_radiance_bwd, quat_to_rows.  "Parity unpinned" for the rest: the forward's per-hit function
+ * (Slang), the projection, the tile tests and the renderer's loops.  The host-side pose math is
+ * pinned by tests/golden/pose_golden.npz (generated from the reference's own Python, see
+ * tests/golden/gen_pose_golden.py).
  *
  * Numerics contract shared with the HIP kernels (so that integer tile/key buffers are bit-exact):
  *   - all arithmetic fp32, evaluated left-to-right as written, NO fused multiply-add
@@ -419,6 +424,42 @@ static void sh_basis(int deg, const float d[3], float Y[16]) {
     }
 }
 
+/* the direction a Gaussian's SH is evaluated along, normalize(mean - sensor position) with one reciprocal, and the distance —
+ * gutProjector.cuh:304-310 */
+static float view_direction(const PoseSet* ps, const float pos[3], float dir[3]) {
+    const float sr[3] = {pos[0] - ps->cam[0], pos[1] - ps->cam[1], pos[2] - ps->cam[2]};
+    const float dist = sqrtf(sr[0] * sr[0] + sr[1] * sr[1] + sr[2] * sr[2]);
+    const float inv_dist = 1.0f / dist;
+    for (int k = 0; k < 3; ++k) dir[k] = sr[k] * inv_dist;
+    return dist;
+}
+
+/* radianceFromSpH(deg, coefficients, dir, clamped = false) — gaussianParticles.cuh:64-96: the basis times the coefficient row,
+ * summed in coefficient order, + 0.5 */
+static void sh_radiance(int deg, const float dir[3], const float* sh48, float out[3]) {
+    float Y[16];
+    sh_basis(deg, dir, Y);
+    const int ncoef = (deg + 1) * (deg + 1);
+    for (int ch = 0; ch < 3; ++ch) {
+        float acc = 0.0f;
+        for (int k = 0; k < ncoef; ++k) acc += Y[k] * sh48[3 * k + ch];
+        out[ch] = acc + 0.5f;
+    }
+}
+
+/* the five-argument radianceFromSpHBwd — gaussianParticles.cuh:120-187: sph_grad[k] += Y_k(dir) (dL/dRGB masked where the unclamped
+ * radiance is not positive).  The cotangent is the double sum of K7's fp32 feature gradients here, so the product is taken in double
+ * (for a cotangent that is an fp32 number it is exact, and rounds to the reference's fp32 product). */
+static void sh_radiance_bwd(int deg, const float dir[3], const float radiance_unclamped[3], const double rad_grad[3], double* sph_grad48) {
+    float Y[16];
+    sh_basis(deg, dir, Y);
+    const int ncoef = (deg + 1) * (deg + 1);
+    for (int ch = 0; ch < 3; ++ch) {
+        const double gmask = radiance_unclamped[ch] > 0.0f ? rad_grad[ch] : 0.0;
+        for (int k = 0; k < ncoef; ++k) sph_grad48[3 * k + ch] += (double)Y[k] * gmask;
+    }
+}
+
 /* ------------------------------------------------------------------------------------------------
  * tile helpers — gutProjector.cuh:32-78
  * ---------------------------------------------------------------------------------------------- */
@@ -579,19 +620,9 @@ void oracle_project(const OracleParams* prm, const OracleCamera* cam, int W, int
         if (cnt == 0) continue;
 
         /* precomputed view-dependent RGB (unclamped), gutProjector.cuh:304-310 */
-        const float sr[3] = {pos[0] - ps.cam[0], pos[1] - ps.cam[1], pos[2] - ps.cam[2]};
-        const float dist = sqrtf(sr[0] * sr[0] + sr[1] * sr[1] + sr[2] * sr[2]);
-        const float inv_dist = 1.0f / dist;
-        const float dir[3] = {sr[0] * inv_dist, sr[1] * inv_dist, sr[2] * inv_dist};
-        float Y[16];
-        sh_basis(sh_degree, dir, Y);
-        const int ncoef = (sh_degree + 1) * (sh_degree + 1);
-        const float* sh = sph48 + (size_t)i * 48;
-        for (int ch = 0; ch < 3; ++ch) {
-            float acc = 0.0f;
-            for (int k = 0; k < ncoef; ++k) acc += Y[k] * sh[3 * k + ch];
-            feat[3 * i + ch] = acc + 0.5f;
-        }
+        float dir[3];
+        const float dist = view_direction(&ps, pos, dir);
+        sh_radiance(sh_degree, dir, sph48 + (size_t)i * 48, feat + 3 * (size_t)i);
         proj_pos[2 * i] = cx; proj_pos[2 * i + 1] = cy;
         for (int k = 0; k < 4; ++k) conic_opacity[4 * i + k] = con[k];
         extent[2 * i] = ext[0]; extent[2 * i + 1] = ext[1];
@@ -1302,6 +1333,101 @@ static void matmul_bw_quat(const float p[3], const float g[3], const float q[4],
     out[0] = dr; out[1] = dx; out[2] = dy; out[3] = dz;
 }
 
+/* One per-hit backward step — processHitBwd<n, false, false>, models/gaussianParticles.cuh:480-738, from the statement after its
+ * accept test (:530) to its end, in the reference's statement order (variant 0 is held to it bit for bit by
+ * tests/test_cpu_reference_hits.py against results recorded from the reference's own header).  `h` is the evaluated pair, `f` the
+ * particle's clamped radiance (the caller clamps: gutKBufferRenderer.cuh:324), T / rgb_run / depth_run the running state before the
+ * hit, T_final / rgb_final / depth_final the reference's integrated* arguments, T_grad / rgb_g / depth_g the cotangents.  Nothing is
+ * accumulated here: the caller decides what an accepted (or, for the flip budget, a nearly accepted) entry does with the terms. */
+typedef struct {
+    float ga_hit, ga_dns, G, w, Tn, depth_after;
+    float res_rad[3], run_after[3], feat_add[3];
+    float add[11];   /* position(3), density, quaternion wxyz(4), scale(3) */
+} HitBwd;
+
+static void hit_bwd_terms(const OracleParams* prm, const float* g, const float rows[3][3], const float ray_d[3], const Hit* hp, const float f[3],
+                          float T, const float rgb_run[3], float depth_run, float T_final, const float rgb_final[3], float depth_final,
+                          float T_grad, const float rgb_g[3], float depth_g, HitBwd* o) {
+    const Hit h = *hp;
+    const float* q = g + 4; const float* s = g + 8; const float sigma = g[3];
+    /* NB: no tmin/tmax test in the backward (gaussianParticles.cuh:530) */
+    const float proj = h.grd[0] * -h.gro[0] + h.grd[1] * -h.gro[1] + h.grd[2] * -h.gro[2];
+    const float grdd[3] = {h.grd[0] * proj, h.grd[1] * proj, h.grd[2] * proj};
+    const float grds[3] = {s[0] * grdd[0], s[1] * grdd[1], s[2] * grdd[2]};
+    const float gsq = grds[0] * grds[0] + grds[1] * grds[1] + grds[2] * grds[2];
+    const float gdist = sqrtf(gsq);
+    const float w = h.alpha * T;
+    const float Tn = (1.0f - h.alpha) * T;
+    /* :542-545 — the running depth takes the hit, the residual is what the integrated depth leaves behind it, clamped at zero */
+    const float depth_after = depth_run + w * gdist;
+    const float res_hit = fmaxf(Tn <= prm->min_transmittance ? 0.0f : (depth_final - depth_after) / Tn, 0.0f);
+    const float ga_hit = (gdist - res_hit) * T * depth_g;
+    float g_grds[3] = {0, 0, 0};
+    if (gsq > 0.0f) for (int c = 0; c < 3; ++c) g_grds[c] = ((2.0f * grds[c] * w) / (2.0f * gdist)) * depth_g;
+    const float gs_hit[3] = {grdd[0] * g_grds[0], grdd[1] * g_grds[1], grdd[2] * g_grds[2]};
+    const float gx0 = h.grd[0] * h.gro[0], gy0 = h.grd[1] * h.gro[1], gz0 = h.grd[2] * h.gro[2];
+    const float ggrd_hit[3] = {-s[0] * (2 * gx0 + gy0 + gz0) * g_grds[0],
+                               -s[1] * (gx0 + 2 * gy0 + gz0) * g_grds[1],
+                               -s[2] * (gx0 + gy0 + 2 * gz0) * g_grds[2]};
+    const float ggro_hit[3] = {-s[0] * h.grd[0] * h.grd[0] * g_grds[0],
+                               -s[1] * h.grd[1] * h.grd[1] * g_grds[1],
+                               -s[2] * h.grd[2] * h.grd[2] * g_grds[2]};
+    const float res_T = h.alpha < 0.999999f ? T_final / (1.0f - h.alpha) : T;
+    const float ga_dns = res_T * -T_grad;
+    for (int c = 0; c < 3; ++c) {
+        o->feat_add[c] = rgb_g[c] * w;
+        o->run_after[c] = rgb_run[c] + w * f[c];
+        const float rr = (Tn <= prm->min_transmittance) ? 0.0f : (rgb_final[c] - o->run_after[c]) / Tn;
+        o->res_rad[c] = rr > 0.0f ? rr : 0.0f;
+    }
+    const float G = ga_hit + ga_dns + T * (f[0] - o->res_rad[0]) * rgb_g[0] + T * (f[1] - o->res_rad[1]) * rgb_g[1] +
+                    T * (f[2] - o->res_rad[2]) * rgb_g[2];
+    const float d_sigma = h.resp * G;
+    const float g_resp = sigma * G;
+    const float g_d2 = kernel_response_grad(prm->kernel_degree, h.d2, h.resp, g_resp);
+    const float cr[3] = {h.grd[1] * h.gro[2] - h.grd[2] * h.gro[1], h.grd[2] * h.gro[0] - h.grd[0] * h.gro[2],
+                         h.grd[0] * h.gro[1] - h.grd[1] * h.gro[0]};
+    const float gc[3] = {2 * cr[0] * g_d2, 2 * cr[1] * g_d2, 2 * cr[2] * g_d2};
+    const float g_grd[3] = {gc[2] * h.gro[1] - gc[1] * h.gro[2], gc[0] * h.gro[2] - gc[2] * h.gro[0],
+                            gc[1] * h.gro[0] - gc[0] * h.gro[1]};
+    const float g_gro[3] = {gc[1] * h.grd[2] - gc[2] * h.grd[1], gc[2] * h.grd[0] - gc[0] * h.grd[2],
+                            gc[0] * h.grd[1] - gc[1] * h.grd[0]};
+    float gs_gro[3], g_gposcr[3];
+    for (int c = 0; c < 3; ++c) {
+        gs_gro[c] = (-h.gposcr[c] / (s[c] * s[c])) * (g_gro[c] + ggro_hit[c]);
+        g_gposcr[c] = (1.0f / s[c]) * (g_gro[c] + ggro_hit[c]);
+    }
+    float g_gposc[3];
+    for (int c = 0; c < 3; ++c) g_gposc[c] = g_gposcr[0] * rows[0][c] + g_gposcr[1] * rows[1][c] + g_gposcr[2] * rows[2][c];
+    float q_a[4];
+    matmul_bw_quat(h.gposc, g_gposcr, q, q_a);
+    /* safe_normalize_bw(grdu, g_grd + ggrd_hit), mathUtils.cuh:420-430 */
+    const float gin[3] = {g_grd[0] + ggrd_hit[0], g_grd[1] + ggrd_hit[1], g_grd[2] + ggrd_hit[2]};
+    float g_grdu[3] = {0, 0, 0};
+    {
+        const float* v = h.grdu;
+        const float l = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+        if (l > 0.0f) {
+            const float il = 1.0f / sqrtf(l);
+            const float il3 = il * il * il;
+            g_grdu[0] = il * gin[0] - il3 * (gin[0] * (v[0] * v[0]) + gin[1] * (v[1] * v[0]) + gin[2] * (v[2] * v[0]));
+            g_grdu[1] = il * gin[1] - il3 * (gin[0] * (v[0] * v[1]) + gin[1] * (v[1] * v[1]) + gin[2] * (v[2] * v[1]));
+            g_grdu[2] = il * gin[2] - il3 * (gin[0] * (v[0] * v[2]) + gin[1] * (v[1] * v[2]) + gin[2] * (v[2] * v[2]));
+        }
+    }
+    float g_rdr[3], d_scale[3];
+    for (int c = 0; c < 3; ++c) {
+        d_scale[c] = gs_hit[c] + gs_gro[c] + (-h.rdr[c] / (s[c] * s[c])) * g_grdu[c];
+        g_rdr[c] = (1.0f / s[c]) * g_grdu[c];
+    }
+    float q_b[4];
+    matmul_bw_quat(ray_d, g_rdr, q, q_b);
+    o->add[0] = -g_gposc[0]; o->add[1] = -g_gposc[1]; o->add[2] = -g_gposc[2]; o->add[3] = d_sigma;
+    for (int c = 0; c < 4; ++c) o->add[4 + c] = q_a[c] + q_b[c];
+    for (int c = 0; c < 3; ++c) o->add[8 + c] = d_scale[c];
+    o->ga_hit = ga_hit; o->ga_dns = ga_dns; o->G = G; o->w = w; o->Tn = Tn; o->depth_after = depth_after;
+}
+
 /* K7: renderBackward — gutKBufferRenderer.cuh:294-386, models/gaussianParticles.cuh:480-738,
  * rayPayloadBackward.cuh:30-58.  Per-pair math in fp32 exactly as the reference; the cross-pixel
  * sums (float atomics in the reference, order undefined) are taken in double here.
@@ -1340,7 +1466,6 @@ static void render_bwd_impl(const OracleParams* prm, const OracleCamera* cam, in
     const PoseSet ps = make_pose_set(cam);
     const int gx = (W + GUT_TILE - 1) / GUT_TILE, gy = (H + GUT_TILE - 1) / GUT_TILE;
     uint64_t traversed_total = 0;
-    (void)dist;
     /* tiles in parallel: the per-Gaussian double accumulators are shared, hence the atomic adds (their order, and with it the
      * last bits of the double sums, depends on the thread schedule; every consumer compares with a tolerance) */
 #pragma omp parallel for schedule(dynamic, 1) reduction(+ : traversed_total)
@@ -1425,9 +1550,8 @@ static void render_bwd_impl(const OracleParams* prm, const OracleCamera* cam, in
                     const uint32_t id = sorted_ids[k];
                     if (id == INVALID_IDX) break;
                     const float* g = density12 + (size_t)id * 12;
-                    const float* q = g + 4; const float* s = g + 8; const float sigma = g[3];
                     float rows[3][3];
-                    quat_to_rows(q, rows);
+                    quat_to_rows(g + 4, rows);
                     Hit h;
                     eval_hit(prm, g, rows, &ray, &h);
                     const int accept = (h.resp > prm->min_kernel_density) && (h.alpha > prm->alpha_threshold);
@@ -1442,81 +1566,21 @@ static void render_bwd_impl(const OracleParams* prm, const OracleCamera* cam, in
                             prone |= fabsf(h.resp * g[3] - prm->alpha_threshold) / (prm->alpha_threshold * eps * nu) < flip_bound;
                     }
                     if (!accept && !prone) continue;
-                    /* NB: no tmin/tmax test in the backward (gaussianParticles.cuh:530) */
-                    const float proj = h.grd[0] * -h.gro[0] + h.grd[1] * -h.gro[1] + h.grd[2] * -h.gro[2];
-                    const float grdd[3] = {h.grd[0] * proj, h.grd[1] * proj, h.grd[2] * proj};
-                    const float grds[3] = {s[0] * grdd[0], s[1] * grdd[1], s[2] * grdd[2]};
-                    const float gsq = grds[0] * grds[0] + grds[1] * grds[1] + grds[2] * grds[2];
-                    const float gdist = sqrtf(gsq);
-                    const float w = h.alpha * T;
-                    const float Tn = (1.0f - h.alpha) * T;
-                    const float res_hit = 0.0f; /* quirk 1 */
-                    const float ga_hit = (gdist - res_hit) * T * depth_g;
-                    float g_grds[3] = {0, 0, 0};
-                    if (gsq > 0.0f) for (int c = 0; c < 3; ++c) g_grds[c] = ((2.0f * grds[c] * w) / (2.0f * gdist)) * depth_g;
-                    const float gs_hit[3] = {grdd[0] * g_grds[0], grdd[1] * g_grds[1], grdd[2] * g_grds[2]};
-                    const float gx0 = h.grd[0] * h.gro[0], gy0 = h.grd[1] * h.gro[1], gz0 = h.grd[2] * h.gro[2];
-                    const float ggrd_hit[3] = {-s[0] * (2 * gx0 + gy0 + gz0) * g_grds[0],
-                                               -s[1] * (gx0 + 2 * gy0 + gz0) * g_grds[1],
-                                               -s[2] * (gx0 + gy0 + 2 * gz0) * g_grds[2]};
-                    const float ggro_hit[3] = {-s[0] * h.grd[0] * h.grd[0] * g_grds[0],
-                                               -s[1] * h.grd[1] * h.grd[1] * g_grds[1],
-                                               -s[2] * h.grd[2] * h.grd[2] * g_grds[2]};
-                    const float res_T = h.alpha < 0.999999f ? T_final / (1.0f - h.alpha) : T;
-                    const float ga_dns = res_T * -T_grad;
-                    float f[3], res_rad[3], run_after[3], feat_add[3];
+                    /* the per-hit terms: processHitBwd.  Quirk 1: the renderer's wrapper hands its running hit distance (never
+                     * updated in this loop: 0) over as the integrated depth and a COPY of the forward's distance as the running one
+                     * (shRadiativeGaussianParticles.cuh:404-406 into gaussianParticles.cuh:499-501), so the residual distance is
+                     * max((0 - (dist + w gdist)) / T', 0) = 0 on every hit */
+                    float f[3];
                     for (int c = 0; c < 3; ++c) {
                         const float fv = feat[3 * (size_t)id + c];
                         f[c] = fv > 0.0f ? fv : 0.0f;
-                        feat_add[c] = rgb_g[c] * w;
-                        run_after[c] = rgb_run[c] + w * f[c];
-                        const float rr = (Tn <= prm->min_transmittance) ? 0.0f : (rgb_final[c] - run_after[c]) / Tn;
-                        res_rad[c] = rr > 0.0f ? rr : 0.0f;
                     }
-                    const float G = ga_hit + ga_dns + T * (f[0] - res_rad[0]) * rgb_g[0] + T * (f[1] - res_rad[1]) * rgb_g[1] +
-                                    T * (f[2] - res_rad[2]) * rgb_g[2];
-                    const float d_sigma = h.resp * G;
-                    const float g_resp = sigma * G;
-                    const float g_d2 = kernel_response_grad(prm->kernel_degree, h.d2, h.resp, g_resp);
-                    const float cr[3] = {h.grd[1] * h.gro[2] - h.grd[2] * h.gro[1], h.grd[2] * h.gro[0] - h.grd[0] * h.gro[2],
-                                         h.grd[0] * h.gro[1] - h.grd[1] * h.gro[0]};
-                    const float gc[3] = {2 * cr[0] * g_d2, 2 * cr[1] * g_d2, 2 * cr[2] * g_d2};
-                    const float g_grd[3] = {gc[2] * h.gro[1] - gc[1] * h.gro[2], gc[0] * h.gro[2] - gc[2] * h.gro[0],
-                                            gc[1] * h.gro[0] - gc[0] * h.gro[1]};
-                    const float g_gro[3] = {gc[1] * h.grd[2] - gc[2] * h.grd[1], gc[2] * h.grd[0] - gc[0] * h.grd[2],
-                                            gc[0] * h.grd[1] - gc[1] * h.grd[0]};
-                    float gs_gro[3], g_gposcr[3];
-                    for (int c = 0; c < 3; ++c) {
-                        gs_gro[c] = (-h.gposcr[c] / (s[c] * s[c])) * (g_gro[c] + ggro_hit[c]);
-                        g_gposcr[c] = (1.0f / s[c]) * (g_gro[c] + ggro_hit[c]);
-                    }
-                    float g_gposc[3];
-                    for (int c = 0; c < 3; ++c) g_gposc[c] = g_gposcr[0] * rows[0][c] + g_gposcr[1] * rows[1][c] + g_gposcr[2] * rows[2][c];
-                    float q_a[4];
-                    matmul_bw_quat(h.gposc, g_gposcr, q, q_a);
-                    /* safe_normalize_bw(grdu, g_grd + ggrd_hit), mathUtils.cuh:420-430 */
-                    const float gin[3] = {g_grd[0] + ggrd_hit[0], g_grd[1] + ggrd_hit[1], g_grd[2] + ggrd_hit[2]};
-                    float g_grdu[3] = {0, 0, 0};
-                    {
-                        const float* v = h.grdu;
-                        const float l = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-                        if (l > 0.0f) {
-                            const float il = 1.0f / sqrtf(l);
-                            const float il3 = il * il * il;
-                            g_grdu[0] = il * gin[0] - il3 * (gin[0] * (v[0] * v[0]) + gin[1] * (v[1] * v[0]) + gin[2] * (v[2] * v[0]));
-                            g_grdu[1] = il * gin[1] - il3 * (gin[0] * (v[0] * v[1]) + gin[1] * (v[1] * v[1]) + gin[2] * (v[2] * v[1]));
-                            g_grdu[2] = il * gin[2] - il3 * (gin[0] * (v[0] * v[2]) + gin[1] * (v[1] * v[2]) + gin[2] * (v[2] * v[2]));
-                        }
-                    }
-                    float g_rdr[3], d_scale[3];
-                    for (int c = 0; c < 3; ++c) {
-                        d_scale[c] = gs_hit[c] + gs_gro[c] + (-h.rdr[c] / (s[c] * s[c])) * g_grdu[c];
-                        g_rdr[c] = (1.0f / s[c]) * g_grdu[c];
-                    }
-                    float q_b[4];
-                    matmul_bw_quat(ray.d, g_rdr, q, q_b);
-                    const double add[11] = {-g_gposc[0], -g_gposc[1], -g_gposc[2], d_sigma, q_a[0] + q_b[0], q_a[1] + q_b[1],
-                                            q_a[2] + q_b[2], q_a[3] + q_b[3], d_scale[0], d_scale[1], d_scale[2]};
+                    HitBwd hb;
+                    hit_bwd_terms(prm, g, rows, ray.d, &h, f, T, rgb_run, dist[pix], T_final, rgb_final, 0.0f, T_grad, rgb_g, depth_g, &hb);
+                    const float w = hb.w, Tn = hb.Tn, G = hb.G, ga_hit = hb.ga_hit, ga_dns = hb.ga_dns;
+                    const float* res_rad = hb.res_rad; const float* run_after = hb.run_after; const float* feat_add = hb.feat_add;
+                    double add[11];
+                    for (int c = 0; c < 11; ++c) add[c] = hb.add[c];
                     if (flip_budget) {
                         /* every geometric term of the hit's gradient is proportional to G, a SUM of terms of either sign (final
                          * transmittance, colour residuals): what moves G is measured against the sum of their magnitudes */
@@ -1653,17 +1717,79 @@ void oracle_project_bwd(const OracleCamera* cam, uint32_t N, int sh_degree,
     for (uint32_t i = 0; i < N; ++i) {
         if (tiles_count[i] == 0) continue;
         const float* g = density12 + (size_t)i * 12;
-        const float sr[3] = {g[0] - ps.cam[0], g[1] - ps.cam[1], g[2] - ps.cam[2]};
-        const float l = sqrtf(sr[0] * sr[0] + sr[1] * sr[1] + sr[2] * sr[2]);
-        const float inv_l = 1.0f / l;
-        const float dir[3] = {sr[0] * inv_l, sr[1] * inv_l, sr[2] * inv_l};
-        float Y[16];
-        sh_basis(sh_degree, dir, Y);
-        const int ncoef = (sh_degree + 1) * (sh_degree + 1);
-        for (int ch = 0; ch < 3; ++ch) {
-            const double gmask = feat[3 * (size_t)i + ch] > 0.0f ? feat_grad[3 * (size_t)i + ch] : 0.0;
-            for (int k = 0; k < ncoef; ++k) sph_grad[48 * (size_t)i + 3 * k + ch] = (double)Y[k] * gmask;
-        }
+        float dir[3];
+        view_direction(&ps, g, dir);
+        sh_radiance_bwd(sh_degree, dir, feat + 3 * (size_t)i, feat_grad + 3 * (size_t)i, sph_grad + 48 * (size_t)i);   /* onto the zeros above */
+    }
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * The per-hit units, exported one by one for tests/test_cpu_reference_hits.py: each wraps the static function that render_bwd_impl,
+ * oracle_project and oracle_project_bwd use, so the tested code is the used code.  The argument layout is that of
+ * oracle/ref_host/ref_hits.cpp, which exports the reference's own functions.
+ * ---------------------------------------------------------------------------------------------- */
+float oracle_kernel_response(int degree, float d2) { return kernel_response(degree, d2); }
+float oracle_kernel_response_grad(int degree, float d2, float resp, float resp_grad) { return kernel_response_grad(degree, d2, resp, resp_grad); }
+
+/* particle12: position(3), density, quaternion wxyz(4), scale(3), padding; thresholds: min response, min alpha, min transmittance;
+ * finals / state_io: transmittance, radiance(3), depth; cot: transmittance gradient, radiance gradient(3), depth gradient.  The alpha
+ * clamp is the backward's literal 0.99 (render_bwd_impl).  Evaluated in the current variant; returns the accept decision. */
+int oracle_hit_bwd_step(int degree, const float* ray_ori, const float* ray_dir, const float* particle12, const float* feat3,
+                        const float* thresholds, const float* finals, const float* cot, float* state_io,
+                        float* density_grad11, float* feat_grad3) {
+    OracleParams prm;
+    oracle_default_params(&prm);
+    prm.kernel_degree = degree;
+    prm.min_kernel_density = thresholds[0]; prm.alpha_threshold = thresholds[1]; prm.min_transmittance = thresholds[2];
+    prm.max_alpha = 0.99f;
+    Ray ray;
+    for (int k = 0; k < 3; ++k) { ray.o[k] = ray_ori[k]; ray.d[k] = ray_dir[k]; }
+    ray.tmin = 0.0f; ray.tmax = 3.4028235e+38f; ray.alive = 1;
+    float rows[3][3];
+    quat_to_rows(particle12 + 4, rows);
+    Hit h;
+    eval_hit(&prm, particle12, rows, &ray, &h);
+    for (int c = 0; c < 11; ++c) density_grad11[c] = 0.0f;
+    for (int c = 0; c < 3; ++c) feat_grad3[c] = 0.0f;
+    if (!((h.resp > prm.min_kernel_density) && (h.alpha > prm.alpha_threshold))) return 0;
+    HitBwd hb;
+    hit_bwd_terms(&prm, particle12, rows, ray.d, &h, feat3, state_io[0], state_io + 1, state_io[4], finals[0], finals + 1, finals[4],
+                  cot[0], cot + 1, cot[4], &hb);
+    for (int c = 0; c < 11; ++c) density_grad11[c] = hb.add[c];
+    for (int c = 0; c < 3; ++c) { feat_grad3[c] = hb.feat_add[c]; state_io[1 + c] = hb.run_after[c]; }
+    state_io[0] = hb.Tn; state_io[4] = hb.depth_after;
+    return 1;
+}
+
+void oracle_sh_radiance(int deg, const float* sph48, const float* dir3, int clamped, float* out3) {
+    sh_radiance(deg, dir3, sph48, out3);
+    if (clamped) for (int c = 0; c < 3; ++c) out3[c] = out3[c] > 0.0f ? out3[c] : 0.0f;   /* as render_impl clamps the precomputed colour */
+}
+
+void oracle_sh_radiance_bwd(int deg, const float* dir3, const double* rad_grad3, const float* radiance_unclamped3, double* sph_grad48) {
+    for (int k = 0; k < 48; ++k) sph_grad48[k] = 0.0;
+    sh_radiance_bwd(deg, dir3, radiance_unclamped3, rad_grad3, sph_grad48);
+}
+
+void oracle_quat_to_rows(const float* q_wxyz, float* rows9) {
+    float r[3][3];
+    quat_to_rows(q_wxyz, r);
+    memcpy(rows9, r, sizeof(r));
+}
+
+/* the direction oracle_project / oracle_project_bwd evaluate a Gaussian's SH along: normalize(position - sensor position) */
+void oracle_view_direction(const OracleCamera* cam, const float* position3, float* dir3) {
+    const PoseSet ps = make_pose_set(cam);
+    view_direction(&ps, position3, dir3);
+}
+
+/* the world-space rays of the compositing passes (make_ray), for the generator of tests/golden/hit_golden.npz */
+void oracle_world_rays(const OracleCamera* cam, uint32_t P, const float* ray_ori, const float* ray_dir, float* out_ori, float* out_dir, int32_t* alive) {
+    const PoseSet ps = make_pose_set(cam);
+    for (uint32_t i = 0; i < P; ++i) {
+        const Ray r = make_ray(&ps, ray_ori + 3 * (size_t)i, ray_dir + 3 * (size_t)i);
+        for (int k = 0; k < 3; ++k) { out_ori[3 * (size_t)i + k] = r.o[k]; out_dir[3 * (size_t)i + k] = r.d[k]; }
+        alive[i] = r.alive;
     }
 }
 

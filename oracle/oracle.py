@@ -1,8 +1,9 @@
 """ctypes front-end of the C oracle (oracle/gut_oracle.c).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's
-cpu_baseline leg, never by the product package.  "parity unpinned" for the device kernels (the
-reference ships no fixtures for this path); see gut_oracle.c header.
+cpu_baseline leg, never by the product package.  The per-hit backward is pinned to the reference's
+own header (HitUnits below, tests/test_cpu_reference_hits.py); "parity unpinned" for the rest of the
+device kernels (the reference ships no fixtures for this path); see gut_oracle.c header.
 """
 import ctypes as C
 import os
@@ -359,3 +360,94 @@ def backward(cam: dict, fwd: dict, rgba_grad, dist_grad, params=None, flip_bound
     if budget is not None:
         return dens_g, sph_g, feat_g, budget
     return dens_g, sph_g, feat_g
+
+
+# ---- the per-hit units, one call each (tests/test_cpu_reference_hits.py, tests/golden/gen_hit_golden.py) ----
+REF_HITS_SO = os.path.join(_HERE, "_ref", "libgut_refhits.so")
+
+
+class HitUnits:
+    """The per-hit functions of ONE library behind one Python surface: `HitUnits()` the oracle's own (gut_oracle.c: oracle_kernel_response
+    ... oracle_quat_to_rows, each a wrapper of the static function the passes use), `HitUnits.reference()` the reference's own header
+    compiled for the host (oracle/ref_host/ref_hits.cpp -> oracle/_ref/libgut_refhits.so, built by `make -C oracle _ref` where the
+    reference tree is at hand; None where it is not).  Both take and return float32 arrays in the same layout."""
+
+    def __init__(self, handle=None, prefix="oracle_"):
+        self.h = handle if handle is not None else lib()
+        self.is_reference = prefix != "oracle_"
+        f = lambda name: getattr(self.h, prefix + name)
+        self._resp, self._resp_grad = f("kernel_response" if not self.is_reference else "particle_response"), \
+            f("kernel_response_grad" if not self.is_reference else "particle_response_grd")
+        self._resp.restype = C.c_float; self._resp.argtypes = [C.c_int, C.c_float]
+        self._resp_grad.restype = C.c_float; self._resp_grad.argtypes = [C.c_int, C.c_float, C.c_float, C.c_float]
+        self._hit = f("hit_bwd_step" if not self.is_reference else "process_hit_bwd")
+        self._hit.restype = C.c_int; self._hit.argtypes = [C.c_int] + [C.c_void_p] * 10
+        self._sh = f("sh_radiance" if not self.is_reference else "radiance_from_sph")
+        self._sh.restype = None; self._sh.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self._sh_bwd = f("sh_radiance_bwd" if not self.is_reference else "radiance_from_sph_bwd")
+        self._sh_bwd.restype = None; self._sh_bwd.argtypes = [C.c_int] + [C.c_void_p] * 4
+        self._quat = f("quat_to_rows" if not self.is_reference else "quaternion_to_matrix")
+        self._quat.restype = None; self._quat.argtypes = [C.c_void_p, C.c_void_p]
+
+    @classmethod
+    def reference(cls):
+        return cls(C.CDLL(REF_HITS_SO), "ref_") if os.path.exists(REF_HITS_SO) else None
+
+    def response(self, degree, d2):
+        return np.float32(self._resp(int(degree), float(np.float32(d2))))
+
+    def response_grad(self, degree, d2, resp, resp_grad):
+        return np.float32(self._resp_grad(int(degree), float(np.float32(d2)), float(np.float32(resp)), float(np.float32(resp_grad))))
+
+    def hit_bwd(self, degree, ray_ori, ray_dir, particle12, feat3, thresholds, finals, cot, state):
+        """One processHitBwd step.  thresholds = (min response, min alpha, min transmittance); finals / state = (transmittance,
+        radiance[3], depth); cot = (transmittance gradient, radiance gradient[3], depth gradient).  Returns (accepted, state after
+        [5], density gradient [11], feature gradient [3])."""
+        a = [_f32(v).reshape(-1) for v in (ray_ori, ray_dir, particle12, feat3, thresholds, finals, cot)]
+        st = _f32(state).reshape(-1).copy()
+        g11 = np.zeros(11, np.float32); g3 = np.zeros(3, np.float32)
+        assert [v.size for v in a] == [3, 3, 12, 3, 3, 5, 5] and st.size == 5
+        acc = self._hit(int(degree), *[_p(v) for v in a], _p(st), _p(g11), _p(g3))
+        return int(acc), st, g11, g3
+
+    def sh_radiance(self, deg, sph48, dir3, clamped):
+        s, d = _f32(sph48).reshape(-1), _f32(dir3).reshape(-1)
+        assert s.size == 48 and d.size == 3
+        out = np.zeros(3, np.float32)
+        self._sh(int(deg), _p(s), _p(d), int(bool(clamped)), _p(out))
+        return out
+
+    def sh_radiance_bwd(self, deg, dir3, rad_grad3, radiance_unclamped3):
+        """[48] coefficient gradient.  The reference's is float32; the oracle's takes a float64 cotangent and returns float64."""
+        d, u = _f32(dir3).reshape(-1), _f32(radiance_unclamped3).reshape(-1)
+        if self.is_reference:
+            g = _f32(rad_grad3).reshape(-1); out = np.zeros(48, np.float32)
+        else:
+            g = np.ascontiguousarray(np.asarray(rad_grad3, np.float64)).reshape(-1); out = np.zeros(48, np.float64)
+        assert d.size == 3 and u.size == 3 and g.size == 3
+        self._sh_bwd(int(deg), _p(d), _p(g), _p(u), _p(out))
+        return out
+
+    def quat_rows(self, q_wxyz):
+        q = _f32(q_wxyz).reshape(-1); out = np.zeros(9, np.float32)
+        assert q.size == 4
+        self._quat(_p(q), _p(out))
+        return out.reshape(3, 3)
+
+
+def world_rays(cam: dict, ray_ori, ray_dir):
+    """The world-space rays the compositing passes walk (make_ray: sensor -> world, the scene-box test): origins [P,3], directions
+    [P,3] float32, alive [P] int32."""
+    c = make_camera(cam)
+    ro = _f32(ray_ori).reshape(-1, 3); rd = _f32(ray_dir).reshape(-1, 3)
+    o = np.zeros_like(ro); d = np.zeros_like(rd); alive = np.zeros(ro.shape[0], np.int32)
+    lib().oracle_world_rays(C.byref(c), C.c_uint32(ro.shape[0]), _p(ro), _p(rd), _p(o), _p(d), _p(alive))
+    return o, d, alive
+
+
+def view_direction(cam: dict, position3):
+    """normalize(position - sensor position) as oracle_project / oracle_project_bwd evaluate it: the direction of a Gaussian's SH."""
+    c = make_camera(cam)
+    p = _f32(position3).reshape(-1); out = np.zeros(3, np.float32)
+    lib().oracle_view_direction(C.byref(c), _p(p), _p(out))
+    return out
