@@ -472,9 +472,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_walk(const WalkOperands o, const 
             if (T > 0.0f) {
                 float o0 = cs.x, o1 = cs.y, o2 = cs.z;
                 if (!kCentred) {
-                    o0 += q1.x * ray.ex + q1.y * ray.ey + q1.z * ray.ez;
-                    o1 += q1.w * ray.ex + q2.x * ray.ey + q2.y * ray.ez;
-                    o2 += q2.z * ray.ex + q2.w * ray.ey + m22 * ray.ez;
+                    // o += M e, the same freedom and the same cure: in both instantiations of k_render (and of k_render_backward) the
+                    // first copy rounds m00 ex, m11 ey, m20 ex and the second m01 ey, m11 ey, m21 ey, then adds the sum to oc; left
+                    // to the compiler this unit rounded m01 ey, m10 ex, m21 ey in its first copy (ISA of all nine instantiations)
+                    o0 += kSecond ? __builtin_fmaf(q1.z, ray.ez, __builtin_fmaf(q1.x, ray.ex, q1.y * ray.ey))
+                                  : __builtin_fmaf(q1.z, ray.ez, __builtin_fmaf(q1.y, ray.ey, q1.x * ray.ex));
+                    o1 += __builtin_fmaf(q2.y, ray.ez, __builtin_fmaf(q1.w, ray.ex, q2.x * ray.ey));
+                    o2 += kSecond ? __builtin_fmaf(m22, ray.ez, __builtin_fmaf(q2.z, ray.ex, q2.w * ray.ey))
+                                  : __builtin_fmaf(m22, ray.ez, __builtin_fmaf(q2.w, ray.ey, q2.z * ray.ex));
                 }
                 const float u0 = kSecond ? __builtin_fmaf(q1.z, ray.dz, __builtin_fmaf(q1.x, ray.dx, q1.y * ray.dy))
                                          : __builtin_fmaf(q1.z, ray.dz, __builtin_fmaf(q1.y, ray.dy, q1.x * ray.dx));

@@ -15,8 +15,9 @@ the reference's backward conventions:
   - alpha clamp min(0.99, .) is straight-through (gaussianParticles.cuh:611-629 are not masked);
   - SH view direction carries no gradient (gaussianParticles.slang:307-318 `no_diff`);
   - the hit-distance output uses a detached transmittance (quirk 1 of SURVEY §8a); its gradient
-    w.r.t. the canonical ray is only diagonal in the reference, so gradient cross-checks are made
-    with dist_grad == 0.
+    w.r.t. the canonical ray is only diagonal in the reference: render_tiled(reference_hit_distance_grad=True)
+    restates that form (_ReferenceHitDistance) for cross-checks with a distance cotangent; the other
+    cross-checks are made with dist_grad == 0.
 """
 import math
 
@@ -136,7 +137,32 @@ class _ReferenceResponse(torch.autograd.Function):
         return out, None
 
 
-def _composite_block(o, d, tmin, tmax, mu, rows, s, sigma, feat, state, kernel_degree=2, reference_response_grad=False):
+class _ReferenceHitDistance(torch.autograd.Function):
+    """hit_t = |grds|, grds = gscl * grd * dot(grd, -gro).  Same forward; the backward is the reference's own
+    (gaussianParticles.cuh:532-548): of d grds / d grd and d grds / d gro it keeps the DIAGONAL only,
+        d hit_t / d gscl = grd dot(grd, -gro) * k,   d / d grd_i = -gscl_i (grd.gro + grd_i gro_i) k_i,   d / d gro_i = -gscl_i grd_i^2 k_i,
+    with k = grds / hit_t (zero where hit_t is zero).  The normalisation of grd and everything in front of it is differentiated
+    as usual (safe_normalize_bw and the chain the reference runs for the response's gradient)."""
+
+    @staticmethod
+    def forward(ctx, gro, grd, s):
+        p = -(grd * gro).sum(-1, keepdim=True)
+        grds = s * grd * p
+        hit_t = grds.norm(dim=-1)
+        ctx.save_for_backward(gro, grd, s, p, grds, hit_t)
+        return hit_t
+
+    @staticmethod
+    def backward(ctx, g):
+        gro, grd, s, p, grds, hit_t = ctx.saved_tensors
+        some = (hit_t > 0)[..., None]
+        k = torch.where(some, grds / torch.where(some, hit_t[..., None], torch.ones_like(hit_t[..., None])), torch.zeros_like(grds)) * g[..., None]
+        x = grd * gro
+        return -s * grd * grd * k, -s * (x.sum(-1, keepdim=True) + x) * k, grd * p * k
+
+
+def _composite_block(o, d, tmin, tmax, mu, rows, s, sigma, feat, state, kernel_degree=2, reference_response_grad=False,
+                     reference_hit_distance_grad=False):
     """One block of P rays against L depth-ordered Gaussians; state = (T, alive, rgb, dist, hits)."""
     T_c, alive_c, rgb, dist, hits = state
     gposc = o[:, None, :] - mu[None]
@@ -150,7 +176,10 @@ def _composite_block(o, d, tmin, tmax, mu, rows, s, sigma, feat, state, kernel_d
     a = resp * sigma[None, :]
     alpha = a + (a.clamp(max=ALPHA_MAX) - a).detach()
     p = -(grd * gro).sum(-1)
-    hit_t = (s * grd * p[..., None]).norm(dim=-1)
+    if reference_hit_distance_grad:
+        hit_t = _ReferenceHitDistance.apply(gro, grd, s[None].expand_as(gro))
+    else:
+        hit_t = (s * grd * p[..., None]).norm(dim=-1)
     accept = (resp > MIN_RESPONSE) & (alpha > ALPHA_MIN) & (hit_t > tmin[:, None]) & (hit_t < tmax[:, None])
     a_eff = torch.where(accept, alpha, torch.zeros_like(alpha))
     one_m = 1 - a_eff
@@ -179,9 +208,10 @@ def _ray_limits(o, d):
 
 
 def render_tiled(params, tq, W, H, ray_ori, ray_dir, tile_ranges, sorted_ids, sh_degree=3, dtype=torch.float64,
-                 chunk=128, kernel_degree=2, reference_response_grad=False):
+                 chunk=128, kernel_degree=2, reference_response_grad=False, reference_hit_distance_grad=False):
     """params: dict of tensors positions[N,3], rotation[N,4], scale[N,3], density[N,1], features[N,48].
-    Returns rgba [H,W,4], dist [H,W], hits [H,W] (torch, differentiable)."""
+    Returns rgba [H,W,4], dist [H,W], hits [H,W] (torch, differentiable).  reference_hit_distance_grad: the gradient of `dist` is the
+    reference's (_ReferenceHitDistance), which a cotangent on the distance needs to be comparable with the C oracle."""
     R, t, Rinv, cam_pos = pose_matrices(tq, dtype)
     pos, rot, scl, dns, sph = (params[k].to(dtype) for k in ("positions", "rotation", "scale", "density", "features"))
     feat_all = precompute_features(pos, sph, cam_pos, sh_degree)
@@ -210,7 +240,7 @@ def render_tiled(params, tq, W, H, ray_ori, ray_dir, tile_ranges, sorted_ids, sh
             if ids.numel() == 0 or not bool(state[1].any()):
                 break
             state = _composite_block(o, d, tmin, tmax, pos[ids], rows_all[ids], scl[ids], dns[ids, 0], feat_all[ids], state,
-                                     kernel_degree, reference_response_grad)
+                                     kernel_degree, reference_response_grad, reference_hit_distance_grad)
         T, _, rgb, dist, hits = state
         out = torch.cat([rgb, (1 - T)[:, None]], dim=1)
         rgba = rgba.index_put((pix[valid],), out[valid])

@@ -20,8 +20,6 @@ from tests.common import COLOUR_TOL, PIX_FLIP, ROW_FLIP_BOUND, cams, make_view, 
 oracle = importlib.import_module("oracle.oracle")
 selection = importlib.import_module("3dgrut_amd.selection")
 
-ATTR_SEEDS = {name: 70 + i for i, name in enumerate(cr.CASES)}
-
 
 def attribute_reference(cam, fwd, attrs, params=None):
     """out [K,H,W] float64 with out[:, py, px] = the sum over the pixel's accepted entries of w * attrs[id]; attrs [N,K]."""
@@ -46,7 +44,7 @@ def attribute_reference(cam, fwd, attrs, params=None):
 
 def random_attributes(name, n, k=4):
     """Seeded uniform [0, 1) attributes float32 [n, k], the last channel all ones."""
-    a = np.random.default_rng(ATTR_SEEDS[name]).uniform(0, 1, (n, k)).astype(np.float32)
+    a = np.random.default_rng(70 + cr.case_index(name)).uniform(0, 1, (n, k)).astype(np.float32)
     a[:, -1] = 1.0
     return a
 

@@ -331,6 +331,56 @@ def four_deep_tiles():
     return _case("four_deep_tiles", sc, 32, 32, 32.0, True, lambda c: _check_deep(c, min_length=K_LAZY_CACHE + K_LAZY_BATCH))
 
 
+EARLY_LENGTH, EARLY_FIRST_OPAQUE = 8193, 4700
+
+
+def deep_list_ending_early():
+    """E: the single-tile list of 8193 entries whose entries of depth rank >= 4700 are opaque (density 0.99) and cover the tile
+    (scales 1.5: every pixel of the tile within 1.5 sigma).  Every ray walks the 4700 faint entries in front — nine selections, the
+    last beyond the depth cache — and ends within a few dozen entries behind them: the walk stops inside the tenth selection, more
+    than six selections before the list's end.  What lies behind is never ordered by the lazy order: ordered_ids keeps its padding
+    there, tile_traversed_fwd < the list length bounds the backward and every walk (`range.y = range.x + min(..., tile_walked)`),
+    and the chunk the walk ends in is cut by s_first_invalid / the depth at which the last ray ended."""
+    sc, listed = _single_tile_base()
+    rng = np.random.default_rng(1000 + EARLY_LENGTH + 1)
+    drop = rng.permutation(listed)[:len(listed) - EARLY_LENGTH]
+    order = listed[~np.isin(listed, drop)]                                   # the kept list, in depth order
+    sc = {k: v.copy() for k, v in sc.items()}
+    opaque = order[EARLY_FIRST_OPAQUE:]
+    sc["density"][opaque] = 0.99
+    sc["scale"][opaque] = 1.5
+    keep = np.setdiff1d(np.arange(len(sc["positions"])), drop)
+    sub = _subset(sc, rng.permutation(keep))
+
+    def check(case):
+        ref = case["ref"]
+        lens = list_lengths(ref)
+        assert lens.tolist() == [EARLY_LENGTH], f"the list has {lens.tolist()} entries, not {EARLY_LENGTH}"
+        assert EARLY_LENGTH > K_LAZY_CACHE + 2 * K_LAZY_BATCH
+        walked = int(ref["tile_traversed_fwd"][0])
+        # at least one selection beyond the cache is made, at least one is never made
+        assert K_LAZY_CACHE + K_LAZY_BATCH < walked < EARLY_LENGTH - K_LAZY_BATCH, walked
+        assert walked > EARLY_FIRST_OPAQUE, "some ray must reach the opaque entries"
+        # no pixel is still alive at the end: every ray's last accepted entry leaves T below min_transmittance
+        prm = case["params"]()
+        cam = case["view"]["oracle_cam"]
+        last_t, ended_at = [], []
+        for py in range(case["H"]):
+            for px in range(case["W"]):
+                e = oracle.debug_ray(cam, ref, px, py, params=prm, max_entries=EARLY_LENGTH)
+                acc = e[e[:, 5] != 0]
+                assert len(acc), (px, py)
+                last_t.append(float(acc[-1, 6]))
+                ended_at.append(len(e))
+        assert max(last_t) < prm.min_transmittance, max(last_t)
+        assert max(ended_at) == walked
+        case["info"].update(list_lengths=lens.tolist(), traversal=[walked], selections_made=int(-(-walked // K_LAZY_BATCH)),
+                            selections_never_made=int(-(-EARLY_LENGTH // K_LAZY_BATCH)) - int(-(-walked // K_LAZY_BATCH)),
+                            first_ray_ends_at=min(ended_at), max_hits=int(ref["hits"].max()))
+
+    return _case("deep_list_ending_early", sub, 16, 16, 16.0, True, check)
+
+
 TIE_GROUPS = (700, 65, 64)
 
 

@@ -14,12 +14,38 @@ import importlib
 
 import numpy as np
 
-from tests import capacity_cases
+from tests import capacity_cases, off_centre_cases
 from tests.common import FLIP_MARGIN_BOUND, FISHEYE_DIST, cams, densified_like_scene, make_view, scenes
 
 oracle = importlib.import_module("oracle.oracle")
 
 CASES = ("pinhole_64x48", "ragged_70x45", "fisheye", "single_tile_1025")
+# Further cases, by name, for the tests that go beyond the four above.  `case` and every reference derived from it
+# (attribute_reference.attribute_case, attribute_gradient_reference.gradient_case, weighted_contribution_reference.weighted_case,
+# surface_reference.surface_case) take these names as well:
+#   "<one of CASES>@<plane>"   the case seen through the origin plane `plane` of tests/off_centre_cases.py (rays that do not start at
+#                              the sensor position: the un-centred instantiation of k_walk)
+#   one of DEEP_CASES          lists beyond the 4096-word depth cache of the lazy order (tests/capacity_cases.py)
+#   a name given to `view_case`  any view of a named case's scene
+DEEP_CASES = ("single_tile_4097", "four_deep_tiles", "ties_across_the_cache", "deep_list_ending_early")
+# The share of a deep case's pixels with a hit that may be NEAR in its surface references (another valid fp32 evaluation may choose
+# another entry; tests/surface_reference.py) is a property of the reference alone.  Rays through thousands of faint entries keep a
+# wide flip budget: 14.1 % of four_deep_tiles' pixels and 11.4 % of ties_across_the_cache's are near at level 0.1; the other 85 % are
+# held to the reference's id exactly.  The two other cases stay under the 5 % of the one-view test.  tests/test_cpu_capacity_cases.py
+# asserts the shares, tests/test_gpu_walk_depth.py allows them.
+DEEP_MAX_NEAR = {"single_tile_4097": 0.05, "four_deep_tiles": 0.15, "ties_across_the_cache": 0.15, "deep_list_ending_early": 0.05}
+_VIEW_CASES = {}
+
+
+def base_name(name):
+    """The case of CASES or DEEP_CASES whose scene the case `name` shows."""
+    return _VIEW_CASES[name][0] if name in _VIEW_CASES else name.split("@")[0]
+
+
+def case_index(name):
+    """A small integer per case name, the offset of the seeds the derived references draw their random inputs with: the position in
+    CASES for the four cases there and for every other view of their scenes, the positions after them for DEEP_CASES."""
+    return (CASES + DEEP_CASES).index(base_name(name))
 
 
 def reference(cam, fwd, params=None, margins=None):
@@ -71,6 +97,33 @@ def case(name):
     """The named case with its oracle forward (`ref`), decision margins, contribution reference (`contrib`) and the oracle backward of
     the cotangent (1, 0, 0, 0): `feat_grad` [N] = d(sum of red)/d(red feature), the second statement of weight_sum, with its flip
     budget and fp32 conditioning."""
+    if "@" in name and name not in _VIEW_CASES:
+        base, plane = name.split("@")
+        view_case(name, base, off_centre_cases.off_centre(_base(base)["view"], plane))
+    if name in _VIEW_CASES:           # another view of a named case's scene (view_case)
+        base, view = _VIEW_CASES[name]
+        b = _base(base)
+        c = dict(b, name=name, view=view, info={}, ref=oracle.forward(view["oracle_cam"], b["W"], b["H"], b["d12"], b["sph"], view["ro"], view["rd"],
+                                                                      sh_degree=3, params=b["params"]()))
+    else:
+        c = dict(_base(name))
+    return _finish(c)
+
+
+def view_case(name, base, view):
+    """The entry point for a view instead of a case name: registers `name` as the scene of the case `base` seen through `view` (a
+    make_view result of the same size, any origin plane) and returns the name; case(name) and the derived references then build it
+    like any other, once.  The cases of CASES themselves are not touched."""
+    assert base in CASES + DEEP_CASES and name not in CASES + DEEP_CASES
+    assert name not in _VIEW_CASES or _VIEW_CASES[name][1] is view, f"{name} is already another view"
+    assert (view["W"], view["H"]) == (_base(base)["W"], _base(base)["H"])
+    _VIEW_CASES.setdefault(name, (base, view))
+    return name
+
+
+@functools.lru_cache(maxsize=None)
+def _base(name):
+    """The scene, view and oracle forward of a case of CASES or DEEP_CASES."""
     if name == "pinhole_64x48":     # the case of tests/test_cpu_pose_gradient.py
         c = _scene_case(name, 300, 0, make_view("pinhole", 64, 48, cams.look_at_c2w((0.3, -0.2, -4.0), (0.0, 0.0, 0.0)), fx=64.0))
     elif name == "ragged_70x45":    # ragged right and bottom tiles, ragged last wave of rows, an orbit pose
@@ -80,8 +133,20 @@ def case(name):
                                                 distortion=FISHEYE_DIST))
     elif name == "single_tile_1025":  # one tile, 1025 entries: five chunks, three lazy-order selections, a last chunk of one entry
         c = dict(capacity_cases.single_tile_list(1025))
+    elif name == "single_tile_4097":  # one entry beyond the depth cache: the ninth selection orders one streamed word
+        c = dict(capacity_cases.single_tile_list(4097))
+    elif name == "four_deep_tiles":
+        c = dict(capacity_cases.four_deep_tiles())
+    elif name == "ties_across_the_cache":
+        c = dict(capacity_cases.ties_across_the_cache())
+    elif name == "deep_list_ending_early":
+        c = dict(capacity_cases.deep_list_ending_early())
     else:
         raise KeyError(name)
+    return c
+
+
+def _finish(c):
     cam, fwd, W, H = c["view"]["oracle_cam"], c["ref"], c["W"], c["H"]
     prm = c["params"]()
     c["margins"] = oracle.render_margins(cam, fwd, params=prm)

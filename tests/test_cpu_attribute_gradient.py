@@ -42,7 +42,7 @@ def test_reference_against_the_oracle_backward(name):
 def test_adjoint_identity(name):
     """sum_p g(p) . render(a)(p) = sum_i a_i . grad_i in float64, signed g and signed a, to 1e-9."""
     c, g = cr.case(name), gr.gradient_case(name)
-    a = np.random.default_rng(130 + cr.CASES.index(name)).uniform(-1, 1, (c["d12"].shape[0], 4))
+    a = np.random.default_rng(130 + cr.case_index(name)).uniform(-1, 1, (c["d12"].shape[0], 4))
     planes = ar.attribute_reference(c["view"]["oracle_cam"], c["ref"], a, params=c["params"]())
     lhs, rhs = float((g["g"].astype(np.float64) * planes).sum()), float((a * g["grad"]).sum())
     print(f"[attribute gradient adjoint {name}] {lhs!r} vs {rhs!r}: difference {abs(lhs - rhs):.3e}")

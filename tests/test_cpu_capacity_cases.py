@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests import capacity_cases as cc
+from tests import contribution_reference as cr
 
 
 @pytest.mark.parametrize("name", list(cc.WINDOW_CASES))
@@ -55,8 +56,43 @@ def test_four_deep_tiles():
     assert len(info["list_lengths"]) == 4 and min(info["list_lengths"]) > cc.K_LAZY_CACHE
 
 
+def test_deep_list_ends_early():
+    """E: the walk ends beyond the depth cache and more than a selection before the list's end; no ray outlives it."""
+    case = cc.deep_list_ending_early()
+    info = cc.check_preconditions(case)
+    print(f"[capacity {case['name']}] {info}")
+    assert info["list_lengths"] == [cc.EARLY_LENGTH]
+    assert cc.K_LAZY_CACHE + cc.K_LAZY_BATCH < info["traversal"][0] < cc.EARLY_LENGTH - cc.K_LAZY_BATCH
+    assert info["selections_made"] > cc.K_LAZY_CACHE // cc.K_LAZY_BATCH + 1 and info["selections_never_made"] >= 1
+    assert not cc.fully_walked(case["ref"])
+
+
 def test_tie_groups_lie_across_selection_boundaries():
     case = cc.ties_across_the_cache()
     info = cc.check_preconditions(case)
     print(f"[capacity {case['name']}] {info}")
     assert info["list_lengths"][0] > 2 * cc.K_LAZY_CACHE and [b - a + 1 for a, b in info["tie_ranks"]] == list(cc.TIE_GROUPS)
+
+
+@pytest.mark.parametrize("name", cr.DEEP_CASES)
+def test_walk_references_of_the_deep_cases(name):
+    """What tests/test_gpu_walk_depth.py rests on, from the references alone: every tile's walk passes the depth cache, rows behind
+    the walked prefixes exist and score nothing, the surface references choose an entry on most pixels, and the share of NEAR pixels
+    (where another fp32 evaluation may choose another entry) stays under the cap that file allows the case."""
+    from tests import surface_reference as sr
+    MAX_NEAR = cr.DEEP_MAX_NEAR
+    c = cr.case(name)
+    ref, k = c["ref"], c["contrib"]
+    assert (ref["tile_traversed_fwd"].astype(np.int64) > cc.K_LAZY_CACHE).all()
+    assert (~k["walked"]).sum() > 0 and not k["pixels"][~k["walked"]].any() and (k["pixels"] > 0).sum() > cc.K_LAZY_CACHE // 2
+    if name == "deep_list_ending_early":
+        behind = ref["sorted_ids"][int(ref["tile_traversed_fwd"][0]):]
+        assert len(behind) > cc.K_LAZY_BATCH and not k["walked"][behind].any()        # listed, never walked
+    s = sr.surface_case(name)
+    shares = {}
+    for level in sr.LEVELS:
+        shares[level] = float(sr.level_planes(name, level)["near"].sum() / s["hit"].sum())
+    shares["max_weight"] = float(sr.max_weight_planes(name)["near"].sum() / s["hit"].sum())
+    print(f"[deep walk {name}] {int(s['hit'].sum())} pixels with a hit, near shares {shares}")
+    assert max(shares.values()) <= MAX_NEAR[name]
+    assert (sr.level_planes(name, 0.5)["id"] >= 0).sum() > 0 and (sr.max_weight_planes(name)["id"] >= 0).sum() == s["hit"].sum()

@@ -375,8 +375,13 @@ def test_two_fp32_evaluations_measure_the_tolerance_model(name):
     tests use — decision margins for pixels, noise + flip budget for gradient rows — must bound it on EVERY pixel and EVERY row
     with every constant divided by K_BAND.  No escape clause: nothing is allowed to exceed the model here."""
     mk, kind, W, H, c2w, kw = BAND_SCENES[name]
-    sc = mk()
-    view = make_view(kind, W, H, c2w(), **kw)
+    check_tolerance_band(name, mk(), make_view(kind, W, H, c2w(), **kw))
+
+
+def check_tolerance_band(name, sc, view):
+    """The band experiment on one scene and view (any origin plane: tests/test_cpu_off_centre_cases.py runs it off-centre).  Returns
+    the report it prints."""
+    W, H = view["W"], view["H"]
     cam = view["oracle_cam"]
     d12, sph = scenes.pack_density(sc), sc["features"]
     rng = np.random.default_rng(11)
@@ -433,6 +438,7 @@ def test_two_fp32_evaluations_measure_the_tolerance_model(name):
         rep["sh"] = round(r_full, 3)
         report[v] = rep
     print(f"[band {name}] {report}")
+    return report
 
 
 def _band_rows(report, tag, gA, gB, sA, sB, budget, sh_degree=3):

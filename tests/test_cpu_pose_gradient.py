@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import off_centre_cases
 from tests.common import cams, pose, scenes
 
 per_ray = importlib.import_module("oracle.per_ray_torch")
@@ -13,7 +14,7 @@ per_ray = importlib.import_module("oracle.per_ray_torch")
 W, H, FX = 64, 48, 64.0
 
 
-def _twist_case(sh_degree):
+def _twist_case(sh_degree, plane=None):
     """scene_c1(300, 0) seen from (0.3, -0.2, -4) at 64 x 48: the loss <cotangent, rgba> of the float64 per-ray render, with the
     first-order world-axis twist (rho, phi) about the camera centre applied to the camera-space rays,
         o_c' = R rho + A o_c,   d_c' = A d_c,   A = R (I + [phi]x) R^T,   R world -> sensor,
@@ -24,6 +25,8 @@ def _twist_case(sh_degree):
     c2w = cams.look_at_c2w((0.3, -0.2, -4.0), (0.0, 0.0, 0.0))
     tq = pose.sensor_pose_from_c2w(c2w).T_world_sensors[0]
     ro, rd = cams.pinhole_rays(W, H, FX, FX)
+    if plane is not None:      # rays that do not start at the sensor position: the twist about the camera centre moves their origins too
+        ro = off_centre_cases.origin_plane(plane, W, H)
     K = cams.pinhole_intrinsics_dict(W, H, FX, FX)
     cam = dict(model="pinhole", principal_point=K["principal_point"], focal_length=K["focal_length"], pose_start=tq)
     dt = torch.float64

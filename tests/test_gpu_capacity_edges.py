@@ -6,10 +6,12 @@ preconditions alone are tests/test_cpu_capacity_cases.py):
     without any small footprint, a partly filled last workgroup with culled rows, large footprints across a window's edge;
   * the depth cache of the lazy per-tile order (lazy_select, K6): single-tile lists of exact lengths around the selection size
     (512), the cache size (4096) and beyond, four deep tiles at once, tie groups of 700 / 65 / 64 clones across selection
-    boundaries and across the cache.
+    boundaries and across the cache, and a list of 8193 entries whose walk ends at 4727 (case E: the selections behind the last
+    ray's end are never made, the backward is bounded by the forward's depth).
 
 Every case is compared with the CPU oracle — tile ranges, counts and offsets bit for bit, the ordered ids over the WHOLE slice of
-every tile (all cases are walked to the end of every list), traversal depths, image and hit counts per pixel against the pixel's
+every tile (cases A - D are walked to the end of every list; case E over its walked prefix, with padding or the oracle's id
+behind it), traversal depths, image and hit counts per pixel against the pixel's
 own flip budget, every gradient block per row against the row's own budget — and with the full stable sort
 (set_lazy_tile_order(False)): outputs and ranges bit-equal, gradients to 1e-5 relative L2.  The inputs are the activated [N,12] /
 [N,48] rows themselves (SplatRaster.trace of the Tracer's wrapper), so the oracle's preconditions hold bit for bit on the device."""
@@ -50,7 +52,9 @@ def _render(case, lazy, rgba_grad):
                 stats=raster.stats())
 
 
-def _check_case(case):
+def _check_case(case, walked_to_the_end=True):
+    """walked_to_the_end=False (case E): the oracle's walk ends inside the list.  The ordered ids are then compared over the walked
+    prefix of every tile; behind it every id is either the oracle's (ordered by the selection the walk ended in) or padding."""
     info = cc.check_preconditions(case)        # again, here: an edited scene must not leave this test testing nothing
     ref, W, H, name = case["ref"], case["W"], case["H"], f"{case['name']}/culling={int(case['tile_culling'])}"
     ocam, prm = case["view"]["oracle_cam"], case["params"]()
@@ -72,7 +76,14 @@ def _check_case(case):
         assert np.array_equal(raster.debug_buffer(key).cpu().numpy().view(np.uint32), ref[key]), f"{name}: {key}"
     _check_ordered_ids(raster, ref)
     ordered = raster.debug_buffer("ordered_ids").cpu().numpy().view(np.uint32)
-    bad = np.nonzero(ordered != ref["sorted_ids"])[0]
+    same = ordered == ref["sorted_ids"]
+    if not walked_to_the_end:
+        behind = np.ones(ordered.size, bool)
+        for t, (b, e) in enumerate(ref["tile_ranges"]):
+            behind[int(b):int(b) + min(int(ref["tile_traversed_fwd"][t]), int(e) - int(b))] = False
+        assert behind.any() and (ordered[behind] == PAD).any(), f"{name}: nothing of the list was left unordered"
+        same |= behind & (ordered == PAD)
+    bad = np.nonzero(~same)[0]
     where = ""
     if bad.size:
         tile = int(np.searchsorted(ref["tile_ranges"][:, 1], bad[0], side="right"))
@@ -134,6 +145,16 @@ def test_four_deep_tiles_at_once():
     """C: four tiles, each list longer than the depth cache by more than a selection, all walked to their ends."""
     info = _check_case(cc.four_deep_tiles())
     assert len(info["list_lengths"]) == 4 and min(info["list_lengths"]) > cc.K_LAZY_CACHE + cc.K_LAZY_BATCH
+
+
+def test_deep_list_that_ends_early():
+    """E: 8193 entries on one tile, opaque from depth rank 4700 on: nine selections are walked whole (the ninth beyond the depth
+    cache), the tenth is cut short when the last ray ends, seven are never made.  The walked prefix is the oracle's order, what lies
+    behind it is ordered or padding, the traversal depth is the oracle's, and the backward — bounded by that depth — gives the
+    oracle's rows, under the lazy order and under the full sort."""
+    info = _check_case(cc.deep_list_ending_early(), walked_to_the_end=False)
+    assert info["list_lengths"] == [cc.EARLY_LENGTH] and cc.K_LAZY_CACHE + cc.K_LAZY_BATCH < info["traversal"][0] < cc.EARLY_LENGTH - cc.K_LAZY_BATCH
+    assert info["selections_never_made"] >= 1
 
 
 def test_depth_ties_across_selections_and_the_cache():

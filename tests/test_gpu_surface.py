@@ -61,7 +61,7 @@ def _bits(t):
 
 
 @pytest.mark.parametrize("name", cr.CASES)
-def test_planes_against_the_reference(name):
+def test_planes_against_the_reference(name, max_near=0.05):
     """Both modes, the levels 0.5, 0.1 and 0.9.  A pixel is NEAR where another valid fp32 evaluation may choose differently: in
     level mode where some accepted entry has |T_after - level| <= slack(p), in largest-weight mode where the two largest reference
     weights differ by at most 2 slack(p), slack(p) = COLOUR_TOL + PIX_FLIP x the pixel's flip budget.  A pixel that is not near has
@@ -88,7 +88,7 @@ def test_planes_against_the_reference(name):
         print(f"[surface {name} {mode} {level}] {int(near.sum())} near of {int(s['hit'].sum())} pixels with a hit; not near: {int(wrong_id.sum())} ids "
               f"differ, worst distance difference {float(dist_err[calm].max()):.3e} (COLOUR_TOL {COLOUR_TOL:.0e}), worst weight difference / slack "
               f"{float((w_err / s['slack'])[calm].max()):.3e}; near: {int(((ids != ref['id']) & near).sum())} ids differ; {int((ids >= 0).sum())} ids")
-        assert near.sum() <= 0.05 * s["hit"].sum()
+        assert near.sum() <= max_near * s["hit"].sum()
         assert not wrong_id.any()
         assert bool((dist_err[calm] <= COLOUR_TOL).all())
         if mode == "max_weight":
@@ -97,7 +97,7 @@ def test_planes_against_the_reference(name):
             assert ids[py, px] == -1 or ids[py, px] in s["entries"][py * W + px][0], (py, px)
         # the three planes say the same thing about which pixels have a surface
         assert np.array_equal(ids >= 0, dist > 0) and np.array_equal(ids >= 0, wgt > 0)
-        if not (name == "single_tile_1025" and mode == "level" and level == 0.1):
+        if not (cr.base_name(name) == "single_tile_1025" and mode == "level" and level == 0.1):
             assert int((ids >= 0).sum()) > 0
         else:
             assert not (ids >= 0).any() and not dist.any() and not wgt.any()          # nothing crosses: the all-none plane

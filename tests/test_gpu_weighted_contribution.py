@@ -134,7 +134,7 @@ def test_exact_identities(name):
     P = ((tx + ty) % 2 == 0).astype(np.float32)
     a, b = _weighted(raster, d12, v, _plane(P), _q32(n)), _weighted(raster, d12, v, _plane(1.0 - P), _q32(n))
     assert torch.equal(a + b, scores[:, 0])
-    if name != "single_tile_1025":
+    if case["ref"]["tile_ranges"].shape[0] > 1:      # (a single tile lies whole in one of the two planes)
         assert bool(a.any()) and bool(b.any())
     # the weighted-only walk gives the array of the walk that writes both
     plane = _plane(wr.weighted_case(name)["plane"])

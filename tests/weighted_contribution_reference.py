@@ -18,8 +18,6 @@ from tests.common import FLIP_MARGIN_BOUND
 
 oracle = importlib.import_module("oracle.oracle")
 
-PLANE_SEEDS = {name: 40 + i for i, name in enumerate(cr.CASES)}
-
 
 def clamp_plane(plane):
     """min(max(e, 0), 1) with a NaN counted as 0, the kernel's clamp on load."""
@@ -53,7 +51,7 @@ def weighted_reference(cam, fwd, plane, params=None):
 
 
 def random_plane(name, H, W):
-    return np.random.default_rng(PLANE_SEEDS[name]).uniform(0, 1, (H, W))
+    return np.random.default_rng(40 + cr.case_index(name)).uniform(0, 1, (H, W))
 
 
 @functools.lru_cache(maxsize=None)
