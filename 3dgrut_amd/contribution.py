@@ -29,7 +29,9 @@ import math
 import numpy as np
 import torch
 
-SCORES = ("weight_sum", "max_weight")
+from .confblock import boolean, check_block, integer, number, one_of
+
+SCORES =("weight_sum", "max_weight")
 
 
 def unpack_scores(scores):
@@ -177,23 +179,11 @@ def compact(stepper, mask, strategy=None):
 
 # the trainer's `compaction` block
 DEFAULTS = {"enabled": False, "keep_fraction": 0.5, "score": "weight_sum", "min_pixels": 1, "finetune_iterations": 0}
+RULES = {"enabled": boolean(), "keep_fraction": number("in (0, 1]", gt=0, le=1), "score": one_of(SCORES), "min_pixels": integer(ge=0),
+         "finetune_iterations": integer(ge=0)}
 
 
 def check_config(block):
     """The resolved `compaction` block: enabled true or false, keep_fraction in (0, 1], score one of SCORES, min_pixels and
     finetune_iterations integers >= 0."""
-    unknown = set(block) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"compaction: unknown keys {sorted(unknown)}")
-    if not isinstance(block["enabled"], bool):
-        raise ValueError(f"compaction.enabled must be true or false, got {block['enabled']!r}")
-    f = block["keep_fraction"]
-    if isinstance(f, (bool, str)) or not (0.0 < float(f) <= 1.0):
-        raise ValueError(f"compaction.keep_fraction must be in (0, 1], got {f!r}")
-    if block["score"] not in SCORES:
-        raise ValueError(f"compaction.score must be one of {SCORES}, got {block['score']!r}")
-    for k in ("min_pixels", "finetune_iterations"):
-        v = block[k]
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
-            raise ValueError(f"compaction.{k} must be an integer >= 0, got {v!r}")
-    return block
+    return check_block("compaction", block, DEFAULTS, RULES)

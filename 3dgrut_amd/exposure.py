@@ -23,30 +23,21 @@ import ctypes as C
 import numpy as np
 import torch
 
+from .confblock import boolean, check_block, integer, number
+
 DEFAULTS = {"enabled": False, "lr": 0.001, "start_iteration": 0, "end_iteration": -1, "beta1": 0.9, "beta2": 0.999, "eps": 1e-15}
 IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+_RATE, _BETA = number("finite and >= 0", ge=0), number("in [0, 1)", ge=0, lt=1)
+RULES = {"enabled": boolean(), "start_iteration": integer(), "end_iteration": integer(), "lr": _RATE, "eps": _RATE, "beta1": _BETA,
+         "beta2": _BETA}
 
 
 def check_config(block):
     """The resolved `exposure` block: rate and eps finite and >= 0, betas in [0, 1), iterations integers (end_iteration -1: to
     the end of the run)."""
-    unknown = set(block) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"exposure: unknown keys {sorted(unknown)}")
-    if not isinstance(block["enabled"], bool):   # (a string such as "false" would be truthy)
-        raise ValueError(f"exposure.enabled must be true or false, got {block['enabled']!r}")
-    for k in ("start_iteration", "end_iteration"):
-        if isinstance(block[k], bool) or not isinstance(block[k], (int, np.integer)):
-            raise ValueError(f"exposure.{k} must be an integer, got {block[k]!r}")
+    check_block("exposure", block, DEFAULTS, RULES)
     if int(block["start_iteration"]) < 0 or int(block["end_iteration"]) < -1:
         raise ValueError("exposure: start_iteration must be >= 0 and end_iteration >= 0, or -1 for the end of the run")
-    for k in ("lr", "eps"):
-        v = float(block[k])
-        if not (0.0 <= v < float("inf")):
-            raise ValueError(f"exposure.{k} must be finite and >= 0, got {block[k]!r}")
-    for k in ("beta1", "beta2"):
-        if not (0.0 <= float(block[k]) < 1.0):
-            raise ValueError(f"exposure.{k} must be in [0, 1), got {block[k]!r}")
     return block
 
 

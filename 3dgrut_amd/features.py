@@ -12,8 +12,9 @@ the premultiplied target:
 alpha the forward's own alpha of the view, held constant.  Per view and iteration: one forward, the walk, the loss, the adjoint walk
 and an Adam step, all on the device; nothing is read back inside the loop.
 """
-import numpy as np
 import torch
+
+from .confblock import boolean, check_block, integer, nonempty_string, number
 
 
 def default_loss(out, alpha, target):
@@ -85,21 +86,9 @@ def score_features(renderer, batches, targets, features):
 
 # the trainer's `features` block
 DEFAULTS = {"enabled": False, "suffix": "_features", "iterations": 200, "lr": 0.03}
+RULES = {"enabled": boolean(), "suffix": nonempty_string(), "iterations": integer(ge=1), "lr": number("a number > 0", gt=0)}
 
 
 def check_config(block):
     """The resolved `features` block: enabled true or false, suffix a non-empty string, iterations an integer >= 1, lr > 0."""
-    unknown = set(block) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"features: unknown keys {sorted(unknown)}")
-    if not isinstance(block["enabled"], bool):
-        raise ValueError(f"features.enabled must be true or false, got {block['enabled']!r}")
-    if not isinstance(block["suffix"], str) or not block["suffix"]:
-        raise ValueError(f"features.suffix must be a non-empty string, got {block['suffix']!r}")
-    it = block["iterations"]
-    if isinstance(it, bool) or not isinstance(it, (int, np.integer)) or int(it) < 1:
-        raise ValueError(f"features.iterations must be an integer >= 1, got {it!r}")
-    lr = block["lr"]
-    if isinstance(lr, (bool, str)) or not (float(lr) > 0.0) or not np.isfinite(float(lr)):
-        raise ValueError(f"features.lr must be a number > 0, got {lr!r}")
-    return block
+    return check_block("features", block, DEFAULTS, RULES)

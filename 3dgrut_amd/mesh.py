@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from .confblock import boolean, check_block, integer, is_number, nullable, number
 
 # the trainer's `mesh` block.  voxel None: the longest edge of the box / resolution; bounds None: the quantile box of volume_for.
 # resolution, truncation_voxels and the quantile box are UNTUNED on real captures.
@@ -27,10 +28,6 @@ DEFAULTS = {"enabled": False, "level": 0.5, "resolution": 256, "voxel": None, "t
 MAX_VOXELS = 1 << 30       # gut_hip.h: X Y Z <= 2^30
 MAX_VIEWS = 32767          # acc is an int32 of quanta of 2^-16, at most 65536 a view
 QUANTILES = (0.01, 0.99)
-
-
-def _number(x):
-    return not isinstance(x, (bool, str)) and isinstance(x, (int, float, np.integer, np.floating)) and math.isfinite(float(x))
 
 
 def check_bounds(bounds):
@@ -45,29 +42,17 @@ def check_bounds(bounds):
     return lo, hi
 
 
+_RESOLUTION = "an integer >= 2 truncation_voxels + 2"
+RULES = {"enabled": boolean(), "level": number("inside (0, 1)", gt=0, lt=1), "truncation_voxels": number("finite and > 0", gt=0),
+         "resolution": integer(words=_RESOLUTION), "voxel": nullable(number("a finite edge length > 0", gt=0)), "min_count": integer(ge=1)}
+
+
 def check_config(block):
     """The resolved `mesh` block: enabled true or false, level inside (0, 1), resolution an integer >= 2 truncation_voxels + 2, voxel null
     or a finite edge > 0, truncation_voxels finite and > 0, min_count an integer >= 1, bounds null or two corners."""
-    unknown = set(block) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"mesh: unknown keys {sorted(unknown)}")
-    if not isinstance(block["enabled"], bool):
-        raise ValueError(f"mesh.enabled must be true or false, got {block['enabled']!r}")
-    t = block["level"]
-    if not (_number(t) and 0.0 < float(t) < 1.0):
-        raise ValueError(f"mesh.level must be inside (0, 1), got {t!r}")
-    tv = block["truncation_voxels"]
-    if not (_number(tv) and float(tv) > 0.0):
-        raise ValueError(f"mesh.truncation_voxels must be finite and > 0, got {tv!r}")
-    r = block["resolution"]
-    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or int(r) < 2.0 * float(tv) + 2.0:
-        raise ValueError(f"mesh.resolution must be an integer >= 2 truncation_voxels + 2, got {r!r}")
-    v = block["voxel"]
-    if v is not None and not (_number(v) and float(v) > 0.0):
-        raise ValueError(f"mesh.voxel must be null or a finite edge length > 0, got {v!r}")
-    m = block["min_count"]
-    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) < 1:
-        raise ValueError(f"mesh.min_count must be an integer >= 1, got {m!r}")
+    check_block("mesh", block, DEFAULTS, RULES)
+    if int(block["resolution"]) < 2.0 * float(block["truncation_voxels"]) + 2.0:
+        raise ValueError(f"mesh.resolution must be {_RESOLUTION}, got {block['resolution']!r}")
     if block["bounds"] is not None:
         check_bounds(block["bounds"])
     return block
@@ -210,7 +195,7 @@ def volume_for(model, resolution=256, voxel=None, bounds=None, truncation_voxels
     resolution, tv = int(resolution), float(truncation_voxels)
     if not (math.isfinite(tv) and tv > 0.0):
         raise ValueError(f"volume_for: truncation_voxels must be finite and > 0, got {truncation_voxels!r}")
-    if voxel is not None and not (_number(voxel) and float(voxel) > 0.0):
+    if voxel is not None and not (is_number(voxel) and float(voxel) > 0.0):
         raise ValueError(f"volume_for: voxel must be a finite edge length > 0, got {voxel!r}")
     if bounds is not None:
         lo, hi = check_bounds(bounds)

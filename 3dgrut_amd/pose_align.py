@@ -30,39 +30,20 @@ import ctypes as C
 import numpy as np
 import torch
 
+from .confblock import boolean, check_block, integer, number
 from .pose import apply_pose_increment, pose_difference
 
 DEFAULTS = {"enabled": False, "validation": False, "iterations": 50, "lr_translation": 0.001, "lr_rotation": 0.0005,
             "beta1": 0.9, "beta2": 0.999, "eps": 1e-15}
+_RATE, _BETA = number("finite and >= 0", ge=0), number("in [0, 1)", ge=0, lt=1)
+RULES = {"enabled": boolean(), "validation": boolean(), "iterations": integer(ge=0), "lr_translation": _RATE, "lr_rotation": _RATE,
+         "eps": _RATE, "beta1": _BETA, "beta2": _BETA}
 
 
 def check_config(block):
     """The resolved `pose_alignment` block: enabled / validation true or false, iterations an integer >= 0, rates and eps finite and
     >= 0, betas in [0, 1)."""
-    unknown = set(block) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"pose_alignment: unknown keys {sorted(unknown)}")
-    for k in ("enabled", "validation"):
-        if not isinstance(block[k], bool):   # (a string such as "false" would be truthy)
-            raise ValueError(f"pose_alignment.{k} must be true or false, got {block[k]!r}")
-    it = block["iterations"]
-    if isinstance(it, bool) or not isinstance(it, (int, np.integer)) or int(it) < 0:
-        raise ValueError(f"pose_alignment.iterations must be an integer >= 0, got {it!r}")
-    for k in ("lr_translation", "lr_rotation", "eps"):
-        try:
-            v = float(block[k])
-        except (TypeError, ValueError):
-            v = float("nan")
-        if isinstance(block[k], bool) or not (0.0 <= v < float("inf")):
-            raise ValueError(f"pose_alignment.{k} must be finite and >= 0, got {block[k]!r}")
-    for k in ("beta1", "beta2"):
-        try:
-            v = float(block[k])
-        except (TypeError, ValueError):
-            v = float("nan")
-        if isinstance(block[k], bool) or not (0.0 <= v < 1.0):
-            raise ValueError(f"pose_alignment.{k} must be in [0, 1), got {block[k]!r}")
-    return block
+    return check_block("pose_alignment", block, DEFAULTS, RULES)
 
 
 def _single_pose(batch):

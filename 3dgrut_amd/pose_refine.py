@@ -26,32 +26,22 @@ import ctypes as C
 import numpy as np
 import torch
 
+from .confblock import boolean, check_block, integer, number
 from .pose import apply_pose_increment, pose_difference
 
 DEFAULTS = {"enabled": False, "lr_translation": 0.001, "lr_rotation": 0.0005, "start_iteration": 0, "end_iteration": -1,
             "beta1": 0.9, "beta2": 0.999, "eps": 1e-15}
+_RATE, _BETA = number("finite and >= 0", ge=0), number("in [0, 1)", ge=0, lt=1)
+RULES = {"enabled": boolean(), "start_iteration": integer(), "end_iteration": integer(), "lr_translation": _RATE, "lr_rotation": _RATE,
+         "eps": _RATE, "beta1": _BETA, "beta2": _BETA}
 
 
 def check_config(block):
     """The resolved `pose_refinement` block: rates and eps finite and >= 0, betas in [0, 1), iterations integers (end_iteration -1:
     to the end of the run)."""
-    unknown = set(block) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"pose_refinement: unknown keys {sorted(unknown)}")
-    if not isinstance(block["enabled"], bool):   # (a string such as "false" would be truthy)
-        raise ValueError(f"pose_refinement.enabled must be true or false, got {block['enabled']!r}")
-    for k in ("start_iteration", "end_iteration"):
-        if isinstance(block[k], bool) or not isinstance(block[k], (int, np.integer)):
-            raise ValueError(f"pose_refinement.{k} must be an integer, got {block[k]!r}")
+    check_block("pose_refinement", block, DEFAULTS, RULES)
     if int(block["start_iteration"]) < 0 or int(block["end_iteration"]) < -1:
         raise ValueError("pose_refinement: start_iteration must be >= 0 and end_iteration >= 0, or -1 for the end of the run")
-    for k in ("lr_translation", "lr_rotation", "eps"):
-        v = float(block[k])
-        if not (0.0 <= v < float("inf")):
-            raise ValueError(f"pose_refinement.{k} must be finite and >= 0, got {block[k]!r}")
-    for k in ("beta1", "beta2"):
-        if not (0.0 <= float(block[k]) < 1.0):
-            raise ValueError(f"pose_refinement.{k} must be in [0, 1), got {block[k]!r}")
     return block
 
 

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import contribution
+from .confblock import boolean, check_block, integer, nonempty_string, number
 
 
 def _host(t):
@@ -89,22 +90,10 @@ def split_rows(stepper_or_model, selected):
 
 # the trainer's `selection` block
 DEFAULTS = {"enabled": False, "mask_suffix": "_object", "threshold": 0.5, "min_pixels": 1}
+RULES = {"enabled": boolean(), "mask_suffix": nonempty_string(), "threshold": number("in [0, 1]", ge=0, le=1), "min_pixels": integer(ge=0)}
 
 
 def check_config(block):
     """The resolved `selection` block: enabled true or false, mask_suffix a non-empty string, threshold in [0, 1], min_pixels an
     integer >= 0."""
-    unknown = set(block) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"selection: unknown keys {sorted(unknown)}")
-    if not isinstance(block["enabled"], bool):
-        raise ValueError(f"selection.enabled must be true or false, got {block['enabled']!r}")
-    if not isinstance(block["mask_suffix"], str) or not block["mask_suffix"]:
-        raise ValueError(f"selection.mask_suffix must be a non-empty string, got {block['mask_suffix']!r}")
-    t = block["threshold"]
-    if isinstance(t, (bool, str)) or not (0.0 <= float(t) <= 1.0):
-        raise ValueError(f"selection.threshold must be in [0, 1], got {t!r}")
-    v = block["min_pixels"]
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
-        raise ValueError(f"selection.min_pixels must be an integer >= 0, got {v!r}")
-    return block
+    return check_block("selection", block, DEFAULTS, RULES)

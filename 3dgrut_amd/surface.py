@@ -15,32 +15,21 @@ at kernel degree 2.
 """
 import math
 
-import numpy as np
 import torch
 
+from .confblock import boolean, check_block, integer, number
 from .contribution import FrozenModel
 
 # the trainer's `points` block: the median points (level 0.5) of every stride-th pixel of the training views, one per voxel of
 # edge `voxel` (0: all of them).  stride and voxel are UNTUNED on real captures.
 DEFAULTS = {"enabled": False, "level": 0.5, "stride": 1, "voxel": 0.0}
+RULES = {"enabled": boolean(), "level": number("inside (0, 1)", gt=0, lt=1), "stride": integer(ge=1),
+         "voxel": number("a finite edge length >= 0", ge=0)}
 
 
 def check_config(block):
     """The resolved `points` block: enabled true or false, level inside (0, 1), stride an integer >= 1, voxel a finite edge >= 0."""
-    unknown = set(block) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"points: unknown keys {sorted(unknown)}")
-    if not isinstance(block["enabled"], bool):
-        raise ValueError(f"points.enabled must be true or false, got {block['enabled']!r}")
-    t = block["level"]
-    if isinstance(t, (bool, str)) or not (math.isfinite(float(t)) and 0.0 < float(t) < 1.0):
-        raise ValueError(f"points.level must be inside (0, 1), got {t!r}")
-    s = block["stride"]
-    if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or int(s) < 1:
-        raise ValueError(f"points.stride must be an integer >= 1, got {s!r}")
-    v = block["voxel"]
-    if isinstance(v, (bool, str)) or not (math.isfinite(float(v)) and float(v) >= 0.0):
-        raise ValueError(f"points.voxel must be a finite edge length >= 0, got {v!r}")
+    return check_block("points", block, DEFAULTS, RULES)
 
 
 class SurfaceRenderer(FrozenModel):

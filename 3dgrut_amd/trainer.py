@@ -20,70 +20,11 @@ strategy's densification buffers as 1-tuples (strategy/gs.py:42-48), and one key
 Everything in it is a tensor, number, string, list, tuple or dict: `torch.load(path, weights_only=True)` reads it.  Checkpoints
 written by the reference itself (an OmegaConf config inside) are not read.
 
-`pose_refinement.enabled` (default off; `--refine-poses`) refines the training views' camera poses while training
-(pose_refine.PoseRefiner): every step's backward leaves the view's pose gradient on the device, a per-view Adam turns it into an
-increment, and the view's next visit renders from the refined pose.  Held-out views (validation, test) are scored at their GIVEN
-poses unless `pose_alignment` is on.  The refiner's poses, moments and visit counts travel in the checkpoint's `native` block as tensors.
-
-`exposure.enabled` (default off; `--exposure`) learns an affine colour transform per training view (exposure.ExposureCompensation,
-DESIGN.md §10): the loss compares A image + b with the photo, its backward leaves d(loss)/d[A | b] on the device, and a per-view
-Adam updates the view's twelve floats there.  Held-out views (validation, test) have no learnt transform and are scored with the
-identity.  The transforms, moments and visit counts travel in the checkpoint's `native` block as tensors.
-
-`evaluation.colour_corrected` (default off; `--cc-metrics`) additionally scores every held-out view COLOUR-CORRECTED:
-before scoring, the render is mapped through the affine colour transform that fits it best to the photo, fitted on the device, so
-that a held-out photo's own exposure is not charged to the model — the number to compare an `--exposure` run with a run without it.
-The plain metrics are unchanged; it needs nothing from the checkpoint and composes with every other option.
-
-`pose_alignment.enabled` (default off; `--aligned-metrics`) additionally scores every held-out view POSE-ALIGNED (DESIGN.md §12,
-pose_align.PoseAligner): after a view has been scored at its given pose, that pose is optimised against the photo with the model
-frozen (`iterations` steps of the six-float Adam on the pose-only backward) and the render at the best pose found is scored next to
-the plain one — the number to compare a `--refine-poses` run with a run without it.  It applies to the final test pass, and with
-`validation: true` to the validation passes too; `lr_translation` is multiplied by the scene extent, the loss weights are the run's.
-The rates and the iteration count are untuned on real captures.  It needs nothing from the checkpoint and writes nothing into it.
-
-`compaction.enabled` (default off; `--compact-to FRACTION`) compacts the trained model (contribution.py): after the
-last training iteration every training view is rendered once more and each Gaussian's contribution to them is accumulated on the
-device (ContributionScores); the best `keep_fraction` of the rows by `score` stay (rows composited in fewer than `min_pixels` pixels
-go first), the others leave with their optimiser state; `finetune_iterations` further steps follow with the strategy detached (no
-densification, the learning-rate schedule continuing); then the usual final checkpoint and test pass.  The test split is scored
-once more BEFORE the pruning, so that both sides of the trade are printed.  One GPU only.
-
-`strategy.densify.criterion: error` (default `gradient`; `--densify-by error`) densifies by rendering error: at every
-densify step `strategy.densify.error.views` training views (0: all; otherwise drawn from epoch_permutation(seed, step // frequency, V)) are
-rendered on the live model — at their refined poses, through their exposure rows, with their masks; a `random` background is scored
-over black — and every Gaussian is charged the per-pixel error it drew (ContributionScores.accumulate_error); the best
-`grow_fraction` of the rows by `score` are cloned or split by the reference's size rule, under `max_n_gaussians`.  The per-step
-gradient statistics are not collected.  The scores are recomputed at every densify step: the checkpoint holds nothing of them.
-GSStrategy, one GPU, the unsorted variant at kernel degree 2 only.  grow_fraction, views and min_pixels are untuned on real captures.
-
-`selection.enabled` (default off; `--select-by-masks [SUFFIX]`) selects Gaussians from 2-D label masks (selection.py),
-after train() and after the compaction when that is on: the label masks `<image stem><mask_suffix>.png` of the training views that
-have one are lifted to the Gaussians (the share of each Gaussian's drawn weight inside the masks), the rows with a share above
-`threshold` and at least `min_pixels` composited pixels are selected, and the selection is rendered into every held-out view and
-scored by IoU against that view's own label mask where it has one.  With an output directory: selection.npy (bool [N]),
-selected.ply, rest.ply and renders_selection/.  The model is not changed.  One GPU only; threshold is untuned on real captures.
-
-`features.enabled` (default off; `--fit-features [SUFFIX]`) learns per-Gaussian features from 2-D maps with the model frozen
-(features.py), after train(), the compaction and the selection: the maps `<image stem><suffix>.npy` (float [K,H,W] or
-[H,W], at the view's training resolution) of the training views that have one are fitted by `iterations` Adam steps at rate `lr`,
-round-robin over those views, and every held-out view that has a map is scored by the same mean squared error.  With an output
-directory: features.npy (float32 [N,K]) and renders_features/<stem>.npy (the held-out views' rendered planes).  The model is not
-changed.  One GPU only; lr and iterations are UNTUNED on real captures.
-
-`points.enabled` (default off; `--export-points`) exports the scene as points (surface.py), after train(), the
-compaction, the selection and the feature fitting: the median surface point (the Gaussian at which the transmittance first drops
-below `level`, 0.5) of every `stride`-th pixel of every training view, at its refined pose, coloured with the rendered pixel, one
-point per cell of edge `voxel` (0: all).  With an output directory: points.ply (x y z red green blue) and renders_depth/<stem>.npy,
-the median distance of every held-out view (float32 [H,W], 0 where there is no surface).  The model is not changed.  One GPU only;
-stride and voxel are UNTUNED on real captures.
-
-`mesh.enabled` (default off; `--export-mesh`) exports the scene as a triangle mesh (mesh.py), after the points: the
-level-`level` distance planes of the training views, at their refined poses, are fused into a TSDF volume (mesh.volume_for: `bounds`
-or the 1 % .. 99 % quantile box of the positions grown by the truncation, `voxel` or the longest edge / `resolution`, truncation =
-`truncation_voxels` voxels) and its zero level is extracted by surface nets among the voxels at least `min_count` views updated.  With
-an output directory: mesh.ply (x y z red green blue, vertex_indices).  The model is not changed.  One GPU, the unsorted variant at
-kernel degree 2 only; resolution, truncation_voxels and the quantile box are UNTUNED on real captures.
+What is not the reference's is off by default and described where it lives: pose refinement and exposure compensation at
+Trainer._build_refiner / _build_exposure, the colour-corrected and pose-aligned metrics at _evaluation_options, densification by
+rendering error at _score_error, and the stages that follow train() — STAGES, in run()'s order — at their methods.  Those stages and
+the error criterion walk the per-pixel lists, which exist for the unsorted variant at kernel degree 2 only: resolve_config refuses
+them elsewhere (require_walk), the Trainer refuses them on several GPUs (require_one_gpu).  FLAGS is the command line.
 
     python -m 3dgrut_amd.trainer --path DIR [--out-dir D] [--n-iterations N] [--strategy gs|mcmc] [--downsample F]
                                  [--test-split-interval 8] [--resume CKPT] [--background black|white|random]
@@ -113,7 +54,9 @@ from . import losses, pose_align, pose_refine
 from . import mesh as mesh_mod
 from . import selection as selection_mod
 from . import surface as surface_mod
+from .confblock import boolean, check_block, integer, nullable, number, one_of
 from .evaluate import _check_batch, evaluate
+from .strategy import CRITERIA, ERROR_SCORES
 
 # configs/base_gs.yaml + configs/strategy/gs.yaml: the keys this trainer reads
 GS_CONFIG = {
@@ -144,24 +87,9 @@ GS_CONFIG = {
     # scene extent, lr_rotation is in radians; validation: the validation passes too, not only the final test pass.  The two rates and
     # the iteration count are untuned on real captures.
     "pose_alignment": dict(pose_align.DEFAULTS),
-    # not a reference key: compaction of the trained model by per-Gaussian contribution scores (contribution.py), after the last
-    # training iteration.  keep_fraction of the rows stay (the best by `score`; rows composited in fewer than min_pixels pixels of the
-    # training views go first), then finetune_iterations further steps without the strategy.
-    "compaction": dict(contribution_mod.DEFAULTS),
-    # not a reference key: a 3-D selection lifted from the training views' 2-D label masks `<image stem><mask_suffix>.png`
-    # (selection.py), after training and compaction; rendered into the held-out views and scored by IoU.  threshold is untuned on
-    # real captures.
-    "selection": dict(selection_mod.DEFAULTS),
-    # not a reference key: per-Gaussian features fitted to the training views' 2-D maps `<image stem><suffix>.npy` with the model
-    # frozen (features.py), after training, compaction and selection; scored on the held-out views' maps.  lr and iterations are
-    # untuned on real captures.
-    "features": dict(features_mod.DEFAULTS),
-    # not a reference key: the scene as points (surface.py), after everything above: the median surface points of the training views,
-    # fused; the held-out views' median distance planes.  stride and voxel are UNTUNED on real captures.
-    "points": dict(surface_mod.DEFAULTS),
-    # not a reference key: the scene as a triangle mesh (mesh.py), after the points: the training views' median distance planes fused
-    # into a TSDF volume, its zero level by surface nets.  resolution, truncation_voxels and the quantile box are UNTUNED on real captures.
-    "mesh": dict(mesh_mod.DEFAULTS),
+    # not reference keys: the stages that follow train() (STAGES; each block is described at its Trainer method)
+    "compaction": dict(contribution_mod.DEFAULTS), "selection": dict(selection_mod.DEFAULTS), "features": dict(features_mod.DEFAULTS),
+    "points": dict(surface_mod.DEFAULTS), "mesh": dict(mesh_mod.DEFAULTS),
     "strategy": {"method": "GSStrategy",
                  # criterion and error are not reference keys: "error" grows, at every densify step, the grow_fraction of the rows
                  # that are responsible for the most rendering error over `views` training views (0: all of them), instead of
@@ -225,7 +153,10 @@ def resolve_config(conf):
     selection_mod.check_config(out["selection"])
     features_mod.check_config(out["features"])
     surface_mod.check_config(out["points"])
-    check_mesh_config(out)
+    mesh_mod.check_config(out["mesh"])
+    for block, _, noun, walks in STAGES:      # (a disabled stage is never refused)
+        if walks and out[block]["enabled"]:
+            require_walk(out, f"{block}: the {noun}")
     check_densify_config(out)
     if "features_specular" not in ((conf.get("optimizer") or {}).get("params") or {}):
         # ${div:${optimizer.params.features_albedo.lr},20}
@@ -233,30 +164,40 @@ def resolve_config(conf):
     return out
 
 
-def check_mesh_config(conf):
-    """The `mesh` block of a resolved conf (mesh.check_config); enabled, it is refused where the surface walk does not exist: the
-    sorted variant (render.splat.k_buffer_size > 0) and kernel degrees other than 2.  The data-parallel refusal needs the stepper and
-    is the Trainer's."""
-    block = mesh_mod.check_config(conf["mesh"])
-    if block["enabled"]:
-        render = conf.get("render") or {}
-        k_buffer = int((render.get("splat") or {}).get("k_buffer_size", 0))
-        degree = int(render.get("particle_kernel_degree", 2))
-        if k_buffer > 0:
-            raise ValueError(f"mesh: the mesh export needs the unsorted variant (render.splat.k_buffer_size is {k_buffer})")
-        if degree != 2:
-            raise ValueError(f"mesh: the mesh export needs render.particle_kernel_degree 2 (it is {degree})")
-    return conf
+# the stages that follow train(), in the order run() walks them: (conf block, Trainer method, the noun of its refusals, whether it
+# walks the per-pixel lists)
+STAGES = (("compaction", "compact", "compaction", True), ("selection", "select_by_masks", "selection", True),
+          ("features", "fit_features", "feature fitting", True), ("points", "export_points", "point export", True),
+          ("mesh", "export_mesh", "mesh export", True))
+
+
+def require_walk(conf, who):
+    """`who` (the subject of the refusal) needs one of the per-pixel walks — contribution, attributes, surface — which exist for the
+    unsorted variant (render.splat.k_buffer_size 0) at kernel degree 2 only."""
+    render = conf.get("render") or {}
+    k_buffer = int((render.get("splat") or {}).get("k_buffer_size", 0))
+    degree = int(render.get("particle_kernel_degree", 2))
+    if k_buffer > 0:
+        raise ValueError(f"{who} needs the unsorted variant (render.splat.k_buffer_size is {k_buffer})")
+    if degree != 2:
+        raise ValueError(f"{who} needs render.particle_kernel_degree 2 (it is {degree})")
+
+
+def require_one_gpu(stepper, block, noun):
+    """None of what this trainer adds to the reference exists data-parallel."""
+    if int(getattr(stepper, "world_size", 1)) > 1:
+        raise ValueError(f"{block}: data-parallel {noun} is out of scope (the stepper's world_size must be 1)")
 
 
 DENSIFY_ERROR_DEFAULTS = GS_CONFIG["strategy"]["densify"]["error"]
+DENSIFY_ERROR_RULES = {"grow_fraction": number("in (0, 1]", gt=0, le=1), "score": one_of(ERROR_SCORES), "min_pixels": integer(ge=0),
+                       "views": integer(ge=0), "max_n_gaussians": nullable(integer(ge=1))}
+EVALUATION_RULES = {"colour_corrected": boolean(), "ridge": number("finite and > 0", gt=0)}
 
 
 def check_densify_config(conf):
-    """strategy.densify.criterion and strategy.densify.error of a resolved conf.  criterion "error" is refused where the weighted
-    contribution walk does not exist: MCMCStrategy, the sorted variant (render.splat.k_buffer_size > 0) and kernel degrees other
-    than 2; the data-parallel refusal needs the stepper and is the Trainer's."""
-    from .strategy import CRITERIA, ERROR_SCORES
+    """strategy.densify.criterion and strategy.densify.error of a resolved conf.  criterion "error" is for GSStrategy, and where the
+    weighted contribution walk exists (require_walk); the data-parallel refusal needs the stepper and is the Trainer's."""
     densify = conf["strategy"].get("densify") or {}
     criterion = densify.get("criterion", "gradient")
     if criterion not in CRITERIA:
@@ -265,30 +206,9 @@ def check_densify_config(conf):
         if criterion != "gradient":
             raise ValueError(f"strategy.densify.criterion: {criterion!r} is for GSStrategy only (MCMC sampling by error is out of scope)")
         return conf
-    block = densify["error"]
-    unknown = set(block) - set(DENSIFY_ERROR_DEFAULTS)
-    if unknown:
-        raise ValueError(f"strategy.densify.error: unknown keys {sorted(unknown)}")
-    f = block["grow_fraction"]
-    if isinstance(f, (bool, str)) or not (0.0 < float(f) <= 1.0):
-        raise ValueError(f"strategy.densify.error.grow_fraction must be in (0, 1], got {f!r}")
-    if block["score"] not in ERROR_SCORES:
-        raise ValueError(f"strategy.densify.error.score must be one of {ERROR_SCORES}, got {block['score']!r}")
-    for k in ("min_pixels", "views"):
-        v = block[k]
-        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
-            raise ValueError(f"strategy.densify.error.{k} must be an integer >= 0, got {v!r}")
-    cap = block["max_n_gaussians"]
-    if cap is not None and (isinstance(cap, bool) or not isinstance(cap, int) or cap < 1):
-        raise ValueError(f"strategy.densify.error.max_n_gaussians must be null or an integer >= 1, got {cap!r}")
+    check_block("strategy.densify.error", densify["error"], DENSIFY_ERROR_DEFAULTS, DENSIFY_ERROR_RULES)
     if criterion == "error":
-        render = conf.get("render") or {}
-        k_buffer = int((render.get("splat") or {}).get("k_buffer_size", 0))
-        degree = int(render.get("particle_kernel_degree", 2))
-        if k_buffer > 0:
-            raise ValueError(f"strategy.densify.criterion: 'error' needs the unsorted variant (render.splat.k_buffer_size is {k_buffer})")
-        if degree != 2:
-            raise ValueError(f"strategy.densify.criterion: 'error' needs render.particle_kernel_degree 2 (it is {degree})")
+        require_walk(conf, "strategy.densify.criterion: 'error'")
         if int(densify["split"]["n_gaussians"]) != 2:
             raise ValueError("strategy.densify.criterion: 'error' grows one row per selected row (strategy.densify.split.n_gaussians must be 2)")
     return conf
@@ -296,15 +216,7 @@ def check_densify_config(conf):
 
 def check_evaluation_config(block):
     """The resolved `evaluation` block: colour_corrected true or false, ridge finite and > 0."""
-    unknown = set(block) - set(GS_CONFIG["evaluation"])
-    if unknown:
-        raise ValueError(f"evaluation: unknown keys {sorted(unknown)}")
-    if not isinstance(block["colour_corrected"], bool):   # (a string such as "false" would be truthy)
-        raise ValueError(f"evaluation.colour_corrected must be true or false, got {block['colour_corrected']!r}")
-    ridge = block["ridge"]
-    if isinstance(ridge, (bool, str)) or not (0.0 < float(ridge) < float("inf")):
-        raise ValueError(f"evaluation.ridge must be finite and > 0, got {ridge!r}")
-    return block
+    return check_block("evaluation", block, GS_CONFIG["evaluation"], EVALUATION_RULES)
 
 
 # what a pose-aligned evaluation adds to the validation entries and to main()'s final JSON, where the evaluator returned it
@@ -474,21 +386,12 @@ class Trainer:
         self.exposure = self._build_exposure(ckpt)
         if ckpt is not None:
             self.global_step = int(ckpt["global_step"])
-        if c["compaction"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
-            raise ValueError("compaction: data-parallel compaction is out of scope (the stepper's world_size must be 1)")
-        if c["selection"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
-            raise ValueError("selection: data-parallel selection is out of scope (the stepper's world_size must be 1)")
-        if c["features"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
-            raise ValueError("features: data-parallel feature fitting is out of scope (the stepper's world_size must be 1)")
-        if c["points"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
-            raise ValueError("points: data-parallel point export is out of scope (the stepper's world_size must be 1)")
-        if c["mesh"]["enabled"] and int(getattr(stepper, "world_size", 1)) > 1:
-            raise ValueError("mesh: data-parallel mesh export is out of scope (the stepper's world_size must be 1)")
+        for block, _, noun, _ in STAGES:
+            if c[block]["enabled"]:
+                require_one_gpu(stepper, block, noun)
         self.densify_criterion = (c["strategy"].get("densify") or {}).get("criterion", "gradient")
         if self.densify_criterion == "error":
-            if int(getattr(stepper, "world_size", 1)) > 1:
-                raise ValueError("strategy.densify.criterion: data-parallel error-based densification is out of scope (the stepper's "
-                                 "world_size must be 1)")
+            require_one_gpu(stepper, "strategy.densify.criterion", "error-based densification")
             if getattr(self.strategy, "error_scorer", None) is None:
                 self.strategy.error_scorer = self._score_error
 
@@ -538,7 +441,11 @@ class Trainer:
         return stepper, tracer
 
     def _build_refiner(self, ckpt):
-        """The PoseRefiner of a run with pose_refinement.enabled (else None), its state restored from a resumed checkpoint."""
+        """The PoseRefiner of a run with pose_refinement.enabled (default off; `--refine-poses`), else None; its state restored
+        from a resumed checkpoint.  It refines the training views' camera poses while training (pose_refine.PoseRefiner): every
+        step's backward leaves the view's pose gradient on the device, a per-view Adam turns it into an increment, and the view's
+        next visit renders from the refined pose.  Held-out views (validation, test) are scored at their GIVEN poses unless
+        `pose_alignment` is on.  The refiner's poses, moments and visit counts travel in the checkpoint's `native` block as tensors."""
         pr = self.conf["pose_refinement"]
         if not pr["enabled"]:
             if ckpt is not None and ckpt.get("native", {}).get("pose_refinement") is not None:
@@ -547,8 +454,7 @@ class Trainer:
                                  "--refine-poses (pose_refinement.enabled: true), with end_iteration 0 to keep the poses as they are")
             return None
         st = self.stepper
-        if int(getattr(st, "world_size", 1)) > 1:
-            raise ValueError("pose_refinement: data-parallel pose refinement is out of scope (the stepper's world_size must be 1)")
+        require_one_gpu(st, "pose_refinement", "pose refinement")
         if getattr(st, "pose_gradient", None) is None:
             raise ValueError(f"pose_refinement: {type(st).__name__} leaves no pose gradient (NativeTrainStep(..., pose_gradient=True) does)")
         refiner = pose_refine.PoseRefiner([b.T_to_world for b in self.train_batches], st.pose_gradient.device,
@@ -561,7 +467,11 @@ class Trainer:
         return refiner
 
     def _build_exposure(self, ckpt):
-        """The ExposureCompensation of a run with exposure.enabled (else None), its state restored from a resumed checkpoint."""
+        """The ExposureCompensation of a run with exposure.enabled (default off; `--exposure`), else None; its state restored from a
+        resumed checkpoint.  It learns an affine colour transform per training view: the loss compares A image + b
+        with the photo, its backward leaves d(loss)/d[A | b] on the device, and a per-view Adam updates the view's twelve floats
+        there.  Held-out views have no learnt transform and are scored with the identity.  The transforms, moments and visit counts
+        travel in the checkpoint's `native` block as tensors."""
         ex = self.conf["exposure"]
         if not ex["enabled"]:
             if ckpt is not None and ckpt.get("native", {}).get("exposure") is not None:
@@ -570,8 +480,7 @@ class Trainer:
                                  "(exposure.enabled: true), with end_iteration 0 to keep the exposures as they are")
             return None
         st = self.stepper
-        if int(getattr(st, "world_size", 1)) > 1:
-            raise ValueError("exposure: data-parallel exposure compensation is out of scope (the stepper's world_size must be 1)")
+        require_one_gpu(st, "exposure", "exposure compensation")
         if getattr(st, "exposure_gradient", None) is None:
             raise ValueError(f"exposure: {type(st).__name__} leaves no exposure gradient (NativeTrainStep(..., exposure_gradient=True) does)")
         comp = exposure_mod.ExposureCompensation(len(self.train_batches), st.exposure_gradient.device, lr=float(ex["lr"]),
@@ -639,6 +548,26 @@ class Trainer:
         d = self.conf.get("out_dir") or ""
         return d or None
 
+    def _renders_dir(self, name):
+        """The directory `name` (renders_*) under the output directory, created."""
+        path = os.path.join(self._out_dir(), name)
+        os.makedirs(path, exist_ok=True)
+        return path
+
+    @staticmethod
+    def _stem(batch, i):
+        """The name of held-out view i's output files: its image's stem where main() attached one."""
+        return getattr(batch, "image_stem", None) or f"{i:05d}"
+
+    def _posed(self, view):
+        """Training batch `view` at its refined pose (its pending increment applied first); the given pose without a refiner."""
+        batch = self.train_batches[view]
+        return batch if self.refiner is None else self.refiner.begin(view, batch)
+
+    def _posed_batches(self, views=None):
+        """The training batches (all, or those of the indices `views`) at their refined poses."""
+        return [self._posed(v) for v in (range(len(self.train_batches)) if views is None else views)]
+
     def _sync(self):
         raw = getattr(self.model, "raw", None)
         if raw is not None and raw.is_cuda:
@@ -647,7 +576,16 @@ class Trainer:
     def _evaluation_options(self, validation=False):
         """The evaluator's keyword arguments: none with evaluation.colour_corrected and pose_alignment.enabled off (an injected
         evaluator is then called with the five positional arguments alone).  pose_aligned: the aligner's settings with the translation
-        rate in world units and the run's loss weights; on validation passes only with pose_alignment.validation."""
+        rate in world units and the run's loss weights; on validation passes only with pose_alignment.validation.
+
+        `evaluation.colour_corrected` (default off; `--cc-metrics`) additionally scores every held-out view COLOUR-CORRECTED
+        (DESIGN.md §11): the render is first mapped through the affine colour transform that fits it best to the photo, fitted on
+        the device, so that a held-out photo's own exposure is not charged to the model — the number to compare an `--exposure` run
+        with a run without it.  `pose_alignment.enabled` (default off; `--aligned-metrics`) additionally scores it POSE-ALIGNED
+        (pose_align.PoseAligner): after a view has been scored at its given pose, that pose is optimised against the
+        photo with the model frozen and the render at the best pose found is scored next to the plain one — the number to compare a
+        `--refine-poses` run with a run without it.  Both leave the plain metrics as they are, need nothing from the checkpoint
+        and compose with every other option; the aligner's rates and iteration count are untuned on real captures."""
         ev = self.conf["evaluation"]
         opts = dict(colour_corrected=True, ridge=float(ev["ridge"])) if ev["colour_corrected"] else {}
         pa = self.conf["pose_alignment"]
@@ -691,13 +629,17 @@ class Trainer:
     def _score_error(self, step):
         """The strategy's error_scorer (criterion "error"): the contribution scores of the live model over _error_views(step), every
         view weighted by its rendering error — at its refined pose, through its exposure row, with its mask, over the run's constant
-        background (`random` is scored over black, as the held-out views are).  Nothing is kept: the next pass starts from zero."""
+        background (`random` is scored over black, as the held-out views are).  Nothing is kept: the next pass starts from zero.
+
+        `strategy.densify.criterion: error` (default `gradient`; `--densify-by error`): at every densify step each
+        Gaussian is charged the per-pixel error it drew (ContributionScores.accumulate_error) and the best `grow_fraction` of the
+        rows by `score` are cloned or split by the reference's size rule, under `max_n_gaussians`.  The per-step gradient statistics
+        are not collected, and the checkpoint holds nothing of the scores.  GSStrategy, one GPU, the unsorted variant at kernel
+        degree 2 only.  grow_fraction, views and min_pixels are untuned on real captures."""
         color = self.conf["model"]["background"]["color"]
         scorer = contribution_mod.ContributionScores(self.model, self.tracer)
         for view in self._error_views(step):
-            batch = self.train_batches[view]
-            if self.refiner is not None:
-                batch = self.refiner.begin(view, batch)
+            batch = self._posed(view)
             if self.exposure is not None:
                 batch = self.exposure.begin(view, batch)
             scorer.accumulate_error(batch, "black" if color == "random" else color, mask=getattr(batch, "mask", None),
@@ -729,16 +671,9 @@ class Trainer:
         t0 = time.perf_counter()
         while self.global_step < n_iter:
             g = self.global_step
-            view = self.batch_index(g)
             if (g > 0 or c["validate_first"]) and g % val_freq == 0:
                 self.validate()
-            refiner, comp = self.refiner, self.exposure
-            batch = self._train_batch(view, g)
-            self._last_loss, _ = self.stepper.step(batch)   # scheduler + SH ramp run at the end of step()
-            if comp is not None and comp.active(g):
-                comp.end(view, self.stepper.exposure_gradient)   # twelve-float Adam on the device: nothing waits
-            if refiner is not None and refiner.active(g):
-                refiner.end(view, self.stepper.pose_gradient)   # queued on the device: no host synchronisation (V >= 2)
+            self._step_once(g)
             self._post_optimizer_step(g)
             self.global_step = g + 1
             if self.global_step in ckpt_steps:
@@ -759,12 +694,22 @@ class Trainer:
             self.stats.update(exposure_mean_gain=sm["mean_gain"], exposure_mean_offset=sm["mean_offset"])
         return self.stats
 
+    def _step_once(self, g):
+        """Global step g on its view (batch_index): the training step and the two per-view Adams behind it.  Returns the view.  The
+        strategy, the step counter and the checkpoints are the caller's."""
+        view = self.batch_index(g)
+        self._last_loss, _ = self.stepper.step(self._train_batch(view, g))   # scheduler + SH ramp run at the end of step()
+        if self.exposure is not None and self.exposure.active(g):
+            self.exposure.end(view, self.stepper.exposure_gradient)   # twelve-float Adam on the device: nothing waits
+        if self.refiner is not None and self.refiner.active(g):
+            self.refiner.end(view, self.stepper.pose_gradient)        # queued on the device: no host synchronisation (V >= 2)
+        return view
+
     def _train_batch(self, view, g):
         """Training batch `view` as step g trains on it: the view's refined pose and exposure row, the gradients' switches set."""
-        batch = self.train_batches[view]
+        batch = self._posed(view)
         refiner = self.refiner
         if refiner is not None:
-            batch = refiner.begin(view, batch)          # the view's refined pose (its pending increment applied first)
             switch = getattr(self.stepper, "enable_pose_gradient", None)
             if switch is not None:                      # outside [start_iteration, end_iteration) the backward reduces nothing
                 switch(refiner.active(g))
@@ -782,18 +727,18 @@ class Trainer:
         return contribution_mod.keep_mask(result, score=cp["score"], keep_fraction=float(cp["keep_fraction"]), min_pixels=int(cp["min_pixels"]))
 
     def compact(self):
-        """The `compaction` block, after train(): the test split scored before the pruning, the contribution scores of the training
-        views (at their refined poses), the pruning, the fine-tuning steps with the strategy detached.  Fills and returns the
-        compaction_* statistics."""
+        """The `compaction` block (default off; `--compact-to FRACTION`; DESIGN.md §13, contribution.py), after train(): every
+        training view is rendered once more, at its refined pose, and each Gaussian's contribution to them is accumulated on the
+        device (ContributionScores); the best `keep_fraction` of the rows by `score` stay (rows composited in fewer than
+        `min_pixels` pixels go first), the others leave with their optimiser state; `finetune_iterations` further steps follow with
+        the strategy detached (no densification, the learning-rate schedule continuing).  The test split is scored once more BEFORE
+        the pruning, so that both sides of the trade are printed.  Fills and returns the compaction_* statistics.  One GPU only."""
         cp = self.conf["compaction"]
         before = None
         if self.test_batches:
             before = self.evaluator(self.model, self.tracer, self.test_batches, None, self.global_step, **self._evaluation_options())
         scorer = contribution_mod.ContributionScores(self.model, self.tracer)
-        for view in range(len(self.train_batches)):
-            batch = self.train_batches[view]
-            if self.refiner is not None:
-                batch = self.refiner.begin(view, batch)
+        for batch in self._posed_batches():
             scorer.accumulate(batch)
         n_before = int(self.model.num_gaussians)
         mask = self._compaction_mask(scorer.result())
@@ -803,15 +748,8 @@ class Trainer:
             detach()    # no densification statistics from here on
         contribution_mod.compact(self.stepper, mask, self.strategy)
         for _ in range(int(cp["finetune_iterations"])):
-            g = self.global_step
-            view = self.batch_index(g)
-            batch = self._train_batch(view, g)
-            self._last_loss, _ = self.stepper.step(batch)
-            if self.exposure is not None and self.exposure.active(g):
-                self.exposure.end(view, self.stepper.exposure_gradient)
-            if self.refiner is not None and self.refiner.active(g):
-                self.refiner.end(view, self.stepper.pose_gradient)
-            self.global_step = g + 1
+            self._step_once(self.global_step)      # (no strategy, no checkpoints)
+            self.global_step += 1
         self._sync()
         out = dict(compaction_n_before=n_before, compaction_n_after=int(self.model.num_gaussians), compaction_score=str(cp["score"]),
                    compaction_test_psnr_before=None if before is None else float(before["mean_psnr"]))
@@ -819,24 +757,26 @@ class Trainer:
         return out
 
     def select_by_masks(self):
-        """The `selection` block, after train() and compact(): lifts the label masks of the training views that carry one (at their
-        refined poses) to the Gaussians, selects, renders the selection into every held-out view and scores the IoU against the
-        label masks those carry.  Writes selection.npy, selected.ply, rest.ply and renders_selection/ into the output directory
-        when there is one.  Fills and returns the selection_* statistics; the model is left as it is."""
+        """The `selection` block (default off; `--select-by-masks [SUFFIX]`; DESIGN.md §15, selection.py), after train() and
+        compact(): the label masks `<image stem><mask_suffix>.png` of the training views that have one are lifted to the Gaussians,
+        at the views' refined poses (the share of each Gaussian's drawn weight inside the masks); the rows with a share above
+        `threshold` and at least `min_pixels` composited pixels are selected, and the selection is rendered into every held-out view
+        and scored by IoU against that view's own label mask where it has one.  With an output directory: selection.npy (bool [N]),
+        selected.ply, rest.ply and renders_selection/.  Fills and returns the selection_* statistics; the model is not changed.
+        One GPU only; threshold is untuned on real captures."""
         from .attributes import AttributeRenderer
         sel = self.conf["selection"]
         labelled = [v for v in range(len(self.train_batches)) if getattr(self.train_batches[v], "label_mask", None) is not None]
         if not labelled:
             raise ValueError(f"selection: no training view has a label mask (<image stem>{sel['mask_suffix']}.png next to its image)")
-        batches = [self.train_batches[v] if self.refiner is None else self.refiner.begin(v, self.train_batches[v]) for v in labelled]
-        lifted = selection_mod.lift_masks(self.model, self.tracer, batches, [self.train_batches[v].label_mask for v in labelled])
+        lifted = selection_mod.lift_masks(self.model, self.tracer, self._posed_batches(labelled),
+                                          [self.train_batches[v].label_mask for v in labelled])
         selected = selection_mod.select(lifted, threshold=float(sel["threshold"]), min_pixels=int(sel["min_pixels"]))
         out_dir = self._out_dir()
         renders = None
         if out_dir is not None:
             from .io_ply import export_native_model
-            renders = os.path.join(out_dir, "renders_selection")
-            os.makedirs(renders, exist_ok=True)
+            renders = self._renders_dir("renders_selection")
             np.save(os.path.join(out_dir, "selection.npy"), selected.detach().cpu().numpy().astype(bool))
             rows_in, rows_out = selection_mod.split_rows(self.model, selected)
             export_native_model(self.model, os.path.join(out_dir, "selected.ply"), rows=rows_in)
@@ -858,10 +798,13 @@ class Trainer:
         return out
 
     def fit_features(self):
-        """The `features` block, after train(), compact() and select_by_masks(): fits per-Gaussian features to the maps of the
-        training views that carry one (batch.feature_map [K,H,W], at their refined poses) with the model frozen and scores them on
-        the held-out views that carry one.  Writes features.npy and renders_features/<stem>.npy into the output directory when
-        there is one.  Fills and returns the features_* statistics; the model is left as it is."""
+        """The `features` block (default off; `--fit-features [SUFFIX]`; DESIGN.md §17, features.py), after train(), compact() and
+        select_by_masks(): the maps `<image stem><suffix>.npy` (float [K,H,W] or [H,W], at the view's training resolution;
+        batch.feature_map) of the training views that have one are fitted with the model frozen, at the views' refined poses, by
+        `iterations` Adam steps at rate `lr`, round-robin over those views, and every held-out view that has a map is scored by the
+        same mean squared error.  With an output directory: features.npy (float32 [N,K]) and renders_features/<stem>.npy (the
+        held-out views' rendered planes).  Fills and returns the features_* statistics; the model is not changed.  One GPU only;
+        lr and iterations are UNTUNED on real captures."""
         from .attributes import AttributeRenderer
         blk = self.conf["features"]
         mapped = [v for v in range(len(self.train_batches)) if getattr(self.train_batches[v], "feature_map", None) is not None]
@@ -872,7 +815,7 @@ class Trainer:
         for v, t in zip(mapped, targets):
             if int(t.shape[0]) != channels:
                 raise ValueError(f"features: the map of training view {v} has {int(t.shape[0])} channels, the first one {channels}")
-        batches = [self.train_batches[v] if self.refiner is None else self.refiner.begin(v, self.train_batches[v]) for v in mapped]
+        batches = self._posed_batches(mapped)
         renderer = AttributeRenderer(self.model, self.tracer)
         feats = features_mod.fit_features(renderer, batches, targets, channels, int(blk["iterations"]), float(blk["lr"]))
         train_mse = features_mod.score_features(renderer, batches, targets, feats)
@@ -885,47 +828,49 @@ class Trainer:
                                                [self.test_batches[i].feature_map for i in held], feats) if held else None
         out_dir = self._out_dir()
         if out_dir is not None:
-            renders = os.path.join(out_dir, "renders_features")
-            os.makedirs(renders, exist_ok=True)
+            renders = self._renders_dir("renders_features")
             np.save(os.path.join(out_dir, "features.npy"), feats.cpu().numpy())
             for i, batch in enumerate(self.test_batches):
-                stem = getattr(batch, "image_stem", None) or f"{i:05d}"
-                np.save(os.path.join(renders, stem + ".npy"), renderer.render(batch, feats).cpu().numpy())
+                np.save(os.path.join(renders, self._stem(batch, i) + ".npy"), renderer.render(batch, feats).cpu().numpy())
         out = dict(features_channels=channels, features_n_views_fitted=len(mapped), features_train_mse=float(train_mse.mean()),
                    features_heldout_mse=None if held_mse is None else float(held_mse.mean()))
         self.stats.update(out)
         return out
 
     def export_points(self):
-        """The `points` block, after train(), compact(), select_by_masks() and fit_features(): fuses the median surface points of
-        the training views (at their refined poses) into one coloured cloud.  Writes points.ply and renders_depth/<stem>.npy (the
-        held-out views' median distance planes) into the output directory when there is one.  Fills and returns the points_*
-        statistics; the model is left as it is."""
+        """The `points` block (default off; `--export-points`; DESIGN.md §18, surface.py), after train(), compact(),
+        select_by_masks() and fit_features(): the median surface point (the Gaussian at which the transmittance first drops below
+        `level`, 0.5) of every `stride`-th pixel of every training view, at its refined pose, coloured with the rendered pixel, one
+        point per cell of edge `voxel` (0: all).  With an output directory: points.ply (x y z red green blue) and
+        renders_depth/<stem>.npy, the median distance of every held-out view (float32 [H,W], 0 where there is no surface).  Fills and
+        returns the points_* statistics; the model is not changed.  One GPU only; stride and voxel are UNTUNED on real captures."""
         blk = self.conf["points"]
         level = float(blk["level"])
         renderer = surface_mod.SurfaceRenderer(self.model, self.tracer)
-        batches = [b if self.refiner is None else self.refiner.begin(v, b) for v, b in enumerate(self.train_batches)]
+        batches = self._posed_batches()
         xyz, rgb, _ = surface_mod.fuse_points(renderer, batches, level=level, stride=int(blk["stride"]), voxel=float(blk["voxel"]))
         out_dir = self._out_dir()
         if out_dir is not None:
             from .io_ply import write_point_cloud
-            renders = os.path.join(out_dir, "renders_depth")
-            os.makedirs(renders, exist_ok=True)
+            renders = self._renders_dir("renders_depth")
             write_point_cloud(os.path.join(out_dir, "points.ply"), xyz.cpu().numpy(), rgb.cpu().numpy())
             for i, batch in enumerate(self.test_batches):
-                stem = getattr(batch, "image_stem", None) or f"{i:05d}"
-                np.save(os.path.join(renders, stem + ".npy"), renderer.render(batch, mode="level", level=level)["distance"].cpu().numpy())
+                np.save(os.path.join(renders, self._stem(batch, i) + ".npy"), renderer.render(batch, mode="level", level=level)["distance"].cpu().numpy())
         out = dict(points_n=int(xyz.shape[0]), points_views=len(batches), points_level=level)
         self.stats.update(out)
         return out
 
     def export_mesh(self):
-        """The `mesh` block, after export_points(): fuses the level-mode distance planes of the training views (at their refined
-        poses) into a TSDF volume sized by mesh.volume_for and extracts its zero level.  Writes mesh.ply into the output directory
-        when there is one.  Fills and returns the mesh_* statistics; the model is left as it is."""
+        """The `mesh` block (default off; `--export-mesh`; DESIGN.md §19, mesh.py), after export_points(): the level-`level`
+        distance planes of the training views, at their refined poses, are fused into a TSDF volume (mesh.volume_for: `bounds` or
+        the 1 % .. 99 % quantile box of the positions grown by the truncation, `voxel` or the longest edge / `resolution`,
+        truncation = `truncation_voxels` voxels) and its zero level is extracted by surface nets among the voxels at least
+        `min_count` views updated.  With an output directory: mesh.ply (x y z red green blue, vertex_indices).  Fills and returns
+        the mesh_* statistics; the model is not changed.  One GPU only; resolution, truncation_voxels and the quantile box are
+        UNTUNED on real captures."""
         blk = self.conf["mesh"]
         renderer = surface_mod.SurfaceRenderer(self.model, self.tracer)
-        batches = [b if self.refiner is None else self.refiner.begin(v, b) for v, b in enumerate(self.train_batches)]
+        batches = self._posed_batches()
         with torch.no_grad():
             volume = mesh_mod.volume_for(self.model, resolution=int(blk["resolution"]), voxel=blk["voxel"], bounds=blk["bounds"],
                                          truncation_voxels=float(blk["truncation_voxels"]), device=renderer.act.device)
@@ -942,19 +887,12 @@ class Trainer:
         return out
 
     def run(self):
-        """train(), (compaction.enabled) compact(), (selection.enabled) select_by_masks(), (features.enabled) fit_features(),
-        (points.enabled) export_points(), (mesh.enabled) export_mesh(), print the statistics table, then (test_last) save ckpt_last.pt and evaluate the test split."""
+        """train(), the enabled STAGES in their order, print the statistics table, then (test_last) save ckpt_last.pt and evaluate
+        the test split."""
         stats = self.train()
-        if self.conf["compaction"]["enabled"]:
-            self.compact()
-        if self.conf["selection"]["enabled"]:
-            self.select_by_masks()
-        if self.conf["features"]["enabled"]:
-            self.fit_features()
-        if self.conf["points"]["enabled"]:
-            self.export_points()
-        if self.conf["mesh"]["enabled"]:
-            self.export_mesh()
+        for block, method, _, _ in STAGES:
+            if self.conf[block]["enabled"]:
+                getattr(self, method)()      # (looked up now: an instance may carry its own)
         print("Training Statistics: " + json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in stats.items()}), flush=True)
         if self.conf["test_last"] and self.test_batches:
             self.save_checkpoint(last=True)
@@ -963,132 +901,115 @@ class Trainer:
         return dict(stats=stats, test=self.test_metrics)
 
 
+# The command line, in the order of --help: (flag, add_argument's keywords, the conf key it sets, how).  how "value": the value
+# where the flag is given; "switch": a flag without a value, True or False into the key; "enables": as "value", and given it also
+# sets `enabled` of the key's block.  No conf key: a run-level argument, read by config_from_args and main() themselves.
+_UNTUNED = " (untuned on real captures)"
+FLAGS = (
+    ("--path", dict(required=True, help="COLMAP scene directory (sparse/0 + images[_F])"), None, None),
+    ("--out-dir", {}, "out_dir", "value"),
+    ("--n-iterations", dict(type=int), "n_iterations", "value"),
+    ("--strategy", dict(choices=("gs", "mcmc"), default="gs"), None, None),
+    ("--downsample", dict(type=int, default=1), None, None),
+    ("--test-split-interval", dict(type=int, default=8), None, None),
+    ("--resume", dict(default=""), None, None),
+    ("--seed", dict(type=int, default=0), None, None),
+    ("--background", dict(choices=BACKGROUND_COLORS, help="model.background.color (default: the config's, black); random = a uniform "
+                                                          "colour per training pixel"), "model.background.color", "value"),
+    ("--refine-poses", dict(help="refine the training views' camera poses while training (pose_refinement.enabled); test views keep "
+                                 "theirs"), "pose_refinement.enabled", "switch"),
+    ("--pose-lr-translation", dict(type=float, help="pose_refinement.lr_translation (times the scene extent)"),
+     "pose_refinement.lr_translation", "value"),
+    ("--pose-lr-rotation", dict(type=float, help="pose_refinement.lr_rotation (radians)"), "pose_refinement.lr_rotation", "value"),
+    ("--exposure", dict(help="learn an affine colour transform per training view (exposure.enabled); test views are scored with the "
+                             "identity (--cc-metrics adds colour-corrected scores)"), "exposure.enabled", "switch"),
+    ("--exposure-lr", dict(type=float, help="exposure.lr"), "exposure.lr", "value"),
+    ("--cc-metrics", dict(help="also score held-out views colour-corrected: through the affine colour transform fitted per view "
+                               "(evaluation.colour_corrected)"), "evaluation.colour_corrected", "switch"),
+    ("--aligned-metrics", dict(help="also score held-out views pose-aligned: each test view's pose is optimised against its photo with "
+                                    "the model frozen before it is scored again (pose_alignment.enabled); the plain scores stay"),
+     "pose_alignment.enabled", "switch"),
+    ("--align-iterations", dict(type=int, help="pose_alignment.iterations"), "pose_alignment.iterations", "value"),
+    ("--compact-to", dict(type=float, metavar="FRACTION", help="after training, keep this fraction of the Gaussians: the best by their "
+                          "contribution to the training views (compaction.enabled, compaction.keep_fraction)"),
+     "compaction.keep_fraction", "enables"),
+    ("--compact-score", dict(choices=contribution_mod.SCORES, help="compaction.score"), "compaction.score", "value"),
+    ("--compact-finetune", dict(type=int, metavar="K", help="compaction.finetune_iterations"), "compaction.finetune_iterations", "value"),
+    ("--select-by-masks", dict(nargs="?", const=selection_mod.DEFAULTS["mask_suffix"], metavar="SUFFIX",
+                               help="after training, select the Gaussians inside the views' label masks <image stem>SUFFIX.png (default "
+                                    "_object), render the selection into the held-out views and score its IoU (selection.enabled, "
+                                    "selection.mask_suffix)"), "selection.mask_suffix", "enables"),
+    ("--select-threshold", dict(type=float, metavar="T", help="selection.threshold"), "selection.threshold", "value"),
+    ("--fit-features", dict(nargs="?", const=features_mod.DEFAULTS["suffix"], metavar="SUFFIX",
+                            help="after training, fit per-Gaussian features to the views' maps <image stem>SUFFIX.npy (default _features) "
+                                 "with the model frozen and score them on the held-out views' maps (features.enabled, features.suffix)"),
+     "features.suffix", "enables"),
+    ("--feature-iterations", dict(type=int, metavar="K", help="features.iterations" + _UNTUNED), "features.iterations", "value"),
+    ("--feature-lr", dict(type=float, metavar="X", help="features.lr" + _UNTUNED), "features.lr", "value"),
+    ("--export-points", dict(help="after training, export the scene as points: the median surface points of the training views, fused "
+                                  "into points.ply, and the held-out views' median distance planes (points.enabled)"),
+     "points.enabled", "switch"),
+    ("--points-level", dict(type=float, metavar="T", help="points.level: the transmittance level, 0.5 = the median"), "points.level", "value"),
+    ("--points-stride", dict(type=int, metavar="S", help="points.stride: every S-th pixel" + _UNTUNED), "points.stride", "value"),
+    ("--points-voxel", dict(type=float, metavar="V", help="points.voxel: one point per cell of this edge length, 0 = all" + _UNTUNED),
+     "points.voxel", "value"),
+    ("--export-mesh", dict(help="after training, export the scene as a triangle mesh: the training views' median distance planes fused "
+                                "into a TSDF volume, its zero level written to mesh.ply (mesh.enabled)"), "mesh.enabled", "switch"),
+    ("--mesh-resolution", dict(type=int, metavar="R", help="mesh.resolution: voxels along the longest edge of the box" + _UNTUNED),
+     "mesh.resolution", "value"),
+    ("--mesh-voxel", dict(type=float, metavar="V", help="mesh.voxel: the voxel edge length, instead of a resolution"), "mesh.voxel", "value"),
+    ("--densify-by", dict(choices=("gradient", "error"), help="strategy.densify.criterion: error = grow the rows responsible for the most "
+                                                              "rendering error (default: gradient)"), "strategy.densify.criterion", "value"),
+    ("--densify-grow-fraction", dict(type=float, metavar="F", help="strategy.densify.error.grow_fraction"),
+     "strategy.densify.error.grow_fraction", "value"),
+    ("--densify-views", dict(type=int, metavar="K", help="strategy.densify.error.views: training views scored per densify step (0: all)"),
+     "strategy.densify.error.views", "value"),
+)
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m 3dgrut_amd.trainer", description="Train a COLMAP scene and score its test split.")
-    ap.add_argument("--path", required=True, help="COLMAP scene directory (sparse/0 + images[_F])")
-    ap.add_argument("--out-dir", default=None)
-    ap.add_argument("--n-iterations", type=int, default=None)
-    ap.add_argument("--strategy", choices=("gs", "mcmc"), default="gs")
-    ap.add_argument("--downsample", type=int, default=1)
-    ap.add_argument("--test-split-interval", type=int, default=8)
-    ap.add_argument("--resume", default="")
-    ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--background", choices=BACKGROUND_COLORS, default=None,
-                    help="model.background.color (default: the config's, black); random = a uniform colour per training pixel")
-    ap.add_argument("--refine-poses", action="store_true",
-                    help="refine the training views' camera poses while training (pose_refinement.enabled); test views keep theirs")
-    ap.add_argument("--pose-lr-translation", type=float, default=None, help="pose_refinement.lr_translation (times the scene extent)")
-    ap.add_argument("--pose-lr-rotation", type=float, default=None, help="pose_refinement.lr_rotation (radians)")
-    ap.add_argument("--exposure", action="store_true",
-                    help="learn an affine colour transform per training view (exposure.enabled); test views are scored with the "
-                         "identity (--cc-metrics adds colour-corrected scores)")
-    ap.add_argument("--exposure-lr", type=float, default=None, help="exposure.lr")
-    ap.add_argument("--cc-metrics", action="store_true",
-                    help="also score held-out views colour-corrected: through the affine colour transform fitted per view "
-                         "(evaluation.colour_corrected)")
-    ap.add_argument("--aligned-metrics", action="store_true",
-                    help="also score held-out views pose-aligned: each test view's pose is optimised against its photo with the model "
-                         "frozen before it is scored again (pose_alignment.enabled); the plain scores stay")
-    ap.add_argument("--align-iterations", type=int, default=None, help="pose_alignment.iterations")
-    ap.add_argument("--compact-to", type=float, default=None, metavar="FRACTION",
-                    help="after training, keep this fraction of the Gaussians: the best by their contribution to the training views "
-                         "(compaction.enabled, compaction.keep_fraction)")
-    ap.add_argument("--compact-score", choices=contribution_mod.SCORES, default=None, help="compaction.score")
-    ap.add_argument("--compact-finetune", type=int, default=None, metavar="K", help="compaction.finetune_iterations")
-    ap.add_argument("--select-by-masks", nargs="?", const=selection_mod.DEFAULTS["mask_suffix"], default=None, metavar="SUFFIX",
-                    help="after training, select the Gaussians inside the views' label masks <image stem>SUFFIX.png (default "
-                         "_object), render the selection into the held-out views and score its IoU (selection.enabled, "
-                         "selection.mask_suffix)")
-    ap.add_argument("--select-threshold", type=float, default=None, metavar="T", help="selection.threshold")
-    ap.add_argument("--fit-features", nargs="?", const=features_mod.DEFAULTS["suffix"], default=None, metavar="SUFFIX",
-                    help="after training, fit per-Gaussian features to the views' maps <image stem>SUFFIX.npy (default _features) with "
-                         "the model frozen and score them on the held-out views' maps (features.enabled, features.suffix)")
-    ap.add_argument("--feature-iterations", type=int, default=None, metavar="K", help="features.iterations (untuned on real captures)")
-    ap.add_argument("--feature-lr", type=float, default=None, metavar="X", help="features.lr (untuned on real captures)")
-    ap.add_argument("--export-points", action="store_true",
-                    help="after training, export the scene as points: the median surface points of the training views, fused into "
-                         "points.ply, and the held-out views' median distance planes (points.enabled)")
-    ap.add_argument("--points-level", type=float, default=None, metavar="T", help="points.level: the transmittance level, 0.5 = the median")
-    ap.add_argument("--points-stride", type=int, default=None, metavar="S", help="points.stride: every S-th pixel (untuned on real captures)")
-    ap.add_argument("--points-voxel", type=float, default=None, metavar="V",
-                    help="points.voxel: one point per cell of this edge length, 0 = all (untuned on real captures)")
-    ap.add_argument("--export-mesh", action="store_true",
-                    help="after training, export the scene as a triangle mesh: the training views' median distance planes fused into a "
-                         "TSDF volume, its zero level written to mesh.ply (mesh.enabled)")
-    ap.add_argument("--mesh-resolution", type=int, default=None, metavar="R",
-                    help="mesh.resolution: voxels along the longest edge of the box (untuned on real captures)")
-    ap.add_argument("--mesh-voxel", type=float, default=None, metavar="V", help="mesh.voxel: the voxel edge length, instead of a resolution")
-    ap.add_argument("--densify-by", choices=("gradient", "error"), default=None,
-                    help="strategy.densify.criterion: error = grow the rows responsible for the most rendering error (default: gradient)")
-    ap.add_argument("--densify-grow-fraction", type=float, default=None, metavar="F", help="strategy.densify.error.grow_fraction")
-    ap.add_argument("--densify-views", type=int, default=None, metavar="K",
-                    help="strategy.densify.error.views: training views scored per densify step (0: all)")
+    for flag, keywords, _, how in FLAGS:
+        ap.add_argument(flag, **(dict(keywords, action="store_true") if how == "switch" else {"default": None, **keywords}))
     return ap
 
 
 def config_from_args(a):
     """The plain conf dict of parsed command-line arguments (build_parser().parse_args(...))."""
     conf = default_config("MCMCStrategy" if a.strategy == "mcmc" else "GSStrategy")
-    if a.out_dir is not None:
-        conf["out_dir"] = a.out_dir
-    if a.n_iterations is not None:
-        conf["n_iterations"] = a.n_iterations
     conf["resume"], conf["seed"] = a.resume, a.seed
-    if a.background is not None:
-        conf["model"]["background"]["color"] = a.background
-    conf["pose_refinement"]["enabled"] = bool(a.refine_poses)
-    if a.pose_lr_translation is not None:
-        conf["pose_refinement"]["lr_translation"] = a.pose_lr_translation
-    if a.pose_lr_rotation is not None:
-        conf["pose_refinement"]["lr_rotation"] = a.pose_lr_rotation
-    conf["exposure"]["enabled"] = bool(a.exposure)
-    if a.exposure_lr is not None:
-        conf["exposure"]["lr"] = a.exposure_lr
-    conf["evaluation"]["colour_corrected"] = bool(a.cc_metrics)
-    conf["pose_alignment"]["enabled"] = bool(a.aligned_metrics)
-    if a.align_iterations is not None:
-        conf["pose_alignment"]["iterations"] = a.align_iterations
-    if a.compact_to is not None:
-        conf["compaction"]["enabled"] = True
-        conf["compaction"]["keep_fraction"] = a.compact_to
-    if a.compact_score is not None:
-        conf["compaction"]["score"] = a.compact_score
-    if a.compact_finetune is not None:
-        conf["compaction"]["finetune_iterations"] = a.compact_finetune
-    if a.select_by_masks is not None:
-        conf["selection"]["enabled"] = True
-        conf["selection"]["mask_suffix"] = a.select_by_masks
-    if a.select_threshold is not None:
-        conf["selection"]["threshold"] = a.select_threshold
-    if a.fit_features is not None:
-        conf["features"]["enabled"] = True
-        conf["features"]["suffix"] = a.fit_features
-    if a.feature_iterations is not None:
-        conf["features"]["iterations"] = a.feature_iterations
-    if a.feature_lr is not None:
-        conf["features"]["lr"] = a.feature_lr
-    conf["points"]["enabled"] = bool(a.export_points)
-    if a.points_level is not None:
-        conf["points"]["level"] = a.points_level
-    if a.points_stride is not None:
-        conf["points"]["stride"] = a.points_stride
-    if a.points_voxel is not None:
-        conf["points"]["voxel"] = a.points_voxel
-    conf["mesh"]["enabled"] = bool(a.export_mesh)
-    if a.mesh_resolution is not None:
-        conf["mesh"]["resolution"] = a.mesh_resolution
-    if a.mesh_voxel is not None:
-        conf["mesh"]["voxel"] = a.mesh_voxel
-    densify = {}
-    if a.densify_by is not None:
-        densify["criterion"] = a.densify_by
-    if a.densify_grow_fraction is not None:
-        densify.setdefault("error", {})["grow_fraction"] = a.densify_grow_fraction
-    if a.densify_views is not None:
-        densify.setdefault("error", {})["views"] = a.densify_views
-    if densify:
-        conf["strategy"]["densify"] = _merge(conf["strategy"].get("densify") or {}, densify)
+    for flag, _, key, how in FLAGS:
+        value = getattr(a, flag[2:].replace("-", "_"))
+        if key is None or (how != "switch" and value is None):
+            continue
+        *blocks, leaf = key.split(".")
+        block = conf
+        for name in blocks:       # (MCMCStrategy's defaults have no strategy.densify)
+            block = block.setdefault(name, {})
+        block[leaf] = value
+        if how == "enables":
+            block["enabled"] = True
     return conf
+
+
+def _attach_label_masks(scene, batches, suffix):
+    """batch.label_mask [H,W] of every view of `scene`: its label mask file, None where there is none."""
+    for i, b in enumerate(batches):
+        label = scene.load_label_mask(i, suffix)
+        b.label_mask = None if label is None else torch.as_tensor(label[0, :, :, 0], device=b.rays_ori.device)
+
+
+def _attach_feature_maps(scene, batches, suffix):
+    """batch.feature_map [K,H,W] of every view of `scene`: its target map at the batch's resolution, None where there is none."""
+    for i, b in enumerate(batches):
+        fmap = scene.load_feature_map(i, suffix, size=(int(b.rays_ori.shape[2]), int(b.rays_ori.shape[1])))
+        b.feature_map = None if fmap is None else torch.as_tensor(fmap, device=b.rays_ori.device)
+
+
+def _attach_image_stems(scene, batches):
+    """batch.image_stem of every view of `scene`: its image's file name without the extension."""
+    for i, b in enumerate(batches):
+        b.image_stem = os.path.splitext(os.path.basename(scene.images[i].name))[0]
 
 
 def main(argv=None):
@@ -1102,20 +1023,13 @@ def main(argv=None):
                                                          default_scale_factor=conf["model"]["default_scale_factor"], seed=a.seed)
     tb = [train.batch(i) for i in range(len(train))]
     vb = [test.batch(i) for i in range(len(test))]
-    if conf["selection"]["enabled"]:      # the views' label masks, where the files are there
-        for scene, batches in ((train, tb), (test, vb)):
-            for i, b in enumerate(batches):
-                label = scene.load_label_mask(i, conf["selection"]["mask_suffix"])
-                b.label_mask = None if label is None else torch.as_tensor(label[0, :, :, 0], device=b.rays_ori.device)
-    if conf["features"]["enabled"]:       # the views' target maps, where the files are there
-        for scene, batches in ((train, tb), (test, vb)):
-            for i, b in enumerate(batches):
-                fmap = scene.load_feature_map(i, conf["features"]["suffix"], size=(int(b.rays_ori.shape[2]), int(b.rays_ori.shape[1])))
-                b.feature_map = None if fmap is None else torch.as_tensor(fmap, device=b.rays_ori.device)
-                b.image_stem = os.path.splitext(os.path.basename(scene.images[i].name))[0]
-    if conf["points"]["enabled"]:         # the names of the held-out views' distance planes
-        for i, b in enumerate(vb):
-            b.image_stem = os.path.splitext(os.path.basename(test.images[i].name))[0]
+    for scene, batches in ((train, tb), (test, vb)):
+        if conf["selection"]["enabled"]:
+            _attach_label_masks(scene, batches, conf["selection"]["mask_suffix"])
+        if conf["features"]["enabled"]:
+            _attach_feature_maps(scene, batches, conf["features"]["suffix"])
+        if conf["features"]["enabled"] or (conf["points"]["enabled"] and scene is test):   # whose outputs are named after the views
+            _attach_image_stems(scene, batches)
     trainer = Trainer(conf, init, tb, val_batches=vb, test_batches=vb, scene_extent=train.cameras_extent)
     res = trainer.run()
     test_res = res["test"]
