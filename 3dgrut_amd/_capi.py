@@ -106,6 +106,21 @@ class GutTsdfView(C.Structure):
                 ("d_rgba", C.c_void_p), ("d_ray_origin", C.c_void_p)]
 
 
+kEnvSlots = 128                    # gut_hip.h, GUT_ENVIRONMENT_SLOTS: texels a 16x16 pixel tile of the adjoint sums in LDS
+ENVIRONMENT_MAX_RESOLUTION = 8192  # gut_hip.h, GUT_ENVIRONMENT_MAX_RESOLUTION
+ENVIRONMENT_TILE = 16
+
+
+class GutEnvironmentView(C.Structure):
+    """One view of the cube-map background (gut_hip.h): the ray table (device), the camera-to-world rotation by value."""
+    _fields_ = [("d_ray_direction", C.c_void_p), ("rotation", C.c_float * 9), ("height", C.c_int32), ("width", C.c_int32)]
+
+
+class GutEnvironmentCotangent(C.Structure):
+    """The adjoint's cotangent: the plane [H,W,3], or the fused loss's pair rgba / rgba_grad [H,W,4]; None = that form is absent."""
+    _fields_ = [("d_plane_grad", C.c_void_p), ("d_rgba", C.c_void_p), ("d_rgba_grad", C.c_void_p)]
+
+
 EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_trace_bwd", "gut_collect_times",
            "gut_get_stats", "gut_debug_buffer", "gut_debug_copy", "gut_kernel_times", "gut_kernel_times_mean", "gut_last_error", "gut_abi_version",
            "gut_ssim_workspace_bytes", "gut_ssim_forward", "gut_ssim_backward",
@@ -121,7 +136,8 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_photometric_exposure_workspace_bytes", "gut_photometric_loss_exposure", "gut_exposure_adam_step",
            "gut_image_metrics_cc_workspace_bytes", "gut_image_metrics_cc", "gut_photometric_loss_run", "gut_trace_bwd_pose",
            "gut_trace_contribution", "gut_trace_contribution_weighted", "gut_pixel_error", "gut_trace_attributes",
-           "gut_trace_attributes_bwd", "gut_trace_surface", "gut_tsdf_integrate", "gut_surface_nets_count", "gut_surface_nets_emit")
+           "gut_trace_attributes_bwd", "gut_trace_surface", "gut_tsdf_integrate", "gut_surface_nets_count", "gut_surface_nets_emit",
+           "gut_environment_sample", "gut_environment_workspace_bytes", "gut_environment_backward", "gut_environment_rotation")
 
 _lib = None
 
@@ -170,6 +186,12 @@ def load():
     lib.gut_tsdf_integrate.argtypes = [vp, C.POINTER(GutTsdfGrid), i32, C.POINTER(GutTsdfView)]
     lib.gut_surface_nets_count.argtypes = [vp, C.POINTER(GutTsdfGrid), u32, vp, vp]
     lib.gut_surface_nets_emit.argtypes = [vp, C.POINTER(GutTsdfGrid), u32, vp, vp, vp, vp, vp, vp, vp]
+    env_p = C.POINTER(GutEnvironmentView)
+    lib.gut_environment_sample.argtypes = [vp, env_p, vp, i32, vp]
+    lib.gut_environment_workspace_bytes.argtypes = [i32]
+    lib.gut_environment_workspace_bytes.restype = C.c_size_t
+    lib.gut_environment_backward.argtypes = [vp, env_p, C.POINTER(GutEnvironmentCotangent), i32, vp, vp]
+    lib.gut_environment_rotation.argtypes = [C.POINTER(GutCamera), C.POINTER(C.c_float)]
     lib.gut_pixel_error.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, vp, vp]
     lib.gut_mcmc_perturb.argtypes = [vp, u32, f_p, f_p, C.c_float, C.c_uint64, C.c_uint64, f_p]
     lib.gut_collect_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]

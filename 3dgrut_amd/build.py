@@ -27,6 +27,7 @@ UNITS = [
     ("gut_train.hip", ["-ffp-contract=fast"]),
     ("gut_pose.hip", ["-ffp-contract=off"]),
     ("gut_fuse.hip", ["-ffp-contract=off"]),   # a voxel's pixel is an integer decision of K1's projection arithmetic
+    ("gut_environment.hip", ["-ffp-contract=off"]),   # a pixel's face and texels are integer decisions; the plane is bit-exact
     ("gut_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 

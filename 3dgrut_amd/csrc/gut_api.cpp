@@ -1477,6 +1477,67 @@ int gut_surface_nets_emit(void* stream_, const GutTsdfGrid* grid, uint32_t min_c
     return 0;
 }
 
+// ---- the cube-map background (gut_environment.hip): handle-free; everything is checked here, before anything is queued ----
+namespace {
+
+int build_environment_view(const char* who, const GutEnvironmentView* view, int32_t resolution, gut::EnvView* v) {
+    if (!view) return fail("%s: null view", who);
+    if (!view->d_ray_direction) return fail("%s: null d_ray_direction", who);
+    if (resolution < 1 || resolution > GUT_ENVIRONMENT_MAX_RESOLUTION)
+        return fail("%s: resolution must be 1 .. %d, got %d", who, GUT_ENVIRONMENT_MAX_RESOLUTION, resolution);
+    if (view->height < 1 || view->width < 1) return fail("%s: an empty image, %d x %d", who, view->height, view->width);
+    if ((uint64_t)view->height * (uint64_t)view->width > (1ull << 30))
+        return fail("%s: %d x %d exceeds 2^30 pixels", who, view->height, view->width);
+    v->ray_direction = view->d_ray_direction;
+    for (int i = 0; i < 9; ++i) v->rotation[i] = view->rotation[i];
+    v->height = view->height;
+    v->width = view->width;
+    return 0;
+}
+
+}  // namespace
+
+int gut_environment_sample(void* stream_, const GutEnvironmentView* view, const float* d_texels, int32_t resolution, float* d_plane_out) {
+    gut::EnvView v;
+    if (int rc = build_environment_view("gut_environment_sample", view, resolution, &v)) return rc;
+    if (!d_texels || !d_plane_out) return fail("gut_environment_sample: null d_texels or d_plane_out");
+    gut::launch_environment_sample(static_cast<hipStream_t>(stream_), v, d_texels, resolution, d_plane_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+size_t gut_environment_workspace_bytes(int32_t resolution) {
+    return (resolution < 1 || resolution > GUT_ENVIRONMENT_MAX_RESOLUTION) ? 0 : gut::environment_workspace_bytes(resolution);
+}
+
+int gut_environment_backward(void* stream_, const GutEnvironmentView* view, const GutEnvironmentCotangent* cotangent, int32_t resolution,
+                             void* d_workspace, float* d_texel_grad) {
+    gut::EnvView v;
+    if (int rc = build_environment_view("gut_environment_backward", view, resolution, &v)) return rc;
+    if (!cotangent) return fail("gut_environment_backward: null cotangent");
+    if (!d_workspace || !d_texel_grad) return fail("gut_environment_backward: null d_workspace or d_texel_grad");
+    if ((reinterpret_cast<uintptr_t>(d_workspace) & 7u) != 0) return fail("gut_environment_backward: d_workspace is not 8-byte aligned");
+    const bool plane = cotangent->d_plane_grad != nullptr, pair = cotangent->d_rgba != nullptr && cotangent->d_rgba_grad != nullptr;
+    if (plane == pair || (plane && (cotangent->d_rgba || cotangent->d_rgba_grad)))
+        return fail("gut_environment_backward: the cotangent is either d_plane_grad or the pair d_rgba, d_rgba_grad");
+    gut::EnvCotangent c{cotangent->d_plane_grad, cotangent->d_rgba, cotangent->d_rgba_grad};
+    HIP_TRY(gut::launch_environment_backward(static_cast<hipStream_t>(stream_), v, c, resolution, d_workspace, d_texel_grad));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int gut_environment_rotation(const GutCamera* camera, float* rotation9) {
+    if (!camera || !rotation9) return fail("gut_environment_rotation: null camera or rotation9");
+    // build_view's sensor->world rotation: the transpose of the world->sensor rotation at the middle of the two poses
+    float mid[7];
+    interpolate_pose(camera->pose_start, camera->pose_end, 0.5f, mid);
+    gut::Affine w2s;
+    pose_affine(mid, &w2s);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) rotation9[3 * r + c] = w2s.r[c][r];
+    return 0;
+}
+
 int gut_set_regularisation(gut_handle h, const GutRegularisation* reg) {
     if (!h) return fail("gut_set_regularisation: null handle");
     if (reg && !(reg->density_coeff >= 0.0f && reg->scale_coeff >= 0.0f && reg->density_coeff < INFINITY && reg->scale_coeff < INFINITY))

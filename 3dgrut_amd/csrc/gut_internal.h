@@ -354,6 +354,23 @@ void launch_surface_nets_count(hipStream_t s, const FuseGrid& g, uint32_t min_co
 void launch_surface_nets_emit(hipStream_t s, const FuseGrid& g, uint32_t min_count, const uint8_t* cell, const uint8_t* quads,
                               const int32_t* vertex_offset, const int32_t* quad_offset, float* vertices, float* colours, int32_t* faces);
 
+// gut_environment.hip: the cube-map background, its sampler and its adjoint.  The records are checked on the host
+// (gut_api.cpp) and travel as kernel arguments.
+struct EnvView {
+    const float* ray_direction;   // [H,W,3], camera space
+    float rotation[9];            // camera-to-world, row-major: the compositor's s2w.r
+    int32_t height, width;
+};
+struct EnvCotangent {
+    const float* plane_grad;      // [H,W,3], or null: then the pair below
+    const float* rgba;            // [H,W,4]
+    const float* rgba_grad;       // [H,W,4]
+};
+size_t environment_workspace_bytes(int resolution);
+void launch_environment_sample(hipStream_t s, const EnvView& v, const float* texels, int resolution, float* plane);
+hipError_t launch_environment_backward(hipStream_t s, const EnvView& v, const EnvCotangent& c, int resolution, void* workspace,
+                                       float* texel_grad);
+
 // scan / sort (rocPRIM device-wide primitives; temp storage owned by the caller)
 size_t scan_temp_bytes(uint32_t n);
 hipError_t run_scan(hipStream_t s, void* temp, size_t temp_bytes, const uint32_t* in, uint32_t* out, uint32_t n);

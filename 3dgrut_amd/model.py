@@ -28,6 +28,7 @@ class GaussianModel(torch.nn.Module):
         self.max_n_features = int(max_n_features)
         self.n_active_features = min(int(sh_degree), self.max_n_features)
         self.background_color = background_color
+        self.environment = None   # an environment.EnvironmentMap: the learnt cube-map background
         self.device = device
 
     @property
@@ -58,6 +59,8 @@ class GaussianModel(torch.nn.Module):
             rgb = rgb + (1.0 - opacity)
         elif self.background_color == "random" and train:
             rgb = rgb + torch.rand_like(rays_d) * (1.0 - opacity)
+        if self.environment is not None:
+            rgb = rgb + self.environment.sample(rays_d, T_to_world).reshape(rays_d.shape) * (1.0 - opacity)
         return rgb, opacity
 
     def param_groups(self, extent=1.0):

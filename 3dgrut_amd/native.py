@@ -124,11 +124,15 @@ class NativeGaussianModel:
         self.last_background = bg[0] if bg.dim() == 4 and bg.shape[0] == 1 else bg
         return self.last_background
 
+    environment = None       # an environment.EnvironmentMap: the learnt cube-map background, composited behind the colour
+
     def background(self, T_to_world, rays_d, rgb, opacity, train=False):
         if self.background_color == "white":
             rgb = rgb + (1.0 - opacity)
         elif self.background_color == "random" and train:
             rgb = rgb + self.draw_background(rays_d).reshape(rays_d.shape) * (1.0 - opacity)
+        if self.environment is not None:   # in training and at evaluation: held-out views are scored over the learnt map
+            rgb = rgb + self.environment.sample(rays_d, T_to_world).reshape(rays_d.shape) * (1.0 - opacity)
         return rgb, opacity
 
 
@@ -136,6 +140,7 @@ class NativeTrainStep:
     OVERLAP_MIN_GAUSSIANS = 1_000_000   # size from which the two-pass optimiser is on by default (see __init__)
     PROBE_FIRST, PROBE_LAST = 2, 9       # steps in which the default-on overlap is timed against the one-pass form, alternating
     supports_masks = True                # step() honours Batch.mask in both loss branches (trainer.Trainer asks before it takes masked views)
+    environment_active = True            # model.environment is learnt by this step (False: composited only; the trainer's iteration window)
 
     def __init__(self, model: NativeGaussianModel, tracer: Tracer, scene_extent=1.0, world_size=1, selective=False,
                  betas=(0.9, 0.999), eps=1e-15, fused_sh_adam=True, rank=0, fused_loss=True, lambda_l1=0.8, lambda_ssim=0.2,
@@ -728,7 +733,14 @@ class NativeTrainStep:
             # (_plane_mask: a view for the reader's float32 [1,H,W,1] device mask, no kernel; a mask of another dtype or device is
             # converted here, one copy per step — keep such masks converted in the batch)
             # (`random`: this step's draw, every pixel over its own colour — the same draw the torch branch below makes)
-            if m.background_color == "random":
+            env = m.environment
+            if env is not None:
+                # the learnt cube map IS the background (the trainer refuses another colour beside it): its plane goes
+                # where the `random` draw goes, and the adjoint below reads the loss's own output
+                if m.background_color != "black":
+                    raise ValueError(f"an environment map is the background: model.background_color must be 'black', got {m.background_color!r}")
+                bg = env.plane(batch, self._ctx[2])
+            elif m.background_color == "random":
                 bg = _plane_background(m.draw_background(batch.rays_dir), H, W, rgba.device)   # (a view: float32 [H,W,3] already)
             else:
                 bg = 1.0 if m.background_color == "white" else 0.0
@@ -738,7 +750,12 @@ class NativeTrainStep:
                                                             None if exposure is None else _exposure12(exposure, rgba.device),
                                                             None if exposure is None else self.exposure_gradient)
             pred_rgb = rgba[..., :3].unsqueeze(0)
-            if m.background_color == "white":
+            if env is not None:
+                pred_rgb = pred_rgb + bg.unsqueeze(0) * (1.0 - rgba[..., 3:].unsqueeze(0))
+                if self.environment_active:   # the scatter and the map's Adam step, same stream, nothing read back
+                    env.backward_from_loss(batch, rgba, rgba_grad, self._ctx[2])
+                    env.step()
+            elif m.background_color == "white":
                 pred_rgb = pred_rgb + (1.0 - rgba[..., 3:].unsqueeze(0))
             elif m.background_color == "random":
                 pred_rgb = pred_rgb + bg.unsqueeze(0) * (1.0 - rgba[..., 3:].unsqueeze(0))
@@ -746,12 +763,23 @@ class NativeTrainStep:
         rgba_leaf = rgba.detach().requires_grad_(True)
         pred_rgb = rgba_leaf[..., :3].unsqueeze(0)
         pred_opacity = rgba_leaf[..., 3:].unsqueeze(0)
-        pred_rgb, pred_opacity = m.background(batch.T_to_world, batch.rays_dir, pred_rgb, pred_opacity, True)
-        E = None
-        if exposure is not None:   # a leaf copy: autograd leaves d(loss)/dE on it, the caller's row is not touched
-            E = _exposure12(exposure, rgba.device).clone().requires_grad_(self.exposure_gradient is not None)
-        loss = photometric_loss(pred_rgb, gt, self.lambda_l1, self.lambda_ssim, mask=mask, exposure=E)
-        loss.backward()  # image-sized autograd only
+        # (an environment map: the graph through background() reaches its texels while the map is being learnt)
+        learn_env = m.environment is not None and self.environment_active
+        if learn_env:
+            m.environment.texels.grad = None
+            m.environment.texels.requires_grad_(True)
+        try:
+            pred_rgb, pred_opacity = m.background(batch.T_to_world, batch.rays_dir, pred_rgb, pred_opacity, True)
+            E = None
+            if exposure is not None:   # a leaf copy: autograd leaves d(loss)/dE on it, the caller's row is not touched
+                E = _exposure12(exposure, rgba.device).clone().requires_grad_(self.exposure_gradient is not None)
+            loss = photometric_loss(pred_rgb, gt, self.lambda_l1, self.lambda_ssim, mask=mask, exposure=E)
+            loss.backward()  # image-sized autograd only
+        finally:
+            if learn_env:   # (the flag is read when the gradient is accumulated: it stays up until the backward has run)
+                m.environment.texels.requires_grad_(False)
+        if learn_env:
+            m.environment.step()
         if E is not None and self.exposure_gradient is not None:
             self.exposure_gradient.copy_(E.grad)
         return loss, pred_rgb, rgba_leaf.grad

@@ -36,6 +36,7 @@ them elsewhere (require_walk), the Trainer refuses them on several GPUs (require
                                  [--fit-features [SUFFIX] [--feature-iterations K] [--feature-lr X]]
                                  [--export-points [--points-level T] [--points-stride S] [--points-voxel V]]
                                  [--export-mesh [--mesh-resolution R] [--mesh-voxel V]]
+                                 [--environment [--environment-resolution R] [--environment-lr X]]
 """
 import argparse
 import copy
@@ -49,6 +50,7 @@ import torch
 
 from . import contribution as contribution_mod
 from . import features as features_mod
+from . import environment as environment_mod
 from . import exposure as exposure_mod
 from . import losses, pose_align, pose_refine
 from . import mesh as mesh_mod
@@ -147,6 +149,11 @@ def resolve_config(conf):
         out["strategy"]["reset_density"]["end_iteration"] = out["strategy"]["densify"]["end_iteration"]
     pose_refine.check_config(out["pose_refinement"])
     exposure_mod.check_config(out["exposure"])
+    # not a reference key, and not among the defaults above: a learnt cube-map background behind the Gaussians (environment.py,
+    # DESIGN.md §20), resolved here over its own defaults.  end_iteration null = to the end of the run; outside the window the map
+    # is still composited.  lr, init and resolution are untuned on real captures.
+    out["environment"] = _merge(environment_mod.DEFAULTS, out.get("environment"))
+    check_environment_config(out)
     check_evaluation_config(out["evaluation"])
     pose_align.check_config(out["pose_alignment"])
     contribution_mod.check_config(out["compaction"])
@@ -214,6 +221,21 @@ def check_densify_config(conf):
     return conf
 
 
+def check_environment_config(conf):
+    """The `environment` block of a resolved conf, and what an enabled map refuses: another background colour beside it (the map IS
+    the background) and pose-aligned metrics (the plane depends on the pose being fitted, and that dependence has no gradient).  The
+    data-parallel refusal needs the stepper and is the Trainer's."""
+    block = environment_mod.check_config(conf["environment"])
+    if block["enabled"]:
+        color = conf["model"]["background"]["color"]
+        if color != "black":
+            raise ValueError(f"environment: the map is the background, model.background.color must be 'black' (it is {color!r})")
+        if conf["pose_alignment"]["enabled"]:
+            raise ValueError("environment: pose-aligned metrics are refused with an environment map (pose_alignment.enabled): the "
+                             "background plane depends on the pose being fitted, and that dependence has no gradient")
+    return conf
+
+
 def check_evaluation_config(block):
     """The resolved `evaluation` block: colour_corrected true or false, ridge finite and > 0."""
     return check_block("evaluation", block, GS_CONFIG["evaluation"], EVALUATION_RULES)
@@ -277,9 +299,9 @@ def _adam_group_template(betas, eps):
     return g
 
 
-def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=None, refiner=None, exposures=None):
+def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=None, refiner=None, exposures=None, environment=None):
     """The checkpoint dictionary of a NativeTrainStep's state (see the module docstring); refiner: the run's PoseRefiner or None;
-    exposures: its ExposureCompensation or None."""
+    exposures: its ExposureCompensation or None; environment: its EnvironmentMap or None."""
     from .io_ply import checkpoint_dict
     st = stepper.state_dict()   # moments brought up to date (sync_moments) and cloned
     m = stepper.model
@@ -313,6 +335,8 @@ def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=No
         extra["native"]["pose_refinement"] = refiner.state_dict()   # tensors only: poses, moments, visit counts
     if exposures is not None:
         extra["native"]["exposure"] = exposures.state_dict()        # tensors only: transforms, moments, visit counts
+    if environment is not None:
+        extra["native"]["environment"] = environment.state_dict()   # tensors only: texels, Adam's moments and step count
     if progressive:
         extra["feature_dim_increase_interval"] = int(prog["increase_frequency"])
         extra["feature_dim_increase_step"] = int(prog["increase_step"])
@@ -384,6 +408,7 @@ class Trainer:
         self.strategy = self._build_strategy(ckpt) if strategy is None else strategy
         self.refiner = self._build_refiner(ckpt)
         self.exposure = self._build_exposure(ckpt)
+        self.environment_map = self._build_environment(ckpt)
         if ckpt is not None:
             self.global_step = int(ckpt["global_step"])
         for block, _, noun, _ in STAGES:
@@ -490,6 +515,35 @@ class Trainer:
         if saved is not None:
             comp.load_state_dict(saved)
         return comp
+
+    def _build_environment(self, ckpt):
+        """The EnvironmentMap of a run with environment.enabled (default off; `--environment`), else None; its state restored from a
+        resumed checkpoint.  It is a learnt radiance at infinity: a cube map [6,R,R,3] composited behind the
+        Gaussians in training and at evaluation (model.environment, through background()), so that sky and far background need no
+        large faint Gaussians.  Inside [start_iteration, end_iteration) every step scatters (1 - alpha) d loss / d rgb onto the
+        texels and takes an Adam step on them, on the device; outside, the map is composited as it is.  With --refine-poses the plane
+        is sampled from the refined pose; the pose gradient does not see the map (as it does not see the SH view direction).  The
+        texels and their Adam state travel in the checkpoint's `native` block as tensors."""
+        blk = self.conf["environment"]
+        if not blk["enabled"]:
+            if ckpt is not None and ckpt.get("native", {}).get("environment") is not None:
+                # continuing over black would silently drop the background the Gaussians were trained against
+                raise ValueError("environment: the checkpoint holds an environment map and environment.enabled is off; resume with "
+                                 "--environment (environment.enabled: true), with end_iteration 0 to keep the map as it is")
+            return None
+        st = self.stepper
+        require_one_gpu(st, "environment", "environment-map training")
+        env = environment_mod.EnvironmentMap(int(blk["resolution"]), float(blk["init"]), self.model.raw.device, lr=float(blk["lr"]),
+                                             start_iteration=int(blk["start_iteration"]), end_iteration=blk["end_iteration"])
+        saved = None if ckpt is None else ckpt["native"].get("environment")
+        if saved is not None:
+            env.load_state_dict(saved)
+        self.model.environment = env
+        return env
+
+    def environment(self):
+        """[6,R,R,3] float32 host tensor: the texels of the environment map, None without one."""
+        return None if self.environment_map is None else self.environment_map.texels.detach().cpu().clone()
 
     def exposures(self):
         """[V,3,4] float32: the training views' current colour transforms [A | b], in train_batches order (identities when exposure
@@ -638,17 +692,20 @@ class Trainer:
         degree 2 only.  grow_fraction, views and min_pixels are untuned on real captures."""
         color = self.conf["model"]["background"]["color"]
         scorer = contribution_mod.ContributionScores(self.model, self.tracer)
+        env = self.environment_map
         for view in self._error_views(step):
             batch = self._posed(view)
             if self.exposure is not None:
                 batch = self.exposure.begin(view, batch)
-            scorer.accumulate_error(batch, "black" if color == "random" else color, mask=getattr(batch, "mask", None),
+            # (an environment map: the view's own plane of it is the background the error is measured over)
+            background = env.plane(batch) if env is not None else ("black" if color == "random" else color)
+            scorer.accumulate_error(batch, background, mask=getattr(batch, "mask", None),
                                     exposure=getattr(batch, "exposure", None))
         return scorer.result()
 
     def checkpoint(self):
         return make_checkpoint(self.stepper, self.conf, self.global_step, self.epoch, self.scene_extent,
-                               self.strategy if self.method == "GSStrategy" else None, self.refiner, self.exposure)
+                               self.strategy if self.method == "GSStrategy" else None, self.refiner, self.exposure, self.environment_map)
 
     def save_checkpoint(self, last=False):
         out = self._out_dir()
@@ -692,6 +749,12 @@ class Trainer:
         if self.exposure is not None:
             sm = self.exposure.summary()
             self.stats.update(exposure_mean_gain=sm["mean_gain"], exposure_mean_offset=sm["mean_offset"])
+        if self.environment_map is not None:
+            self.stats.update(environment_resolution=int(self.environment_map.resolution),
+                              environment_mean_colour=self.environment_map.mean_colour())
+            if self._out_dir() is not None:
+                os.makedirs(self._out_dir(), exist_ok=True)
+                np.save(os.path.join(self._out_dir(), "environment.npy"), self.environment().numpy())
         return self.stats
 
     def _step_once(self, g):
@@ -719,6 +782,8 @@ class Trainer:
             switch = getattr(self.stepper, "enable_exposure_gradient", None)
             if switch is not None:                      # outside [start_iteration, end_iteration) the loss reduces nothing
                 switch(comp.active(g))
+        if self.environment_map is not None:            # outside [start_iteration, end_iteration) nothing is scattered or stepped
+            self.stepper.environment_active = self.environment_map.active(g)
         return batch
 
     def _compaction_mask(self, result):
@@ -965,20 +1030,30 @@ FLAGS = (
     ("--densify-views", dict(type=int, metavar="K", help="strategy.densify.error.views: training views scored per densify step (0: all)"),
      "strategy.densify.error.views", "value"),
 )
+# The environment map's flags, in FLAGS' form: main() parses FLAGS + ENVIRONMENT_FLAGS.  They are a table of their own so that
+# build_parser() and config_from_args() without arguments stay what they were: the conf of a command line without these flags has
+# no `environment` key (resolve_config supplies the block's defaults).
+ENVIRONMENT_FLAGS = (
+    ("--environment", dict(help="learn an environment map: a cube-map background behind the Gaussians, composited in training and at "
+                                "evaluation (environment.enabled); needs a black background"), "environment.enabled", "switch"),
+    ("--environment-resolution", dict(type=int, metavar="R", help="environment.resolution: texels along a face's edge" + _UNTUNED),
+     "environment.resolution", "value"),
+    ("--environment-lr", dict(type=float, metavar="X", help="environment.lr" + _UNTUNED), "environment.lr", "value"),
+)
 
 
-def build_parser():
+def build_parser(flags=FLAGS):
     ap = argparse.ArgumentParser(prog="python -m 3dgrut_amd.trainer", description="Train a COLMAP scene and score its test split.")
-    for flag, keywords, _, how in FLAGS:
+    for flag, keywords, _, how in flags:
         ap.add_argument(flag, **(dict(keywords, action="store_true") if how == "switch" else {"default": None, **keywords}))
     return ap
 
 
-def config_from_args(a):
-    """The plain conf dict of parsed command-line arguments (build_parser().parse_args(...))."""
+def config_from_args(a, flags=FLAGS):
+    """The plain conf dict of parsed command-line arguments (build_parser(flags).parse_args(...))."""
     conf = default_config("MCMCStrategy" if a.strategy == "mcmc" else "GSStrategy")
     conf["resume"], conf["seed"] = a.resume, a.seed
-    for flag, _, key, how in FLAGS:
+    for flag, _, key, how in flags:
         value = getattr(a, flag[2:].replace("-", "_"))
         if key is None or (how != "switch" and value is None):
             continue
@@ -1013,9 +1088,9 @@ def _attach_image_stems(scene, batches):
 
 
 def main(argv=None):
-    a = build_parser().parse_args(argv)
+    a = build_parser(FLAGS + ENVIRONMENT_FLAGS).parse_args(argv)
     from .io_colmap import ColmapScene
-    conf = config_from_args(a)
+    conf = config_from_args(a, FLAGS + ENVIRONMENT_FLAGS)
     train = ColmapScene(a.path, "train", a.downsample, a.test_split_interval)
     test = ColmapScene(a.path, "test", a.downsample, a.test_split_interval)
     # configs/initialization/colmap.yaml: observation-point scales, the model's default density / scale factor

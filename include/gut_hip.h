@@ -900,6 +900,51 @@ int gut_surface_nets_emit(void* stream, const GutTsdfGrid* grid, uint32_t min_co
                           const int32_t* d_vertex_offset, const int32_t* d_quad_offset, float* d_vertices, float* d_colours,
                           int32_t* d_faces);
 
+/* ---- A learnt radiance at infinity: a cube-map background (new functionality, the reference has none) ----
+ * The map is d_texels [6, R, R, 3] float32, plain RGB, indexed [face, row, column, channel].  For pixel p with the camera-space
+ * direction d = d_ray_direction[p] and the camera-to-world rotation M (row-major, the nine floats the compositors apply to a ray), in
+ * fp32 without contraction:
+ *     e_i = (M[i][0] d0 + M[i][1] d1) + M[i][2] d2;   a_i = |e_i|
+ *     axis = 0 if a0 >= a1 && a0 >= a2, else 1 if a1 >= a2, else 2;   m = a_axis;   face = 2 axis + (e_axis < 0)
+ *     u = e_(axis+1)%3 / m,  v = e_(axis+2)%3 / m           (no sign flips)
+ *     s = (u + 1) (0.5 R) - 0.5,  i0 = floor(s),  fx = s - i0;   t, j0, fy likewise from v
+ *     columns clamp(i0, 0, R-1), clamp(i0+1, 0, R-1); rows likewise from j0 (clamped to the edge WITHIN the face)
+ *     w00 = (1-fx)(1-fy), w10 = fx (1-fy), w01 = (1-fx) fy, w11 = fx fy    (w_ab: column a, row b)
+ *     B(p)_k = ((w00 T00_k + w10 T10_k) + w01 T01_k) + w11 T11_k
+ * A pixel with m == 0 or a non-finite e_i is VOID: its plane value is +0 and it scatters nothing.
+ * gut_environment_sample writes the [H,W,3] plane in full, one launch.
+ * gut_environment_backward is the adjoint grad[texel, k] = sum_p w(p, texel) c(p)_k of a cotangent c, given either as the plane
+ * d_plane_grad [H,W,3] or as the pair d_rgba / d_rgba_grad [H,W,4] of the fused loss, from which c_k = (1 - alpha) g_k is formed
+ * (1 - alpha rounded first, then each product).  Exactly one of the two forms is set.  A non-finite c counts as 0.  Every product
+ * w c_k is rounded to fp32 on its own, multiplied by 2^s (exact), rounded to nearest even to an integer and added with integer
+ * atomics: identical inputs give identical bits.  s comes from the largest finite |c| of the call, |c| < 2^e: s = 40 - e, less
+ * ceil(log2(H W)) - 22 for more than 2^22 pixels, clamped to -126 .. 126, 0 for a zero cotangent; one s for the three channels.
+ * Every element of d_texel_grad is written as float(sum) 2^-s.  Products below the normal fp32 range are outside the contract.
+ * Queued on `stream`, nothing read back: one memset of the workspace (gut_environment_workspace_bytes, 0 for a resolution that is
+ * refused), the maximum, the scatter (a 16x16 pixel tile per workgroup, summed in an LDS table of GUT_ENVIRONMENT_SLOTS texels, one
+ * 64-bit atomic per occupied slot and channel; a contribution that finds no slot adds to the workspace directly), the conversion.
+ * Return 1, on the host, nothing queued: a NULL pointer, resolution < 1 or > GUT_ENVIRONMENT_MAX_RESOLUTION (18 R^2 stays below
+ * 2^31), height or width < 1, more than 2^30 pixels, both or neither cotangent form; a HIP error is reported the same way.  gut_last_error says which.
+ * gut_environment_rotation (host only): M of a camera, the sensor-to-world rotation at the middle of its two poses exactly as the
+ * trace calls build it. */
+#define GUT_ENVIRONMENT_SLOTS 128
+#define GUT_ENVIRONMENT_MAX_RESOLUTION 8192
+typedef struct GutEnvironmentView {
+    const float* d_ray_direction;   /* [H,W,3] */
+    float rotation[9];              /* M, row-major */
+    int32_t height, width;
+} GutEnvironmentView;
+typedef struct GutEnvironmentCotangent {
+    const float* d_plane_grad;      /* [H,W,3], or NULL */
+    const float* d_rgba;            /* [H,W,4], or NULL; with d_rgba_grad */
+    const float* d_rgba_grad;       /* [H,W,4], or NULL */
+} GutEnvironmentCotangent;
+int gut_environment_sample(void* stream, const GutEnvironmentView* view, const float* d_texels, int32_t resolution, float* d_plane_out);
+size_t gut_environment_workspace_bytes(int32_t resolution);
+int gut_environment_backward(void* stream, const GutEnvironmentView* view, const GutEnvironmentCotangent* cotangent, int32_t resolution,
+                             void* d_workspace, float* d_texel_grad);
+int gut_environment_rotation(const GutCamera* camera, float* rotation9);
+
 const char* gut_last_error(void);
 int gut_abi_version(void);
 
