@@ -59,7 +59,7 @@ def build_diagnostic(out, defines, verbose=False):
 def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ_DIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "gut_internal.h"), os.path.join(CSRC, "gut_camera.h"), os.path.join(CSRC, "gut_render_common.h"), os.path.join(CSRC, "gut_render_diag.h"),
+    headers = [os.path.join(CSRC, "gut_internal.h"), os.path.join(CSRC, "gut_camera.h"), os.path.join(CSRC, "gut_rows.h"), os.path.join(CSRC, "gut_render_common.h"), os.path.join(CSRC, "gut_render_diag.h"),
                os.path.join(CSRC, "gut_render.hip"),
                os.path.join(HERE, "..", "include", "gut_hip.h")]
     objs = []

@@ -13,6 +13,7 @@
 // sums the partials in a fixed order.  The grid depends on N alone, so the six numbers are a pure function of the rows.
 // gut_trace_bwd_pose launches a CONSUMING form of k_pose_partials: the same numbers, and the rows it read are left zero.
 #include "gut_internal.h"
+#include "gut_rows.h"
 
 namespace gut {
 
@@ -44,8 +45,7 @@ __global__ __launch_bounds__(kBlock) void k_pose_partials(uint32_t n, const uint
         const float4 g0 = grad16[4 * i + 0];   // d pos3, d density
         const float4 g1 = grad16[4 * i + 1];   // d quat wxyz
         if constexpr (kRows == kPoseConsumeStore) {
-            const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-            grad16[4 * i + 0] = zero; grad16[4 * i + 1] = zero; grad16[4 * i + 2] = zero; grad16[4 * i + 3] = zero;
+            clear_gradient_row(grad16, i);
         } else if constexpr (kRows == kPoseConsumeTest) {
             const float4 g2 = grad16[4 * i + 2], g3 = grad16[4 * i + 3];   // d scale3 and the colour slots: not summed, zeroed
             const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);

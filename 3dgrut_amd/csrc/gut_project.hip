@@ -13,6 +13,7 @@
 // The camera projection itself (sensor-space point -> pixel) lives in gut_camera.h, shared with
 // gut_fuse.hip; the shutter, the sigma points and everything per Gaussian are here.
 #include "gut_camera.h"
+#include "gut_rows.h"
 
 namespace gut {
 
@@ -137,35 +138,6 @@ __device__ __forceinline__ int project_world(const ViewParams& v, float wx, floa
         valid = project_camera<kVariant>(v, cx, cy, cz, tol, ox, oy);
     }
     return valid;
-}
-
-// real SH basis up to degree 3 (gaussianParticles.cuh:57-96)
-__device__ __forceinline__ void sh_basis(int deg, float x, float y, float z, float Y[16]) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) Y[i] = 0.0f;
-    Y[0] = 0.28209479177387814f;
-    if (deg > 0) {
-        Y[1] = -0.4886025119029199f * y;
-        Y[2] = 0.4886025119029199f * z;
-        Y[3] = -0.4886025119029199f * x;
-        if (deg > 1) {
-            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            Y[4] = 1.0925484305920792f * xy;
-            Y[5] = -1.0925484305920792f * yz;
-            Y[6] = 0.31539156525252005f * (2.0f * zz - xx - yy);
-            Y[7] = -1.0925484305920792f * xz;
-            Y[8] = 0.5462742152960396f * (xx - yy);
-            if (deg > 2) {
-                Y[9] = -0.5900435899266435f * y * (3.0f * xx - yy);
-                Y[10] = 2.890611442640554f * xy * z;
-                Y[11] = -0.4570457994644658f * y * (4.0f * zz - xx - yy);
-                Y[12] = 0.3731763325901154f * z * (2.0f * zz - 3.0f * xx - 3.0f * yy);
-                Y[13] = -0.4570457994644658f * x * (4.0f * zz - xx - yy);
-                Y[14] = 1.445305721320277f * z * (xx - yy);
-                Y[15] = -0.5900435899266435f * x * (xx - 3.0f * yy);
-            }
-        }
-    }
 }
 
 __device__ __forceinline__ int clamp_tile(float v, int grid) {
@@ -967,13 +939,12 @@ __global__ __launch_bounds__(kBlock) void k_tile_ranges(uint32_t m, const uint64
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K8: per-Gaussian epilogue of the backward.  Reads the 64-byte gradient row K7 accumulated
-// (pos3, density, quat4, scale3, dRGB3, pad2), writes the [N,12] density gradient and the [N,48] SH
-// gradient in full (zeros for Gaussians that touched no tile), so the caller never zero-fills them.
+// K8: per-Gaussian epilogue of the backward.  Consumes the 64-byte gradient row K7 accumulated (gut_rows.h), writes the
+// [N,12] density gradient and the [N,48] SH gradient in full (zeros for Gaussians that touched no tile), so the caller
+// never zero-fills them.
 // ---------------------------------------------------------------------------------------------------
-// kRawGrads: additionally chain d(position, density, quaternion, scale) through the model's activations
-// (sigmoid, normalise, exp — threedgrut/model/model.py:74-93) so that the rows can be fed to the optimiser as
-// gradients of the RAW parameters; |quat| is read from the pad column written by k_activate_pack.
+// kRawGrads: additionally chain d(position, density, quaternion, scale) through the model's activations (chain_to_raw),
+// so that the rows can be fed to the optimiser as gradients of the RAW parameters.
 // kSplitSH (with `fields` only): the SH gradient goes out as the model's two tensors, fields.alb [N,3] and fields.spec [N,45]
 // (model.py:68-75) — the wave's 64 x 45 block is transposed through LDS and written with coalesced 16-byte stores.
 template <bool kRawGrads, bool kSplitSH>
@@ -992,27 +963,13 @@ __global__ __launch_bounds__(kBlock) void k_project_backward(ViewParams v, uint3
 #pragma unroll
     for (int k = 0; k < 48; ++k) out[k] = 0.0f;
     if (live && tiles_count[i] != 0) {
-        g0 = grad16[4 * (size_t)i + 0];
-        g1 = grad16[4 * (size_t)i + 1];
-        g2 = grad16[4 * (size_t)i + 2];
-        const float4 g3 = grad16[4 * (size_t)i + 3];
-        // the row is consumed: leave it zero for the next backward (no 64 N-byte clear per step)
-        grad16[4 * (size_t)i + 0] = make_float4(0.f, 0.f, 0.f, 0.f);
-        grad16[4 * (size_t)i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
-        grad16[4 * (size_t)i + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
-        grad16[4 * (size_t)i + 3] = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float dr = g2.w, dg = g3.x, db = g3.y;
-        g2.w = 0.0f;
+        const ConsumedRow row = consume_gradient_row(grad16, feat, i);
         const float4 a = density12[3 * (size_t)i];
         if (kRawGrads) {
-            const float4 qn = density12[3 * (size_t)i + 1];
-            const float4 sc = density12[3 * (size_t)i + 2];
-            g0.w = g0.w * a.w * (1.0f - a.w);                                   // sigmoid'
-            const float dot = g1.x * qn.x + g1.y * qn.y + g1.z * qn.z + g1.w * qn.w;
-            const float inv = 1.0f / sc.w;                                      // 1/|quat_raw|
-            g1 = make_float4((g1.x - qn.x * dot) * inv, (g1.y - qn.y * dot) * inv, (g1.z - qn.z * dot) * inv,
-                             (g1.w - qn.w * dot) * inv);                        // normalise'
-            g2.x *= sc.x; g2.y *= sc.y; g2.z *= sc.z;                           // exp'
+            const Row12 raw = chain_to_raw(row.g0, row.g1, row.g2, a.w, density12[3 * (size_t)i + 1], density12[3 * (size_t)i + 2]);
+            g0 = raw.a; g1 = raw.q; g2 = raw.s;
+        } else {
+            g0 = row.g0; g1 = row.g1; g2 = row.g2;
         }
         const float rx = a.x - v.s2w.t[0], ry = a.y - v.s2w.t[1], rz = a.z - v.s2w.t[2];
         const float dist = sqrtf(rx * rx + ry * ry + rz * rz);
@@ -1020,15 +977,12 @@ __global__ __launch_bounds__(kBlock) void k_project_backward(ViewParams v, uint3
         float Y[16];
         sh_basis(sh_degree, rx * inv_dist, ry * inv_dist, rz * inv_dist, Y);
         const int ncoef = (sh_degree + 1) * (sh_degree + 1);
-        const float m0 = feat[3 * (size_t)i + 0] > 0.0f ? dr : 0.0f;
-        const float m1 = feat[3 * (size_t)i + 1] > 0.0f ? dg : 0.0f;
-        const float m2 = feat[3 * (size_t)i + 2] > 0.0f ? db : 0.0f;
 #pragma unroll
         for (int k = 0; k < 16; ++k)
             if (k < ncoef) {
-                out[3 * k + 0] = Y[k] * m0;
-                out[3 * k + 1] = Y[k] * m1;
-                out[3 * k + 2] = Y[k] * m2;
+                out[3 * k + 0] = Y[k] * row.r;
+                out[3 * k + 1] = Y[k] * row.g;
+                out[3 * k + 2] = Y[k] * row.b;
             }
     }
     if (live) {
@@ -1088,9 +1042,10 @@ __global__ __launch_bounds__(kBlock) void k_pack_fields(uint32_t n, const float*
                                                        float4* __restrict__ density12) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    density12[3 * (size_t)i + 0] = make_float4(pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2], dns[i]);
-    density12[3 * (size_t)i + 1] = rot[i];
-    density12[3 * (size_t)i + 2] = make_float4(scl[3 * (size_t)i], scl[3 * (size_t)i + 1], scl[3 * (size_t)i + 2], 0.0f);
+    const Row12 row = load_field_row(pos, dns, rot, scl, i);
+    density12[3 * (size_t)i + 0] = row.a;
+    density12[3 * (size_t)i + 1] = row.q;
+    density12[3 * (size_t)i + 2] = row.s;
 }
 
 // K8c: compact per-Gaussian epilogue for the fused optimiser / compact data-parallel exchange.  Writes the [N,12]
@@ -1108,27 +1063,11 @@ __global__ __launch_bounds__(kBlock) void k_project_backward_compact(uint32_t n,
     float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0, g2 = g0;
     float m0 = 0.f, m1 = 0.f, m2 = 0.f;
     if (tiles_count[i] != 0) {
-        g0 = grad16[4 * (size_t)i + 0];
-        g1 = grad16[4 * (size_t)i + 1];
-        g2 = grad16[4 * (size_t)i + 2];
-        const float4 g3 = grad16[4 * (size_t)i + 3];
-        // the row is consumed: leave it zero for the next backward (no 64 N-byte clear per step)
-        grad16[4 * (size_t)i + 0] = make_float4(0.f, 0.f, 0.f, 0.f);
-        grad16[4 * (size_t)i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
-        grad16[4 * (size_t)i + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
-        grad16[4 * (size_t)i + 3] = make_float4(0.f, 0.f, 0.f, 0.f);
-        m0 = feat[3 * (size_t)i + 0] > 0.0f ? g2.w : 0.0f;
-        m1 = feat[3 * (size_t)i + 1] > 0.0f ? g3.x : 0.0f;
-        m2 = feat[3 * (size_t)i + 2] > 0.0f ? g3.y : 0.0f;
-        g2.w = 0.0f;
+        const ConsumedRow row = consume_gradient_row(grad16, feat, i);
+        m0 = row.r; m1 = row.g; m2 = row.b;
         const float4 a = density12[3 * (size_t)i];
-        const float4 qn = density12[3 * (size_t)i + 1];
-        const float4 sc = density12[3 * (size_t)i + 2];
-        g0.w = g0.w * a.w * (1.0f - a.w);
-        const float dot = g1.x * qn.x + g1.y * qn.y + g1.z * qn.z + g1.w * qn.w;
-        const float inv = 1.0f / sc.w;
-        g1 = make_float4((g1.x - qn.x * dot) * inv, (g1.y - qn.y * dot) * inv, (g1.z - qn.z * dot) * inv, (g1.w - qn.w * dot) * inv);
-        g2.x *= sc.x; g2.y *= sc.y; g2.z *= sc.z;
+        const Row12 raw = chain_to_raw(row.g0, row.g1, row.g2, a.w, density12[3 * (size_t)i + 1], density12[3 * (size_t)i + 2]);
+        g0 = raw.a; g1 = raw.q; g2 = raw.s;
     }
     raw_grad12[3 * (size_t)i + 0] = g0;
     raw_grad12[3 * (size_t)i + 1] = g1;

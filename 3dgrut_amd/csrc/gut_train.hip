@@ -9,31 +9,9 @@
 #include <type_traits>
 
 #include "gut_internal.h"
+#include "gut_rows.h"
 
 namespace gut {
-
-// raw row: pos3 | density logit | quat4 (unnormalised) | log-scale3 | unused
-// act row: pos3 | sigmoid       | quat4 / |quat|       | exp3       | |quat|   (the norm rides in the pad column so
-//          that the backward epilogue can chain through the normalisation without re-reading the raw row)
-// (the three float4 of the row depend on one raw float4 each, plus the quaternion's norm for the last)
-__device__ __forceinline__ float4 activate_position_density(const float4& a) {
-    return make_float4(a.x, a.y, a.z, 1.0f / (1.0f + expf(-a.w)));
-}
-__device__ __forceinline__ float4 activate_quaternion(const float4& q, float* clamped_norm) {
-    const float nrm = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-    const float inv = 1.0f / fmaxf(nrm, 1e-12f);  // torch.nn.functional.normalize eps
-    *clamped_norm = fmaxf(nrm, 1e-12f);
-    return make_float4(q.x * inv, q.y * inv, q.z * inv, q.w * inv);
-}
-__device__ __forceinline__ float4 activate_scale(const float4& s, float clamped_norm) {
-    return make_float4(expf(s.x), expf(s.y), expf(s.z), clamped_norm);
-}
-__device__ __forceinline__ void activate_row(const float4& a, const float4& q, const float4& s, float4* __restrict__ act_row) {
-    float nrm;
-    act_row[0] = activate_position_density(a);
-    act_row[1] = activate_quaternion(q, &nrm);
-    act_row[2] = activate_scale(s, nrm);
-}
 
 __global__ __launch_bounds__(kBlock) void k_activate_pack(uint32_t n, const float4* __restrict__ raw, float4* __restrict__ act) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -43,15 +21,14 @@ __global__ __launch_bounds__(kBlock) void k_activate_pack(uint32_t n, const floa
 
 // k_pack_activate_fields: the model's PRE-ACTIVATION tensors (positions [N,3], density logit [N,1], un-normalised quaternion [N,4],
 // log-scale [N,3]; threedgrut/model/model.py:74-93 with base_gs.yaml's sigmoid / normalize / exp) -> the activated [N,12] rows the
-// renderer reads, |quat| in the pad column for the backward's chain rule: the model's three activation kernels and the tracer's
-// torch.cat as one coalesced pass (gut_trace_raw_model_fields)
+// renderer reads: the model's three activation kernels and the tracer's torch.cat as one coalesced pass (gut_trace_raw_model_fields)
 __global__ __launch_bounds__(kBlock) void k_pack_activate_fields(uint32_t n, const float* __restrict__ pos, const float* __restrict__ dns,
                                                                 const float4* __restrict__ rot, const float* __restrict__ scl,
                                                                 float4* __restrict__ act) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    activate_row(make_float4(pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2], dns[i]), rot[i],
-                 make_float4(scl[3 * (size_t)i], scl[3 * (size_t)i + 1], scl[3 * (size_t)i + 2], 0.0f), act + 3 * (size_t)i);
+    const Row12 raw = load_field_row(pos, dns, rot, scl, i);
+    activate_row(raw.a, raw.q, raw.s, act + 3 * (size_t)i);
 }
 
 struct AdamParams {
@@ -279,28 +256,6 @@ __global__ __launch_bounds__(kBlock) void k_position_gradient_statistics(uint32_
                                 pos[(size_t)i * pos_stride + 2], cam, accum + i, denom + i);
 }
 
-__device__ __forceinline__ void sh_basis_fast(int deg, float x, float y, float z, float Y[16]) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) Y[i] = 0.0f;
-    Y[0] = 0.28209479177387814f;
-    if (deg > 0) {
-        Y[1] = -0.4886025119029199f * y; Y[2] = 0.4886025119029199f * z; Y[3] = -0.4886025119029199f * x;
-        if (deg > 1) {
-            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            Y[4] = 1.0925484305920792f * xy; Y[5] = -1.0925484305920792f * yz;
-            Y[6] = 0.31539156525252005f * (2.0f * zz - xx - yy); Y[7] = -1.0925484305920792f * xz;
-            Y[8] = 0.5462742152960396f * (xx - yy);
-            if (deg > 2) {
-                Y[9] = -0.5900435899266435f * y * (3.0f * xx - yy); Y[10] = 2.890611442640554f * xy * z;
-                Y[11] = -0.4570457994644658f * y * (4.0f * zz - xx - yy);
-                Y[12] = 0.3731763325901154f * z * (2.0f * zz - 3.0f * xx - 3.0f * yy);
-                Y[13] = -0.4570457994644658f * x * (4.0f * zz - xx - yy); Y[14] = 1.445305721320277f * z * (xx - yy);
-                Y[15] = -0.5900435899266435f * x * (xx - 3.0f * yy);
-            }
-        }
-    }
-}
-
 // sqrt(x), x >= 0, from the hardware approximation (v_sqrt_f32, 1 ulp) — moved into its normal range first, because second
 // moments of tiny gradients are denormal and the instruction does not take those
 __device__ __forceinline__ float sqrt_approx_pos(float x) {
@@ -377,6 +332,38 @@ __device__ __forceinline__ void adam4_lazy(const LazyAdam& la, const float4& lr,
     GUT_ADAM_LANE(z)
     GUT_ADAM_LANE(w)
 #undef GUT_ADAM_LANE
+}
+// The two halves of a lazy wave's update, written once for the kernels that run it (the side-stream pass, k_sh_adam's lazy branch;
+// the narrow side-stream kernel keeps its own text, which is its register allocation).
+// Raw [N,12] row i: the parameters and the next forward's activated row are written, the moments only read.
+__device__ __forceinline__ void lazy_raw_row(LazyAdam l12, const AdamParams& a12, float4* p12, const float4* m12,
+                                             const float4* v12, float4* act12, size_t i) {
+    float4 a = p12[3 * i + 0], b = p12[3 * i + 1], c = p12[3 * i + 2];
+    adam4_lazy(l12, make_float4(a12.lr[0], a12.lr[1], a12.lr[2], a12.lr[3]), a, m12[3 * i + 0], v12[3 * i + 0]);
+    p12[3 * i + 0] = a;
+    adam4_lazy(l12, make_float4(a12.lr[4], a12.lr[5], a12.lr[6], a12.lr[7]), b, m12[3 * i + 1], v12[3 * i + 1]);
+    p12[3 * i + 1] = b;
+    adam4_lazy(l12, make_float4(a12.lr[8], a12.lr[9], a12.lr[10], a12.lr[11]), c, m12[3 * i + 2], v12[3 * i + 2]);
+    p12[3 * i + 2] = c;
+    if (act12) activate_row(a, b, c, act12 + 3 * i);
+}
+// The wave's contiguous [rows_here, 48] block: the coalesced 16-byte sweep, a float4 of four columns per lane and turn.
+// lr4(col) fetches the learning rates of columns col .. col + 3: from LDS in the side-stream kernel, from the kernel argument in k_sh_adam.
+template <typename Lr4>
+__device__ __forceinline__ void lazy_sweep48(LazyAdam l48, Lr4 lr4, float4* p48, const float4* m48, const float4* v48,
+                                             uint32_t wave_first, uint32_t rows_here, uint32_t lane) {
+    float4* bp = p48 + (size_t)wave_first * 12;
+    const float4* bm = m48 + (size_t)wave_first * 12;
+    const float4* bv = v48 + (size_t)wave_first * 12;
+#pragma unroll 4
+    for (int it = 0; it < 12; ++it) {
+        const uint32_t q = (uint32_t)it * 64u + lane;
+        if (q >= rows_here * 12u) continue;
+        const uint32_t row = q / 12u, col = (q - row * 12u) * 4u;
+        float4 pp = bp[q];
+        adam4_lazy(l48, lr4(col), pp, bm[q], bv[q]);
+        bp[q] = pp;
+    }
 }
 
 // ---- the MCMC regularisers (Regularisation, gut_internal.h) ----
@@ -480,25 +467,10 @@ __global__ __launch_bounds__(kBlock) void k_sh_adam(std::conditional_t<kReg, ShA
                 reg_adam_raw_row(sp.reg, sp.a12, p12, m12, v12, act12, i, &sig, &esum);
             }
         } else if (i < sp.n) {
-            float4 a = p12[3 * (size_t)i + 0], b = p12[3 * (size_t)i + 1], c = p12[3 * (size_t)i + 2];
-            adam4_lazy(l12, make_float4(sp.a12.lr[0], sp.a12.lr[1], sp.a12.lr[2], sp.a12.lr[3]), a, m12[3 * (size_t)i + 0], v12[3 * (size_t)i + 0]);
-            adam4_lazy(l12, make_float4(sp.a12.lr[4], sp.a12.lr[5], sp.a12.lr[6], sp.a12.lr[7]), b, m12[3 * (size_t)i + 1], v12[3 * (size_t)i + 1]);
-            adam4_lazy(l12, make_float4(sp.a12.lr[8], sp.a12.lr[9], sp.a12.lr[10], sp.a12.lr[11]), c, m12[3 * (size_t)i + 2], v12[3 * (size_t)i + 2]);
-            p12[3 * (size_t)i + 0] = a; p12[3 * (size_t)i + 1] = b; p12[3 * (size_t)i + 2] = c;
-            if (act12) activate_row(a, b, c, act12 + 3 * (size_t)i);
+            lazy_raw_row(l12, sp.a12, p12, m12, v12, act12, i);
         }
-        float4* bp = p48 + (size_t)wave_first * 12;
-        const float4* bm = m48 + (size_t)wave_first * 12;
-        const float4* bv = v48 + (size_t)wave_first * 12;
-#pragma unroll 4
-        for (int it = 0; it < 12; ++it) {
-            const uint32_t q = (uint32_t)it * 64u + lane;
-            if (q >= rows_here * 12u) continue;
-            const uint32_t row = q / 12u, col = (q - row * 12u) * 4u;
-            float4 pp = bp[q];
-            adam4_lazy(l48, make_float4(sp.a48.lr[col], sp.a48.lr[col + 1], sp.a48.lr[col + 2], sp.a48.lr[col + 3]), pp, bm[q], bv[q]);
-            bp[q] = pp;
-        }
+        lazy_sweep48(l48, [&](uint32_t col) { return make_float4(sp.a48.lr[col], sp.a48.lr[col + 1], sp.a48.lr[col + 2], sp.a48.lr[col + 3]); },
+                     p48, m48, v48, wave_first, rows_here, lane);
         return;
     }
     float G[48];
@@ -518,28 +490,14 @@ __global__ __launch_bounds__(kBlock) void k_sh_adam(std::conditional_t<kReg, ShA
             if (kScratch) {
                 g0 = make_float4(0.f, 0.f, 0.f, 0.f); g1 = g0; g2 = g0;
                 if (tiles_count[i] != 0) {
-                    g0 = grad12[4 * (size_t)i + 0];
-                    g1 = grad12[4 * (size_t)i + 1];
-                    g2 = grad12[4 * (size_t)i + 2];
-                    const float4 g3 = grad12[4 * (size_t)i + 3];
-                    // the renderer's gradient row is consumed: leave it zero for the next backward
-                    grad12[4 * (size_t)i + 0] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    grad12[4 * (size_t)i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    grad12[4 * (size_t)i + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    grad12[4 * (size_t)i + 3] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    own_r = feat[3 * (size_t)i + 0] > 0.0f ? g2.w : 0.0f;
-                    own_g = feat[3 * (size_t)i + 1] > 0.0f ? g3.x : 0.0f;
-                    own_b = feat[3 * (size_t)i + 2] > 0.0f ? g3.y : 0.0f;
-                    if (sp.stat_accum && (g0.x != 0.0f || g0.y != 0.0f || g0.z != 0.0f))
-                        position_gradient_statistic(g0.x, g0.y, g0.z, px, py, pz, sp.cam, sp.stat_accum + i, sp.stat_denom + i);
+                    const ConsumedRow row = consume_gradient_row(grad12, feat, i);
+                    own_r = row.r; own_g = row.g; own_b = row.b;
+                    if (sp.stat_accum && (row.g0.x != 0.0f || row.g0.y != 0.0f || row.g0.z != 0.0f))
+                        position_gradient_statistic(row.g0.x, row.g0.y, row.g0.z, px, py, pz, sp.cam, sp.stat_accum + i, sp.stat_denom + i);
                     float4 act[3];
                     activate_row(a, b, c, act);
-                    g0.w = g0.w * act[0].w * (1.0f - act[0].w);                      // sigmoid
-                    const float dot = g1.x * act[1].x + g1.y * act[1].y + g1.z * act[1].z + g1.w * act[1].w;
-                    const float inv = 1.0f / act[2].w;                                // 1 / |quat|
-                    g1 = make_float4((g1.x - act[1].x * dot) * inv, (g1.y - act[1].y * dot) * inv, (g1.z - act[1].z * dot) * inv,
-                                     (g1.w - act[1].w * dot) * inv);                  // normalise
-                    g2.x *= act[2].x; g2.y *= act[2].y; g2.z *= act[2].z;             // exp
+                    const Row12 raw = chain_to_raw(row.g0, row.g1, row.g2, act[0].w, act[1], act[2]);
+                    g0 = raw.a; g1 = raw.q; g2 = raw.s;
                 }
             } else {
                 g0 = grad12[3 * (size_t)i + 0]; g1 = grad12[3 * (size_t)i + 1]; g2 = grad12[3 * (size_t)i + 2];
@@ -589,7 +547,7 @@ __global__ __launch_bounds__(kBlock) void k_sh_adam(std::conditional_t<kReg, ShA
                 const float dx = px - sp.cam[3 * vw + 0], dy = py - sp.cam[3 * vw + 1], dz = pz - sp.cam[3 * vw + 2];
                 const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
                 float Y[16];
-                sh_basis_fast(sp.sh_degree, dx * inv, dy * inv, dz * inv, Y);
+                sh_basis(sp.sh_degree, dx * inv, dy * inv, dz * inv, Y);
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
                     G[3 * k + 0] += Y[k] * r;
@@ -694,6 +652,8 @@ __global__ __launch_bounds__(kBlock, 4) void k_adam_rows_without_gradient(AdamPa
             float sig = 0.0f, esum = 0.0f;
             if (mine) reg_adam_raw_row(reg, a12, p12, m12, v12, act12, i, &sig, &esum);
             reg_wave_partials(reg, sig, esum, wave_first >> 6, lane);
+            // (the [N,48] sweep stays written out here: through lazy_sweep48 this instance's schedule changes, and the side-stream
+            //  kernels are tuned to fit beside the compositors — same arithmetic, adam4_lazy)
             float4* bp = p48 + (size_t)wave_first * 12;
             float4* bm = m48 + (size_t)wave_first * 12;
             float4* bv = v48 + (size_t)wave_first * 12;
@@ -718,28 +678,8 @@ __global__ __launch_bounds__(kBlock, 4) void k_adam_rows_without_gradient(AdamPa
         }
         if (kLazy) {   // lazy moment decay: read p, m, v; write p and the activation row
             const LazyAdam l12 = make_lazy_adam(a12, dk), l48 = make_lazy_adam(a48, dk);
-            if (mine) {
-                float4 a = p12[3 * (size_t)i + 0], b = p12[3 * (size_t)i + 1], c = p12[3 * (size_t)i + 2];
-                adam4_lazy(l12, make_float4(a12.lr[0], a12.lr[1], a12.lr[2], a12.lr[3]), a, m12[3 * (size_t)i + 0], v12[3 * (size_t)i + 0]);
-                p12[3 * (size_t)i + 0] = a;
-                adam4_lazy(l12, make_float4(a12.lr[4], a12.lr[5], a12.lr[6], a12.lr[7]), b, m12[3 * (size_t)i + 1], v12[3 * (size_t)i + 1]);
-                p12[3 * (size_t)i + 1] = b;
-                adam4_lazy(l12, make_float4(a12.lr[8], a12.lr[9], a12.lr[10], a12.lr[11]), c, m12[3 * (size_t)i + 2], v12[3 * (size_t)i + 2]);
-                p12[3 * (size_t)i + 2] = c;
-                if (act12) activate_row(a, b, c, act12 + 3 * (size_t)i);
-            }
-            float4* bp = p48 + (size_t)wave_first * 12;
-            const float4* bm = m48 + (size_t)wave_first * 12;
-            const float4* bv = v48 + (size_t)wave_first * 12;
-#pragma unroll 4
-            for (int it = 0; it < 12; ++it) {
-                const uint32_t q = (uint32_t)it * 64u + lane;
-                if (q >= rows_here * 12u) continue;
-                const uint32_t row = q / 12u, col = (q - row * 12u) * 4u;
-                float4 pp = bp[q];
-                adam4_lazy(l48, s_lr48[col >> 2], pp, bm[q], bv[q]);
-                bp[q] = pp;
-            }
+            if (mine) lazy_raw_row(l12, a12, p12, m12, v12, act12, i);
+            lazy_sweep48(l48, [&](uint32_t col) { return s_lr48[col >> 2]; }, p48, m48, v48, wave_first, rows_here, lane);
             continue;
         }
         if (mine) {
@@ -908,14 +848,11 @@ __global__ __launch_bounds__(kBlock) void k_compact_gradient_rows(uint32_t n, co
                                                                  uint32_t* __restrict__ count) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63;
-    float4 g0, g1, g2, g3;
+    GradientRow row;
     bool have = false;
     if (i < n && tiles_count[i] != 0) {
-        g0 = grad16[4 * (size_t)i + 0];
-        g1 = grad16[4 * (size_t)i + 1];
-        g2 = grad16[4 * (size_t)i + 2];
-        g3 = grad16[4 * (size_t)i + 3];
-        have = any_bits(g0) || any_bits(g1) || any_bits(g2) || any_bits(g3);
+        row = load_gradient_row(grad16, i);
+        have = any_bits(row.g0) || any_bits(row.g1) || any_bits(row.g2) || any_bits(row.g3);
     }
     const unsigned long long bal = __ballot(have);
     if (bal == 0ull) return;
@@ -924,20 +861,14 @@ __global__ __launch_bounds__(kBlock) void k_compact_gradient_rows(uint32_t n, co
     base = __shfl(base, 0);
     const uint32_t slot = base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
     if (!have || slot >= capacity) return;  // (capacity is the number of Gaussians: never exceeded)
-    const float m0 = feat[3 * (size_t)i + 0] > 0.0f ? g2.w : 0.0f;
-    const float m1 = feat[3 * (size_t)i + 1] > 0.0f ? g3.x : 0.0f;
-    const float m2 = feat[3 * (size_t)i + 2] > 0.0f ? g3.y : 0.0f;
+    const ConsumedRow c = mask_gradient_row(row, feat, i);
     const float4 a = act12[3 * (size_t)i], qn = act12[3 * (size_t)i + 1], sc = act12[3 * (size_t)i + 2];
-    g0.w = g0.w * a.w * (1.0f - a.w);                                               // sigmoid
-    const float dot = g1.x * qn.x + g1.y * qn.y + g1.z * qn.z + g1.w * qn.w;
-    const float inv = 1.0f / sc.w;                                                  // 1 / |quat| (pad column of the activated row)
-    g1 = make_float4((g1.x - qn.x * dot) * inv, (g1.y - qn.y * dot) * inv, (g1.z - qn.z * dot) * inv, (g1.w - qn.w * dot) * inv);
-    records[4 * (size_t)slot + 0] = g0;
-    records[4 * (size_t)slot + 1] = g1;
-    records[4 * (size_t)slot + 2] = make_float4(g2.x * sc.x, g2.y * sc.y, g2.z * sc.z, __uint_as_float(i));   // exp
-    records[4 * (size_t)slot + 3] = make_float4(m0, m1, m2, 0.0f);
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    grad16[4 * (size_t)i + 0] = z; grad16[4 * (size_t)i + 1] = z; grad16[4 * (size_t)i + 2] = z; grad16[4 * (size_t)i + 3] = z;
+    const Row12 raw = chain_to_raw(c.g0, c.g1, c.g2, a.w, qn, sc);
+    records[4 * (size_t)slot + 0] = raw.a;
+    records[4 * (size_t)slot + 1] = raw.q;
+    records[4 * (size_t)slot + 2] = make_float4(raw.s.x, raw.s.y, raw.s.z, __uint_as_float(i));
+    records[4 * (size_t)slot + 3] = make_float4(c.r, c.g, c.b, 0.0f);
+    clear_gradient_row(grad16, i);
 }
 
 // d_count != nullptr: the number of valid records is read on the device (at most `count` of them are taken): the data-parallel

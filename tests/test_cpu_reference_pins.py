@@ -292,11 +292,11 @@ def test_qvec_to_rotation_and_scene_extent(G):
 
 
 def test_sh_constants_against_the_reference(G):
-    """threedgrut/utils/render.py: the constants compiled into the kernels / oracle (gut_project.hip, gut_oracle.c)."""
+    """threedgrut/utils/render.py: the constants compiled into the kernels / oracle (sh_basis in gut_rows.h, gut_oracle.c)."""
     prt = importlib.import_module("oracle.per_ray_torch")
     assert prt._C0 == float(G["sh_C0"]) and prt._C1 == float(G["sh_C1"])
     assert np.array_equal(np.array(prt._C2), G["sh_C2"]) and np.array_equal(np.array(prt._C3), G["sh_C3"])
-    src = open(os.path.join(os.path.dirname(GOLD), "..", "3dgrut_amd", "csrc", "gut_project.hip")).read()
+    src = open(os.path.join(os.path.dirname(GOLD), "..", "3dgrut_amd", "csrc", "gut_rows.h")).read()
     osrc = open(os.path.join(os.path.dirname(GOLD), "..", "oracle", "gut_oracle.c")).read()
     for c in [float(G["sh_C0"]), float(G["sh_C1"])] + [abs(float(v)) for v in G["sh_C2"]] + [abs(float(v)) for v in G["sh_C3"]]:
         assert repr(c) + "f" in src and repr(c) + "f" in osrc, c
