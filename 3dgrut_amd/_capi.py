@@ -121,6 +121,16 @@ class GutEnvironmentCotangent(C.Structure):
     _fields_ = [("d_plane_grad", C.c_void_p), ("d_rgba", C.c_void_p), ("d_rgba_grad", C.c_void_p)]
 
 
+BILATERAL_MAX_DIM = 256   # gut_hip.h, GUT_BILATERAL_MAX_DIM
+BILATERAL_TABLE = 1024    # gut_hip.h, GUT_BILATERAL_TABLE: 64-bit sums a 16x16 pixel tile of the adjoint holds in LDS
+BILATERAL_TILE = 16
+
+
+class GutBilateralGrid(C.Structure):
+    """One view's bilateral grid (gut_hip.h): d_grid [12, levels, rows, columns] float32 on the device."""
+    _fields_ = [("d_grid", C.c_void_p), ("levels", C.c_int32), ("rows", C.c_int32), ("columns", C.c_int32)]
+
+
 EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_trace_bwd", "gut_collect_times",
            "gut_get_stats", "gut_debug_buffer", "gut_debug_copy", "gut_kernel_times", "gut_kernel_times_mean", "gut_last_error", "gut_abi_version",
            "gut_ssim_workspace_bytes", "gut_ssim_forward", "gut_ssim_backward",
@@ -137,7 +147,9 @@ EXPORTS = ("gut_default_config", "gut_create", "gut_destroy", "gut_trace", "gut_
            "gut_image_metrics_cc_workspace_bytes", "gut_image_metrics_cc", "gut_photometric_loss_run", "gut_trace_bwd_pose",
            "gut_trace_contribution", "gut_trace_contribution_weighted", "gut_pixel_error", "gut_trace_attributes",
            "gut_trace_attributes_bwd", "gut_trace_surface", "gut_tsdf_integrate", "gut_surface_nets_count", "gut_surface_nets_emit",
-           "gut_environment_sample", "gut_environment_workspace_bytes", "gut_environment_backward", "gut_environment_rotation")
+           "gut_environment_sample", "gut_environment_workspace_bytes", "gut_environment_backward", "gut_environment_rotation",
+           "gut_bilateral_workspace_bytes", "gut_bilateral_slice", "gut_bilateral_backward", "gut_bilateral_backward_image",
+           "gut_bilateral_adam_step")
 
 _lib = None
 
@@ -192,6 +204,13 @@ def load():
     lib.gut_environment_workspace_bytes.restype = C.c_size_t
     lib.gut_environment_backward.argtypes = [vp, env_p, C.POINTER(GutEnvironmentCotangent), i32, vp, vp]
     lib.gut_environment_rotation.argtypes = [C.POINTER(GutCamera), C.POINTER(C.c_float)]
+    bil_p = C.POINTER(GutBilateralGrid)
+    lib.gut_bilateral_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.gut_bilateral_workspace_bytes.restype = C.c_size_t
+    lib.gut_bilateral_slice.argtypes = [vp, i32, i32, vp, vp, C.c_float, bil_p, vp]
+    lib.gut_bilateral_backward.argtypes = [vp, i32, i32, vp, vp, C.c_float, bil_p, vp, C.c_float, vp, vp, vp]
+    lib.gut_bilateral_backward_image.argtypes = [vp, i32, i32, vp, vp, C.c_float, bil_p, vp, vp]
+    lib.gut_bilateral_adam_step.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float]
     lib.gut_pixel_error.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, vp, vp]
     lib.gut_mcmc_perturb.argtypes = [vp, u32, f_p, f_p, C.c_float, C.c_uint64, C.c_uint64, f_p]
     lib.gut_collect_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]

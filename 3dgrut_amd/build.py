@@ -28,6 +28,7 @@ UNITS = [
     ("gut_pose.hip", ["-ffp-contract=off"]),
     ("gut_fuse.hip", ["-ffp-contract=off"]),   # a voxel's pixel is an integer decision of K1's projection arithmetic
     ("gut_environment.hip", ["-ffp-contract=off"]),   # a pixel's face and texels are integer decisions; the plane is bit-exact
+    ("gut_bilateral.hip", ["-ffp-contract=off"]),   # slice, adjoint, TV term and step are bit-exact against a float32 restatement
     ("gut_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 
@@ -59,7 +60,7 @@ def build_diagnostic(out, defines, verbose=False):
 def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ_DIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "gut_internal.h"), os.path.join(CSRC, "gut_camera.h"), os.path.join(CSRC, "gut_rows.h"), os.path.join(CSRC, "gut_render_common.h"), os.path.join(CSRC, "gut_render_diag.h"),
+    headers = [os.path.join(CSRC, "gut_internal.h"), os.path.join(CSRC, "gut_camera.h"), os.path.join(CSRC, "gut_rows.h"), os.path.join(CSRC, "gut_render_common.h"), os.path.join(CSRC, "gut_render_diag.h"), os.path.join(CSRC, "gut_fixed.h"),
                os.path.join(CSRC, "gut_render.hip"),
                os.path.join(HERE, "..", "include", "gut_hip.h")]
     objs = []

@@ -1538,6 +1538,102 @@ int gut_environment_rotation(const GutCamera* camera, float* rotation9) {
     return 0;
 }
 
+// ---- per-view bilateral grids (gut_bilateral.hip): handle-free; everything is checked here, before anything is queued ----
+namespace {
+
+bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+int build_bilateral_view(const char* who, int32_t height, int32_t width, const float* d_rgba, const float* d_background, float background,
+                         const GutBilateralGrid* grid, gut::BilView* v) {
+    if (!grid) return fail("%s: null grid", who);
+    if (!grid->d_grid) return fail("%s: null d_grid", who);
+    if (!d_rgba) return fail("%s: null d_rgba", who);
+    const int32_t dims[3] = {grid->levels, grid->rows, grid->columns};
+    for (int32_t d : dims)
+        if (d < 1 || d > GUT_BILATERAL_MAX_DIM)
+            return fail("%s: grid dimensions must be 1 .. %d, got %d x %d x %d (levels, rows, columns)", who, GUT_BILATERAL_MAX_DIM,
+                        grid->levels, grid->rows, grid->columns);
+    if (height < 1 || width < 1) return fail("%s: an empty image, %d x %d", who, height, width);
+    if ((uint64_t)height * (uint64_t)width > (1ull << 30)) return fail("%s: %d x %d exceeds 2^30 pixels", who, height, width);
+    if (misaligned16(d_rgba)) return fail("%s: d_rgba is not 16-byte aligned", who);
+    v->rgba = d_rgba;
+    v->background_plane = d_background;
+    v->background = background;
+    v->grid = grid->d_grid;
+    v->levels = grid->levels;
+    v->rows = grid->rows;
+    v->columns = grid->columns;
+    v->height = height;
+    v->width = width;
+    v->scale_x = width > 1 ? (float)(grid->columns - 1) / (float)(width - 1) : 0.0f;
+    v->scale_y = height > 1 ? (float)(grid->rows - 1) / (float)(height - 1) : 0.0f;
+    return 0;
+}
+
+}  // namespace
+
+size_t gut_bilateral_workspace_bytes(int32_t levels, int32_t rows, int32_t columns) {
+    const int32_t dims[3] = {levels, rows, columns};
+    for (int32_t d : dims)
+        if (d < 1 || d > GUT_BILATERAL_MAX_DIM) return 0;
+    return gut::bilateral_workspace_bytes(levels, rows, columns);
+}
+
+int gut_bilateral_slice(void* stream_, int32_t height, int32_t width, const float* d_rgba, const float* d_background, float background,
+                        const GutBilateralGrid* grid, float* d_rgba_out) {
+    gut::BilView v;
+    if (int rc = build_bilateral_view("gut_bilateral_slice", height, width, d_rgba, d_background, background, grid, &v)) return rc;
+    if (!d_rgba_out) return fail("gut_bilateral_slice: null d_rgba_out");
+    if (misaligned16(d_rgba_out)) return fail("gut_bilateral_slice: d_rgba_out is not 16-byte aligned");
+    gut::launch_bilateral_slice(static_cast<hipStream_t>(stream_), v, d_rgba_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int gut_bilateral_backward(void* stream_, int32_t height, int32_t width, const float* d_rgba, const float* d_background, float background,
+                           const GutBilateralGrid* grid, const float* d_rgba_out_grad, float lambda_tv, void* d_workspace,
+                           float* d_rgba_grad, float* d_grid_grad) {
+    gut::BilView v;
+    if (int rc = build_bilateral_view("gut_bilateral_backward", height, width, d_rgba, d_background, background, grid, &v)) return rc;
+    if (!d_rgba_out_grad || !d_workspace || !d_rgba_grad || !d_grid_grad)
+        return fail("gut_bilateral_backward: null d_rgba_out_grad, d_workspace, d_rgba_grad or d_grid_grad");
+    if (!std::isfinite(lambda_tv)) return fail("gut_bilateral_backward: lambda_tv must be finite");
+    if (misaligned16(d_rgba_out_grad) || misaligned16(d_rgba_grad))
+        return fail("gut_bilateral_backward: d_rgba_out_grad or d_rgba_grad is not 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_workspace) & 7u) != 0) return fail("gut_bilateral_backward: d_workspace is not 8-byte aligned");
+    // 2 / n_axis, n_axis = 12 times the adjacent pairs along the axis; unused for an axis of length 1
+    const int64_t L = v.levels, Gh = v.rows, Gw = v.columns;
+    const int64_t pairs[3] = {(Gw - 1) * Gh * L, Gw * (Gh - 1) * L, Gw * Gh * (L - 1)};
+    float coeff[3];
+    for (int a = 0; a < 3; ++a) coeff[a] = pairs[a] > 0 ? 2.0f / (float)(12 * pairs[a]) : 0.0f;
+    HIP_TRY(gut::launch_bilateral_backward(static_cast<hipStream_t>(stream_), v, d_rgba_out_grad, lambda_tv, coeff, d_workspace, d_rgba_grad,
+                                           d_grid_grad));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int gut_bilateral_backward_image(void* stream_, int32_t height, int32_t width, const float* d_rgba, const float* d_background,
+                                 float background, const GutBilateralGrid* grid, const float* d_rgba_out_grad, float* d_rgba_grad) {
+    gut::BilView v;
+    if (int rc = build_bilateral_view("gut_bilateral_backward_image", height, width, d_rgba, d_background, background, grid, &v)) return rc;
+    if (!d_rgba_out_grad || !d_rgba_grad) return fail("gut_bilateral_backward_image: null d_rgba_out_grad or d_rgba_grad");
+    if (misaligned16(d_rgba_out_grad) || misaligned16(d_rgba_grad))
+        return fail("gut_bilateral_backward_image: d_rgba_out_grad or d_rgba_grad is not 16-byte aligned");
+    gut::launch_bilateral_backward_image(static_cast<hipStream_t>(stream_), v, d_rgba_out_grad, d_rgba_grad);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int gut_bilateral_adam_step(void* stream_, const float* d_grad, float* d_grid, float* d_m, float* d_v, int32_t* d_count, int64_t n, float lr,
+                            float beta1, float beta2, float eps) {
+    if (!d_grad || !d_grid || !d_m || !d_v || !d_count) return fail("gut_bilateral_adam_step: null pointer argument");
+    const int64_t most = 12ll * GUT_BILATERAL_MAX_DIM * GUT_BILATERAL_MAX_DIM * GUT_BILATERAL_MAX_DIM;
+    if (n < 1 || n > most) return fail("gut_bilateral_adam_step: n must be 1 .. %lld, got %lld", (long long)most, (long long)n);
+    gut::launch_bilateral_adam(static_cast<hipStream_t>(stream_), d_grad, d_grid, d_m, d_v, d_count, (uint32_t)n, lr, beta1, beta2, eps);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int gut_set_regularisation(gut_handle h, const GutRegularisation* reg) {
     if (!h) return fail("gut_set_regularisation: null handle");
     if (reg && !(reg->density_coeff >= 0.0f && reg->scale_coeff >= 0.0f && reg->density_coeff < INFINITY && reg->scale_coeff < INFINITY))

@@ -10,6 +10,7 @@
 // sampler and the adjoint share ONE copy of the coordinate code (env_taps).  No float atomics anywhere: the sums are integers, so a
 // texel's total does not depend on the order in which workgroups, waves or the two routes (LDS table, direct) deliver it.
 #include "gut_render_common.h"
+#include "gut_fixed.h"   // the fixed-point unit: pow2f_env, finite_or_zero_env, env_scale_exponent
 
 namespace gut {
 
@@ -22,9 +23,6 @@ constexpr int kEnvTile = 16;                            // the scatter's workgro
 constexpr uint32_t kEnvMaxBlocks = 1024;                // grid of the maximum's grid-stride loop
 static_assert((kEnvSlots & (kEnvSlots - 1u)) == 0u && kEnvSlots <= (uint32_t)kBlock, "one flushing thread per slot");
 static_assert(kEnvTile * kEnvTile == kBlock, "one thread per pixel of the tile");
-
-__device__ __forceinline__ float pow2f_env(int s) { return __uint_as_float((uint32_t)(s + 127) << 23); }   // s in -126..126
-__device__ __forceinline__ float finite_or_zero_env(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u ? 0.0f : x; }
 
 // The four taps of a pixel: texel (first of its three channels) and weight, w_ab pairing column a with row b in the order
 // 00, 10, 01, 11.  Returns false for a void pixel: a direction that is zero or not finite.  Steps 1 to 5 of DESIGN.md §20.
@@ -106,17 +104,6 @@ __global__ __launch_bounds__(kBlock) void k_env_max_abs(EnvCotangent c, size_t p
     }
     m = dpp_wave_max_lane63(m);
     if ((threadIdx.x & 63u) == 63u && m > 0.0f) atomicMax(max_bits, __float_as_uint(m));   // non-negative floats order as their bits
-}
-
-// The exponent s of the fixed-point unit 2^-s (DESIGN.md §17's rule with pixels in the place of tiles): the largest finite |c| has
-// the bits max_bits, |c| < 2^e with e read from the exponent field, and s = 40 - e less the bits by which the view has more than
-// 2^22 pixels.  A pixel's four weights sum to 1, so a texel's total stays below 2^62 (+ the roundings).  Clamped so that 2^s and
-// 2^-s are normal floats; a cotangent of zeros takes s = 0.
-__device__ __forceinline__ int env_scale_exponent(uint32_t max_bits, uint64_t pixels) {
-    if (max_bits == 0u) return 0;
-    const int e = max((int)(max_bits >> 23), 1) - 126;
-    const int extra = pixels > (1ull << 22) ? (64 - (int)__clzll((long long)(pixels - 1ull)) - 22) : 0;   // ceil(log2(pixels)) - 22
-    return min(max(40 - e - extra, -126), 126);
 }
 
 template <bool kRgba>

@@ -371,6 +371,25 @@ void launch_environment_sample(hipStream_t s, const EnvView& v, const float* tex
 hipError_t launch_environment_backward(hipStream_t s, const EnvView& v, const EnvCotangent& c, int resolution, void* workspace,
                                        float* texel_grad);
 
+// gut_bilateral.hip: per-view bilateral grids of affine colour transforms, the slice and its adjoint.  The record
+// is checked on the host (gut_api.cpp), which also forms the two scale factors, and travels as a kernel argument.
+struct BilView {
+    const float* rgba;               // [H,W,4]
+    const float* background_plane;   // [H,W,3], or null: then `background`
+    float background;
+    const float* grid;               // [12, L, Gh, Gw]
+    int32_t levels, rows, columns;
+    int32_t height, width;
+    float scale_x, scale_y;          // (Gw - 1) / (W - 1) and (Gh - 1) / (H - 1) as float32 divisions; 0 for W == 1 / H == 1
+};
+size_t bilateral_workspace_bytes(int levels, int rows, int columns);
+void launch_bilateral_slice(hipStream_t s, const BilView& v, float* rgba_out);
+hipError_t launch_bilateral_backward(hipStream_t s, const BilView& v, const float* out_grad, float lambda_tv, const float (&tv_coeff)[3],
+                                     void* workspace, float* rgba_grad, float* grid_grad);
+void launch_bilateral_backward_image(hipStream_t s, const BilView& v, const float* out_grad, float* rgba_grad);
+void launch_bilateral_adam(hipStream_t s, const float* grad, float* grid, float* m1, float* m2, int32_t* count, uint32_t n, float lr,
+                           float beta1, float beta2, float eps);
+
 // scan / sort (rocPRIM device-wide primitives; temp storage owned by the caller)
 size_t scan_temp_bytes(uint32_t n);
 hipError_t run_scan(hipStream_t s, void* temp, size_t temp_bytes, const uint32_t* in, uint32_t* out, uint32_t n);

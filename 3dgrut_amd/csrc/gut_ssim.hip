@@ -31,6 +31,7 @@
 #include <utility>
 
 #include "gut_internal.h"
+#include "gut_fixed.h"
 
 namespace gut {
 
@@ -505,13 +506,7 @@ __global__ __launch_bounds__(64) void k_exposure_adam(const float* __restrict__ 
     __syncthreads();
     if (k == 0) count[0] = t;
     if (k >= 12) return;
-    const float g = grad12[k];
-    const float m = beta1 * m12[k] + (1.0f - beta1) * g;
-    const float v = beta2 * v12[k] + ((1.0f - beta2) * g) * g;
-    m12[k] = m;
-    v12[k] = v;
-    const float c1 = (float)(1.0 - pow((double)beta1, (double)t)), c2 = (float)(1.0 - pow((double)beta2, (double)t));
-    e12[k] = e12[k] - (lr * (m / c1)) / (sqrtf(v / c2) + eps);
+    view_adam_element(grad12[k], e12 + k, m12 + k, v12 + k, t, lr, beta1, beta2, eps);   // gut_fixed.h: shared with the bilateral grids
 }
 
 // Colour-corrected metrics (gut_image_metrics_cc), pass 1: the 22 moments of the ridge-regularised affine fit of the

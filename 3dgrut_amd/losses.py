@@ -197,6 +197,56 @@ def apply_exposure(pred_rgb, exposure):
     return pred_rgb @ E[:, :3].transpose(0, 1) + E[:, 3]
 
 
+def bilateral_slice(comp, grid):
+    """The bilateral slice of a view, the definition in plain differentiable torch: comp [H,W,3] or [1,H,W,3] (the
+    image composited over its background), grid [12,L,Gh,Gw] of comp's dtype and device -> the image of comp's shape, every pixel
+    through the 3x4 transform the grid holds at (x, y, luminance), trilinear with corners aligned.  Differentiable in both; the
+    guidance is differentiated (inside 0 < g < 1: at a level boundary the derivative of the piece the pixel lies in, outside 0)."""
+    if comp.shape[-1] != 3 or comp.dim() not in (3, 4) or (comp.dim() == 4 and comp.shape[0] != 1):
+        raise ValueError(f"bilateral_slice: comp must be [H,W,3] or [1,H,W,3], got {tuple(comp.shape)}")
+    if grid.dim() != 4 or grid.shape[0] != 12:
+        raise ValueError(f"bilateral_slice: grid must be [12,L,Gh,Gw], got {tuple(grid.shape)}")
+    H, W = int(comp.shape[-3]), int(comp.shape[-2])
+    L, Gh, Gw = (int(n) for n in grid.shape[1:])
+    c = comp.reshape(H, W, 3)
+    dt, dev = c.dtype, c.device
+    g = (0.299 * c[..., 0] + 0.587 * c[..., 1]) + 0.114 * c[..., 2]
+    inside = (g > 0) & (g < 1)
+    gc = torch.where(inside, g, torch.nan_to_num(g.detach(), nan=0.0).clamp(0.0, 1.0))   # the gradient passes inside only
+
+    def axis(s, n):
+        i0 = torch.floor(s.detach())
+        f = s - i0
+        i0 = i0.long().clamp(0, n - 1)
+        return f, i0, (i0 + 1).clamp(max=n - 1)
+
+    sx = torch.arange(W, dtype=dt, device=dev) * ((Gw - 1) / (W - 1) if W > 1 else 0.0)
+    sy = torch.arange(H, dtype=dt, device=dev) * ((Gh - 1) / (H - 1) if H > 1 else 0.0)
+    fx, c0, c1 = axis(sx[None, :].expand(H, W), Gw)
+    fy, r0, r1 = axis(sy[:, None].expand(H, W), Gh)
+    fz, z0, z1 = axis(gc * (L - 1), L)
+    A = None
+    for z, wz in ((z0, 1 - fz), (z1, fz)):
+        for r, wy in ((r0, 1 - fy), (r1, fy)):
+            for col, wx in ((c0, 1 - fx), (c1, fx)):
+                term = ((wx * wy) * wz)[None] * grid[:, z, r, col]           # [12,H,W]
+                A = term if A is None else A + term
+    A = A.reshape(3, 4, H, W)
+    out = ((A[:, 0] * c[..., 0] + A[:, 1] * c[..., 1]) + A[:, 2] * c[..., 2]) + A[:, 3]   # [3,H,W]
+    return out.permute(1, 2, 0).reshape(comp.shape)
+
+
+def bilateral_total_variation(grid):
+    """TV(G) of DESIGN.md §21 for grid [...,12,L,Gh,Gw]: per axis the mean of the squared differences of adjacent cells (over the
+    pairs and the 12 channels), summed over the axes; an axis of length 1 adds 0.  Differentiable; [...] out."""
+    tv = grid.new_zeros(grid.shape[:-4])
+    for dim in (-1, -2, -3):
+        if grid.shape[dim] > 1:
+            d = grid.narrow(dim, 1, grid.shape[dim] - 1) - grid.narrow(dim, 0, grid.shape[dim] - 1)
+            tv = tv + (d * d).mean(dim=(-4, -3, -2, -1))
+    return tv
+
+
 def photometric_loss(pred_rgb, gt_rgb, lambda_l1=0.8, lambda_ssim=0.2, mask=None, exposure=None):
     """pred/gt [B,H,W,3].  lambda_l1*L1 + lambda_ssim*(1-SSIM)  (configs/base_gs.yaml:111-119, trainer.py:425-449).
     mask [B,H,W,1] (Batch.mask) or None: both images are multiplied by it first, as the reference's get_losses does

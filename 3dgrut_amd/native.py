@@ -146,7 +146,10 @@ class NativeTrainStep:
                  betas=(0.9, 0.999), eps=1e-15, fused_sh_adam=True, rank=0, fused_loss=True, lambda_l1=0.8, lambda_ssim=0.2,
                  dp_chunks=4, dp_chunk_min_rows=1 << 20, fuse_epilogue=True, schedule=None,
                  overlap_optimizer=None, dp_exchange="sparse", dp_side_stream=True, lazy_moments=True, lambda_opacity=0.0,
-                 lambda_scale=0.0, pose_gradient=False, exposure_gradient=False):
+                 lambda_scale=0.0, pose_gradient=False, exposure_gradient=False, bilateral_gradient=False):
+        if bilateral_gradient and world_size > 1:
+            raise ValueError("bilateral_gradient: a bilateral grid belongs to ONE view per step; data-parallel training with bilateral "
+                             "grids is out of scope (world_size must be 1)")
         if exposure_gradient and world_size > 1:
             raise ValueError("exposure_gradient: the exposure belongs to ONE view per step; data-parallel exposure compensation is out of "
                              "scope (world_size must be 1)")
@@ -262,6 +265,14 @@ class NativeTrainStep:
         self._exposure_on = bool(exposure_gradient)
         self._exposure_buffer = torch.zeros(12, dtype=torch.float32, device=dev) if exposure_gradient else None
         self.exposure_gradient = self._exposure_buffer
+        # bilateral_gradient=True: a batch with `.bilateral_grid` (a float32 [12,L,Gh,Gw] device tensor, bilateral.py) is compared
+        # through its slice in BOTH loss branches and every such step leaves d(loss)/dG, the TV term of
+        # `.bilateral_lambda_tv` included, in `self.bilateral_gradient`, a device tensor laid out like the grid, valid after step().
+        # A batch without `.bilateral_grid` trains as without the switch.  False: `.bilateral_grid` is not looked at.
+        self._bilateral_on = bool(bilateral_gradient)
+        self._bilateral_active = bool(bilateral_gradient)
+        self._bilateral_buffer, self._bilateral_ws, self._bilateral_rgba, self._bilateral_rgba_grad = None, None, None, None
+        self.bilateral_gradient = None
         self.resize_workspace()
         self.phase_timing = False   # record HIP events around the phases of step() (bench / profiling)
         self._phase_events = []
@@ -289,6 +300,29 @@ class NativeTrainStep:
                 raise ValueError("enable_exposure_gradient: the stepper was built without exposure_gradient=True")
             return
         self.exposure_gradient = self._exposure_buffer if on else None
+
+    def enable_bilateral_gradient(self, on):
+        """Switch the grid-gradient output of a stepper built with bilateral_gradient=True off and on again between steps (the trainer
+        does outside the grids' window): off, `bilateral_gradient` is None after a step; the batch's grid is still applied, the image
+        gradient passes through the slice's adjoint in one launch (gut_bilateral_backward_image) and nothing is summed for the grid."""
+        if not self._bilateral_on:
+            if on:
+                raise ValueError("enable_bilateral_gradient: the stepper was built without bilateral_gradient=True")
+            return
+        self._bilateral_active = bool(on)
+        if not on:
+            self.bilateral_gradient = None
+
+    def _bilateral_buffers(self, rgba, grid):
+        """The step's buffers for a batch with a grid: rgba' and the image gradient like rgba, the gradient like the grid, the
+        adjoint's workspace."""
+        from .bilateral import workspace_for
+        if self._bilateral_rgba is None or self._bilateral_rgba.shape != rgba.shape:
+            self._bilateral_rgba = torch.empty_like(rgba)
+            self._bilateral_rgba_grad = torch.empty_like(rgba)
+        if self._bilateral_buffer is None or self._bilateral_buffer.shape != grid.shape:
+            self._bilateral_buffer = torch.empty_like(grid)
+        self._bilateral_ws = workspace_for(self._lib, grid, self._bilateral_ws)
 
     @property
     def probe_pending(self):
@@ -720,6 +754,18 @@ class NativeTrainStep:
         # Batch.exposure (ExposureCompensation.begin) or None: the prediction goes through A image + b inside the loss, before the
         # mask; the pred_rgb returned stays the uncompensated render
         exposure = getattr(batch, "exposure", None) if self._exposure_on else None
+        # Batch.bilateral_grid (BilateralGrids.begin) or None: the composited prediction goes through the grid's slice before the loss
+        # (DESIGN.md §21); the pred_rgb returned stays the uncorrected render
+        grid = getattr(batch, "bilateral_grid", None) if self._bilateral_on else None
+        if grid is not None:
+            if exposure is not None:
+                raise ValueError("a bilateral grid contains the global affine: a batch carries `.exposure` or `.bilateral_grid`, not both")
+            if grid.dtype != torch.float32 or grid.device != rgba.device or grid.dim() != 4 or grid.shape[0] != 12 or not grid.is_contiguous():
+                raise ValueError(f"batch.bilateral_grid must be a contiguous float32 [12,L,Gh,Gw] tensor on {rgba.device}, got "
+                                 f"{tuple(grid.shape)} {grid.dtype} on {grid.device}")
+            lambda_tv = float(getattr(batch, "bilateral_lambda_tv", 0.0))
+        elif self._bilateral_on:
+            self.bilateral_gradient = None   # (valid after a step WITH a grid only: not the previous view's)
         if self.fused_loss and m.background_color in ("black", "white", "random") and gt.dtype == torch.float32 and gt.is_contiguous() \
                 and gt.numel() == rgba.shape[0] * rgba.shape[1] * 3:
             # loss value and d(loss)/d(rgba) in two HIP launches plus the per-pixel post-pass (csrc/gut_ssim.hip: gut_photometric_loss_run)
@@ -744,11 +790,27 @@ class NativeTrainStep:
                 bg = _plane_background(m.draw_background(batch.rays_dir), H, W, rgba.device)   # (a view: float32 [H,W,3] already)
             else:
                 bg = 1.0 if m.background_color == "white" else 0.0
-            # (an exposure: one more argument pair, E read on the device from the caller's row, and the entry point of the affine form)
-            self._loss3, rgba_grad = _photometric_loss_call(self._lib, H, W, rgba, gt, bg, self.lambda_l1, self.lambda_ssim,
-                                                            None if mask is None else _plane_mask(mask, H, W, rgba.device), self._loss_ws,
-                                                            None if exposure is None else _exposure12(exposure, rgba.device),
-                                                            None if exposure is None else self.exposure_gradient)
+            if grid is not None:
+                # slice with the step's own background operand, the fused loss on rgba' over 0 (it sees `out` exactly), and the slice's
+                # adjoint from the loss's output into the rgba_grad the backward receives: d loss / d comp in its rgb channels, which
+                # is what env.backward_from_loss reads below
+                from .bilateral import backward_call, backward_image_call, slice_call
+                self._bilateral_buffers(rgba, grid)
+                sliced = slice_call(self._lib, H, W, rgba, bg, grid, self._bilateral_rgba)
+                self._loss3, out_grad = _photometric_loss_call(self._lib, H, W, sliced, gt, 0.0, self.lambda_l1, self.lambda_ssim,
+                                                               None if mask is None else _plane_mask(mask, H, W, rgba.device), self._loss_ws)
+                if self._bilateral_active:
+                    rgba_grad, self.bilateral_gradient = backward_call(self._lib, H, W, rgba, bg, grid, out_grad, lambda_tv, self._bilateral_ws,
+                                                                       self._bilateral_rgba_grad, self._bilateral_buffer)
+                else:   # outside the window: the image gradient alone, one launch; nothing is summed, converted or stepped
+                    rgba_grad = backward_image_call(self._lib, H, W, rgba, bg, grid, out_grad, self._bilateral_rgba_grad)
+                    self.bilateral_gradient = None
+            else:
+                # (an exposure: one more argument pair, E read on the device from the caller's row, and the entry point of the affine form)
+                self._loss3, rgba_grad = _photometric_loss_call(self._lib, H, W, rgba, gt, bg, self.lambda_l1, self.lambda_ssim,
+                                                                None if mask is None else _plane_mask(mask, H, W, rgba.device), self._loss_ws,
+                                                                None if exposure is None else _exposure12(exposure, rgba.device),
+                                                                None if exposure is None else self.exposure_gradient)
             pred_rgb = rgba[..., :3].unsqueeze(0)
             if env is not None:
                 pred_rgb = pred_rgb + bg.unsqueeze(0) * (1.0 - rgba[..., 3:].unsqueeze(0))
@@ -773,8 +835,16 @@ class NativeTrainStep:
             E = None
             if exposure is not None:   # a leaf copy: autograd leaves d(loss)/dE on it, the caller's row is not touched
                 E = _exposure12(exposure, rgba.device).clone().requires_grad_(self.exposure_gradient is not None)
-            loss = photometric_loss(pred_rgb, gt, self.lambda_l1, self.lambda_ssim, mask=mask, exposure=E)
-            loss.backward()  # image-sized autograd only
+            G, compared = None, pred_rgb
+            if grid is not None:   # a leaf copy, as for the exposure; the TV term joins the loss's graph, not its value
+                from .losses import bilateral_slice, bilateral_total_variation
+                G = grid.detach().clone().requires_grad_(self._bilateral_active)
+                compared = bilateral_slice(pred_rgb, G)
+            loss = photometric_loss(compared, gt, self.lambda_l1, self.lambda_ssim, mask=mask, exposure=E)
+            total = loss
+            if G is not None and self._bilateral_active and lambda_tv != 0.0:
+                total = loss + lambda_tv * bilateral_total_variation(G)
+            total.backward()  # image-sized autograd only
         finally:
             if learn_env:   # (the flag is read when the gradient is accumulated: it stays up until the backward has run)
                 m.environment.texels.requires_grad_(False)
@@ -782,6 +852,8 @@ class NativeTrainStep:
             m.environment.step()
         if E is not None and self.exposure_gradient is not None:
             self.exposure_gradient.copy_(E.grad)
+        if G is not None:
+            self.bilateral_gradient = G.grad if self._bilateral_active else None
         return loss, pred_rgb, rgba_leaf.grad
 
     def _act_written(self):

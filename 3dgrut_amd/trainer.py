@@ -37,6 +37,7 @@ them elsewhere (require_walk), the Trainer refuses them on several GPUs (require
                                  [--export-points [--points-level T] [--points-stride S] [--points-voxel V]]
                                  [--export-mesh [--mesh-resolution R] [--mesh-voxel V]]
                                  [--environment [--environment-resolution R] [--environment-lr X]]
+                                 [--bilateral [--bilateral-grid X Y L] [--bilateral-lr X] [--bilateral-tv X]]
 """
 import argparse
 import copy
@@ -50,6 +51,7 @@ import torch
 
 from . import contribution as contribution_mod
 from . import features as features_mod
+from . import bilateral as bilateral_mod
 from . import environment as environment_mod
 from . import exposure as exposure_mod
 from . import losses, pose_align, pose_refine
@@ -154,6 +156,11 @@ def resolve_config(conf):
     # is still composited.  lr, init and resolution are untuned on real captures.
     out["environment"] = _merge(environment_mod.DEFAULTS, out.get("environment"))
     check_environment_config(out)
+    # likewise: a learnt bilateral grid of affine colour transforms per training view (bilateral.py), resolved over
+    # its own defaults (gsplat's published settings, untuned here).  end_iteration -1 = to the end of the run; outside the window
+    # the grids are still applied.
+    out["bilateral"] = _merge(bilateral_mod.DEFAULTS, out.get("bilateral"))
+    check_bilateral_config(out)
     check_evaluation_config(out["evaluation"])
     pose_align.check_config(out["pose_alignment"])
     contribution_mod.check_config(out["compaction"])
@@ -236,6 +243,17 @@ def check_environment_config(conf):
     return conf
 
 
+def check_bilateral_config(conf):
+    """The `bilateral` block of a resolved conf, and what enabled grids refuse: exposure compensation beside them (a grid contains the
+    global affine, and the two are degenerate against each other).  The data-parallel refusal needs the stepper and is the
+    Trainer's."""
+    block = bilateral_mod.check_config(conf["bilateral"])
+    if block["enabled"] and conf["exposure"]["enabled"]:
+        raise ValueError("bilateral: a bilateral grid contains the global affine of exposure.enabled, and the two are degenerate against "
+                         "each other; enable one of them")
+    return conf
+
+
 def check_evaluation_config(block):
     """The resolved `evaluation` block: colour_corrected true or false, ridge finite and > 0."""
     return check_block("evaluation", block, GS_CONFIG["evaluation"], EVALUATION_RULES)
@@ -299,9 +317,10 @@ def _adam_group_template(betas, eps):
     return g
 
 
-def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=None, refiner=None, exposures=None, environment=None):
+def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=None, refiner=None, exposures=None, environment=None,
+                    bilateral=None):
     """The checkpoint dictionary of a NativeTrainStep's state (see the module docstring); refiner: the run's PoseRefiner or None;
-    exposures: its ExposureCompensation or None; environment: its EnvironmentMap or None."""
+    exposures: its ExposureCompensation or None; environment: its EnvironmentMap or None; bilateral: its BilateralGrids or None."""
     from .io_ply import checkpoint_dict
     st = stepper.state_dict()   # moments brought up to date (sync_moments) and cloned
     m = stepper.model
@@ -337,6 +356,8 @@ def make_checkpoint(stepper, conf, global_step, epoch, scene_extent, strategy=No
         extra["native"]["exposure"] = exposures.state_dict()        # tensors only: transforms, moments, visit counts
     if environment is not None:
         extra["native"]["environment"] = environment.state_dict()   # tensors only: texels, Adam's moments and step count
+    if bilateral is not None:
+        extra["native"]["bilateral"] = bilateral.state_dict()       # tensors only: grids, moments, visit counts
     if progressive:
         extra["feature_dim_increase_interval"] = int(prog["increase_frequency"])
         extra["feature_dim_increase_step"] = int(prog["increase_step"])
@@ -409,6 +430,7 @@ class Trainer:
         self.refiner = self._build_refiner(ckpt)
         self.exposure = self._build_exposure(ckpt)
         self.environment_map = self._build_environment(ckpt)
+        self.bilateral = self._build_bilateral(ckpt)
         if ckpt is not None:
             self.global_step = int(ckpt["global_step"])
         for block, _, noun, _ in STAGES:
@@ -454,7 +476,8 @@ class Trainer:
         stepper = NativeTrainStep(model, tracer, scene_extent=self.scene_extent, selective=c["optimizer"]["type"] == "selective_adam",
                                   eps=float(c["optimizer"].get("eps", 1e-15)), schedule=sched,
                                   pose_gradient=bool(c["pose_refinement"]["enabled"]),
-                                  exposure_gradient=bool(c["exposure"]["enabled"]), **losses.loss_weights(c["loss"]))
+                                  exposure_gradient=bool(c["exposure"]["enabled"]),
+                                  bilateral_gradient=bool(c["bilateral"]["enabled"]), **losses.loss_weights(c["loss"]))
         stepper.lr12[0:3] = sched.position_lr
         stepper.lr12[3] = lr["density"]
         stepper.lr12[4:8] = lr["rotation"]
@@ -540,6 +563,42 @@ class Trainer:
             env.load_state_dict(saved)
         self.model.environment = env
         return env
+
+    def _build_bilateral(self, ckpt):
+        """The BilateralGrids of a run with bilateral.enabled (default off; `--bilateral`), else None; their state restored from a
+        resumed checkpoint.  Every training view gets a grid [12, L, Gh, Gw] of affine colour transforms, sliced by
+        pixel position and luminance and applied to the render before the loss: what varies WITHIN a photo — vignetting, local tone
+        mapping, a white balance that differs across the frame — goes into the grid and not into the Gaussians.  Inside
+        [start_iteration, end_iteration) every step leaves d(loss)/dG, the total-variation term included, on the device and a
+        per-view Adam updates the view's grid there; outside, the grid is applied as it is.  Held-out views have no grid and are
+        scored uncorrected: `--cc-metrics` is the number to compare with a run without grids.  Composes with masks, pose
+        refinement, the environment map, every background colour, both strategies and every render variant; refused beside
+        exposure.enabled.  The error criterion of densification scores the uncorrected render.  The grids, moments and visit
+        counts travel in the checkpoint's `native` block as tensors.  grid, lr and lambda_tv are gsplat's published settings,
+        untuned here."""
+        blk = self.conf["bilateral"]
+        if not blk["enabled"]:
+            if ckpt is not None and ckpt.get("native", {}).get("bilateral") is not None:
+                # continuing without them would silently drop the transforms the Gaussians were trained against
+                raise ValueError("bilateral: the checkpoint holds learnt bilateral grids and bilateral.enabled is off; resume with "
+                                 "--bilateral (bilateral.enabled: true), with end_iteration 0 to keep the grids as they are")
+            return None
+        st = self.stepper
+        require_one_gpu(st, "bilateral", "training with bilateral grids")
+        if getattr(st, "enable_bilateral_gradient", None) is None or not getattr(st, "_bilateral_on", True):
+            raise ValueError(f"bilateral: {type(st).__name__} leaves no grid gradient (NativeTrainStep(..., bilateral_gradient=True) does)")
+        grids = bilateral_mod.BilateralGrids(len(self.train_batches), tuple(int(n) for n in blk["grid"]), self.model.raw.device,
+                                             lr=float(blk["lr"]), betas=(float(blk["beta1"]), float(blk["beta2"])), eps=float(blk["eps"]),
+                                             lambda_tv=float(blk["lambda_tv"]), start_iteration=int(blk["start_iteration"]),
+                                             end_iteration=int(blk["end_iteration"]))
+        saved = None if ckpt is None else ckpt["native"].get("bilateral")
+        if saved is not None:
+            grids.load_state_dict(saved)
+        return grids
+
+    def bilateral_grids(self):
+        """[V,12,L,Gh,Gw] float32 host tensor: the training views' current bilateral grids, in train_batches order; None without them."""
+        return None if self.bilateral is None else self.bilateral.grids()
 
     def environment(self):
         """[6,R,R,3] float32 host tensor: the texels of the environment map, None without one."""
@@ -705,7 +764,8 @@ class Trainer:
 
     def checkpoint(self):
         return make_checkpoint(self.stepper, self.conf, self.global_step, self.epoch, self.scene_extent,
-                               self.strategy if self.method == "GSStrategy" else None, self.refiner, self.exposure, self.environment_map)
+                               self.strategy if self.method == "GSStrategy" else None, self.refiner, self.exposure, self.environment_map,
+                               self.bilateral)
 
     def save_checkpoint(self, last=False):
         out = self._out_dir()
@@ -755,6 +815,12 @@ class Trainer:
             if self._out_dir() is not None:
                 os.makedirs(self._out_dir(), exist_ok=True)
                 np.save(os.path.join(self._out_dir(), "environment.npy"), self.environment().numpy())
+        if self.bilateral is not None:
+            sm = self.bilateral.summary()
+            self.stats.update(bilateral_grid=sm["grid"], bilateral_mean_tv=sm["mean_tv"], bilateral_mean_gain=sm["mean_gain"])
+            if self._out_dir() is not None:
+                os.makedirs(self._out_dir(), exist_ok=True)
+                np.save(os.path.join(self._out_dir(), "bilateral_grids.npy"), self.bilateral_grids().numpy())
         return self.stats
 
     def _step_once(self, g):
@@ -766,6 +832,8 @@ class Trainer:
             self.exposure.end(view, self.stepper.exposure_gradient)   # twelve-float Adam on the device: nothing waits
         if self.refiner is not None and self.refiner.active(g):
             self.refiner.end(view, self.stepper.pose_gradient)        # queued on the device: no host synchronisation (V >= 2)
+        if self.bilateral is not None and self.bilateral.active(g):
+            self.bilateral.end(view, self.stepper.bilateral_gradient)   # the view's grid, one launch on the device: nothing waits
         return view
 
     def _train_batch(self, view, g):
@@ -784,6 +852,9 @@ class Trainer:
                 switch(comp.active(g))
         if self.environment_map is not None:            # outside [start_iteration, end_iteration) nothing is scattered or stepped
             self.stepper.environment_active = self.environment_map.active(g)
+        if self.bilateral is not None:
+            batch = self.bilateral.begin(view, batch)   # batch.bilateral_grid: the view's grid of the device state
+            self.stepper.enable_bilateral_gradient(self.bilateral.active(g))   # outside the window the grid is applied, not learnt
         return batch
 
     def _compaction_mask(self, result):
@@ -1042,6 +1113,20 @@ ENVIRONMENT_FLAGS = (
 )
 
 
+# The bilateral grids' flags, likewise a table of their own: main() parses FLAGS + ENVIRONMENT_FLAGS + BILATERAL_FLAGS.
+BILATERAL_FLAGS = (
+    ("--bilateral", dict(help="learn a bilateral grid of affine colour transforms per training view, sliced by pixel position and "
+                              "luminance (bilateral.enabled); not with --exposure; test views have no grid and are scored uncorrected: "
+                              "--cc-metrics is the number to compare with a run without grids"), "bilateral.enabled", "switch"),
+    ("--bilateral-grid", dict(type=int, nargs=3, metavar=("X", "Y", "L"), help="bilateral.grid: cells along x, y and luminance" + _UNTUNED),
+     "bilateral.grid", "value"),
+    ("--bilateral-lr", dict(type=float, metavar="X", help="bilateral.lr" + _UNTUNED), "bilateral.lr", "value"),
+    ("--bilateral-tv", dict(type=float, metavar="X", help="bilateral.lambda_tv: the weight of the grids' total variation" + _UNTUNED),
+     "bilateral.lambda_tv", "value"),
+)
+MAIN_FLAGS = FLAGS + ENVIRONMENT_FLAGS + BILATERAL_FLAGS
+
+
 def build_parser(flags=FLAGS):
     ap = argparse.ArgumentParser(prog="python -m 3dgrut_amd.trainer", description="Train a COLMAP scene and score its test split.")
     for flag, keywords, _, how in flags:
@@ -1088,9 +1173,9 @@ def _attach_image_stems(scene, batches):
 
 
 def main(argv=None):
-    a = build_parser(FLAGS + ENVIRONMENT_FLAGS).parse_args(argv)
+    a = build_parser(MAIN_FLAGS).parse_args(argv)
     from .io_colmap import ColmapScene
-    conf = config_from_args(a, FLAGS + ENVIRONMENT_FLAGS)
+    conf = config_from_args(a, MAIN_FLAGS)
     train = ColmapScene(a.path, "train", a.downsample, a.test_split_interval)
     test = ColmapScene(a.path, "test", a.downsample, a.test_split_interval)
     # configs/initialization/colmap.yaml: observation-point scales, the model's default density / scale factor

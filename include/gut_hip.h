@@ -51,7 +51,8 @@ extern "C" {
  * gut_pixel_error, new entry points: gut_trace_contribution and every other call queue what they queued before; added under 6
  * without a bump: gut_trace_attributes, a new entry point: every other call queues what it queued before; gut_trace_attributes_bwd,
  * likewise; gut_trace_surface, likewise; gut_tsdf_integrate, gut_surface_nets_count and gut_surface_nets_emit, handle-free new entry
- * points). */
+ * points; gut_bilateral_workspace_bytes, gut_bilateral_slice, gut_bilateral_backward, gut_bilateral_backward_image and gut_bilateral_adam_step with
+ * GutBilateralGrid, handle-free new entry points: every other call, gut_exposure_adam_step included, queues what it queued before). */
 #define GUT_ABI_VERSION 6
 
 typedef struct gut_context* gut_handle;
@@ -944,6 +945,57 @@ size_t gut_environment_workspace_bytes(int32_t resolution);
 int gut_environment_backward(void* stream, const GutEnvironmentView* view, const GutEnvironmentCotangent* cotangent, int32_t resolution,
                              void* d_workspace, float* d_texel_grad);
 int gut_environment_rotation(const GutCamera* camera, float* rotation9);
+
+/* ---- Per-view bilateral grids of affine colour transforms (new functionality, the reference has none) ----
+ * A view's grid is d_grid [12, L, Gh, Gw] float32 (levels, rows, columns); channel 4 i + j is entry [i][j] of a 3x4 transform.  For
+ * pixel (x, y), in fp32 without contraction and in this order:
+ *     comp_k = rgb_k + B_k (1 - alpha)          B: `background` (d_background NULL) or the [H,W,3] plane d_background
+ *     g = (0.299 comp_0 + 0.587 comp_1) + 0.114 comp_2;  gc = min(max(g, 0), 1), a NaN g as 0;  inside = 0 < g < 1
+ *     sx = x ((Gw-1)/(W-1)), sy = y ((Gh-1)/(H-1)) (scales formed once, on the host, 0 for an axis of one pixel), sz = gc (L-1)
+ *     i0 = floor(s), f = s - i0, indices i0 and min(i0+1, n-1), weights 1-f and f per axis;  w_abc = (wa wb) wc, x fastest
+ *     A_k = sum over the eight taps in order of w_n G[k, tap_n];   out_i = ((A_i0 comp_0 + A_i1 comp_1) + A_i2 comp_2) + A_i3
+ * gut_bilateral_slice writes rgba' = (out, alpha) in full, one launch.
+ * gut_bilateral_backward takes d_rgba_out_grad [H,W,4], the gradient a loss wrote for rgba' (g' = its rgb part, a non-finite value as
+ * 0), and writes d_rgba_grad [H,W,4] and d_grid_grad [12, L, Gh, Gw], every element of both:
+ *     grid_grad[4i+j, tap_n] = sum_pixels w_n (g'_i c4_j), c4 = (comp, 1): each product rounded to fp32 on its own (a non-finite
+ *         g'_i c4_j as 0), times 2^s (exact), to nearest even, integer adds only: identical inputs give identical bits.  s is
+ *         gut_environment_backward's with the magnitude m = max_pixels max_i |g'_i| max(1, max_j |comp_j|) over the finite comp_j.
+ *     d comp_j = ((A_0j g'_0 + A_1j g'_1) + A_2j g'_2) [+ (lum_j (L-1)) D if inside],  lum = (0.299, 0.587, 0.114),
+ *         D = (g'_0 d_0 + g'_1 d_1) + g'_2 d_2,  d_i = ((dA_i0 comp_0 + dA_i1 comp_1) + dA_i2 comp_2) + dA_i3,
+ *         dA_k = sum over the xy taps in order of (wa wb) (G[k, z1] - G[k, z0])
+ *     rgba_grad.rgb = d comp;  rgba_grad.a = -((B_0 d comp_0 + B_1 d comp_1) + B_2 d comp_2) + rgba_out_grad.a
+ *     lambda_tv != 0: grid_grad += lambda_tv dTV/dG, TV = sum_axes (1 / n_axis) sum_pairs (G[next] - G[cur])^2, n_axis = 12 pairs:
+ *         acc = 0; per axis x, y, z of length > 1: acc = acc + (2 / n_axis) (a - b), a = G[c] - G[previous] (0 at the first
+ *         index), b = G[next] - G[c] (0 at the last); grad = grad + lambda_tv acc.  lambda_tv == 0 adds nothing.
+ * Queued on `stream`, nothing read back: one memset of the workspace (gut_bilateral_workspace_bytes, 0 for dimensions that are
+ * refused), the maximum, the adjoint (a 16x16 pixel tile per workgroup, summed in a direct-indexed LDS table of GUT_BILATERAL_TABLE
+ * 64-bit sums over the tile's footprint in the grid, one 64-bit atomic per non-zero sum; a tile whose footprint exceeds the table
+ * adds to the workspace directly), the conversion with the TV term.
+ * gut_bilateral_backward_image writes d_rgba_grad alone, the same bits, in one launch: no maximum, no sums, no atomics and no
+ * workspace (a step outside the grids' iteration window: the image gradient has to pass through the slice, the grid learns nothing).
+ * gut_bilateral_adam_step: one Adam step on the n = 12 L Gh Gw floats of one view, in place, gut_exposure_adam_step's arithmetic:
+ * *d_count (the view's visit count, below 2^20) is advanced once and gives the bias correction.  One launch.
+ * Return 1, on the host, nothing queued: a NULL pointer other than d_background, a dimension outside 1 .. GUT_BILATERAL_MAX_DIM,
+ * height or width < 1, more than 2^30 pixels, a non-finite lambda_tv, an image pointer that is not 16-byte aligned or a workspace
+ * that is not 8-byte aligned, n outside 1 .. 12 GUT_BILATERAL_MAX_DIM^3; a HIP error is reported the same way.  gut_last_error says
+ * which. */
+#define GUT_BILATERAL_MAX_DIM 256
+#define GUT_BILATERAL_TABLE 1024
+typedef struct GutBilateralGrid {
+    float* d_grid;                  /* [12, levels, rows, columns] */
+    int32_t levels, rows, columns;
+} GutBilateralGrid;
+size_t gut_bilateral_workspace_bytes(int32_t levels, int32_t rows, int32_t columns);
+int gut_bilateral_slice(void* stream, int32_t height, int32_t width, const float* d_rgba,
+                        const float* d_background  /* [H,W,3] or NULL: then `background` is the constant */,
+                        float background, const GutBilateralGrid* grid, float* d_rgba_out);
+int gut_bilateral_backward(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_background, float background,
+                           const GutBilateralGrid* grid, const float* d_rgba_out_grad, float lambda_tv, void* d_workspace,
+                           float* d_rgba_grad, float* d_grid_grad);
+int gut_bilateral_backward_image(void* stream, int32_t height, int32_t width, const float* d_rgba, const float* d_background,
+                                 float background, const GutBilateralGrid* grid, const float* d_rgba_out_grad, float* d_rgba_grad);
+int gut_bilateral_adam_step(void* stream, const float* d_grad, float* d_grid, float* d_m, float* d_v, int32_t* d_count, int64_t n,
+                            float lr, float beta1, float beta2, float eps);
 
 const char* gut_last_error(void);
 int gut_abi_version(void);
